@@ -20,9 +20,14 @@ its RNG on the global env id).
 world size (anything else exits non-zero -- a `--gpus 8` request never prints `"n_gpus": 1`); started bare with N > 1 it
 launches its own N rank processes BEFORE this process makes any GPU call and forwards rank 0's line.
 
-Timing: W warm-up steps, then `--repeats` (default 30) timed regions of EXACTLY K steps each, every region bracketed by a
-barrier + torch.cuda.synchronize() on both sides and max-reduced over ranks; `ms_per_step` / `value` are the MEDIAN region
-(a single sub-millisecond sample is fragile), `steps` stays K, `repeats` and the spread are reported beside it.
+Timing: W warm-up steps, then ONE timed region of EXACTLY K steps, bracketed by a barrier + torch.cuda.synchronize() on
+both sides and max-reduced over ranks; `ms_per_step` is that region's wall time / K.  `--repeats R` (opt-in) times R such
+regions of K steps each and reports the MEDIAN region (a single sub-millisecond sample is fragile), `steps` stays K,
+`repeats` and the spread are reported beside it.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step handed its caller (see dump_outputs()) as
+DIR/<name>.npy; the inputs (scenarios, action pool, step count) depend on the arguments alone, so two builds run with the
+same arguments can be compared array for array.
 
 One JSON line on rank 0.  `roofline` prices the step kernel against HBM:
 algorithmic bytes per env-step = 94 words (40 read + 54
@@ -77,7 +82,8 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=100)
-    ap.add_argument("--repeats", type=int, default=30, help="timed regions of --steps launches each; the median is reported")
+    ap.add_argument("--repeats", type=int, default=1, help="timed regions of --steps launches each; the median is reported "
+                                                          "(default 1: exactly --steps timed steps)")
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
     ap.add_argument("--dtype", default="float64", choices=["float64", "float32"])
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a hipGraph")
@@ -86,12 +92,45 @@ def parse():
     ap.add_argument("--sweep", action="store_true", help="also print an N-sweep (stderr) 2^10..2^22")
     ap.add_argument("--task", default="waypoints", choices=sorted(TASKS),
                     help="step kernel to time (default: the headline FixedwingWaypoints workload of BASELINE.json)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (rank 0's envs, <= 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.repeats < 1:
+        ap.error("--steps and --repeats must be >= 1, --warmup >= 0")
+    return args
 
 
 def action_pool(n, dtype, device):
     g = torch.Generator(device="cpu").manual_seed(0)
     return [(torch.rand((n, 4), generator=g, dtype=torch.float64) * 2 - 1).to(dtype).to(device) for _ in range(POOL)]
+
+
+DUMP_BYTES = 64 << 20            # --dump-outputs: at most this much in all
+
+
+def dump_outputs(env, out_dir, budget=DUMP_BYTES):
+    """--dump-outputs: what the timed path handed its caller in the last timed step -- the env-owned tensors step_tensor()
+    returns (obs, rewards, terminated, truncated) and the two it leaves as attributes (terminal_obs, info) -- as
+    out_dir/<name>.npy.  obs / rewards / terminal_obs keep the env dtype; the uint8 flags become float32 and the int32 info
+    float64 (both exact).  When all of it would exceed `budget` bytes, a fixed sample of env rows (numpy seed 0, sorted) is
+    written instead, the same rows in every array, and their global env ids as env_index.npy.  Returns the names written."""
+    if env.obs.is_cuda:
+        torch.cuda.synchronize(env.device)
+    arrays = {"obs": env.obs, "rewards": env.rewards,
+              "terminated": env.terminated.to(torch.float32), "truncated": env.truncated.to(torch.float32),
+              "terminal_obs": env.terminal_obs, "info": env.info.to(torch.float64)}
+    n = env.num_envs
+    row_bytes = sum(t[0].numel() * t.element_size() for t in arrays.values())
+    if n * row_bytes > budget - 4096:                                   # (4 KB for the .npy headers)
+        m = max(1, (budget - 4096) // (row_bytes + 8))
+        rows = np.sort(np.random.default_rng(0).choice(n, size=m, replace=False))
+        idx = torch.as_tensor(rows, device=env.obs.device)
+        arrays = {k: t.index_select(0, idx) for k, t in arrays.items()}
+        arrays["env_index"] = torch.as_tensor(rows + env.global_env_offset, dtype=torch.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    return sorted(arrays)
 
 
 class Stepper:
@@ -164,6 +203,30 @@ def host_cores():
     return cores, nproc, avail, quota
 
 
+def build_cpu_baseline_lib():
+    """The -O3 -march=native build of the oracle C that cpu_baseline() times, compiled for THIS host's cores by
+    oracle/Makefile's own recipe -- on a copy of its sources in a temporary directory: the benchmark writes nothing into the
+    tree, which need not be writable where it runs.  The library becomes the oracle module's fast library (what
+    OracleEnv(fast=True) / set_threads(fast=True) load).  Returns None, or the error that leaves cpu_baseline out."""
+    import ctypes
+    import shutil
+    import subprocess
+    import tempfile
+    from oracle import fw_oracle as O
+    tmp = tempfile.mkdtemp(prefix="fw_bench_oracle_")
+    try:
+        for rel in ("oracle/Makefile", "oracle/fw_oracle.c", "include/fwsim.h"):
+            os.makedirs(os.path.join(tmp, os.path.dirname(rel)), exist_ok=True)
+            shutil.copy(os.path.join(ROOT, rel), os.path.join(tmp, rel))
+        subprocess.run(["make", "-C", os.path.join(tmp, "oracle"), "libfw_oracle_fast.so"], check=True, capture_output=True, text=True)
+        O._fast = O._bind(ctypes.CDLL(os.path.join(tmp, "oracle", "libfw_oracle_fast.so")))
+        return None
+    except (OSError, subprocess.CalledProcessError) as e:
+        return f"{type(e).__name__}: {e} {getattr(e, 'stderr', '') or ''}".strip()
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)            # (the loaded library stays mapped)
+
+
 def cpu_baseline(cfg, n, seconds_target=20.0):
     """the C restatement of the env step (the PyBullet reference cannot run here) on ALL host cores
     the job may use on the GPU box (host_cores(): affinity mask capped by the cgroup CPU quota), OpenMP over envs, same
@@ -171,7 +234,7 @@ def cpu_baseline(cfg, n, seconds_target=20.0):
     reference worker).  Bounded to about `seconds_target` seconds of CPU work (the protocol's 2 000 timed vec-steps per
     repeat is the upper limit)."""
     from oracle import fw_oracle as O          # checker code used as the reported CPU baseline only
-    # (-O3 -march=native build of the same C, made by main() before the GPU was touched; the strict build stays the checker)
+    # (-O3 -march=native build of the same C, made by build_cpu_baseline_lib() before the GPU was touched; the strict build stays the checker)
     cores_all, nproc, avail, quota = host_cores()
     want = int(os.environ.get("FW_BENCH_THREADS", "0")) or cores_all
     env = O.OracleEnv(cfg, n, seed=42, fast=True)
@@ -397,11 +460,11 @@ def main():
     # the only way to run the RCCL branches (device tensors, all_gather_into_tensor) without a second GPU
     dist = world > 1 or (bool(os.environ.get("FW_DIST_FORCE")) and env_world is not None)
     dry = bool(os.environ.get("FW_BENCH_DRY"))         # launcher rehearsal on a box without a GPU (tests only): no env, no timing
+    cpu_lib_error = None
     if not args.no_cpu_baseline and world == 1 and not dry:
         # the CPU-baseline library is compiled for THIS machine's cores (-march=native); do it before anything touches the
         # GPU: a process that has initialised the GPU must not start other programs (make / gcc) on the GPU boxes
-        from oracle import fw_oracle as _O
-        _O.build_fast()
+        cpu_lib_error = build_cpu_baseline_lib()
     if not dry and not torch.cuda.is_available():
         print(json.dumps({"error": "no HIP device: pyflyt_drone_amd has no CPU fallback"}))
         sys.exit(2)
@@ -442,8 +505,13 @@ def main():
             os._exit(9)
         t = torch.tensor([float(rank + 1)], dtype=torch.float64)
         per_rank = [float(rank + 1)]
+
+        def host_barrier():
+            # every rank must arrive, as at td.barrier() -- which on gloo asks the HIP runtime for the device count and so
+            # opens the GPU in every rehearsal rank on a GPU box; an all-reduce of a host tensor touches no device
+            td.all_reduce(torch.zeros(1))
         if dist:
-            td.barrier(); td.all_reduce(t, op=td.ReduceOp.MAX)
+            host_barrier(); td.all_reduce(t, op=td.ReduceOp.MAX)
             per_rank = gather_per_rank(float(rank + 1), "cpu")
         seen = count_ranks("cpu")
         if rank == 0:
@@ -451,7 +519,7 @@ def main():
                               "n_gpus": world, "ranks_seen": seen, "backend": backend_name, "per_rank": per_rank,
                               "max_rank_plus_one": float(t.item()), "steps": args.steps, "warmup": args.warmup}), flush=True)
         if dist:
-            td.barrier(); td.destroy_process_group()
+            host_barrier(); td.destroy_process_group()
         if seen != args.gpus:
             sys.exit(4)
         return
@@ -502,6 +570,8 @@ def main():
         walls.append(wall); devs.append(ev0.elapsed_time(ev1))
     wall = float(np.median(walls))
     dev_ms = float(np.median(devs))
+    # the outputs of the last timed step, before anything else runs on the GPU (rank 0's envs)
+    dumped = dump_outputs(env, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     # every rank's OWN clock beside the max-reduced one: the launch time its HIP events saw (median region), so that a slow GPU or a
     # rank that waits in the barriers shows in the scaling record instead of disappearing in the max
     per_rank_ms = gather_per_rank(dev_ms / args.steps, env.device if backend == "nccl" else "cpu")
@@ -619,7 +689,8 @@ def main():
             "config": {"workload": f"{task_name}, "
                                    f"{n} envs/GPU x {world} GPU, physics-only step(), motor noise + auto-reset on",
                        "envs_per_gpu": n, "obs_dim": env.obs_dim, "ticks_per_env_step": 8, "lanes_per_env": env.lanes_per_env, "waves_per_simd": (env.g8_waves if env.lanes_per_env == 8 else 2),
-                       "launch": stepper.describe(timed), "timing": f"median of {reps} regions of {args.steps} launches, each between barrier + synchronize",
+                       "launch": stepper.describe(timed), "timing": (f"median of {reps} regions of {args.steps} launches, each" if reps > 1 else f"one region of {args.steps} launches,")
+                                 + " between barrier + synchronize",
                        "parallelism": f"env-shard x{world}"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic, "traffic_source": traffic_src,
@@ -631,11 +702,13 @@ def main():
         }
         if allgather is not None:
             out["update_allgather"] = allgather
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if dist:
             out["per_rank_kernel_ms_per_step"] = per_rank_ms
             out["per_rank_kernel_ms_per_step_min"], out["per_rank_kernel_ms_per_step_max"] = min(per_rank_ms), max(per_rank_ms)
         if not args.no_cpu_baseline and world == 1:          # timed on rank 0 at N = 1 only
-            out["cpu_baseline"] = cpu_baseline(cfg, n)
+            out["cpu_baseline"] = cpu_baseline(cfg, n) if cpu_lib_error is None else {"error": cpu_lib_error}
         if world == 1 and not args.no_collector and not args.no_cpu_baseline and n <= 8192:
             out["collector"] = collector_rates(args.task, n)
     if dist and not args.no_collector and n <= 8192:

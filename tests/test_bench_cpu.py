@@ -125,3 +125,60 @@ def test_learner_accounting_matches_the_documented_figures():
     assert A.render(4096, 32)["bytes"] == 33_554_432
     p = A.ppo_pack(10240, 128, 28)
     assert p["items"]["packed rows written ((D rounded up to 4) + 8 floats)"] == 10240 * 128 * 36 * 4
+
+
+def test_dump_outputs_writes_the_step_outputs_as_float_arrays_within_the_budget(tmp_path):
+    """`--dump-outputs DIR`: the outputs of the last timed step as DIR/<name>.npy in float32 / float64; above the budget a
+    fixed seeded sample of env rows (the same rows in every array, their ids in env_index.npy)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Env:                                    # the output tensors of FixedwingVecEnv, on the host
+        num_envs, global_env_offset = 1000, 4096
+        g = torch.Generator().manual_seed(1)
+        obs = torch.rand((1000, 28), generator=g, dtype=torch.float64)
+        rewards = torch.rand(1000, generator=g, dtype=torch.float64)
+        terminated = (torch.rand(1000, generator=g) < 0.1).to(torch.uint8)
+        truncated = (torch.rand(1000, generator=g) < 0.1).to(torch.uint8)
+        terminal_obs = torch.rand((1000, 28), generator=g, dtype=torch.float64)
+        info = torch.randint(-5, 5, (1000, 8), generator=g, dtype=torch.int32)
+
+    full = bench.dump_outputs(Env, str(tmp_path / "full"))
+    assert full == ["info", "obs", "rewards", "terminal_obs", "terminated", "truncated"]
+    for name in full:
+        a = np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.dtype in (np.float32, np.float64), name
+        np.testing.assert_array_equal(a, getattr(Env, name).numpy().astype(a.dtype))
+    budget = 64 << 10                             # 1000 rows x 540 B do not fit: a sample does
+    names = bench.dump_outputs(Env, str(tmp_path / "a"), budget=budget)
+    assert names == sorted(full + ["env_index"])
+    assert sum(os.path.getsize(tmp_path / "a" / f"{k}.npy") for k in names) <= budget
+    rows = np.load(tmp_path / "a" / "env_index.npy").astype(np.int64) - Env.global_env_offset
+    assert 50 < len(rows) < 1000 and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "obs.npy"), Env.obs.numpy()[rows])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "info.npy"), Env.info.numpy()[rows].astype(np.float64))
+    bench.dump_outputs(Env, str(tmp_path / "b"), budget=budget)                   # the same sample every time
+    for k in names:
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy"))
+
+
+def test_cpu_baseline_library_is_built_outside_the_tree():
+    """bench.py compiles the -march=native oracle that `cpu_baseline` times in a temporary directory: the benchmark must run
+    from a tree it cannot write to, and leaves nothing in it."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import fw_oracle as O
+    from pyflyt_drone_amd import config as K
+    oracle_dir = os.path.join(ROOT, "oracle")
+    before = {f: os.path.getmtime(os.path.join(oracle_dir, f)) for f in os.listdir(oracle_dir)}
+    assert bench.build_cpu_baseline_lib() is None
+    assert {f: os.path.getmtime(os.path.join(oracle_dir, f)) for f in os.listdir(oracle_dir)} == before
+    assert not os.path.exists(O._fast._name)                                  # the temporary build is gone, the library stays loaded
+    env = O.OracleEnv(K.train_waypoints_v3_config(), 16, seed=42, fast=True)
+    ref = O.OracleEnv(K.train_waypoints_v3_config(), 16, seed=42)
+    np.testing.assert_allclose(env.reset(), ref.reset(), rtol=0, atol=1e-9)
+    a = np.random.default_rng(0).uniform(-1, 1, size=(16, 4))
+    np.testing.assert_allclose(env.step(a)[0], ref.step(a)[0], rtol=1e-6, atol=1e-6)

@@ -73,3 +73,26 @@ def test_gpus_mismatch_is_an_error_not_a_one_gpu_line(launcher):
     rc, out, _ = launcher([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8"], env={"WORLD_SIZE": "1", "RANK": "0"})
     b = _line(out)
     assert rc != 0 and "error" in b and "n_gpus" not in b
+
+
+def test_dump_outputs_hold_the_last_timed_step_and_repeat_run_to_run(launcher, tmp_path):
+    """`--dump-outputs DIR`: the arrays the last timed step handed its caller; with the same arguments two runs write the same
+    arrays (what lets two builds be compared output for output).  Without --repeats exactly --steps launches are timed."""
+    import numpy as np
+    names = ["info", "obs", "rewards", "terminal_obs", "terminated", "truncated"]
+    runs = []
+    for k in ("a", "b"):
+        d = tmp_path / k
+        rc, out, err = launcher([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "70", "--warmup", "5", "--no-cpu-baseline",
+                                 "--dump-outputs", str(d)])
+        assert rc == 0, err
+        b = _line(out)
+        assert b["steps"] == 70 and b["repeats"] == 1 and b["config"]["launch"] == "hipGraph(64 launches) x1 replays + 6 eager"
+        assert b["dump_outputs"]["arrays"] == names
+        runs.append({n: np.load(d / f"{n}.npy") for n in names})
+    a = runs[0]
+    assert a["obs"].shape == a["terminal_obs"].shape == (4096, 28) and a["obs"].dtype == a["rewards"].dtype == np.float64
+    assert a["terminated"].dtype == np.float32 and a["info"].shape == (4096, 8) and a["info"].dtype == np.float64
+    assert np.isfinite(a["obs"]).all() and np.isfinite(a["rewards"]).all() and a["obs"].any()
+    for n in names:
+        np.testing.assert_array_equal(a[n], runs[1][n], err_msg=n)

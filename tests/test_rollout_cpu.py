@@ -464,8 +464,9 @@ def test_n_steps_for_holds_the_reference_samples_per_update():
 def _worker_samples(rank, world, port, q):
     import torch.distributed as td
     torch.set_num_threads(1)
+    # FW_DIST_SINGLE_DEVICE: where a GPU is visible, both ranks bind device 0 (a one-GPU box has no device 1)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(world), RANK=str(rank), LOCAL_RANK=str(rank),
-                      FW_DIST_BACKEND="gloo")
+                      FW_DIST_BACKEND="gloo", FW_DIST_SINGLE_DEVICE="1")
     w, r, _ = R.init_distributed_from_env()                      # what the examples call first
     try:
         S, n = 64, 8                                             # samples per update of the (toy) reference config, envs per rank
