@@ -72,7 +72,8 @@ enum {
 enum {
   FW_TASK_WAYPOINTS = 0,        /* PyFlyt/Fixedwing-Waypoints-v3 (train/train_Fixedwing_Waypoints_v3.py:100-110) */
   FW_TASK_OBJLOCK = 1,          /* envs/fixedwing_objlock_env.py */
-  FW_TASK_WAYPOINT_OBJLOCK = 2  /* envs/fixedwing_waypoint_objlock_env.py */
+  FW_TASK_WAYPOINT_OBJLOCK = 2, /* envs/fixedwing_waypoint_objlock_env.py */
+  FW_TASK_LOWLEVEL = 3          /* envs/fixedwing_envs/fixedwing_lowlevel_env.py: six actuator commands, heading / height / speed tracking */
 };
 
 /* fw_config.dtype */
@@ -149,7 +150,9 @@ typedef struct fw_config {
   int32_t duck_vision_no_deltas; /* ObjLock: 1 = duck_vision_use_deltas=False of the reference (envs/fixedwing_objlock_env.py:69-70, 440-441):
                                   * the observation ends with the 27 history values, without the 4 frame-to-frame deltas (52 wide, not 56).
                                   * (Round 5; one of the former reserved words, which callers zero: same layout, same ABI version.) */
-  int32_t reserved_i[7];
+  int32_t lowlevel_max_episode_steps; /* FW_TASK_LOWLEVEL: truncation at this many agent steps (2000, fixedwing_lowlevel_env.py:137).
+                                  * (A former reserved word, which callers zero: same layout, same ABI version.) */
+  int32_t reserved_i[6];
 
   /* ---- env / task scalars ---- */
   double flight_dome_size;
@@ -205,7 +208,10 @@ typedef struct fw_config {
   double camera_fov_deg;            /* 90 */
   double camera_near;               /* 0.1   fixedwing_objlock_env.py:692 */
   double camera_far;                /* 255.0 */
-  double reserved_d[8];
+  /* ---- low-level task (envs/fixedwing_envs/fixedwing_lowlevel_env.py:32-33, 86-91); former reserved words, zero elsewhere ---- */
+  double lowlevel_speed_range[2];   /* V_ref ~ U(lo, hi), (10, 20) */
+  double lowlevel_height_range[2];  /* h_ref ~ U(lo, hi), (5, 20) */
+  double reserved_d[4];
 } fw_config;
 
 /* ---- canonical per-env state record (doubles; used by fw_get_state/fw_set_state) ---- */
@@ -252,6 +258,14 @@ enum {
   FW_ST_DIM = 110
 };
 
+/* low-level tail (offsets from FW_S_TASK): the episode's target and the action its observation shows.  The episode's step
+ * count is FW_S_STEP_COUNT, as for every task. */
+enum {
+  FW_SL_TARGET = 0,        /* 3: psi_ref, h_ref, V_ref            fixedwing_lowlevel_env.py:86-91 */
+  FW_SL_PREV_ACTION = 3,   /* 6: the last action (obs[12:18])     :99 */
+  FW_SL_DIM = 9
+};
+
 /* info_i32 columns written by fw_step (info of the step that just ran, i.e. of
  * the finished episode when the env was auto-reset). */
 enum {
@@ -285,8 +299,10 @@ int32_t fw_sizeof_config(void);
 int32_t fw_abi_version(void);
 int32_t fw_state_dim(void);      /* FW_STATE_DIM of the canonical state record */
 
-/* Observation width D for a config (22/23 attitude + task part); <0 on error. */
+/* Observation width D for a config (22/23 attitude + task part; 21 for FW_TASK_LOWLEVEL); <0 on error. */
 int32_t fw_obs_dim(const fw_config* cfg);
+/* Action width A for a config: 6 for FW_TASK_LOWLEVEL (the actuator commands), 4 otherwise ([roll, pitch, yaw, thrust]); <0 on error. */
+int32_t fw_act_dim(const fw_config* cfg);
 
 /* Validate a config exactly like the reference constructors do.  On error
  * returns FW_EINVAL and writes a message (same wording class as the
@@ -320,7 +336,7 @@ typedef struct fw_scenario {
 int32_t fw_reset(fw_handle h, const uint8_t* mask, const fw_scenario* scenario, void* obs_out, void* hip_stream);
 
 /* One agent step for all N envs.
- *   actions       T[N,4]  in [-1,1] (caller clips, as SB3 does)
+ *   actions       T[N,A]  in [-1,1] (caller clips, as SB3 does); A = fw_act_dim(cfg)
  *   obs           T[N,D]  next observation (first obs of the new episode if auto-reset fired)
  *   reward        T[N]
  *   terminated    u8[N]

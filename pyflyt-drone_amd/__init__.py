@@ -6,12 +6,12 @@ BASELINE.json: the fixed-wing flight-dynamics step + reward + observation of
 SB3 ``VecEnv`` surface the reference's training scripts consume.
 """
 from . import config
-from .config import (FwConfig, train_waypoints_v3_config, waypoints_config)
+from .config import (FwConfig, lowlevel_config, train_waypoints_v3_config, waypoints_config)
 from .spaces import Box
-from .vec_env import (FixedwingObjLockVecEnv, FixedwingVecEnv, FixedwingWaypointObjLockVecEnv,
+from .vec_env import (FixedwingLowLevelVecEnv, FixedwingObjLockVecEnv, FixedwingVecEnv, FixedwingWaypointObjLockVecEnv,
                       FixedwingWaypointsVecEnv)
 from . import rollout
 from . import checkpoint, evaluate
 
 __all__ = ["config", "FwConfig", "Box", "FixedwingVecEnv", "FixedwingWaypointsVecEnv", "FixedwingObjLockVecEnv", "FixedwingWaypointObjLockVecEnv",
-           "waypoints_config", "train_waypoints_v3_config"]
+           "FixedwingLowLevelVecEnv", "waypoints_config", "train_waypoints_v3_config", "lowlevel_config"]

@@ -18,7 +18,7 @@ LIB_PATH = os.environ.get("FWSIM_LIB") or os.path.join(CSRC, "libfwsim_hip.so") 
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 
 EXPORTS = (
-    "fw_sizeof_config", "fw_abi_version", "fw_state_dim", "fw_obs_dim", "fw_validate_config", "fw_create", "fw_reset",
+    "fw_sizeof_config", "fw_abi_version", "fw_state_dim", "fw_obs_dim", "fw_act_dim", "fw_validate_config", "fw_create", "fw_reset",
     "fw_step", "fw_seed", "fw_get_state", "fw_set_state", "fw_get_counters", "fw_observe", "fw_render", "fw_num_envs", "fw_lanes_per_env", "fw_capture_wave", "fw_last_error",
     "fw_destroy", "fw_gae", "fw_eval_track", "fw_normalize_obs", "fw_normalize_obs_workspace_bytes", "fw_ppo_update_workspace_bytes", "fw_ppo_param_count", "fw_ppo_moment_count", "fw_ppo_moment_map", "fw_ppo_update", "fw_policy_act", "fw_policy_terminal_value", "fw_rollout_post", "fw_collect_act", "fw_collect_stats", "fw_collect_stats_workspace_bytes", "fw_collect_step", "fw_collect_finish", "fw_collect_step_workspace_bytes", "fw_collect_workspace_init", "fw_collect_close", "fw_collect_status", "fw_ppo_update_status",
 )
@@ -83,6 +83,7 @@ def lib() -> C.CDLL:
         L.fw_abi_version.restype = i32; L.fw_abi_version.argtypes = []
         L.fw_state_dim.restype = i32; L.fw_state_dim.argtypes = []
         L.fw_obs_dim.restype = i32; L.fw_obs_dim.argtypes = [vp]
+        L.fw_act_dim.restype = i32; L.fw_act_dim.argtypes = [vp]
         L.fw_validate_config.restype = i32; L.fw_validate_config.argtypes = [vp, C.c_char_p, i32]
         L.fw_create.restype = i32; L.fw_create.argtypes = [vp, i32, i32, u64, i64, C.POINTER(vp)]
         L.fw_reset.restype = i32; L.fw_reset.argtypes = [vp, vp, vp, vp, vp]

@@ -30,7 +30,7 @@ FW_STATE_DIM = 176
 FW_INFO_DIM = 8
 
 FW_OK, FW_EINVAL, FW_EHIP, FW_ENOMEM, FW_EVERSION, FW_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
-FW_TASK_WAYPOINTS, FW_TASK_OBJLOCK, FW_TASK_WAYPOINT_OBJLOCK = 0, 1, 2
+FW_TASK_WAYPOINTS, FW_TASK_OBJLOCK, FW_TASK_WAYPOINT_OBJLOCK, FW_TASK_LOWLEVEL = 0, 1, 2, 3
 FW_F64, FW_F32 = 0, 1
 FW_WIND_OFF, FW_WIND_CONSTANT, FW_WIND_GUST_SINE = 0, 1, 2
 FW_WIND_COUPLE_NONE, FW_WIND_COUPLE_FORCE, FW_WIND_COUPLE_AIRSPEED = 0, 1, 2
@@ -43,6 +43,8 @@ S_WIND, S_EP_RETURN, S_TARGETS, S_TASK = 29, 36, 37, 61
 ST_DUCK_POS, ST_LOCK_STEPS, ST_PREV_EST, ST_LAST_CX, ST_LAST_CY = 0, 3, 4, 5, 6
 ST_LAST_AREA, ST_LAST_DEPTH, ST_SINCE_SEEN, ST_HIST_FILLED, ST_FRAME_HAS, ST_FRAME, ST_HIST = 7, 8, 9, 10, 11, 12, 20
 ST_DUCK_PHASE, ST_SEEN_CONSEC, ST_NUM_OBST, ST_OBST, ST_DIM = 47, 48, 49, 50, 110
+# low-level tail (offsets from S_TASK; fwsim.h FW_SL_*): target (psi_ref, h_ref, V_ref), previous action (6)
+SL_TARGET, SL_PREV_ACTION, SL_DIM = 0, 3, 9
 
 INFO_NUM_TARGETS_REACHED, INFO_COLLISION, INFO_OUT_OF_BOUNDS, INFO_ENV_COMPLETE = 0, 1, 2, 3
 INFO_DUCK_STRIKE, INFO_IS_SUCCESS, INFO_EP_LEN = 4, 5, 6
@@ -80,7 +82,8 @@ class FwConfig(C.Structure):
         ("n_collision_pts", C.c_int32), ("num_obstacles", C.c_int32),
         ("duck_camera_capture_interval_steps", C.c_int32), ("duck_lock_hold_steps", C.c_int32),
         ("duck_lock_decay_steps", C.c_int32), ("duck_switch_min_consecutive_seen", C.c_int32),
-        ("camera_resolution", C.c_int32), ("duck_vision_no_deltas", C.c_int32), ("reserved_i", C.c_int32 * 7),
+        ("camera_resolution", C.c_int32), ("duck_vision_no_deltas", C.c_int32),
+        ("lowlevel_max_episode_steps", C.c_int32), ("reserved_i", C.c_int32 * 6),
         # env / task scalars
         ("flight_dome_size", C.c_double), ("max_duration_seconds", C.c_double),
         ("goal_reach_distance", C.c_double), ("waypoint_min_height", C.c_double),
@@ -109,7 +112,9 @@ class FwConfig(C.Structure):
         ("obstacle_avoid_max_penalty", C.c_double),
         ("camera_offset", C.c_double * 3), ("camera_angle_deg", C.c_double),
         ("camera_fov_deg", C.c_double), ("camera_near", C.c_double), ("camera_far", C.c_double),
-        ("reserved_d", C.c_double * 8),
+        # low-level task
+        ("lowlevel_speed_range", C.c_double * 2), ("lowlevel_height_range", C.c_double * 2),
+        ("reserved_d", C.c_double * 4),
     ]
 
     def copy(self) -> "FwConfig":
@@ -589,11 +594,49 @@ def waypoint_objlock_config_from_reference_kwargs(*, dtype: str = "float64", mot
                                    camera_resolution=res, **env_kwargs)
 
 
+def lowlevel_config(*, dtype: str = "float64", target_speed_range=(10.0, 20.0), target_height_range=(5.0, 20.0),
+                    max_episode_steps: int = 2000, wind_config: Optional[Mapping[str, Any]] = None, motor_noise: bool = True,
+                    auto_reset: bool = True) -> FwConfig:
+    """``FixedwingLowLevelEnv`` (envs/fixedwing_envs/fixedwing_lowlevel_env.py, the version train/train_lowlevel_cmd.py imports):
+    start at [0, 0, 10] with zero orientation and world velocity [15, 0, 0] (:29-49), physics 240 Hz, one Aviary step (2
+    ticks at the 120 Hz control rate) per agent step, no warm-up steps after ``Aviary.reset()`` (:75); a target (psi_ref,
+    h_ref, V_ref) per episode from the given ranges (:32-33, 86-91); truncation at ``max_episode_steps`` (:137).  The
+    altitude bounds (1 / 100 m) and the reward weights are the reference's literals, compiled in."""
+    c = base_config(task=FW_TASK_LOWLEVEL, dtype=dtype, angle_representation="euler", agent_hz=120, flight_dome_size=100.0,
+                    max_duration_seconds=float(max_episode_steps) / 120.0, start_pos=(0.0, 0.0, 10.0), wind_config=wind_config,
+                    motor_noise=motor_noise, auto_reset=auto_reset)
+    c.warmup_aviary_steps = 0
+    _set_vec(c.start_vel, (15.0, 0.0, 0.0))
+    c.num_targets, c.context_length = 0, 0
+    lo, hi = (float(v) for v in target_speed_range)
+    c.lowlevel_speed_range[0], c.lowlevel_speed_range[1] = lo, hi
+    lo, hi = (float(v) for v in target_height_range)
+    c.lowlevel_height_range[0], c.lowlevel_height_range[1] = lo, hi
+    c.lowlevel_max_episode_steps = int(max_episode_steps)
+    return c
+
+
+def lowlevel_config_from_reference_kwargs(*, render_mode=None, wind_config: Optional[Mapping[str, Any]] = None,
+                                          dtype: str = "float64", motor_noise: bool = True, auto_reset: bool = True) -> FwConfig:
+    """The keywords of ``FixedwingLowLevelEnv.__init__`` (envs/fixedwing_envs/fixedwing_lowlevel_env.py:21-23), as passed by
+    train/train_lowlevel_cmd.py:58; the device env has no renderer, so ``render_mode`` must be None."""
+    if render_mode is not None:
+        raise ValueError(f"Invalid render mode {render_mode}, rendering is not part of the device env.")
+    return lowlevel_config(dtype=dtype, wind_config=wind_config, motor_noise=motor_noise, auto_reset=auto_reset)
+
+
 def obs_dim(c: FwConfig) -> int:
+    if c.task == FW_TASK_LOWLEVEL:
+        return 21                                                   # envs/fixedwing_envs/fixedwing_lowlevel_env.py:65-66
     att = (12 if c.angle_representation == 0 else 13) + 4 + 6
     if c.task == FW_TASK_OBJLOCK:
         return att + 3 + FW_VISION_FEATS * FW_VISION_HIST + (0 if c.duck_vision_no_deltas else 4)      # (:163-165)
     return att + 3 * c.context_length
+
+
+def act_dim(c: FwConfig) -> int:
+    """Action width (``fw_act_dim``): the low-level task's six actuator commands, [roll, pitch, yaw, thrust] otherwise."""
+    return 6 if c.task == FW_TASK_LOWLEVEL else 4
 
 
 def max_steps(c: FwConfig) -> int:

@@ -1308,6 +1308,257 @@ void fw_reset_kernel(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// FW_TASK_LOWLEVEL (envs/fixedwing_envs/fixedwing_lowlevel_env.py, the version train/train_lowlevel_cmd.py imports): the six
+// actions are the actuator commands (mode -1, no mixer), one Aviary step (2 physics ticks) per agent step, a target
+// (psi_ref, h_ref, V_ref) per episode, tracking reward, termination on height, truncation on the step count.  A kernel of its
+// own rather than a task kind of step_body: there is no sub-step loop, no warm-up and no hand-off, so none of step_body's
+// machinery applies, and the other tasks' kernels stay exactly as they were.  The physics is the same inlined Aviary step.
+// The reset is inline (no warm-up, three draws): a wave that contains one runs ~50 more instructions per lane.
+// ------------------------------------------------------------------------------------------
+// wrap to [-pi, pi): Python's (a + pi) % (2 pi) - pi (:158-159), the sign of the modulus taken from the divisor
+template <typename T> __device__ __forceinline__ T ll_wrap_pi(T a) {
+  const T two_pi = (T)(2.0 * kPi);
+  T r = ::fmod(a + (T)kPi, two_pi);
+  r = (r < (T)0) ? r + two_pi : r;
+  return r - (T)kPi;
+}
+// the episode's target, drawn on a stream of its own keyed on (seed, global env, episode): :86-91
+template <typename T> __device__ __forceinline__ void ll_target(const Params<T>& P, uint32_t genv, uint32_t ep, T tgt[3]) {
+  const double k = 1.0 / 9007199254740992.0;
+  const double u0 = (double)(rng_u64(P, genv, ep, STREAM_LL_TARGET, 0) >> 11) * k;
+  const double u1 = (double)(rng_u64(P, genv, ep, STREAM_LL_TARGET, 1) >> 11) * k;
+  const double u2 = (double)(rng_u64(P, genv, ep, STREAM_LL_TARGET, 2) >> 11) * k;
+  tgt[0] = (T)(-kPi + (2.0 * kPi) * u0);
+  tgt[1] = (T)(P.ll_height[0] + (P.ll_height[1] - P.ll_height[0]) * u1);
+  tgt[2] = (T)(P.ll_speed[0] + (P.ll_speed[1] - P.ll_speed[0]) * u2);
+}
+// Aviary.reset() + reset() (:73-95): start pose and velocity, zero actuators, no warm-up; the wind of the episode; the target
+template <typename T, int G>
+__device__ __forceinline__ void ll_begin_episode(const Params<T>& P, const DevState<T>& D, int env, int32_t episode, Rigid<T>& S,
+                                                 int32_t& tick, T tgt[3], T wb[3], T wa[3], T& wph) {
+  Scenario<T> sc;
+  sample_scenario_inl<T, G>(&P, D.r, (size_t)D.npad, env, (uint32_t)episode, &sc);      // wind rows (num_targets = 0: no waypoints)
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { wb[k] = sc.wb[k]; wa[k] = sc.wa[k]; }
+  wph = sc.wph;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { S.p[k] = P.start_pos[k]; S.v[k] = P.start_vel[k]; S.w[k] = (T)0; }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) S.q[k] = P.start_quat[k];
+#pragma unroll
+  for (int k = 0; k < FW_NUM_ACTUATORS; ++k) S.act[k] = (T)0;
+  tick = 0;
+  ll_target<T>(P, (uint32_t)(P.env_offset + env), (uint32_t)episode, tgt);
+}
+// _compute_obs() (:144-156): [ang_vel, ang_pos (Euler), lin_vel, lin_pos] -- the first 12 values of the Euler attitude block --
+// then the previous action (6) and the target (3).  Also hands back psi, z and |v| for the reward.
+template <typename T, typename W>
+__device__ __forceinline__ void ll_write_obs(const Rigid<T>& S, const T act[6], const T tgt[3], T& psi, T& speed, W&& put) {
+  T R[9], ang_vel[3], lin_vel[3], eul[3];
+  rot_from_quat(S.q, R);
+  mtv(R, S.w, ang_vel);
+  mtv(R, S.v, lin_vel);
+  (void)euler_from_quat(S.q, eul);
+  int o = 0;
+  put(o++, ang_vel[0]); put(o++, ang_vel[1]); put(o++, ang_vel[2]);
+  put(o++, eul[0]); put(o++, eul[1]); put(o++, eul[2]);
+  put(o++, lin_vel[0]); put(o++, lin_vel[1]); put(o++, lin_vel[2]);
+  put(o++, S.p[0]); put(o++, S.p[1]); put(o++, S.p[2]);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) put(o++, act[k]);
+  put(o++, tgt[0]); put(o++, tgt[1]); put(o++, tgt[2]);
+  psi = eul[2];
+  speed = M<T>::sqrt_(lin_vel[0] * lin_vel[0] + lin_vel[1] * lin_vel[1] + lin_vel[2] * lin_vel[2]);
+}
+template <typename T>
+__device__ __forceinline__ void ll_load_tail(const DevState<T>& D, int env, T tgt[3], T act[6]) {
+  const size_t n = D.npad;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) tgt[k] = D.r[(size_t)(RF_TASK + FW_SL_TARGET + k) * n + env];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) act[k] = D.r[(size_t)(RF_TASK + FW_SL_PREV_ACTION + k) * n + env];
+}
+template <typename T>
+__device__ __forceinline__ void ll_store_tail(const DevState<T>& D, int env, const T tgt[3], const T act[6]) {
+  const size_t n = D.npad;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) D.r[(size_t)(RF_TASK + FW_SL_TARGET + k) * n + env] = tgt[k];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) D.r[(size_t)(RF_TASK + FW_SL_PREV_ACTION + k) * n + env] = act[k];
+}
+
+// K1 (low-level task): one agent step.  G lanes per env as in step_body (G = 8: lane j evaluates lifting surface j); WIND = the
+// config has wind (per-env wind registers and gust clock).  The lanes of an env's group compute the same scalars; lane 0 stores.
+template <typename T, int G, bool WIND>
+__global__ __launch_bounds__(kWave) void fw_step_kernel_ll(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp, DevState<T> Dg,
+                                                           const T* __restrict__ actions, T* __restrict__ obs, T* __restrict__ reward,
+                                                           uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated,
+                                                           T* __restrict__ terminal_obs, int32_t* __restrict__ info) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  T* tile = reinterpret_cast<T*>(smem_raw);
+  const Params<T>& P = *Pp;
+  constexpr int EPW = kWave / G, Dobs = 21, ld = Dobs + 1;
+  Dg.epoch = launch_index(Dg.lctr);
+  const DevState<T> D = tile_view<T, EPW>(Dg, (int)blockIdx.x);
+  const int lane = threadIdx.x, sub = (G == 1) ? 0 : (lane & (G - 1)), row = lane / G;
+  const bool leader = sub == 0;
+  const int env0 = (int)blockIdx.x * EPW, env = env0 + row;
+  const bool active = env < D.n;
+  const int envc = active ? env : D.n - 1;           // inactive lanes shadow the last env and never store
+  const size_t n = D.npad;
+
+  int32_t step_count = D.i[IF_STEP * n + envc];
+  int32_t tick = D.i[IF_TICK * n + envc];
+  int32_t episode = D.i[IF_EPISODE * n + envc];
+  int32_t flags = D.i[IF_FLAGS * n + envc];
+  Rigid<T> S;
+  load_rigid<T>(D, envc, S);
+  T ep_return = D.r[RF_EP_RETURN * n + envc];
+  T tgt[3], act[6];
+  ll_load_tail<T>(D, envc, tgt, act);
+  T wb[3] = {(T)0, (T)0, (T)0}, wa[3] = {(T)0, (T)0, (T)0}, wphase = (T)0;
+  if (WIND) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { wb[k] = D.r[(RF_WIND + k) * n + envc]; wa[k] = D.r[(RF_WIND + 3 + k) * n + envc]; }
+    wphase = D.r[(RF_WIND + 6) * n + envc];
+  }
+  TickC<T> C; SurfC<T> mine; T wmask;
+  load_tick_constants<T, G>(Pp, C, mine, wmask);
+  normalize_quat<T>(S.q);
+  T R[9];
+  rot_from_unit_quat<T>(S.q, R);
+  T gust[2] = {(T)0, (T)1};
+  if (WIND) gust_init<T>(P, wphase, tick, gust);
+
+  // An env that is already done (an un-reset env, or a finished one without auto-reset) is inert: it keeps its state and returns
+  // its observation with reward 0 and its flags.
+  const bool done_at_entry = (flags & (FL_TERM | FL_TRUNC)) != 0;
+  const bool stepping = !done_at_entry;
+  if (stepping) {
+    // :97-103: prev_action = action; set_all_setpoints(action) in mode -1 -- the surfaces take a[0..4] as given, the throttle
+    // command is 0.5 a[5] + 0.5 (the mode-0 path's map: DESIGN.md section 2, build-owned)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) act[k] = actions[(size_t)envc * 6 + k];
+  }
+  const T cmd[FW_NUM_ACTUATORS] = { act[0], act[1], act[2], act[3], act[4], act[5] * (T)0.5 + (T)0.5 };
+  LaneAct<T> LA; LA.a = (T)0; LA.cmd = (T)0;
+  if (G == 8) { lane_act_scatter<T>(S, LA); LA.cmd = lane_pick5<T>(cmd[0], cmd[1], cmd[2], cmd[3], cmd[4]); }
+  // one Aviary step; the motor-noise normals are those of every task: Aviary step tick / ticks_per_aviary of the episode
+  const uint32_t genv = (uint32_t)(P.env_offset + envc);
+  T z0 = (T)0, z1 = (T)0;
+  if (P.has_noise && stepping) rng_normal2<T>(P, genv, (uint32_t)episode, (uint32_t)(tick / P.ticks_per_aviary), z0, z1);
+  ObjState<T> O;                                     // (no task objects: aviary_step<..., OBJ = false> never touches it)
+  if (stepping) (void)aviary_step<T, WIND, G, false>(P, C, *OCp, D, envc, O, S, R, cmd, tick, z0, z1, wb, wa, gust, mine, wmask, LA);
+  if (G == 8) lane_act_gather<T>(S, LA);
+
+  // observation, reward, termination, truncation (:105-142)
+  T* trow = tile + row * ld;
+  T psi, speed;
+  ll_write_obs<T>(S, act, tgt, psi, speed, [&](int k, T v) { if (leader) trow[k] = v; });
+  T rew = (T)0;
+  if (stepping) {
+    step_count += 1;
+    const T z = S.p[2];
+    const T psi_err = M<T>::fabs_(ll_wrap_pi<T>(tgt[0] - psi)), h_err = M<T>::fabs_(tgt[1] - z), v_err = M<T>::fabs_(tgt[2] - speed);
+    rew = -((T)1 * psi_err + (T)1 * h_err + (T)0.5 * v_err);
+    rew += (T)0.1;
+    flags = 0;
+    if (z < (T)1 || z > (T)100) { flags |= FL_TERM; rew -= (T)100; }      // :132-134
+    if (step_count >= P.ll_max_steps) flags |= FL_TRUNC;                  // :137-138
+    ep_return += rew;
+  }
+  if (active && leader) {
+    reward[env] = rew;
+    terminated[env] = (uint8_t)((flags & FL_TERM) ? 1 : 0);
+    truncated[env] = (uint8_t)((flags & FL_TRUNC) ? 1 : 0);
+    if (info) {
+      int4* ip = reinterpret_cast<int4*>(info + (size_t)env * FW_INFO_DIM);
+      ip[0] = make_int4(0, 0, 0, 0);
+      ip[1] = make_int4(0, 0, step_count, 0);
+    }
+  }
+  // SB3 worker auto-reset: the row just written is the terminal observation; the new episode's first observation replaces it
+  if ((flags & (FL_TERM | FL_TRUNC)) && P.auto_reset) {
+    if (active && leader && terminal_obs) {
+      T* out = terminal_obs + (size_t)env * Dobs;
+      for (int k = 0; k < Dobs; ++k) out[k] = trow[k];
+    }
+    episode += 1;
+    ll_begin_episode<T, G>(P, D, envc, episode, S, tick, tgt, wb, wa, wphase);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) act[k] = (T)0;
+    step_count = 0; flags = 0; ep_return = (T)0;
+    ll_write_obs<T>(S, act, tgt, psi, speed, [&](int k, T v) { if (leader) trow[k] = v; });
+    if (active && leader) { stat_add(D.stats, FW_CTR_RESETS); stat_add(D.stats, FW_CTR_FALLBACKS); }
+  }
+  if (active && leader) {
+    store_rigid<T>(D, env, S);
+    ll_store_tail<T>(D, env, tgt, act);
+    D.r[RF_EP_RETURN * n + env] = ep_return;
+    D.i[IF_STEP * n + env] = step_count;
+    D.i[IF_TICK * n + env] = tick;
+    D.i[IF_EPISODE * n + env] = episode;
+    D.i[IF_FLAGS * n + env] = flags;
+  }
+  __syncthreads();
+  flush_obs_tile<T>(tile, ld, obs, env0, EPW, D.n, Dobs);
+  launch_done(Dg.lctr, Dg.epoch);
+}
+
+// K2 (low-level task): reset (masked) + observation, fw_reset / fw_observe.  A caller-supplied scenario's wind replaces the draw.
+template <typename T, int G>
+__global__ __launch_bounds__(kWave) void fw_reset_kernel_ll(const Params<T>* __restrict__ Pp, DevState<T> Dg, const uint8_t* __restrict__ mask,
+                                                            T* __restrict__ obs, int do_reset, ScenOv ov) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  T* tile = reinterpret_cast<T*>(smem_raw);
+  const Params<T>& P = *Pp;
+  constexpr int EPW = kWave / G, Dobs = 21, ld = Dobs + 1;
+  const DevState<T> D = tile_view<T, EPW>(Dg, (int)blockIdx.x);
+  const int lane = threadIdx.x, sub = (G == 1) ? 0 : (lane & (G - 1)), row = lane / G;
+  const bool leader = sub == 0;
+  const int env0 = (int)blockIdx.x * EPW, env = env0 + row;
+  const bool active = env < D.n;
+  const int envc = active ? env : D.n - 1;
+  const size_t n = D.npad;
+  Rigid<T> S;
+  load_rigid<T>(D, envc, S);
+  T tgt[3], act[6];
+  ll_load_tail<T>(D, envc, tgt, act);
+  const bool resetting = active && do_reset && (!mask || mask[envc]);
+  if (resetting) {
+    int32_t episode = D.i[IF_EPISODE * n + env] + 1, tick = 0;
+    T wb[3], wa[3], wph;
+    ll_begin_episode<T, G>(P, D, env, episode, S, tick, tgt, wb, wa, wph);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) act[k] = (T)0;
+    if (leader) {
+      if (P.wind_mode != FW_WIND_OFF) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          if (ov.wind_base) D.r[(RF_WIND + k) * n + env] = (T)ov.wind_base[3 * (size_t)env + k];
+          if (ov.gust_amp) D.r[(RF_WIND + 3 + k) * n + env] = (T)ov.gust_amp[3 * (size_t)env + k];
+        }
+        if (ov.gust_phase) D.r[(RF_WIND + 6) * n + env] = (T)ov.gust_phase[env];
+      }
+      store_rigid<T>(D, env, S);
+      ll_store_tail<T>(D, env, tgt, act);
+      D.r[RF_EP_RETURN * n + env] = (T)0;
+      D.i[IF_STEP * n + env] = 0;
+      D.i[IF_TICK * n + env] = tick;
+      D.i[IF_EPISODE * n + env] = episode;
+      D.i[IF_FLAGS * n + env] = 0;
+      D.i[IF_NUM_REACHED * n + env] = 0;
+    }
+  }
+  if (obs) {
+    T psi, speed;
+    if (active && leader) ll_write_obs<T>(S, act, tgt, psi, speed, [&](int k, T v) { tile[row * ld + k] = v; });
+    __syncthreads();
+    flush_obs_tile<T>(tile, ld, obs, env0, EPW, D.n, Dobs);
+  }
+}
+
 // ======================================================================
 // host side
 // ======================================================================
@@ -1342,13 +1593,31 @@ int validate(const fw_config* c, std::string& msg) {
       if (!(c->gust_amp_enu_mps_range[i][0] <= c->gust_amp_enu_mps_range[i][1])) { snprintf(buf, sizeof buf, "Invalid gust_amp_enu_mps_range"); return fail(FW_EINVAL); }
     }
   }
-  if (c->task < FW_TASK_WAYPOINTS || c->task > FW_TASK_WAYPOINT_OBJLOCK) { snprintf(buf, sizeof buf, "unknown task %d", c->task); return fail(FW_EINVAL); }
+  if (c->task < FW_TASK_WAYPOINTS || c->task > FW_TASK_LOWLEVEL) { snprintf(buf, sizeof buf, "unknown task %d", c->task); return fail(FW_EINVAL); }
+  if (c->task == FW_TASK_LOWLEVEL) {
+    // fixedwing_lowlevel_env.py:32-33, 46, 137: numpy's uniform(low, high) needs low < high to be a range at all
+    if (!(c->lowlevel_speed_range[0] < c->lowlevel_speed_range[1])) {
+      snprintf(buf, sizeof buf, "target_speed_range must be (low, high) with low < high, got (%g, %g)", c->lowlevel_speed_range[0], c->lowlevel_speed_range[1]);
+      return fail(FW_EINVAL);
+    }
+    if (!(c->lowlevel_height_range[0] < c->lowlevel_height_range[1])) {
+      snprintf(buf, sizeof buf, "target_height_range must be (low, high) with low < high, got (%g, %g)", c->lowlevel_height_range[0], c->lowlevel_height_range[1]);
+      return fail(FW_EINVAL);
+    }
+    if (c->num_targets != 0) { snprintf(buf, sizeof buf, "the low-level task has no waypoints: num_targets must be 0, got %d", c->num_targets); return fail(FW_EINVAL); }
+    if (c->lowlevel_max_episode_steps <= 0) { snprintf(buf, sizeof buf, "lowlevel_max_episode_steps must be positive, got %d", c->lowlevel_max_episode_steps); return fail(FW_EINVAL); }
+    if (c->physics_hz != 240 || c->control_hz != 120 || c->agent_hz != 120) {
+      snprintf(buf, sizeof buf, "the low-level task steps one Aviary step per agent step: physics_hz 240, control_hz 120, agent_hz 120 (got %d, %d, %d)",
+               c->physics_hz, c->control_hz, c->agent_hz);
+      return fail(FW_EINVAL);
+    }
+  }
   if (c->dtype != FW_F64 && c->dtype != FW_F32) { snprintf(buf, sizeof buf, "unknown dtype %d", c->dtype); return fail(FW_EINVAL); }
   if (c->num_targets < 0 || c->num_targets > FW_MAX_TARGETS) { snprintf(buf, sizeof buf, "num_targets must be in [0,%d]", FW_MAX_TARGETS); return fail(FW_EINVAL); }
   if (c->task != FW_TASK_OBJLOCK && (c->context_length < 0 || c->context_length > FW_MAX_TARGETS + 1)) { snprintf(buf, sizeof buf, "bad context_length"); return fail(FW_EINVAL); }
   if (c->n_collision_pts < 0 || c->n_collision_pts > FW_MAX_COLLISION_PTS) { snprintf(buf, sizeof buf, "bad n_collision_pts"); return fail(FW_EINVAL); }
   if (c->num_obstacles < 0 || c->num_obstacles > FW_MAX_OBSTACLES) { snprintf(buf, sizeof buf, "bad num_obstacles"); return fail(FW_EINVAL); }
-  if (c->task != FW_TASK_WAYPOINTS && (c->camera_resolution < 0 || c->camera_resolution > 1024)) { snprintf(buf, sizeof buf, "camera_resolution must be in [1, 1024]"); return fail(FW_EINVAL); }
+  if ((c->task == FW_TASK_OBJLOCK || c->task == FW_TASK_WAYPOINT_OBJLOCK) && (c->camera_resolution < 0 || c->camera_resolution > 1024)) { snprintf(buf, sizeof buf, "camera_resolution must be in [1, 1024]"); return fail(FW_EINVAL); }
   if (c->physics_hz <= 0 || c->control_hz <= 0 || c->physics_hz % c->control_hz != 0) { snprintf(buf, sizeof buf, "physics_hz must be a multiple of control_hz"); return fail(FW_EINVAL); }
   if (!(c->mass > 0.0)) { snprintf(buf, sizeof buf, "mass must be > 0"); return fail(FW_EINVAL); }
   if (c->wind_coupling < FW_WIND_COUPLE_NONE || c->wind_coupling > FW_WIND_COUPLE_AIRSPEED) { snprintf(buf, sizeof buf, "bad wind_coupling"); return fail(FW_EINVAL); }
@@ -1356,6 +1625,7 @@ int validate(const fw_config* c, std::string& msg) {
 }
 
 int obs_dim_of(const fw_config* c) {
+  if (c->task == FW_TASK_LOWLEVEL) return 21;       // fixedwing_lowlevel_env.py:65-66
   int att = (c->angle_representation == 0 ? 12 : 13) + 4 + 6;
   if (c->task == FW_TASK_OBJLOCK) return att + 3 + FW_VISION_FEATS * FW_VISION_HIST + (c->duck_vision_no_deltas ? 0 : 4);
   return att + 3 * c->context_length;
@@ -1456,6 +1726,8 @@ bool build_params(const fw_config& c, uint64_t seed, int64_t env_offset, Params<
   P.warm_valid = (P.wind_coupling == FW_WIND_COUPLE_NONE && c.task == FW_TASK_WAYPOINTS) ? 1 : 0;   // (the duck cannot be in contact during warm-up: it spawns >= start height away only by chance; contacts there are ignored by the reference too)
   P.seed_lo = (uint32_t)seed; P.seed_hi = (uint32_t)(seed >> 32);
   P.env_offset = env_offset;
+  for (int k = 0; k < 2; ++k) { P.ll_speed[k] = c.lowlevel_speed_range[k]; P.ll_height[k] = c.lowlevel_height_range[k]; }
+  P.ll_max_steps = c.lowlevel_max_episode_steps;
   if (P.obs_dim > kMaxObs) { err = "obs_dim exceeds kMaxObs"; return false; }
   return true;
 }
@@ -1556,7 +1828,7 @@ inline int zrow_stride_of(int res) { return ((res + 31) / 32) * 32 + 8; }
 // row buffer of the analytic camera (1 / t of the nearest cylinder fragment per column), 8 envs x zrow_stride words
 template <typename T> size_t tile_bytes(const fw_env* h) {
   size_t b = sizeof(T) * (size_t)(kWave / h->lanes_per_env) * (size_t)(obs_dim_of(&h->cfg) + 1);
-  if (h->cfg.task != FW_TASK_WAYPOINTS && h->lanes_per_env == 8) {
+  if ((h->cfg.task == FW_TASK_OBJLOCK || h->cfg.task == FW_TASK_WAYPOINT_OBJLOCK) && h->lanes_per_env == 8) {
     const int res = h->cfg.camera_resolution > 0 ? h->cfg.camera_resolution : 128;
     b = std::max(b, cam_lds(sizeof(T), zrow_stride_of(res), res, h->cfg.num_obstacles > 0).total);   // camera map (fwsim_objlock.hpp): 2 KB without, 48 KB with cylinders at 480 columns
   }
@@ -1633,7 +1905,7 @@ int create_T(fw_env* h) {
   // shadow warm-up whenever the reset warm-up cannot be cached (wind acting on the dynamics, camera tasks)
   const bool cached = (h->cfg.task == FW_TASK_WAYPOINTS) &&
                       (h->cfg.wind_mode == FW_WIND_OFF || h->cfg.wind_coupling == FW_WIND_COUPLE_NONE);
-  h->shadow_on = (!cached && h->cfg.auto_reset && !getenv("FWSIM_NO_SHADOW")) ? 1 : 0;
+  h->shadow_on = (!cached && h->cfg.auto_reset && h->cfg.task != FW_TASK_LOWLEVEL && !getenv("FWSIM_NO_SHADOW")) ? 1 : 0;   // (low-level: no warm-up to hand off)
   // wind-free waypoints on the latency mapping: workers only pre-sample the next episode's waypoints (scenario_worker)
   if (h->cfg.task == FW_TASK_WAYPOINTS && h->cfg.wind_mode == FW_WIND_OFF && h->cfg.auto_reset && h->lanes_per_env == 8 &&
       !getenv("FWSIM_NO_SHADOW"))
@@ -1692,7 +1964,10 @@ int step_T(fw_env* h, const void* actions, void* obs, void* reward, uint8_t* ter
   dim3 step_grid = grid_of(h);
   const bool two_wave = g8 && h->capture_wave && h->cfg.task != FW_TASK_WAYPOINTS;
   if (h->shadow_on && !two_wave) step_grid.x *= 2;          // second half of the grid = shadow workers (two-wave workgroups: the capture wave is the worker)
-  if (h->cfg.task == FW_TASK_OBJLOCK) {
+  if (h->cfg.task == FW_TASK_LOWLEVEL) {
+    if (g8) { if (general) FW_LAUNCH_STEP((fw_step_kernel_ll<T, 8, true>)); else FW_LAUNCH_STEP((fw_step_kernel_ll<T, 8, false>)); }
+    else { if (general) FW_LAUNCH_STEP((fw_step_kernel_ll<T, 1, true>)); else FW_LAUNCH_STEP((fw_step_kernel_ll<T, 1, false>)); }
+  } else if (h->cfg.task == FW_TASK_OBJLOCK) {
     if (g8 && h->capture_wave) FW_LAUNCH_STEP_H((fw_step_kernel_obj_g8h<T, FW_TASK_OBJLOCK>));
     else if (g8) FW_LAUNCH_STEP((fw_step_kernel_obj_g8<T, FW_TASK_OBJLOCK>)); else FW_LAUNCH_STEP((fw_step_kernel_obj_g1<T, FW_TASK_OBJLOCK>));
   } else if (h->cfg.task == FW_TASK_WAYPOINT_OBJLOCK) {
@@ -1716,7 +1991,11 @@ int step_T(fw_env* h, const void* actions, void* obs, void* reward, uint8_t* ter
 template <typename T>
 int reset_T(fw_env* h, const uint8_t* mask, void* obs, int do_reset, hipStream_t st, ScenOv ov = ScenOv{}) {
   const bool g8 = h->lanes_per_env == 8;
-  if (h->cfg.task == FW_TASK_OBJLOCK) {
+  if (h->cfg.task == FW_TASK_LOWLEVEL) {
+#define FW_LAUNCH_RESET_LL(KERNEL) hipLaunchKernelGGL((KERNEL), grid_of(h), dim3(kWave), tile_bytes<T>(h), st, (const Params<T>*)h->params_dev, dev_state<T>(h), mask, (T*)obs, do_reset, ov)
+    if (g8) FW_LAUNCH_RESET_LL((fw_reset_kernel_ll<T, 8>)); else FW_LAUNCH_RESET_LL((fw_reset_kernel_ll<T, 1>));
+#undef FW_LAUNCH_RESET_LL
+  } else if (h->cfg.task == FW_TASK_OBJLOCK) {
     if (g8) FW_LAUNCH_RESET((fw_reset_kernel<T, 8, FW_TASK_OBJLOCK>)); else FW_LAUNCH_RESET((fw_reset_kernel<T, 1, FW_TASK_OBJLOCK>));
   } else if (h->cfg.task == FW_TASK_WAYPOINT_OBJLOCK) {
     if (g8) FW_LAUNCH_RESET((fw_reset_kernel<T, 8, FW_TASK_WAYPOINT_OBJLOCK>)); else FW_LAUNCH_RESET((fw_reset_kernel<T, 1, FW_TASK_WAYPOINT_OBJLOCK>));
@@ -1854,6 +2133,7 @@ int32_t fw_sizeof_config(void) { return (int32_t)sizeof(fw_config); }
 int32_t fw_abi_version(void) { return FW_ABI_VERSION; }
 int32_t fw_state_dim(void) { return FW_STATE_DIM; }
 int32_t fw_obs_dim(const fw_config* cfg) { return cfg ? obs_dim_of(cfg) : FW_EINVAL; }
+int32_t fw_act_dim(const fw_config* cfg) { return cfg ? (cfg->task == FW_TASK_LOWLEVEL ? 6 : 4) : FW_EINVAL; }
 
 int32_t fw_validate_config(const fw_config* cfg, char* msg, int32_t msg_len) {
   std::string m;
@@ -1887,7 +2167,8 @@ int32_t fw_create(const fw_config* cfg, int32_t num_envs, int32_t device, uint64
   // Camera tasks with obstacles stay on the 8-lane mapping at every size: there the cylinders are drawn by the wave from LDS
   // work lists; one lane per env tests every pixel against every cylinder (combined, 20 cylinders: 330 us vs 7.8 ms per
   // step at 32 768 envs).
-  const bool cyl_camera = cfg->task != FW_TASK_WAYPOINTS && cfg->num_obstacles > 0;
+  const bool camera = cfg->task == FW_TASK_OBJLOCK || cfg->task == FW_TASK_WAYPOINT_OBJLOCK;
+  const bool cyl_camera = camera && cfg->num_obstacles > 0;
   const bool wp = cfg->task == FW_TASK_WAYPOINTS, windy = wp && cfg->wind_mode != FW_WIND_OFF;
   const int one_wave_max = windy ? 6144 : 8192;                 // up to here the one-wave-per-SIMD build wins
   const int g8_max = !wp ? kG8MaxEnvs : (windy ? 12288 : 24576);   // ... and up to here the 8-lane mapping
@@ -1906,7 +2187,7 @@ int32_t fw_create(const fw_config* cfg, int32_t num_envs, int32_t device, uint64
   // (fwsim_objlock.hpp, "The capture wave").  Off by default: measured in round 5 it shortens the MEAN wave (ObjLock - 6 %,
   // combined - 8 %) but not the launch, which lasts as long as its slowest wave (CHANGELOG round 5).
   h->capture_wave = 0;
-  if (const char* ev = getenv("FWSIM_CAPTURE_WAVE")) { if (atoi(ev) != 0 && h->lanes_per_env == 8 && !wp) h->capture_wave = 1; }
+  if (const char* ev = getenv("FWSIM_CAPTURE_WAVE")) { if (atoi(ev) != 0 && h->lanes_per_env == 8 && camera) h->capture_wave = 1; }
   DeviceGuard g(device);
   rc = (cfg->dtype == FW_F64) ? create_T<double>(h) : create_T<float>(h);
   if (rc != FW_OK) {
@@ -1975,6 +2256,7 @@ int32_t fw_render(fw_handle h, int32_t res, float* out, void* hip_stream) {
   if (!h) return FW_EINVAL;
   if (!out) { h->err = "fw_render: out is NULL"; return FW_EINVAL; }
   if (h->cfg.task == FW_TASK_WAYPOINTS) { h->err = "fw_render: the waypoints task has no camera"; return FW_EUNSUPPORTED; }
+  if (h->cfg.task == FW_TASK_LOWLEVEL) { h->err = "fw_render: the low-level task has no camera"; return FW_EUNSUPPORTED; }
   if (res < 1 || res > 1024) { h->err = "fw_render: res must be in [1, 1024]"; return FW_EINVAL; }
   DeviceGuard g(h->device);
   const fw_config& c = h->cfg;
@@ -2292,6 +2574,10 @@ int64_t fw_collect_step_workspace_bytes(fw_handle h) { return h ? (int64_t)colle
 
 // checks and argument block shared by fw_collect_step and fw_collect_close
 static int32_t collect_fill(fw_handle h, const fw_collect_args* a, const char* who, bool close, CollectArgs& CA) {
+  if (h->cfg.task == FW_TASK_LOWLEVEL) {
+    h->err = std::string(who) + " serves the four-action tasks; the low-level task's six actions go through the policy in torch and fw_step";
+    return FW_EUNSUPPORTED;
+  }
   if (h->lanes_per_env != 8) {
     h->err = std::string(who) + " serves the 8-lanes-per-env mapping (what fw_create picks for waypoints up to 24576 envs per GPU, 12288 with wind, and "
              "for the camera tasks up to 16384 envs or at any size with obstacles); use fw_collect_act / fw_step / fw_collect_stats";

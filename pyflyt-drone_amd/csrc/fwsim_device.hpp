@@ -86,6 +86,9 @@ struct Params {
   int32_t has_noise;
   uint32_t seed_lo, seed_hi;
   int64_t env_offset;
+  // FW_TASK_LOWLEVEL (behind everything the other tasks read, so their kernels address Params exactly as before)
+  double ll_speed[2], ll_height[2];       // V_ref / h_ref ranges
+  int32_t ll_max_steps;                   // truncation step count
 };
 
 template <typename T>
@@ -295,7 +298,7 @@ template <int G> __device__ __forceinline__ bool group_any(bool pred) {
 }
 
 // ---- Philox4x32-10, identical counter/key convention to the spec in DESIGN.md ----
-enum { STREAM_SCENARIO = 0, STREAM_NOISE = 1 };
+enum { STREAM_SCENARIO = 0, STREAM_NOISE = 1, STREAM_LL_TARGET = 2 };   // STREAM_LL_TARGET: the low-level task's target, j = 0 psi, 1 h, 2 V
 enum { J_WIND_BASE = 0, J_WIND_AMP = 3, J_WIND_PHASE = 6, J_THETA = 8, J_PHI = 16, J_DIST = 24,
        J_DUCK_X = 32, J_DUCK_Y = 33, J_DUCK_YAW = 34, J_OBST = 40 };
 

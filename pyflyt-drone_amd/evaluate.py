@@ -102,7 +102,7 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
     cur_len = torch.zeros(n, dtype=torch.int64, device=env.device)
     res = EvalResult([], [])
     has_info = hasattr(venv, "info")
-    is_objlock = getattr(getattr(venv, "cfg", None), "task", K.FW_TASK_WAYPOINTS) != K.FW_TASK_WAYPOINTS
+    is_objlock = getattr(getattr(venv, "cfg", None), "task", K.FW_TASK_WAYPOINTS) in (K.FW_TASK_OBJLOCK, K.FW_TASK_WAYPOINT_OBJLOCK)
     obs = env.reset()
     steps = 0
     while (counts < targets).any():
@@ -184,7 +184,7 @@ class ReplayedEvaluation:
         self.venv, self.n, self.dev, self.targets = venv, n, dev, targets
         self.E = E = max(int(targets.max()), 1)
         self.has_info = hasattr(venv, "info")
-        self.is_objlock = getattr(getattr(venv, "cfg", None), "task", K.FW_TASK_WAYPOINTS) != K.FW_TASK_WAYPOINTS
+        self.is_objlock = getattr(getattr(venv, "cfg", None), "task", K.FW_TASK_WAYPOINTS) in (K.FW_TASK_OBJLOCK, K.FW_TASK_WAYPOINT_OBJLOCK)
         self.tg = torch.as_tensor(targets, device=dev)
         self.ar = torch.arange(n, device=dev)
         self.counts = torch.zeros(n, dtype=torch.int64, device=dev)
@@ -470,7 +470,7 @@ class EvalCallback:
                      ep_lengths=np.array(self.evaluations_length, dtype=object), **kw)
         mean_reward = getattr(r, "mean_reward_override", r.mean_reward)
         self.last_mean_reward = mean_reward
-        is_objlock = getattr(getattr(self.eval_env.venv, "cfg", None), "task", 0) != K.FW_TASK_WAYPOINTS
+        is_objlock = getattr(getattr(self.eval_env.venv, "cfg", None), "task", 0) in (K.FW_TASK_OBJLOCK, K.FW_TASK_WAYPOINT_OBJLOCK)
         self.last_scalars = r.scalars(self.num_targets_total, has_duck=is_objlock)
         self.last_scalars["time/total_timesteps"] = timesteps
         if self.verbose and writer:

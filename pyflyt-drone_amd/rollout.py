@@ -189,6 +189,7 @@ class VecNormalizeDevice:
         self.venv = venv
         self.device = venv.device
         self.num_envs, self.obs_dim = venv.num_envs, venv.obs_dim
+        self.act_dim = int(getattr(venv, "act_dim", 4))
         self.training, self.norm_obs, self.norm_reward = training, norm_obs, norm_reward
         self.clip_obs, self.clip_reward, self.gamma, self.epsilon = clip_obs, clip_reward, gamma, epsilon
         self.obs_rms = RunningMeanStd((self.obs_dim,), self.device)
@@ -754,7 +755,8 @@ class PPO:
             raise ValueError("detector must be 'none' or 'cnn'")
         if policy is None and cfg.detector == "cnn":
             policy = CnnDetectorPolicy(env.obs_dim, image_res=cfg.image_res, cnn_features=cfg.cnn_features)
-        self.policy = (policy or MlpPolicy(env.obs_dim)).to(self.device)
+        self.act_dim = int(getattr(env, "act_dim", 4))      # the env's action width (6 actuator commands on the low-level task)
+        self.policy = (policy or MlpPolicy(env.obs_dim, self.act_dim)).to(self.device)
         self._img = bool(getattr(self.policy, "uses_image", False))
         if self._img and not hasattr(env.venv, "render_tensor"):
             raise ValueError("a policy with a CNN front end needs an env with render_tensor() (a camera task on the device)")
@@ -817,7 +819,7 @@ class PPO:
         T, N, D = cfg.n_steps, env.num_envs, env.obs_dim
         f32 = dict(dtype=torch.float32, device=self.device)
         self.buf_obs = torch.zeros((T, N, D), **f32)
-        self.buf_act = torch.zeros((T, N, 4), **f32)
+        self.buf_act = torch.zeros((T, N, self.act_dim), **f32)
         self.buf_rew = torch.zeros((T, N), **f32)
         self.buf_start = torch.zeros((T, N), **f32)
         self.buf_val = torch.zeros((T, N), **f32)
@@ -1143,7 +1145,7 @@ class PPO:
     def _update_buffers(self):
         """``(obs, act, old_logp, adv, ret)`` flattened to [B, ...] as the update walks them: the rank's own rollout, or --
         replicated update of a sharded job -- the rollouts of ALL ranks, all-gathered once (obs / actions / log-probs /
-        advantages / returns packed into one [T, N, D + 7] float32 tensor: one collective of ~9 MB per 65 536 samples) and
+        advantages / returns packed into one [T, N, D + A + 3] float32 tensor, A = the action width: one collective of ~9 MB per 65 536 samples) and
         laid out exactly like the buffer of one big job over the concatenated envs ([T, W * N], rank-major env order)."""
         T, N, D = self.cfg.n_steps, self.env.num_envs, self.env.obs_dim
         if not self._replicated:
@@ -1154,19 +1156,20 @@ class PPO:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         t0 = time.perf_counter()
-        g = all_gather_cat(pack, dim=1)                          # [T, W * N, D + 7]
+        A = self.act_dim
+        g = all_gather_cat(pack, dim=1)                          # [T, W * N, D + A + 3]
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         self.allgather_ms = (time.perf_counter() - t0) * 1e3
         self.allgather_bytes = pack.numel() * 4
         B = g.shape[0] * g.shape[1]
-        g = g.reshape(B, D + 7)
+        g = g.reshape(B, D + A + 3)
         if self._gathered is None:                               # persistent: a captured update graph holds these addresses
             f32 = dict(dtype=torch.float32, device=self.device)
-            self._gathered = (torch.empty((B, D), **f32), torch.empty((B, 4), **f32), torch.empty(B, **f32),
+            self._gathered = (torch.empty((B, D), **f32), torch.empty((B, A), **f32), torch.empty(B, **f32),
                               torch.empty(B, **f32), torch.empty(B, **f32))
         o, a, lp, ad, rt = self._gathered
-        o.copy_(g[:, :D]); a.copy_(g[:, D:D + 4]); lp.copy_(g[:, D + 4]); ad.copy_(g[:, D + 5]); rt.copy_(g[:, D + 6])
+        o.copy_(g[:, :D]); a.copy_(g[:, D:D + A]); lp.copy_(g[:, D + A]); ad.copy_(g[:, D + A + 1]); rt.copy_(g[:, D + A + 2])
         return self._gathered
 
     def replica_checksum(self) -> float:

@@ -113,11 +113,12 @@ class FixedwingVecEnv(_VecEnvBase):
         self.global_env_offset = int(global_env_offset)
         self.seed_value = int(seed)
         self.obs_dim = K.obs_dim(cfg)
+        self.act_dim = K.act_dim(cfg)          # 6 actuator commands (low-level task), [roll, pitch, yaw, thrust] otherwise
         self.np_dtype = np.float64 if cfg.dtype == K.FW_F64 else np.float32
         self.torch_dtype = torch.float64 if cfg.dtype == K.FW_F64 else torch.float32
         self.render_mode = None
         _VecEnvBase.__init__(self, self.num_envs, Box(-np.inf, np.inf, (self.obs_dim,), self.np_dtype),
-                             Box(-1.0, 1.0, (4,), self.np_dtype))
+                             Box(-1.0, 1.0, (self.act_dim,), self.np_dtype))
 
         h = C.c_void_p()
         rc = _lib.lib().fw_create(C.byref(self.cfg), self.num_envs, int(dev.index), int(seed) & (2**64 - 1),
@@ -137,7 +138,7 @@ class FixedwingVecEnv(_VecEnvBase):
         self.truncated = torch.zeros((n,), dtype=torch.uint8, **kw)
         self.terminal_obs = torch.zeros((n, d), dtype=self.torch_dtype, **kw)
         self.info = torch.zeros((n, K.FW_INFO_DIM), dtype=torch.int32, **kw)
-        self._actions_dev = torch.zeros((n, 4), dtype=self.torch_dtype, **kw)
+        self._actions_dev = torch.zeros((n, self.act_dim), dtype=self.torch_dtype, **kw)
         self._pending = False
 
     # ------------------------------------------------------------------ device fast path
@@ -159,14 +160,14 @@ class FixedwingVecEnv(_VecEnvBase):
         return self.obs
 
     def step_tensor(self, actions: torch.Tensor):
-        """One agent step.  ``actions``: device tensor [N,4] of the env dtype in [-1,1]
+        """One agent step.  ``actions``: device tensor [N, act_dim] of the env dtype in [-1,1]
         (the caller clips, as SB3's collector does).  Returns views of the env-owned
         output tensors ``(obs, rewards, terminated, truncated)``; ``terminal_obs`` and
         ``info`` are attributes.  No host synchronisation."""
         if actions.device != self.device or actions.dtype != self.torch_dtype or not actions.is_contiguous():
             actions = actions.to(device=self.device, dtype=self.torch_dtype).contiguous()
-        if actions.shape != (self.num_envs, 4):
-            raise ValueError(f"actions must have shape ({self.num_envs}, 4), got {tuple(actions.shape)}")
+        if actions.shape != (self.num_envs, self.act_dim):
+            raise ValueError(f"actions must have shape ({self.num_envs}, {self.act_dim}), got {tuple(actions.shape)}")
         rc = _lib.lib().fw_step(self._h, _devptr(actions), _devptr(self.obs), _devptr(self.rewards),
                                 _devptr(self.terminated), _devptr(self.truncated), _devptr(self.terminal_obs),
                                 _devptr(self.info), self._stream())
@@ -205,7 +206,7 @@ class FixedwingVecEnv(_VecEnvBase):
         return a if a.dtype == want else a.astype(want)
 
     def step_async(self, actions: np.ndarray) -> None:
-        a = torch.as_tensor(np.asarray(actions), dtype=self.torch_dtype).reshape(self.num_envs, 4)
+        a = torch.as_tensor(np.asarray(actions), dtype=self.torch_dtype).reshape(self.num_envs, self.act_dim)
         self._actions_dev.copy_(a, non_blocking=False)
         self.step_tensor(self._actions_dev)
         self._pending = True
@@ -222,6 +223,8 @@ class FixedwingVecEnv(_VecEnvBase):
         dones = term | trunc
         infos: List[dict] = []
         tobs = self._np_obs(self.terminal_obs) if dones.any() else None
+        if self.cfg.task == K.FW_TASK_LOWLEVEL:
+            return obs, rewards, dones, self._lowlevel_infos(obs, tobs, term, trunc, dones, info)
         for i in range(self.num_envs):
             d = {
                 "out_of_bounds": bool(info[i, K.INFO_OUT_OF_BOUNDS]),
@@ -238,6 +241,20 @@ class FixedwingVecEnv(_VecEnvBase):
                 d["episode_length"] = int(info[i, K.INFO_EP_LEN])
             infos.append(d)
         return obs, rewards, dones, infos
+
+    def _lowlevel_infos(self, obs, tobs, term, trunc, dones, info) -> List[dict]:
+        """``{"target": [psi_ref, h_ref, V_ref]}`` of the episode the step belonged to (fixedwing_lowlevel_env.py:140): the last
+        three observation values -- of the terminal observation where the env was auto-reset -- plus SB3's worker keys."""
+        infos: List[dict] = []
+        for i in range(self.num_envs):
+            ended = dones[i] and self.cfg.auto_reset
+            d = {"target": (tobs[i] if ended else obs[i])[18:21].astype(np.float64),
+                 "TimeLimit.truncated": bool(trunc[i] and not term[i])}
+            if ended:
+                d["terminal_observation"] = tobs[i].copy()
+                d["episode_length"] = int(info[i, K.INFO_EP_LEN])
+            infos.append(d)
+        return infos
 
     def step(self, actions: np.ndarray):
         self.step_async(actions)
@@ -385,3 +402,20 @@ class FixedwingWaypointObjLockVecEnv(FixedwingVecEnv):
         cfg = K.waypoint_objlock_config_from_reference_kwargs(dtype=dtype, motor_noise=motor_noise,
                                                               context_length=context_length, **env_kwargs)
         super().__init__(cfg, num_envs, device=device, seed=seed, global_env_offset=global_env_offset)
+
+
+class FixedwingLowLevelVecEnv(FixedwingVecEnv):
+    """``FixedwingLowLevelEnv(render_mode, wind_config)`` vectorised (envs/fixedwing_envs/fixedwing_lowlevel_env.py, constructed at
+    train/train_lowlevel_cmd.py:54-61): six actuator commands in [-1, 1], a 21-value float64 observation (attitude, velocity,
+    position, previous action, target) and ``infos[i]["target"]``.  See ``config.lowlevel_config``."""
+
+    def __init__(self, num_envs: int, *, render_mode=None, wind_config: Optional[dict] = None, dtype: str = "float64",
+                 motor_noise: bool = True, device=None, seed: int = 0, global_env_offset: int = 0):
+        cfg = K.lowlevel_config_from_reference_kwargs(render_mode=render_mode, wind_config=wind_config, dtype=dtype,
+                                                      motor_noise=motor_noise)
+        super().__init__(cfg, num_envs, device=device, seed=seed, global_env_offset=global_env_offset)
+
+    def reset(self) -> np.ndarray:
+        obs = super().reset()
+        self.reset_infos = [{"target": obs[i, 18:21].astype(np.float64)} for i in range(self.num_envs)]      # (:94)
+        return obs
