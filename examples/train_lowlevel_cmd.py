@@ -4,7 +4,8 @@ The low-level controller of the hierarchical design: six actuator commands track
 episode (envs/fixedwing_envs/fixedwing_lowlevel_env.py).  Same PPO hyper-parameters (lr 3e-4, batch 64, 10 epochs, gamma 0.99,
 lambda 0.95, clip 0.2, no entropy bonus, vf 0.5, max-grad-norm 0.5) and VecNormalize(norm_obs, norm_reward, clip_obs=10); the env
 count goes from 32 to thousands and n_steps shrinks so that one update still sees 32 x 2048 = 65 536 samples.  Six actions: the
-policy update runs on the torch path (the fused collector / update kernels are written for four).
+policy update runs on the torch path by default; --fused_learner puts it on the fused six-action learner (fw_ppo_update_a and the
+three-launch collector fw_collect_act_a -> fw_step -> fw_collect_stats, PPOConfig.fused_six_actions).
 
     python examples/train_lowlevel_cmd.py --total_timesteps 2000000 --num_envs 4096 --out runs/lowlevel
 """
@@ -30,6 +31,7 @@ def main():
     ap.add_argument("--total_timesteps", type=int, default=None)
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--out", type=str, default="runs/lowlevel_ppo")
+    ap.add_argument("--fused_learner", action="store_true", help="the fused six-action update / collector kernels instead of the torch path")
     a = ap.parse_args()
     cfg = TRAIN_CONFIG
     model_dir, log_dir = os.path.join(a.out, "models"), os.path.join(a.out, "logs")
@@ -48,7 +50,8 @@ def main():
     n_steps = R.n_steps_for(cfg["samples_per_update"], a.num_envs, world)      # holds the samples per update: n_steps ~ 1 / (envs x world)
     model = R.PPO(env, R.PPOConfig(n_steps=n_steps, batch_size=cfg["batch_size"], n_epochs=cfg["n_epochs"], learning_rate=cfg["learning_rate"],
                                    gamma=cfg["gamma"], gae_lambda=cfg["gae_lambda"], clip_range=cfg["clip_range"], ent_coef=cfg["ent_coef"],
-                                   vf_coef=cfg["vf_coef"], max_grad_norm=cfg["max_grad_norm"], seed=cfg["seed"]))
+                                   vf_coef=cfg["vf_coef"], max_grad_norm=cfg["max_grad_norm"], seed=cfg["seed"],
+                                   fused_six_actions=a.fused_learner))
     if a.pretrained_model:
         checkpoint.set_parameters(a.pretrained_model, model)
     ev = evaluate.EvalCallback(eval_env, n_eval_episodes=max(cfg["n_eval_episodes"], 16), eval_freq=max(10000 // a.num_envs, 1) * 50,

@@ -466,6 +466,24 @@ int32_t fw_ppo_update(float* params, float* mom_m, float* mom_v, const float* ob
                       int32_t n_minibatches, int32_t batch_size, int32_t obs_dim, const fw_ppo_hyper* hyper,
                       float* loss_acc, void* workspace, int64_t workspace_bytes, void* hip_stream);
 int32_t fw_ppo_update_status(const void* workspace, int64_t workspace_bytes, uint32_t* status_out, uint32_t* paths_out, void* hip_stream);
+/* The same learner for a policy head of act_dim actions: act_dim = 4 runs exactly what the entry points above run; act_dim = 6 (the
+ * low-level control task's six actuator commands) runs a six-action instantiation of the same kernel, every cut and exchange form
+ * included.  Any other act_dim: FW_EINVAL (fw_last_error says why).  With A = act_dim:
+ *   flat layout   for net in (pi, vf): W1[Dp][64] b1[64] W2[64][64] b2[64] Wo[64][KO] bo[KO] (KO = A, 1), then log_std[A]
+ *                 -- fw_ppo_param_count_a(obs_dim, act_dim) elements;
+ *   moments       fw_ppo_moment_count_a(act_dim) slots each, mapped by fw_ppo_moment_map_a (A = 6 adds one slot row: the policy
+ *                 head's 64 x 6 weights are two per-thread elements of 256 threads);
+ *   act           [S, A]; the packed rows of the workspace are (obs_dim rounded up to 4) + 4 ceil(A / 4) + 4 floats wide, which
+ *                 fw_ppo_update_workspace_bytes_a accounts for.
+ * The size and layout functions return FW_EINVAL (negative) for bad arguments. */
+int32_t fw_ppo_param_count_a(int32_t obs_dim, int32_t act_dim);
+int32_t fw_ppo_moment_count_a(int32_t act_dim);
+int32_t fw_ppo_moment_map_a(int32_t obs_dim, int32_t act_dim, int32_t* flat_index_of_slot /* host, [fw_ppo_moment_count_a(act_dim)] */);
+int64_t fw_ppo_update_workspace_bytes_a(int32_t n_minibatches, int32_t batch_size, int32_t obs_dim, int32_t act_dim);
+int32_t fw_ppo_update_a(float* params, float* mom_m, float* mom_v, const float* obs, const float* act,
+                        const float* old_logp, const float* adv, const float* ret, const int32_t* perm,
+                        int32_t n_minibatches, int32_t batch_size, int32_t obs_dim, int32_t act_dim, const fw_ppo_hyper* hyper,
+                        float* loss_acc, void* workspace, int64_t workspace_bytes, void* hip_stream);
 
 /* Rollout collection between two env steps (SB3 OnPolicyAlgorithm.collect_rollouts + VecNormalize reward path,
  * train/train_Fixedwing_Waypoints_v3.py:260,293-310), for the same MlpPolicy / flat parameter image as fw_ppo_update.
@@ -511,6 +529,19 @@ int32_t fw_collect_act(const float* params, const void* raw_obs, int32_t obs_is_
                        const void* prev_reward, const uint8_t* prev_terminated, const uint8_t* prev_truncated, const void* prev_terminal_obs,
                        const double* ret_var, int32_t norm_reward, float clip_reward, float eps_reward, float gamma, float* rew_out,
                        float* start_out, void* hip_stream);
+/* fw_policy_act_a / fw_collect_act_a: the same for a flat image of the act_dim layout above (act_dim 4: exactly fw_policy_act /
+ * fw_collect_act; 6: act_raw and act_env are [N, 6]).  Sampling with six actions: components 0-3 are the four-action draw bit for bit,
+ * components 4, 5 come from a second Philox4x32-10 block of the same key (seed) and counter except bit 31 of counter word 3, through
+ * the same Box-Muller map.  fw_collect_step / fw_collect_close stay four-action: they refuse the low-level task's handle. */
+int32_t fw_policy_act_a(const float* params, const float* obs, int32_t N, int32_t obs_dim, int32_t act_dim, int32_t nets, int32_t deterministic,
+                        const uint64_t* rng, int64_t env_offset, float* obs_copy, float* act_raw, void* act_env,
+                        int32_t act_is_f64, float* logp, float* value, void* hip_stream);
+int32_t fw_collect_act_a(const float* params, const void* raw_obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, int32_t act_dim,
+                         const double* obs_mean, const double* obs_var, float clip_obs, float eps_obs, int32_t nets, int32_t deterministic,
+                         const uint64_t* rng, int64_t env_offset, float* obs_copy, float* act_raw, void* act_env, int32_t act_is_f64, float* logp,
+                         float* value, const void* prev_reward, const uint8_t* prev_terminated, const uint8_t* prev_truncated,
+                         const void* prev_terminal_obs, const double* ret_var, int32_t norm_reward, float clip_reward, float eps_reward,
+                         float gamma, float* rew_out, float* start_out, void* hip_stream);
 int64_t fw_collect_stats_workspace_bytes(int32_t D);
 int32_t fw_collect_stats(const void* obs, int32_t obs_is_f64, int32_t N, int32_t D, double* obs_mean, double* obs_var, double* obs_count,
                          int32_t update_obs, const void* reward, int32_t rew_is_f64, const uint8_t* terminated, const uint8_t* truncated,

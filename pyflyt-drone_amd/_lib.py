@@ -21,6 +21,8 @@ EXPORTS = (
     "fw_sizeof_config", "fw_abi_version", "fw_state_dim", "fw_obs_dim", "fw_act_dim", "fw_validate_config", "fw_create", "fw_reset",
     "fw_step", "fw_seed", "fw_get_state", "fw_set_state", "fw_get_counters", "fw_observe", "fw_render", "fw_num_envs", "fw_lanes_per_env", "fw_capture_wave", "fw_last_error",
     "fw_destroy", "fw_gae", "fw_eval_track", "fw_normalize_obs", "fw_normalize_obs_workspace_bytes", "fw_ppo_update_workspace_bytes", "fw_ppo_param_count", "fw_ppo_moment_count", "fw_ppo_moment_map", "fw_ppo_update", "fw_policy_act", "fw_policy_terminal_value", "fw_rollout_post", "fw_collect_act", "fw_collect_stats", "fw_collect_stats_workspace_bytes", "fw_collect_step", "fw_collect_finish", "fw_collect_step_workspace_bytes", "fw_collect_workspace_init", "fw_collect_close", "fw_collect_status", "fw_ppo_update_status",
+    "fw_ppo_param_count_a", "fw_ppo_moment_count_a", "fw_ppo_moment_map_a", "fw_ppo_update_workspace_bytes_a", "fw_ppo_update_a",
+    "fw_policy_act_a", "fw_collect_act_a",
 )
 
 
@@ -130,6 +132,18 @@ def lib() -> C.CDLL:
         L.fw_collect_close.restype = i32; L.fw_collect_close.argtypes = [vp, vp, vp, vp]
         L.fw_collect_status.restype = i32; L.fw_collect_status.argtypes = [vp, vp, i64, vp, vp]
         L.fw_ppo_update_status.restype = i32; L.fw_ppo_update_status.argtypes = [vp, i64, vp, vp, vp]
+        # the *_a forms: the same with the action width (4 or 6) after obs_dim
+        L.fw_ppo_param_count_a.restype = i32; L.fw_ppo_param_count_a.argtypes = [i32, i32]
+        L.fw_ppo_moment_count_a.restype = i32; L.fw_ppo_moment_count_a.argtypes = [i32]
+        L.fw_ppo_moment_map_a.restype = i32; L.fw_ppo_moment_map_a.argtypes = [i32, i32, vp]
+        L.fw_ppo_update_workspace_bytes_a.restype = i64; L.fw_ppo_update_workspace_bytes_a.argtypes = [i32, i32, i32, i32]
+        L.fw_ppo_update_a.restype = i32
+        L.fw_ppo_update_a.argtypes = [vp] * 9 + [i32, i32, i32, i32, vp, vp, vp, i64, vp]
+        L.fw_policy_act_a.restype = i32
+        L.fw_policy_act_a.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
+        L.fw_collect_act_a.restype = i32
+        L.fw_collect_act_a.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, f32, f32, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp,
+                                       vp, vp, vp, vp, vp, i32, f32, f32, f32, vp, vp, vp]
         L.fw_rollout_post.restype = i32
         L.fw_rollout_post.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.c_double, C.c_float, C.c_float, vp, vp, vp, vp, vp]
         if L.fw_abi_version() != K.FW_ABI_VERSION:

@@ -1791,7 +1791,7 @@ int device_of(const void* p) {
 }
 // Opt an LDS-resident learner kernel into `bytes` of dynamic LDS: done when a device first sees a size larger than any
 // before (i.e. on the first call per observation width), never again on the launch path.
-int ensure_learner_lds(int dev, int which /*0: fw_ppo_update, 1: fw_policy_act*/, size_t bytes);
+int ensure_learner_lds(int dev, int which /*0: fw_ppo_update, 1: fw_policy_act, 2 / 3: their six-action kernels*/, size_t bytes);
 
 template <typename T> size_t tile_bytes(const fw_env* h);
 template <typename T> size_t step_lds_bytes(const fw_env* h);
@@ -2059,7 +2059,7 @@ int set_state_T(fw_env* h, const double* in) {
 
 namespace {
 int ensure_learner_lds(int dev, int which, size_t bytes) {
-  static size_t have[64][2] = {};
+  static size_t have[64][4] = {};
   if (dev < 0 || dev >= 64) { g_err = "device index out of range"; return FW_EINVAL; }
   if (bytes <= have[dev][which]) return FW_OK;
   if (which == 0) {
@@ -2067,8 +2067,14 @@ int ensure_learner_lds(int dev, int which, size_t bytes) {
                          (const void*)fw_ppo_update_kernel<64, 4>, (const void*)fw_ppo_update_kernel<32, 4>, (const void*)fw_ppo_update_kernel<16, 4>,
                          (const void*)fw_ppo_update_kernel<64, 8>, (const void*)fw_ppo_update_kernel<32, 8>, (const void*)fw_ppo_update_kernel<16, 8>};
     for (const void* fn : fns) HIP_TRY((fw_env*)nullptr, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  } else if (which == 2) {
+    const void* fns[] = {(const void*)fw_ppo_update_kernel_a6<64, 0>, (const void*)fw_ppo_update_kernel_a6<32, 0>, (const void*)fw_ppo_update_kernel_a6<16, 0>,
+                         (const void*)fw_ppo_update_kernel_a6<64, 4>, (const void*)fw_ppo_update_kernel_a6<32, 4>, (const void*)fw_ppo_update_kernel_a6<16, 4>,
+                         (const void*)fw_ppo_update_kernel_a6<64, 8>, (const void*)fw_ppo_update_kernel_a6<32, 8>, (const void*)fw_ppo_update_kernel_a6<16, 8>};
+    for (const void* fn : fns) HIP_TRY((fw_env*)nullptr, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   } else {
-    HIP_TRY((fw_env*)nullptr, hipFuncSetAttribute((const void*)fw_policy_act_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    const void* fn = which == 3 ? (const void*)fw_policy_act_kernel<6> : (const void*)fw_policy_act_kernel<4>;
+    HIP_TRY((fw_env*)nullptr, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
   }
   have[dev][which] = bytes;
   return FW_OK;
@@ -2427,6 +2433,29 @@ int32_t fw_ppo_moment_map(int32_t obs_dim, int32_t* flat_index_of_slot) {
   for (int i = kPMomentSlots; i < 2 * kPMomentSlots; ++i) flat_index_of_slot[i] = -1;
   return FW_OK;
 }
+// the action width of the *_a entry points: 4 (the entry points above) or 6 (the low-level control task)
+static bool act_dim_ok(int32_t act_dim, const char* who) {
+  if (act_dim == 4 || act_dim == 6) return true;
+  g_err = std::string(who) + ": act_dim must be 4 or 6 (got " + std::to_string(act_dim) + ")";
+  return false;
+}
+int32_t fw_ppo_param_count_a(int32_t obs_dim, int32_t act_dim) {
+  if (!act_dim_ok(act_dim, "fw_ppo_param_count_a")) return FW_EINVAL;
+  if (obs_dim <= 0) { g_err = "fw_ppo_param_count_a: obs_dim must be positive"; return FW_EINVAL; }
+  return ppo_total_params_a((obs_dim + 1) & ~1, act_dim);
+}
+int32_t fw_ppo_moment_count_a(int32_t act_dim) {
+  if (!act_dim_ok(act_dim, "fw_ppo_moment_count_a")) return FW_EINVAL;
+  return 2 * ppo_moment_slots(act_dim);      // (the second half unused, as for fw_ppo_moment_count)
+}
+int32_t fw_ppo_moment_map_a(int32_t obs_dim, int32_t act_dim, int32_t* flat_index_of_slot) {
+  if (!act_dim_ok(act_dim, "fw_ppo_moment_map_a")) return FW_EINVAL;
+  if (obs_dim <= 0 || obs_dim > 64 || !flat_index_of_slot) { g_err = "fw_ppo_moment_map_a: bad arguments"; return FW_EINVAL; }
+  const int ns = ppo_moment_slots(act_dim);
+  ppo_moment_map(obs_dim, flat_index_of_slot, act_dim);
+  for (int i = ns; i < 2 * ns; ++i) flat_index_of_slot[i] = -1;
+  return FW_OK;
+}
 
 // Dev knob: FWSIM_SPIN_LOG2=k bounds every in-grid wait (fw_collect_step, fw_ppo_update) to 2^k polls instead of its default --
 // tests use it to provoke the timeout paths and assert that the status words surface on the host side.
@@ -2442,35 +2471,46 @@ static long long spin_budget(long long dflt) {
 static constexpr size_t kPpoWsXch = 65536;
 static_assert(kPpoWords * sizeof(unsigned long long) <= kPpoWsXch, "exchange words");
 static constexpr size_t kPpoWsGx = sizeof(float) * (4 * kPMaxSplit * (size_t)kPGxSlots);      // [parity][net][part]: gradient partial + weight share
+static size_t ppo_ws_gx(int act_dim) { return sizeof(float) * (4 * kPMaxSplit * (size_t)ppo_gx_slots(act_dim)); }      // (4: kPpoWsGx)
 int64_t fw_ppo_update_workspace_bytes(int32_t n_minibatches, int32_t batch_size, int32_t obs_dim) {
   if (n_minibatches <= 0 || batch_size <= 0 || obs_dim <= 0 || obs_dim > 64) return FW_EINVAL;
   return (int64_t)(kPpoWsXch + kPpoWsGx + sizeof(float) * (size_t)n_minibatches * (size_t)batch_size * (size_t)ppo_pack_width(obs_dim));
 }
+int64_t fw_ppo_update_workspace_bytes_a(int32_t n_minibatches, int32_t batch_size, int32_t obs_dim, int32_t act_dim) {
+  if (!act_dim_ok(act_dim, "fw_ppo_update_workspace_bytes_a")) return FW_EINVAL;
+  if (n_minibatches <= 0 || batch_size <= 0 || obs_dim <= 0 || obs_dim > 64) { g_err = "fw_ppo_update_workspace_bytes_a: bad arguments"; return FW_EINVAL; }
+  return (int64_t)(kPpoWsXch + ppo_ws_gx(act_dim) + sizeof(float) * (size_t)n_minibatches * (size_t)batch_size * (size_t)ppo_pack_width(obs_dim, act_dim));
+}
 
-int32_t fw_ppo_update(float* params, float* mom_m, float* mom_v, const float* obs, const float* act, const float* old_logp,
-                      const float* adv, const float* ret, const int32_t* perm, int32_t n_minibatches, int32_t batch_size,
-                      int32_t obs_dim, const fw_ppo_hyper* hyper, float* loss_acc, void* workspace, int64_t workspace_bytes,
-                      void* hip_stream) {
+// fw_ppo_update and fw_ppo_update_a (who: the entry point's name, for the messages)
+static int32_t ppo_update(float* params, float* mom_m, float* mom_v, const float* obs, const float* act, const float* old_logp,
+                          const float* adv, const float* ret, const int32_t* perm, int32_t n_minibatches, int32_t batch_size,
+                          int32_t obs_dim, int32_t act_dim, const fw_ppo_hyper* hyper, float* loss_acc, void* workspace, int64_t workspace_bytes,
+                          void* hip_stream, const char* who) {
   static_assert(sizeof(fw_ppo_hyper) == sizeof(PpoHyper), "fw_ppo_hyper layout");
+  const std::string w = who;
   if (!params || !mom_m || !mom_v || !obs || !act || !old_logp || !adv || !ret || !perm || !hyper || n_minibatches <= 0) {
-    g_err = "fw_ppo_update: bad arguments"; return FW_EINVAL;
+    g_err = w + ": bad arguments"; return FW_EINVAL;
   }
-  if (batch_size <= 0 || batch_size % 16 != 0) { g_err = "fw_ppo_update: batch_size must be a multiple of 16"; return FW_EINVAL; }
-  if (obs_dim <= 0 || obs_dim > 64) { g_err = "fw_ppo_update: obs_dim must be in [1, 64]"; return FW_EINVAL; }
-  if (!workspace || workspace_bytes < fw_ppo_update_workspace_bytes(n_minibatches, batch_size, obs_dim)) {
-    g_err = "fw_ppo_update: workspace smaller than fw_ppo_update_workspace_bytes(n_minibatches, batch_size, obs_dim)"; return FW_EINVAL;
+  if (batch_size <= 0 || batch_size % 16 != 0) { g_err = w + ": batch_size must be a multiple of 16"; return FW_EINVAL; }
+  if (obs_dim <= 0 || obs_dim > 64) { g_err = w + ": obs_dim must be in [1, 64]"; return FW_EINVAL; }
+  const bool a6 = act_dim == 6;
+  if (!workspace || workspace_bytes < fw_ppo_update_workspace_bytes_a(n_minibatches, batch_size, obs_dim, act_dim)) {
+    g_err = w + (a6 ? ": workspace smaller than fw_ppo_update_workspace_bytes_a(n_minibatches, batch_size, obs_dim, act_dim)"
+                    : ": workspace smaller than fw_ppo_update_workspace_bytes(n_minibatches, batch_size, obs_dim)");
+    return FW_EINVAL;
   }
-  const size_t lds = ppo_lds_bytes(obs_dim);
-  if (lds > 160 * 1024) { g_err = "fw_ppo_update: networks do not fit the 160 KB of LDS"; return FW_EINVAL; }
+  const size_t lds = ppo_lds_bytes(obs_dim, act_dim);
+  if (lds > 160 * 1024) { g_err = w + ": networks do not fit the 160 KB of LDS"; return FW_EINVAL; }
   hipStream_t st = (hipStream_t)hip_stream;
   const int dev = device_of(params);
   DeviceGuard g(dev);
-  int rc = ensure_learner_lds(dev, 0, lds);
+  int rc = ensure_learner_lds(dev, a6 ? 2 : 0, lds);
   if (rc != FW_OK) return rc;
   // everything the blocks exchange lives in the caller's workspace: two learners (or two streams) never share a word
   unsigned long long* xch = (unsigned long long*)workspace;
   float* gx = (float*)((char*)workspace + kPpoWsXch);
-  float* packed = (float*)((char*)workspace + kPpoWsXch + kPpoWsGx);
+  float* packed = (float*)((char*)workspace + kPpoWsXch + ppo_ws_gx(act_dim));
   HIP_TRY((fw_env*)nullptr, hipMemsetAsync(xch, 0, kPpoWords * sizeof(unsigned long long), st));
   PpoArgs A;
   A.params = params; A.mom_m = mom_m; A.mom_v = mom_v; A.packed = packed;
@@ -2485,7 +2525,8 @@ int32_t fw_ppo_update(float* params, float* mom_m, float* mom_v, const float* ob
   PpoPackArgs P;
   P.obs = obs; P.act = act; P.old_logp = old_logp; P.adv = adv; P.ret = ret; P.perm = perm; P.B = batch_size; P.D = obs_dim;
   P.norm_adv = A.H.norm_adv; P.adv_mean = A.H.adv_mean; P.adv_std = A.H.adv_std; P.out = packed;
-  hipLaunchKernelGGL(fw_ppo_pack_kernel, dim3(n_minibatches), dim3(256), 0, st, P);
+  if (a6) hipLaunchKernelGGL(fw_ppo_pack_kernel_a6, dim3(n_minibatches), dim3(256), 0, st, P);
+  else hipLaunchKernelGGL(fw_ppo_pack_kernel, dim3(n_minibatches), dim3(256), 0, st, P);
   // four / eight blocks per network: gradient tiles by reduce-scatter, updated weights by all-gather (FWSIM_PPO_RS=0: all-to-all, as for two
   // blocks -- written for up to four, so the cut is then chosen among round 4's)
   bool rs_env = true;
@@ -2495,17 +2536,33 @@ int32_t fw_ppo_update(float* params, float* mom_m, float* mom_v, const float* ob
     int ch = 0, ns = 0;
     if (sscanf(e, "%dx%d", &ch, &ns) == 2 && (ch == 16 || ch == 32 || ch == 64) && (ns == 1 || ns == 2 || ns == 4 || (ns == 8 && rs_env)) && batch_size % ch == 0 && batch_size / ch >= ns) {
       cut.ch = ch; cut.nsplit = ns;
-    } else { g_err = "fw_ppo_update: FWSIM_PPO_SPLIT must be CHxN with CH in {16, 32, 64}, N in {1, 2, 4, 8} (8: not with FWSIM_PPO_RS=0), N chunks of CH samples in a minibatch"; return FW_EINVAL; }
+    } else { g_err = w + ": FWSIM_PPO_SPLIT must be CHxN with CH in {16, 32, 64}, N in {1, 2, 4, 8} (8: not with FWSIM_PPO_RS=0), N chunks of CH samples in a minibatch"; return FW_EINVAL; }
   }
   const int ns = cut.nsplit >= 4 && rs_env ? cut.nsplit : 0;      // the kernel's NS: 0 = all-to-all swap of whole partials
   const dim3 grid(16 * cut.nsplit);                 // (every 8th block works -- see the kernel)
-#define FW_PPO_LAUNCH(CH_, NS_) hipLaunchKernelGGL((fw_ppo_update_kernel<CH_, NS_>), grid, dim3(kPThreads), lds, st, A)
+#define FW_PPO_LAUNCH(CH_, NS_) do { if (a6) hipLaunchKernelGGL((fw_ppo_update_kernel_a6<CH_, NS_>), grid, dim3(kPThreads), lds, st, A); \
+                                     else hipLaunchKernelGGL((fw_ppo_update_kernel<CH_, NS_>), grid, dim3(kPThreads), lds, st, A); } while (0)
   if (cut.ch == 64) { if (ns == 8) FW_PPO_LAUNCH(64, 8); else if (ns == 4) FW_PPO_LAUNCH(64, 4); else FW_PPO_LAUNCH(64, 0); }
   else if (cut.ch == 32) { if (ns == 8) FW_PPO_LAUNCH(32, 8); else if (ns == 4) FW_PPO_LAUNCH(32, 4); else FW_PPO_LAUNCH(32, 0); }
   else { if (ns == 8) FW_PPO_LAUNCH(16, 8); else if (ns == 4) FW_PPO_LAUNCH(16, 4); else FW_PPO_LAUNCH(16, 0); }
 #undef FW_PPO_LAUNCH
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
+}
+int32_t fw_ppo_update(float* params, float* mom_m, float* mom_v, const float* obs, const float* act, const float* old_logp,
+                      const float* adv, const float* ret, const int32_t* perm, int32_t n_minibatches, int32_t batch_size,
+                      int32_t obs_dim, const fw_ppo_hyper* hyper, float* loss_acc, void* workspace, int64_t workspace_bytes,
+                      void* hip_stream) {
+  return ppo_update(params, mom_m, mom_v, obs, act, old_logp, adv, ret, perm, n_minibatches, batch_size, obs_dim, 4, hyper, loss_acc,
+                    workspace, workspace_bytes, hip_stream, "fw_ppo_update");
+}
+int32_t fw_ppo_update_a(float* params, float* mom_m, float* mom_v, const float* obs, const float* act, const float* old_logp,
+                        const float* adv, const float* ret, const int32_t* perm, int32_t n_minibatches, int32_t batch_size,
+                        int32_t obs_dim, int32_t act_dim, const fw_ppo_hyper* hyper, float* loss_acc, void* workspace, int64_t workspace_bytes,
+                        void* hip_stream) {
+  if (!act_dim_ok(act_dim, "fw_ppo_update_a")) return FW_EINVAL;
+  return ppo_update(params, mom_m, mom_v, obs, act, old_logp, adv, ret, perm, n_minibatches, batch_size, obs_dim, act_dim, hyper, loss_acc,
+                    workspace, workspace_bytes, hip_stream, "fw_ppo_update_a");
 }
 
 int32_t fw_ppo_update_status(const void* workspace, int64_t workspace_bytes, uint32_t* status_out, uint32_t* paths_out, void* hip_stream) {
@@ -2521,42 +2578,61 @@ int32_t fw_ppo_update_status(const void* workspace, int64_t workspace_bytes, uin
   return FW_OK;
 }
 
-int32_t fw_policy_act(const float* params, const float* obs, int32_t N, int32_t obs_dim, int32_t nets, int32_t deterministic,
-                      const uint64_t* rng, int64_t env_offset, float* obs_copy, float* act_raw, void* act_env, int32_t act_is_f64,
-                      float* logp, float* value, void* hip_stream) {
-  if (!params || !obs || N <= 0 || obs_dim <= 0 || obs_dim > 64 || (nets & ~3) || !nets) { g_err = "fw_policy_act: bad arguments"; return FW_EINVAL; }
-  if ((nets & 1) && (!act_raw || !act_env || !logp || (!deterministic && !rng))) { g_err = "fw_policy_act: policy outputs missing"; return FW_EINVAL; }
-  if ((nets & 2) && !value) { g_err = "fw_policy_act: value output missing"; return FW_EINVAL; }
-  const size_t lds = act_lds_bytes(obs_dim);
+// fw_policy_act / fw_collect_act and their *_a forms (who: the entry point's name, for the messages)
+static int32_t policy_act(const float* params, const float* obs, int32_t N, int32_t obs_dim, int32_t act_dim, int32_t nets, int32_t deterministic,
+                          const uint64_t* rng, int64_t env_offset, float* obs_copy, float* act_raw, void* act_env, int32_t act_is_f64,
+                          float* logp, float* value, void* hip_stream, const char* who) {
+  const std::string w = who;
+  if (!params || !obs || N <= 0 || obs_dim <= 0 || obs_dim > 64 || (nets & ~3) || !nets) { g_err = w + ": bad arguments"; return FW_EINVAL; }
+  if ((nets & 1) && (!act_raw || !act_env || !logp || (!deterministic && !rng))) { g_err = w + ": policy outputs missing"; return FW_EINVAL; }
+  if ((nets & 2) && !value) { g_err = w + ": value output missing"; return FW_EINVAL; }
+  const bool a6 = act_dim == 6;
+  const size_t lds = act_lds_bytes(obs_dim, act_dim);
   const int dev = device_of(params);
   DeviceGuard g(dev);
-  if (int rc = ensure_learner_lds(dev, 1, lds)) return rc;
+  if (int rc = ensure_learner_lds(dev, a6 ? 3 : 1, lds)) return rc;
   ActArgs A;
   std::memset(&A, 0, sizeof A);
   A.params = params; A.obs = obs; A.N = N; A.D = obs_dim; A.nets = nets; A.deterministic = deterministic; A.act_is_f64 = act_is_f64;
   A.rng = rng; A.env_offset = env_offset; A.obs_copy = obs_copy; A.act_raw = act_raw; A.act_env = act_env; A.logp = logp; A.value = value;
   A.raw = nullptr; A.raw_is_f64 = 0; A.mean = A.var = nullptr; A.clip = A.eps = 0.f; A.terminated = A.truncated = nullptr;
-  hipLaunchKernelGGL(fw_policy_act_kernel, dim3((N + kPChunk - 1) / kPChunk, 2), dim3(kPThreads), lds, (hipStream_t)hip_stream, A);
+  if (a6) hipLaunchKernelGGL((fw_policy_act_kernel<6>), dim3((N + kPChunk - 1) / kPChunk, 2), dim3(kPThreads), lds, (hipStream_t)hip_stream, A);
+  else hipLaunchKernelGGL((fw_policy_act_kernel<4>), dim3((N + kPChunk - 1) / kPChunk, 2), dim3(kPThreads), lds, (hipStream_t)hip_stream, A);
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }
+int32_t fw_policy_act(const float* params, const float* obs, int32_t N, int32_t obs_dim, int32_t nets, int32_t deterministic,
+                      const uint64_t* rng, int64_t env_offset, float* obs_copy, float* act_raw, void* act_env, int32_t act_is_f64,
+                      float* logp, float* value, void* hip_stream) {
+  return policy_act(params, obs, N, obs_dim, 4, nets, deterministic, rng, env_offset, obs_copy, act_raw, act_env, act_is_f64, logp, value,
+                    hip_stream, "fw_policy_act");
+}
+int32_t fw_policy_act_a(const float* params, const float* obs, int32_t N, int32_t obs_dim, int32_t act_dim, int32_t nets, int32_t deterministic,
+                        const uint64_t* rng, int64_t env_offset, float* obs_copy, float* act_raw, void* act_env, int32_t act_is_f64,
+                        float* logp, float* value, void* hip_stream) {
+  if (!act_dim_ok(act_dim, "fw_policy_act_a")) return FW_EINVAL;
+  return policy_act(params, obs, N, obs_dim, act_dim, nets, deterministic, rng, env_offset, obs_copy, act_raw, act_env, act_is_f64, logp, value,
+                    hip_stream, "fw_policy_act_a");
+}
 
-int32_t fw_collect_act(const float* params, const void* raw_obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, const double* obs_mean,
-                       const double* obs_var, float clip_obs, float eps_obs, int32_t nets, int32_t deterministic, const uint64_t* rng,
-                       int64_t env_offset, float* obs_copy, float* act_raw, void* act_env, int32_t act_is_f64, float* logp, float* value,
-                       const void* prev_reward, const uint8_t* prev_terminated, const uint8_t* prev_truncated, const void* prev_terminal_obs,
-                       const double* ret_var, int32_t norm_reward, float clip_reward, float eps_reward, float gamma, float* rew_out,
-                       float* start_out, void* hip_stream) {
-  if (!params || !raw_obs || !obs_mean || !obs_var || N <= 0 || obs_dim <= 0 || obs_dim > 64 || (nets & ~3) || !nets) { g_err = "fw_collect_act: bad arguments"; return FW_EINVAL; }
-  if ((nets & 1) && (!act_raw || !act_env || !logp || (!deterministic && !rng))) { g_err = "fw_collect_act: policy outputs missing"; return FW_EINVAL; }
-  if ((nets & 2) && !value) { g_err = "fw_collect_act: value output missing"; return FW_EINVAL; }
+static int32_t collect_act(const float* params, const void* raw_obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, int32_t act_dim,
+                           const double* obs_mean, const double* obs_var, float clip_obs, float eps_obs, int32_t nets, int32_t deterministic,
+                           const uint64_t* rng, int64_t env_offset, float* obs_copy, float* act_raw, void* act_env, int32_t act_is_f64,
+                           float* logp, float* value, const void* prev_reward, const uint8_t* prev_terminated, const uint8_t* prev_truncated,
+                           const void* prev_terminal_obs, const double* ret_var, int32_t norm_reward, float clip_reward, float eps_reward,
+                           float gamma, float* rew_out, float* start_out, void* hip_stream, const char* who) {
+  const std::string w = who;
+  if (!params || !raw_obs || !obs_mean || !obs_var || N <= 0 || obs_dim <= 0 || obs_dim > 64 || (nets & ~3) || !nets) { g_err = w + ": bad arguments"; return FW_EINVAL; }
+  if ((nets & 1) && (!act_raw || !act_env || !logp || (!deterministic && !rng))) { g_err = w + ": policy outputs missing"; return FW_EINVAL; }
+  if ((nets & 2) && !value) { g_err = w + ": value output missing"; return FW_EINVAL; }
   if (prev_reward && (!(nets & 2) || !prev_terminated || !prev_truncated || !prev_terminal_obs || !ret_var || !rew_out || !start_out)) {
-    g_err = "fw_collect_act: finalising the previous step needs the value network and all of its buffers"; return FW_EINVAL;
+    g_err = w + ": finalising the previous step needs the value network and all of its buffers"; return FW_EINVAL;
   }
-  const size_t lds = act_lds_bytes(obs_dim);
+  const bool a6 = act_dim == 6;
+  const size_t lds = act_lds_bytes(obs_dim, act_dim);
   const int dev = device_of(params);
   DeviceGuard g(dev);
-  if (int rc = ensure_learner_lds(dev, 1, lds)) return rc;
+  if (int rc = ensure_learner_lds(dev, a6 ? 3 : 1, lds)) return rc;
   ActArgs A;
   std::memset(&A, 0, sizeof A);
   A.params = params; A.N = N; A.D = obs_dim; A.nets = nets; A.deterministic = deterministic; A.act_is_f64 = act_is_f64;
@@ -2565,9 +2641,31 @@ int32_t fw_collect_act(const float* params, const void* raw_obs, int32_t obs_is_
   A.prev_reward = prev_reward; A.prev_term = prev_terminated; A.prev_trunc = prev_truncated; A.prev_tobs = prev_terminal_obs;
   A.ret_var = ret_var; A.norm_reward = norm_reward; A.clip_reward = clip_reward; A.rew_eps = eps_reward; A.gamma = gamma;
   A.rew_out = rew_out; A.start_out = start_out;
-  hipLaunchKernelGGL(fw_policy_act_kernel, dim3((N + kPChunk - 1) / kPChunk, 2), dim3(kPThreads), lds, (hipStream_t)hip_stream, A);
+  if (a6) hipLaunchKernelGGL((fw_policy_act_kernel<6>), dim3((N + kPChunk - 1) / kPChunk, 2), dim3(kPThreads), lds, (hipStream_t)hip_stream, A);
+  else hipLaunchKernelGGL((fw_policy_act_kernel<4>), dim3((N + kPChunk - 1) / kPChunk, 2), dim3(kPThreads), lds, (hipStream_t)hip_stream, A);
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
+}
+int32_t fw_collect_act(const float* params, const void* raw_obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, const double* obs_mean,
+                       const double* obs_var, float clip_obs, float eps_obs, int32_t nets, int32_t deterministic, const uint64_t* rng,
+                       int64_t env_offset, float* obs_copy, float* act_raw, void* act_env, int32_t act_is_f64, float* logp, float* value,
+                       const void* prev_reward, const uint8_t* prev_terminated, const uint8_t* prev_truncated, const void* prev_terminal_obs,
+                       const double* ret_var, int32_t norm_reward, float clip_reward, float eps_reward, float gamma, float* rew_out,
+                       float* start_out, void* hip_stream) {
+  return collect_act(params, raw_obs, obs_is_f64, N, obs_dim, 4, obs_mean, obs_var, clip_obs, eps_obs, nets, deterministic, rng, env_offset,
+                     obs_copy, act_raw, act_env, act_is_f64, logp, value, prev_reward, prev_terminated, prev_truncated, prev_terminal_obs,
+                     ret_var, norm_reward, clip_reward, eps_reward, gamma, rew_out, start_out, hip_stream, "fw_collect_act");
+}
+int32_t fw_collect_act_a(const float* params, const void* raw_obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, int32_t act_dim,
+                         const double* obs_mean, const double* obs_var, float clip_obs, float eps_obs, int32_t nets, int32_t deterministic,
+                         const uint64_t* rng, int64_t env_offset, float* obs_copy, float* act_raw, void* act_env, int32_t act_is_f64, float* logp,
+                         float* value, const void* prev_reward, const uint8_t* prev_terminated, const uint8_t* prev_truncated,
+                         const void* prev_terminal_obs, const double* ret_var, int32_t norm_reward, float clip_reward, float eps_reward,
+                         float gamma, float* rew_out, float* start_out, void* hip_stream) {
+  if (!act_dim_ok(act_dim, "fw_collect_act_a")) return FW_EINVAL;
+  return collect_act(params, raw_obs, obs_is_f64, N, obs_dim, act_dim, obs_mean, obs_var, clip_obs, eps_obs, nets, deterministic, rng, env_offset,
+                     obs_copy, act_raw, act_env, act_is_f64, logp, value, prev_reward, prev_terminated, prev_truncated, prev_terminal_obs,
+                     ret_var, norm_reward, clip_reward, eps_reward, gamma, rew_out, start_out, hip_stream, "fw_collect_act_a");
 }
 
 int64_t fw_collect_step_workspace_bytes(fw_handle h) { return h ? (int64_t)collect_ws(h).total : FW_EINVAL; }
@@ -2741,7 +2839,7 @@ int32_t fw_policy_terminal_value(const float* params, const void* terminal_obs, 
   A.params = params; A.N = N; A.D = obs_dim; A.nets = 2; A.deterministic = 1; A.value = value;
   A.raw = terminal_obs; A.raw_is_f64 = obs_is_f64; A.mean = mean; A.var = var; A.clip = clip; A.eps = eps;
   A.terminated = terminated; A.truncated = truncated;
-  hipLaunchKernelGGL(fw_policy_act_kernel, dim3((N + kPChunk - 1) / kPChunk, 2), dim3(kPThreads), lds, (hipStream_t)hip_stream, A);
+  hipLaunchKernelGGL((fw_policy_act_kernel<4>), dim3((N + kPChunk - 1) / kPChunk, 2), dim3(kPThreads), lds, (hipStream_t)hip_stream, A);
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }

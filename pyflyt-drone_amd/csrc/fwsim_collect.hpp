@@ -21,8 +21,8 @@ struct ActArgs {
   const uint64_t* rng;        // [2] device: seed, draw counter (advanced by fw_rollout_post)
   int64_t env_offset;         // global env id of row 0 (multi-process sharding keeps streams distinct)
   float* obs_copy;            // [N, D] or null: rollout buffer slot of this step
-  float* act_raw;             // [N, 4] sampled action (unclipped: what PPO stores)
-  void* act_env;              // [N, 4] clipped to [-1, 1] in the env's dtype (fw_step input)
+  float* act_raw;             // [N, A] sampled action (unclipped: what PPO stores); A = 4, or 6 in the six-action kernel
+  void* act_env;              // [N, A] clipped to [-1, 1] in the env's dtype (fw_step input)
   float* logp;                // [N]
   float* value;               // [N]
   // value-of-terminal-observation mode (obs == nullptr): rows are normalised on load from the env's raw buffer and
@@ -59,9 +59,22 @@ __device__ __forceinline__ void act_normal4(uint64_t seed, uint64_t draw, uint64
     z[2 * h] = rad * cs; z[2 * h + 1] = rad * sn;
   }
 }
+// Six actions: components 0-3 are act_normal4's draw, bit for bit; components 4, 5 come from a second Philox block of the same key
+// whose counter differs in bit 31 of word 3 (word 3 = (draw >> 32) ^ 0xAC7C0DE ^ 0x80000000) -- disjoint from every first-block
+// counter for draw counts below 2^63 -- and Box-Muller of its words 0, 1 (words 2, 3 are not used).
+__device__ __forceinline__ void act_normal2_hi(uint64_t seed, uint64_t draw, uint64_t env, float z[2]) {
+  uint32_t o[4];
+  philox4x32_10((uint32_t)env, (uint32_t)(env >> 32), (uint32_t)draw, ((uint32_t)(draw >> 32) ^ 0xAC7C0DEu) ^ 0x80000000u, (uint32_t)seed, (uint32_t)(seed >> 32), o);
+  const float u1 = ((float)(o[0] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float u2 = ((float)(o[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float rad = sqrtf(-2.0f * logf(u1));
+  float sn, cs;
+  sincosf(6.283185307179586f * u2, &sn, &cs);
+  z[0] = rad * cs; z[1] = rad * sn;
+}
 
-// X[64, Dp] -> tanh -> H1 -> tanh -> H2 -> head: out[64, 4] (KO columns used); all operands in LDS, 4 waves = 2 x 2 tiles of 32 x 32
-__device__ __forceinline__ void act_forward(const PpoNetLds& W, const float* X, float* H1, float* H2, float* out, int KO, int Dp, int ldx) {
+// X[64, Dp] -> tanh -> H1 -> tanh -> H2 -> head: out[64, ldo] (KO <= ldo columns used); all operands in LDS, 4 waves = 2 x 2 tiles of 32 x 32
+__device__ __forceinline__ void act_forward(const PpoNetLds& W, const float* X, float* H1, float* H2, float* out, int KO, int Dp, int ldx, int ldo = 4) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, hh = lane >> 5;
   const int mt = wave >> 1, nt = wave & 1;
   {
@@ -94,18 +107,21 @@ __device__ __forceinline__ void act_forward(const PpoNetLds& W, const float* X, 
     c = ppo_mfma_k([&](int k0) { return a[k0]; }, [&](int k0) { return r < KO ? wo[k0 * KO] : 0.f; }, kPH, c);
     if (r < KO) {
 #pragma unroll
-      for (int v = 0; v < 16; ++v) out[(wave * 32 + ppo_acc_row(v)) * 4 + r] = c[v];
+      for (int v = 0; v < 16; ++v) out[(wave * 32 + ppo_acc_row(v)) * ldo + r] = c[v];
     }
   }
   __syncthreads();
 }
 
-// grid = (ceil(N / 64), 2): block (c, net) runs network `net` on rows 64 c .. 64 c + 63; 256 threads.
+// grid = (ceil(N / 64), 2): block (c, net) runs network `net` on rows 64 c .. 64 c + 63; 256 threads.  NA: the width of the action
+// (4, or 6: the flat image then has the six-action layout of fwsim_ppo.hpp; the four-action kernel is the one of before, verbatim)
+template <int NA>
 __global__ __launch_bounds__(kPThreads) void fw_policy_act_kernel(ActArgs A) {
   extern __shared__ __align__(16) float lds[];
+  constexpr int LDO = NA == 6 ? 8 : 4;            // row stride of the head output
   const int net = blockIdx.y;
   if (!((A.nets >> net) & 1)) return;
-  const int KO = net == 0 ? 4 : 1;
+  const int KO = net == 0 ? NA : 1;
   const int t = threadIdx.x;
   const int D = A.D, Dp = (D + 1) & ~1, ldx = Dp + 1;
   const int row0 = blockIdx.x * kPChunk;
@@ -117,12 +133,12 @@ __global__ __launch_bounds__(kPThreads) void fw_policy_act_kernel(ActArgs A) {
 
   float* p = lds;
   PpoNetLds W;
-  W.W1 = p; p += Dp * kPH; W.b1 = p; p += kPH; W.W2 = p; p += kPH * kPLdh; W.b2 = p; p += kPH; W.Wo = p; p += kPH * 4; W.bo = p; p += 4;
-  float* log_std = p; p += 4;
+  W.W1 = p; p += Dp * kPH; W.b1 = p; p += kPH; W.W2 = p; p += kPH * kPLdh; W.b2 = p; p += kPH; W.Wo = p; p += kPH * NA; W.bo = p; p += NA;
+  float* log_std = p; p += NA;
   float* X = p;  p += kPChunk * ldx;
   float* H1 = p; p += kPChunk * kPLdh;
   float* H2 = p; p += kPChunk * kPLdh;
-  float* out = p; p += kPChunk * 4;
+  float* out = p; p += kPChunk * LDO;
 
   // small loads whose results are only needed later leave first, so that their round trips hide behind the weight loads:
   // the column statistics (raw-observation modes) and, for the value block, what it needs to finalise the previous step
@@ -154,7 +170,7 @@ __global__ __launch_bounds__(kPThreads) void fw_policy_act_kernel(ActArgs A) {
   load_batch(t);
   uint64_t rng_key = 0, rng_ctr = 0;
   if (net == 0 && !A.deterministic && t < kPChunk) { rng_key = A.rng[0]; rng_ctr = A.rng[1]; }
-  const int nP0 = ppo_net_params(Dp, 4);
+  const int nP0 = ppo_net_params(Dp, NA);
   const int oW1 = net == 0 ? 0 : nP0, ob1 = oW1 + Dp * kPH, oW2 = ob1 + kPH, ob2 = oW2 + kPH * kPH, oWo = ob2 + kPH;
   const int oLs = nP0 + ppo_net_params(Dp, 1);
   const float* __restrict__ params = A.params;
@@ -162,7 +178,7 @@ __global__ __launch_bounds__(kPThreads) void fw_policy_act_kernel(ActArgs A) {
   for (int i = t; i < kPH; i += kPThreads) { W.b1[i] = params[ob1 + i]; W.b2[i] = params[ob2 + i]; }
   for (int i = t; i < kPH * kPH; i += kPThreads) W.W2[(i >> 6) * kPLdh + (i & 63)] = params[oW2 + i];
   for (int i = t; i < kPH * KO + KO; i += kPThreads) W.Wo[i] = params[oWo + i];
-  if (t < 4) log_std[t] = params[oLs + t];
+  if (t < NA) log_std[t] = params[oLs + t];
   // raw-observation modes: sqrt(var + eps) of every column once per block (the division stays per element: bit-identical to
   // fw_normalize_obs); kept in the H2 area, which the forward pass only writes after X has been built
   double* cstd = reinterpret_cast<double*>(H2);
@@ -191,31 +207,61 @@ __global__ __launch_bounds__(kPThreads) void fw_policy_act_kernel(ActArgs A) {
   }
   __syncthreads();
 
-  act_forward(W, X, H1, H2, out, KO, Dp, ldx);
+  act_forward(W, X, H1, H2, out, KO, Dp, ldx, LDO);
   if (t < kPChunk) {
     const int row = row0 + t;
     if (row < A.N) {
       if (net == 1) {
-        A.value[row] = out[t * 4];
+        A.value[row] = out[t * LDO];
       } else {
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        if (!A.deterministic) act_normal4(rng_key, rng_ctr, (uint64_t)(A.env_offset + row), z);
-        float lp = 0.f, a[4];
+        if constexpr (NA == 4) {
+          float z[4] = {0.f, 0.f, 0.f, 0.f};
+          if (!A.deterministic) act_normal4(rng_key, rng_ctr, (uint64_t)(A.env_offset + row), z);
+          float lp = 0.f, a[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float ls = log_std[k];
-          a[k] = out[t * 4 + k] + z[k] * expf(ls);
-          lp += -0.5f * z[k] * z[k] - ls - 0.9189385332046727f;
-        }
-        reinterpret_cast<float4*>(A.act_raw)[row] = make_float4(a[0], a[1], a[2], a[3]);
-        A.logp[row] = lp;
+          for (int k = 0; k < 4; ++k) {
+            const float ls = log_std[k];
+            a[k] = out[t * 4 + k] + z[k] * expf(ls);
+            lp += -0.5f * z[k] * z[k] - ls - 0.9189385332046727f;
+          }
+          reinterpret_cast<float4*>(A.act_raw)[row] = make_float4(a[0], a[1], a[2], a[3]);
+          A.logp[row] = lp;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) a[k] = fminf(fmaxf(a[k], -1.0f), 1.0f);
-        if (A.act_is_f64) {
-          double* o = reinterpret_cast<double*>(A.act_env) + (size_t)row * 4;
-          o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3];
-        } else {
-          reinterpret_cast<float4*>(A.act_env)[row] = make_float4(a[0], a[1], a[2], a[3]);
+          for (int k = 0; k < 4; ++k) a[k] = fminf(fmaxf(a[k], -1.0f), 1.0f);
+          if (A.act_is_f64) {
+            double* o = reinterpret_cast<double*>(A.act_env) + (size_t)row * 4;
+            o[0] = a[0]; o[1] = a[1]; o[2] = a[2]; o[3] = a[3];
+          } else {
+            reinterpret_cast<float4*>(A.act_env)[row] = make_float4(a[0], a[1], a[2], a[3]);
+          }
+        } else {                                   // six actions: rows of 24 bytes (float2 stores), components 4, 5 from act_normal2_hi
+          float z[NA];
+#pragma unroll
+          for (int k = 0; k < NA; ++k) z[k] = 0.f;
+          if (!A.deterministic) {
+            act_normal4(rng_key, rng_ctr, (uint64_t)(A.env_offset + row), z);
+            act_normal2_hi(rng_key, rng_ctr, (uint64_t)(A.env_offset + row), z + 4);
+          }
+          float lp = 0.f, a[NA];
+#pragma unroll
+          for (int k = 0; k < NA; ++k) {
+            const float ls = log_std[k];
+            a[k] = out[t * LDO + k] + z[k] * expf(ls);
+            lp += -0.5f * z[k] * z[k] - ls - 0.9189385332046727f;
+          }
+#pragma unroll
+          for (int k = 0; k < NA; k += 2) reinterpret_cast<float2*>(A.act_raw + (size_t)row * NA)[k / 2] = make_float2(a[k], a[k + 1]);
+          A.logp[row] = lp;
+#pragma unroll
+          for (int k = 0; k < NA; ++k) a[k] = fminf(fmaxf(a[k], -1.0f), 1.0f);
+          if (A.act_is_f64) {
+            double* o = reinterpret_cast<double*>(A.act_env) + (size_t)row * NA;
+#pragma unroll
+            for (int k = 0; k < NA; ++k) o[k] = a[k];
+          } else {
+#pragma unroll
+            for (int k = 0; k < NA; k += 2) reinterpret_cast<float2*>(reinterpret_cast<float*>(A.act_env) + (size_t)row * NA)[k / 2] = make_float2(a[k], a[k + 1]);
+          }
         }
       }
     }
@@ -238,7 +284,7 @@ __global__ __launch_bounds__(kPThreads) void fw_policy_act_kernel(ActArgs A) {
         X[e] = x;
       }
       __syncthreads();
-      act_forward(W, X, H1, H2, out, 1, Dp, ldx);
+      act_forward(W, X, H1, H2, out, 1, Dp, ldx, LDO);
     }
     if (mine) {
       double rn = f_rew;
@@ -247,16 +293,18 @@ __global__ __launch_bounds__(kPThreads) void fw_policy_act_kernel(ActArgs A) {
         rn = rn > A.clip_reward ? A.clip_reward : (rn < -A.clip_reward ? -A.clip_reward : rn);
       }
       float o = (float)rn;
-      if (timeout) o += A.gamma * out[t * 4];                      // SB3: bootstrap truncated episodes with V(terminal_observation)
+      if (timeout) o += A.gamma * out[t * LDO];                    // SB3: bootstrap truncated episodes with V(terminal_observation)
       A.rew_out[row] = o;
       A.start_out[row] = (f_term || f_trunc) ? 1.0f : 0.0f;
     }
   }
 }
+template __global__ void fw_policy_act_kernel<4>(ActArgs);
+template __global__ void fw_policy_act_kernel<6>(ActArgs);
 
-inline size_t act_lds_bytes(int D) {
-  const int Dp = (D + 1) & ~1, ldx = Dp + 1;
-  return sizeof(float) * ((size_t)Dp * kPH + kPH + kPH * kPLdh + kPH + kPH * 4 + 4 + 4 + (size_t)kPChunk * ldx + 2 * (size_t)kPChunk * kPLdh + kPChunk * 4);
+inline size_t act_lds_bytes(int D, int NA = 4) {
+  const int Dp = (D + 1) & ~1, ldx = Dp + 1, LDO = NA == 6 ? 8 : 4;
+  return sizeof(float) * ((size_t)Dp * kPH + kPH + kPH * kPLdh + kPH + kPH * NA + NA + NA + (size_t)kPChunk * ldx + 2 * (size_t)kPChunk * kPLdh + kPChunk * LDO);
 }
 
 struct PostArgs {

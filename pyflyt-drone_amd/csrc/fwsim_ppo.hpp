@@ -15,8 +15,10 @@
 // depends on an index.
 //
 // Flat parameter layout (floats), used for params / exp_avg / exp_avg_sq alike (rollout.py builds it):
-//   for net in (pi, vf):  W1[Dp][64]  b1[64]  W2[64][64]  b2[64]  Wo[64][KO]  bo[KO]     (KO = 4 / 1)
-//   then log_std[4].       W*[in][out] = torch Linear.weight^T;  Dp = D rounded up to even (zero row).
+//   for net in (pi, vf):  W1[Dp][64]  b1[64]  W2[64][64]  b2[64]  Wo[64][KO]  bo[KO]     (KO = A / 1)
+//   then log_std[A].       W*[in][out] = torch Linear.weight^T;  Dp = D rounded up to even (zero row).
+// A, the width of the action, is 4 (the reference's tasks) or 6 (the low-level control task's direct actuator commands): a
+// compile-time parameter of the network body (NA), instantiated for both.  The four-action instantiation is the kernel of before.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -44,6 +46,7 @@ constexpr int kPThreads = 256;
 
 __host__ __device__ inline int ppo_net_params(int Dp, int KO) { return Dp * kPH + kPH + kPH * kPH + kPH + kPH * KO + KO; }
 __host__ __device__ inline int ppo_total_params(int Dp) { return ppo_net_params(Dp, 4) + ppo_net_params(Dp, 1) + 4; }
+__host__ __device__ inline int ppo_total_params_a(int Dp, int NA) { return ppo_net_params(Dp, NA) + ppo_net_params(Dp, 1) + NA; }
 
 // LDS image of one network
 struct PpoNetLds { float *W1, *b1, *W2, *b2, *Wo, *bo; };
@@ -181,10 +184,12 @@ __device__ __forceinline__ float ppo_tanh(float x) {
 
 // Adam moments are kept in "slot" order: slot = ((net * 3 + kind) * 4 + wave) * 1024 + lane * 16 + v for the
 // accumulator tiles (kind 0 = W2, 1 = W1; kind 2 is unused since round 3), then kPTileSlots + q * 256 + thread for the
-// per-thread elements (q = 3 net + {0: b1, 1: b2, 2: bo}, q = 6: log_std, q = 7 + net: Wo[thread / 4][thread % 4]).
+// per-thread elements (q = 3 net + {0: b1, 1: b2, 2: bo}, q = 6: log_std, q = 7 + net: Wo[thread / 4][thread % 4]; six actions:
+// q = 9: the policy head's Wo[thread / 4][4 + thread % 4], thread % 4 < 2 -- 64 x 6 elements do not fit one row of 256 threads).
 // Slots nobody owns are padding.
 constexpr int kPTileSlots = 2 * 3 * 4 * 64 * 16;
 constexpr int kPMomentSlots = kPTileSlots + 9 * kPThreads;
+__host__ __device__ constexpr int ppo_moment_slots(int NA) { return kPMomentSlots + (NA == 6 ? kPThreads : 0); }
 __host__ __device__ inline int ppo_tile_slot(int net, int kind, int wave, int lane) { return (((net * 3 + kind) * 4 + wave) * 64 + lane) * 16; }
 // A block's gradient partial in the exchange buffer: [kind W2 | W1][wave][quarter q of the lane's 16 elements][lane][4] for the tiles -- one wave-level
 // 16-byte access is 1 KB in a row (the partners read it past their L1: every access is a request to the L2, and in moment-slot order, 64 bytes
@@ -199,16 +204,19 @@ constexpr int kPGxTile = 2 * 4 * 4 * 64 * 4;
 // blocks walked them in the same order.
 constexpr int kPWxShare = 3 * kPThreads * 4;      // (three tagged granules per thread in the self-announcing form, two plain float4s otherwise)
 constexpr int kPGxSlots = kPGxTile + 2 * kPThreads + kPWxShare;
+// six actions: one more per-thread element, the policy head's second Wo word (component 4 + thread % 4), behind the weight share
+constexpr int kPGxWo2 = kPGxSlots;
+__host__ __device__ constexpr int ppo_gx_slots(int NA) { return kPGxSlots + (NA == 6 ? kPThreads : 0); }
 __host__ __device__ inline int ppo_gx_tile(int kind, int wave, int lane) { return (kind * 4 + wave) * 4 * 256 + lane * 4; }      // + q * 256
 
 // flat parameter index of every moment slot (-1 = padding); host side of the layout above
-inline void ppo_moment_map(int D, int32_t* flat_of_slot) {
+inline void ppo_moment_map(int D, int32_t* flat_of_slot, int NA = 4) {
   const int Dp = (D + 1) & ~1;
   const int tilesW1 = ((Dp + 31) / 32) * 2;
-  for (int i = 0; i < kPMomentSlots; ++i) flat_of_slot[i] = -1;
+  for (int i = 0; i < ppo_moment_slots(NA); ++i) flat_of_slot[i] = -1;
   int off = 0, oLs = 0;
   for (int n = 0; n < 2; ++n) {
-    const int KO = n == 0 ? 4 : 1;
+    const int KO = n == 0 ? NA : 1;
     const int oW1 = off, ob1 = oW1 + Dp * kPH, oW2 = ob1 + kPH, ob2 = oW2 + kPH * kPH, oWo = ob2 + kPH, obo = oWo + kPH * KO;
     off = obo + KO;
     for (int wave = 0; wave < 4; ++wave)
@@ -223,26 +231,27 @@ inline void ppo_moment_map(int D, int32_t* flat_of_slot) {
     for (int t = 0; t < kPH; ++t) { flat_of_slot[kPTileSlots + (n * 3 + 0) * kPThreads + t] = ob1 + t; flat_of_slot[kPTileSlots + (n * 3 + 1) * kPThreads + t] = ob2 + t; }
     for (int t = 0; t < KO; ++t) flat_of_slot[kPTileSlots + (n * 3 + 2) * kPThreads + t] = obo + t;
     for (int t = 0; t < kPThreads; ++t) if ((t & 3) < KO) flat_of_slot[kPTileSlots + (7 + n) * kPThreads + t] = oWo + (t >> 2) * KO + (t & 3);
+    for (int t = 0; t < kPThreads; ++t) if ((t & 3) + 4 < KO) flat_of_slot[kPTileSlots + 9 * kPThreads + t] = oWo + (t >> 2) * KO + 4 + (t & 3);
     oLs = off;
   }
-  for (int t = 0; t < 4; ++t) flat_of_slot[kPTileSlots + 6 * kPThreads + t] = oLs + t;
+  for (int t = 0; t < NA; ++t) flat_of_slot[kPTileSlots + 6 * kPThreads + t] = oLs + t;
 }
 
 // Pre-pass of fw_ppo_update, off the sequential path: one workgroup per minibatch PACKS the rows the update will walk, in the
-// order it will walk them, into one contiguous array -- row = [obs, zero-padded to a multiple of 4 | action 4 | old log-prob,
+// order it will walk them, into one contiguous array -- row = [obs, zero-padded to a multiple of 4 | action 4 (six: 6, padded to 8) | old log-prob,
 // advantage (normalised), return, 0] -- so that the sequential kernel fetches a 64-sample chunk as one contiguous block with
 // three or four coalesced 16-byte loads per thread and no index, no scattered scalar and no division on its path.  (Round 3
 // gathered inside the sequential kernel: per chunk and thread a dependent index load, 7-16 scattered dwords of the observation row
 // and three scattered scalars, ~40 wave-level loads of 16 cache lines each through the CU's one address path: 2.2-2.8 k
 // cycles per chunk just to issue them.)  It also does what fw_ppo_adv_stats_kernel did: the minibatch's advantage statistics
 // (SB3: advantages = (a - a.mean()) / (a.std() + 1e-8) with the unbiased std).
-__host__ __device__ inline int ppo_pack_width(int D) { return ((D + 3) & ~3) + 8; }       // floats per packed row (a multiple of 4)
+__host__ __device__ inline int ppo_pack_width(int D, int NA = 4) { return ((D + 3) & ~3) + (NA == 6 ? 12 : 8); }       // floats per packed row (a multiple of 4)
 struct PpoPackArgs {
   const float *obs, *act, *old_logp, *adv, *ret;
   const int32_t* perm;
   int32_t B, D, norm_adv;            // norm_adv as PpoHyper
   float adv_mean, adv_std;
-  float* out;                        // [n_mb][B][ppo_pack_width(D)]
+  float* out;                        // [n_mb][B][ppo_pack_width(D, NA)]
 };
 __global__ __launch_bounds__(256) void fw_ppo_pack_kernel(PpoPackArgs P) {
   __shared__ float st[2];
@@ -274,6 +283,48 @@ __global__ __launch_bounds__(256) void fw_ppo_pack_kernel(PpoPackArgs P) {
       else { const int left = D - 4 * q; v = make_float4(o[0], left > 1 ? o[1] : 0.f, left > 2 ? o[2] : 0.f, left > 3 ? o[3] : 0.f); }
     } else if (q == Dv4) {
       v = *reinterpret_cast<const float4*>(P.act + (size_t)si * 4);
+    } else {
+      float a = P.adv[si];
+      if (P.norm_adv != 0) a = (a - mean) / (sd + 1e-8f);
+      v = make_float4(P.old_logp[si], a, P.ret[si], 0.f);
+    }
+    out[e] = v;
+  }
+}
+
+// the same pre-pass for six-action rows (the low-level control task): the action takes two float4s
+__global__ __launch_bounds__(256) void fw_ppo_pack_kernel_a6(PpoPackArgs P) {
+  __shared__ float st[2];
+  const int32_t* idx = P.perm + (size_t)blockIdx.x * P.B;
+  const int t = threadIdx.x, B = P.B, D = P.D;
+  if (t < 64) {                                      // (the arithmetic of round 3's statistics kernel: one wave, strided sums)
+    float mean = P.adv_mean, sd = P.adv_std;
+    if (P.norm_adv == 1) {
+      float s1 = 0.f;
+      for (int i = t; i < B; i += 64) s1 += P.adv[idx[i]];
+      mean = ppo_wave_sum(s1) / (float)B;
+      float s2 = 0.f;
+      for (int i = t; i < B; i += 64) { const float d = P.adv[idx[i]] - mean; s2 += d * d; }
+      sd = sqrtf(ppo_wave_sum(s2) / (float)(B > 1 ? B - 1 : 1));
+    }
+    if (t == 0) { st[0] = mean; st[1] = sd; }
+  }
+  __syncthreads();
+  const float mean = st[0], sd = st[1];
+  const int Dv4 = (D + 3) >> 2, W4 = Dv4 + 3;      // float4s per row: observation, then action (two), then scalars
+  float4* out = reinterpret_cast<float4*>(P.out) + (size_t)blockIdx.x * B * W4;
+  const bool vec = (D & 3) == 0;
+  for (int e = t; e < B * W4; e += 256) {
+    const int row = e / W4, q = e - row * W4, si = idx[row];
+    float4 v;
+    if (q < Dv4) {
+      const float* o = P.obs + (size_t)si * D + 4 * q;
+      if (vec) v = *reinterpret_cast<const float4*>(o);
+      else { const int left = D - 4 * q; v = make_float4(o[0], left > 1 ? o[1] : 0.f, left > 2 ? o[2] : 0.f, left > 3 ? o[3] : 0.f); }
+    } else if (q < Dv4 + 2) {                      // six components, 8-byte aligned rows: [a0 a1 a2 a3] [a4 a5 0 0]
+      const float2* a2 = reinterpret_cast<const float2*>(P.act + (size_t)si * 6) + 2 * (q - Dv4);
+      const float2 x = a2[0], y = q == Dv4 ? a2[1] : make_float2(0.f, 0.f);
+      v = make_float4(x.x, x.y, y.x, y.y);
     } else {
       float a = P.adv[si];
       if (P.norm_adv != 0) a = (a - mean) / (sd + 1e-8f);
@@ -409,8 +460,12 @@ template <int N> __device__ __forceinline__ float ppo_tree_sum(const float (&v)[
   else if constexpr (N == 4) return (v[0] + v[1]) + (v[2] + v[3]);
   else return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
 }
-template <int NET, int CH, int NS>
+// NA: the width of the action (4, or 6: see the top of the file).  Six actions change the policy head only: the head / loss threads take
+// component hc and, where hc < 2, also component 4 + hc; Wo's thread elements gain a second word (moment slot row 9, exchange slot
+// kPGxWo2); gout / sA rows are 8 floats wide; the packed rows carry two action float4s.
+template <int NET, int CH, int NS, int NA>
 __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const int part, const int nsplit) {
+  static_assert(NA == 4 || NA == 6, "action width");
   static_assert(NS == 0 || NS == 4 || NS == 8, "blocks per network in the reduce-scatter form");
   constexpr bool RS = NS != 0;
   constexpr int NSd = RS ? NS : 4;                     // (array extents; the divisor where NS may be 0)
@@ -420,7 +475,12 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
                                                        // per wave from seven partners that sixteen blocks poll at once (7.88 -> 8.25 us)
   static_assert(CH == 64 || CH == 32 || CH == 16, "chunk size");
   constexpr int RT = CH == 64 ? 1 : CH / 16;     // row tiles of 16 in the 16 x 16 forms
-  constexpr int n = NET, KO = NET == 0 ? 4 : 1;
+  constexpr int n = NET, KO = NET == 0 ? NA : 1;
+  constexpr bool A6 = NET == 0 && NA == 6;             // the policy block of the six-action form
+  constexpr int SA = NA == 6 ? 8 : 4;                  // row stride of gout / sA
+  constexpr int NAQ = NA == 6 ? 2 : 1;                 // float4s of the action in a packed row
+  constexpr int SR = NA == 6 ? 16 : 8;                 // floats of sred per wave
+  constexpr int GXS = ppo_gx_slots(NA);                // floats per block in the exchange buffer
   float* __restrict__ params = A.params;
   float* __restrict__ mom_m = A.mom_m; float* __restrict__ mom_v = A.mom_v;
   const int n_mb = A.n_mb, B = A.B, D = A.D;
@@ -438,21 +498,22 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
   float* p = lds;
   PpoNetLds W;
   W.W1 = p; p += K1 * ldw1; W.b1 = p; p += kPH; W.W2 = p; p += kPH * kPLdh; W.b2 = p; p += kPH; W.Wo = p; p += kPH * KO; W.bo = p; p += KO;
-  float* log_std = p; p += 4;
+  float* log_std = p; p += NA;
   float* X = p;  p += CH * ldx + 64;              // (+64: the padded dW1 tile reads a few floats past the last row)
   float* H1 = p; p += CH * kPLdh;
   float* H2 = p; p += CH * kPLdh > 2112 ? CH * kPLdh : 2112;      // (>= 2048 floats: dW1's split partials pass through it)
-  float* gout = p; p += CH * 4;                   // head output, then dL/d(head output) of the chunk
-  float* sA = p; p += CH * 4;                     // gathered actions
+  float* gout = p; p += CH * SA;                  // head output, then dL/d(head output) of the chunk
+  float* sA = p; p += CH * SA;                    // gathered actions
   float* sS = p; p += CH * 4;                     // per-sample scalars: old_logp, adv (normalised), ret, -
   float* bred = p; p += 2 * 4 * kPH;              // bias-gradient partials [b1 | b2][wave][64]
   float* red = p; p += 8;
-  float* sred = p; p += 32;                       // per wave: the four components of dbo and of dlog_std over its samples
+  float* sred = p; p += 4 * SR;                   // per wave: the four components of dbo and of dlog_std over its samples (six actions:
+                                                  // [0, 4) dbo, [4, 8) dlog_std of components 0-3, [8, 10) dbo, [12, 14) dlog_std of 4-5)
   float* sink = p; p += kPThreads;                // one word per thread: where the Adam of a W1 tile "updates" the rows the network does not have
   float* red8 = p; p += 2 * kPMaxSplit;           // (RS) the blocks' shares of the squared gradient norm, [net][part]
 
   // flat offsets of this net
-  const int nP0 = ppo_net_params(Dp, 4);
+  const int nP0 = ppo_net_params(Dp, NA);
   const int oW1 = n == 0 ? 0 : nP0, ob1 = oW1 + Dp * kPH, oW2 = ob1 + kPH, ob2 = oW2 + kPH * kPH, oWo = ob2 + kPH;
   const int oLs = nP0 + ppo_net_params(Dp, 1);
 
@@ -463,7 +524,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
   for (int i = t; i < kPH; i += kPThreads) { W.b1[i] = params[ob1 + i]; W.b2[i] = params[ob2 + i]; }
   for (int i = t; i < kPH * kPH; i += kPThreads) W.W2[(i >> 6) * kPLdh + (i & 63)] = params[oW2 + i];
   for (int i = t; i < kPH * KO + KO; i += kPThreads) W.Wo[i] = params[oWo + i];              // Wo and bo are contiguous in both images
-  if (t < 4) log_std[t] = params[oLs + t];
+  if (t < NA) log_std[t] = params[oLs + t];
   for (int i = t; i < CH * ldx + 64; i += kPThreads) X[i] = 0.f;                                // incl. the pad the dW1 tiles read
   __syncthreads();
 
@@ -527,20 +588,20 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
   // chunk ahead -- float4 e of the chunk by thread e % 256 in pass e / 256 (coalesced: a wave-level load is 1 KB in a row) --
   // and scattered to X / sA / sS when the chunk's turn comes.  Where a float4 lands is the same for every chunk: computed once.
   const int cpm = B / CH;
-  const int W4 = ((D + 3) >> 2) + 2, npass = (CH * W4 + kPThreads - 1) / kPThreads;      // 64 samples: 9 float4s per row, 3 passes (obs 28); 16, 4 (obs 56); 18, 5 (obs 64)
+  const int W4 = ((D + 3) >> 2) + 1 + NAQ, npass = (CH * W4 + kPThreads - 1) / kPThreads;      // 64 samples: 9 float4s per row, 3 passes (obs 28); 16, 4 (obs 56); 18, 5 (obs 64)
   typedef float ppo_x4 __attribute__((ext_vector_type(4)));
   constexpr int kPass = 5;                           // 64 rows x (16 + 2) float4s / 256 threads, rounded up (obs 57 .. 64; 28: 3, 56: 4)
   ppo_x4 pre_x[kPass];
   int pre_dst[kPass];                                    // LDS destination (float offset) of pass p's float4; < 0: nothing of mine / not this network's
   {
-    const int Dv4 = W4 - 2;
+    const int Dv4 = W4 - 1 - NAQ;
 #pragma unroll
     for (int p_ = 0; p_ < kPass; ++p_) {
       const int e = t + p_ * kPThreads, row = e / W4, q = e - row * W4;
       int d = -1;
       if (p_ < npass && e < CH * W4) {
         if (q < Dv4) d = (int)(X - lds) + row * ldx + 4 * q;          // (the row's zero padding lands on columns that hold zero anyway)
-        else if (q == Dv4) d = NET == 0 ? (int)(sA - lds) + row * 4 : -1;
+        else if (NAQ == 1 ? q == Dv4 : q < Dv4 + NAQ) d = NET == 0 ? (int)(sA - lds) + row * SA + 4 * (q - Dv4) : -1;
         else d = (int)(sS - lds) + row * 4;                           // old log-prob, advantage (normalised), return, -
       }
       pre_dst[p_] = d;
@@ -599,12 +660,14 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
       else { pm[1][q] = make_float4(0.f, 0.f, 0.f, 0.f); pv[1][q] = pm[1][q]; }
     }
   }
-  // per-thread elements: b1[t], b2[t] (t < 64), bo[t] (t < KO), Wo[t / 4][t % 4] (t % 4 < KO), log_std[t] (t < 4, pi block)
-  constexpr int NQ = NET == 0 ? 5 : 4;
+  // per-thread elements: b1[t], b2[t] (t < 64), bo[t] (t < KO), Wo[t / 4][t % 4] (t % 4 < KO), six actions: Wo[t / 4][4 + t % 4]
+  // (t % 4 < 2), log_std[t] (t < NA, pi block)
+  constexpr int NQ = NET == 0 ? (A6 ? 6 : 5) : 4;
   int sl[NQ];
   float smm[NQ], svv[NQ];
   sl[0] = kPTileSlots + (n * 3 + 0) * kPThreads + t; sl[1] = kPTileSlots + (n * 3 + 1) * kPThreads + t;
   sl[2] = kPTileSlots + (n * 3 + 2) * kPThreads + t; sl[3] = kPTileSlots + (7 + n) * kPThreads + t;
+  if constexpr (A6) sl[4] = kPTileSlots + 9 * kPThreads + t;
   if (NET == 0) sl[NQ - 1] = kPTileSlots + 6 * kPThreads + t;
 #pragma unroll
   for (int q = 0; q < NQ; ++q) { smm[q] = mom_m[sl[q]]; svv[q] = mom_v[sl[q]]; }
@@ -622,11 +685,14 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
     // (policy head: log_std and 1 / sigma^2 of the action component this lane takes -- they only change with the Adam step)
     const float ls_c = NET == 0 ? log_std[(t % HSL) & 3] : 0.f;
     const float iv_c = NET == 0 ? expf(-2.0f * ls_c) : 0.f;
+    const float ls_c2 = A6 ? log_std[A6 ? 4 + ((t % HSL) & 1) : 0] : 0.f;      // (six actions: component 4 + hc of the lanes with hc < 2)
+    const float iv_c2 = A6 ? expf(-2.0f * ls_c2) : 0.f;
     // gradient accumulators of this minibatch (registers)
     f32x16 gW2, gW1;
     float gb1p = 0.f, gb2p = 0.f;                                     // column-sum partials of this thread's 16 rows
     float gWoq[KO];                                                   // dWo[hidden unit us][0 .. KO) over sample quarter uq of every chunk
     float gbo_p = 0.f, gls_p = 0.f;                                   // component hq of dbo / dlog_std over this thread's samples
+    float gbo_p2 = 0.f, gls_p2 = 0.f;                                 // (six actions) component 4 + hq of them, hq < 2
 #pragma unroll
     for (int v = 0; v < 16; ++v) { gW2[v] = 0.f; gW1[v] = 0.f; }
 #pragma unroll
@@ -740,25 +806,34 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
         const int s = hs, hc = hq & 3;
         float hv[HPER];
         float4 w4[HPER];
+        float2 w2[HPER];                                              // (six actions: components 4, 5 of the row)
         const float* h2 = H2 + hs * kPLdh + HPER * hq;
         const float* wo = W.Wo + HPER * hq * KO;
 #pragma unroll
         for (int j = 0; j < HPER; ++j) {
           hv[j] = h2[j];
           if (KO == 4) w4[j] = reinterpret_cast<const float4*>(wo)[j];
+          else if (KO == 6) {                                         // (rows of 24 bytes: three 8-byte loads)
+            const float2* r2 = reinterpret_cast<const float2*>(wo + 6 * j);
+            const float2 a = r2[0], b = r2[1];
+            w4[j] = make_float4(a.x, a.y, b.x, b.y); w2[j] = r2[2];
+          }
           else w4[j] = make_float4(wo[j], 0.f, 0.f, 0.f);
         }
-        const float bo_c = W.bo[KO == 4 ? hc : 0];
-        float act_c = 0.f, old_lp = 0.f, adv_s = 0.f, ret_s = 0.f;
-        if (NET == 0) { act_c = sA[s * 4 + hc]; const float2 sv = *reinterpret_cast<const float2*>(sS + s * 4); old_lp = sv.x; adv_s = sv.y; }
+        const float bo_c = W.bo[KO >= 4 ? hc : 0];
+        const float bo_c2 = A6 ? W.bo[A6 ? 4 + (hc & 1) : 0] : 0.f;
+        float act_c = 0.f, act_c2 = 0.f, old_lp = 0.f, adv_s = 0.f, ret_s = 0.f;
+        if (NET == 0) { act_c = sA[s * SA + hc]; const float2 sv = *reinterpret_cast<const float2*>(sS + s * 4); old_lp = sv.x; adv_s = sv.y; }
         else ret_s = sS[s * 4 + 2];
+        if constexpr (A6) act_c2 = sA[s * SA + 4 + (hc & 1)];
         float o[KO];
 #pragma unroll
         for (int k = 0; k < KO; ++k) o[k] = 0.f;
 #pragma unroll
         for (int j = 0; j < HPER; ++j) {
           o[0] += hv[j] * w4[j].x;
-          if (KO == 4) { o[KO > 1 ? 1 : 0] += hv[j] * w4[j].y; o[KO > 2 ? 2 : 0] += hv[j] * w4[j].z; o[KO > 3 ? 3 : 0] += hv[j] * w4[j].w; }
+          if (KO >= 4) { o[KO > 1 ? 1 : 0] += hv[j] * w4[j].y; o[KO > 2 ? 2 : 0] += hv[j] * w4[j].z; o[KO > 3 ? 3 : 0] += hv[j] * w4[j].w; }
+          if (KO == 6) { o[KO > 4 ? 4 : 0] += hv[j] * w2[j].x; o[KO > 5 ? 5 : 0] += hv[j] * w2[j].y; }
         }
 #pragma unroll
         for (int k = 0; k < KO; ++k) {
@@ -774,6 +849,12 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
           const float ls = ls_c, iv = iv_c;                   // log_std and 1 / sigma^2 of component hc: per minibatch (see the top of the loop)
           const float z = act_c - mu;
           float logp = -0.5f * z * z * iv - ls - 0.9189385332046727f;
+          // (six actions: lanes hc = 0, 1 of the quad also take components 4, 5 -- the quad's sum below is then over all six)
+          float z2 = 0.f;
+          if constexpr (A6) {
+            z2 = act_c2 - ((hc & 1 ? o[KO > 5 ? 5 : 0] : o[KO > 4 ? 4 : 0]) + bo_c2);
+            if (hc < 2) logp += -0.5f * z2 * z2 * iv_c2 - ls_c2 - 0.9189385332046727f;
+          }
           logp += ppo_dpp<kDppXor1>(logp); logp += ppo_dpp<kDppXor2>(logp);
           const float a = adv_s;
           const float ratio = expf(logp - old_lp);
@@ -789,12 +870,19 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
           const float g = coef * z * iv;                                  // dL/dmu_k = dL/dlogp * (a_k - mu_k) / sigma_k^2
           gls_p += hl ? coef * (z * z * iv - 1.0f) : 0.f;                 // dL/dlog_std_k of this thread's samples
           gbo_p += hl ? g : 0.f;
-          if (hl) gout[s * 4 + hc] = g;
+          if (hl) gout[s * SA + hc] = g;
+          if constexpr (A6) {
+            const bool hl2 = hl && hc < 2;
+            const float g2 = coef * z2 * iv_c2;
+            gls_p2 += hl2 ? coef * (z2 * z2 * iv_c2 - 1.0f) : 0.f;
+            gbo_p2 += hl2 ? g2 : 0.f;
+            if (hl2) gout[s * SA + 4 + hc] = g2;
+          }
         } else {
           const float dv = (o[0] + bo_c) - ret_s;
           if (hq == 0) acc_l += dv * dv;
           const float g = H.vf_coef * 2.0f * dv * invB;
-          if (hq == 0) { gout[s * 4] = g; gbo_p += g; }
+          if (hq == 0) { gout[s * SA] = g; gbo_p += g; }
         }
       }
       __syncthreads();
@@ -802,21 +890,26 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
       // ---- dWo += H2^T gout (before H2 is overwritten): thread (hidden unit us, quarter uq) over a quarter of the chunk's samples ----
       {
         const float* h2 = H2 + (CH / 4) * uq * kPLdh + us;
-        const float* go = gout + (CH / 4) * uq * 4;
+        const float* go = gout + (CH / 4) * uq * SA;
 #pragma unroll
         for (int j = 0; j < CH / 4; ++j) {
           const float h = h2[j * kPLdh];
           if (KO == 4) {
             const float4 g4 = reinterpret_cast<const float4*>(go)[j];
             gWoq[0] += h * g4.x; gWoq[KO > 1 ? 1 : 0] += h * g4.y; gWoq[KO > 2 ? 2 : 0] += h * g4.z; gWoq[KO > 3 ? 3 : 0] += h * g4.w;
+          } else if (KO == 6) {
+            const float4 g4 = *reinterpret_cast<const float4*>(go + j * SA);
+            const float2 g2 = *reinterpret_cast<const float2*>(go + j * SA + 4);
+            gWoq[0] += h * g4.x; gWoq[KO > 1 ? 1 : 0] += h * g4.y; gWoq[KO > 2 ? 2 : 0] += h * g4.z; gWoq[KO > 3 ? 3 : 0] += h * g4.w;
+            gWoq[KO > 4 ? 4 : 0] += h * g2.x; gWoq[KO > 5 ? 5 : 0] += h * g2.y;
           } else {
-            gWoq[0] += h * go[j * 4];
+            gWoq[0] += h * go[j * SA];
           }
         }
       }
       __syncthreads();
       PPO_PHASE(3);
-      // ---- G2 = (gout Wo^T) * (1 - H2^2), in place over H2 (K = KO <= 4) ----
+      // ---- G2 = (gout Wo^T) * (1 - H2^2), in place over H2 (K = KO <= 6) ----
       if constexpr (CH != 64) {
         float* hp = H2 + (g16 * 4) * kPLdh + wave * 16 + l16;
         float hv[RT][4];
@@ -826,11 +919,14 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
           for (int v = 0; v < 4; ++v) hv[rt][v] = hp[(16 * rt + v) * kPLdh];
         const int k = g16 < KO ? g16 : 0;
         const float bv = g16 < KO ? W.Wo[(wave * 16 + l16) * KO + k] : 0.f;
+        const bool on2 = KO > 4 && g16 + 4 < KO;                    // (six actions: a second K = 4 step over components 4, 5)
+        const float bv2 = on2 ? W.Wo[(wave * 16 + l16) * KO + 4 + (on2 ? g16 : 0)] : 0.f;
         const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) {
-          const float av = g16 < KO ? gout[(16 * rt + l16) * 4 + k] : 0.f;
-          const f32x4 c = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, z4, 0, 0, 0);
+          const float av = g16 < KO ? gout[(16 * rt + l16) * SA + k] : 0.f;
+          f32x4 c = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, z4, 0, 0, 0);
+          if constexpr (KO > 4) c = __builtin_amdgcn_mfma_f32_16x16x4f32(on2 ? gout[(16 * rt + l16) * SA + 4 + (on2 ? g16 : 0)] : 0.f, bv2, c, 0, 0, 0);
 #pragma unroll
           for (int v = 0; v < 4; ++v) hv[rt][v] = c[v] * (1.0f - hv[rt][v] * hv[rt][v]);
         }
@@ -851,7 +947,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
 #pragma unroll
         for (int k0 = 0; k0 < KO; k0 += 2) {
           const int k = k0 + hh;
-          const float av = k < KO ? gout[(mt * 32 + r) * 4 + (k < KO ? k : 0)] : 0.f;
+          const float av = k < KO ? gout[(mt * 32 + r) * SA + (k < KO ? k : 0)] : 0.f;
           const float bv = k < KO ? W.Wo[(nt * 32 + r) * KO + (k < KO ? k : 0)] : 0.f;
           c = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, c, 0, 0, 0);
         }
@@ -923,23 +1019,30 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
 #endif
     // ---- finish the per-thread gradients: the four row-block partials of the biases; dWo over the quad's sample quarters;
     // dbo / dlog_std component hq over all samples ----
-    float my_gwo = 0.f;
+    float my_gwo = 0.f, my_gwo2 = 0.f;                 // Wo[us][uq]; six actions: Wo[us][4 + uq] (uq < 2)
 #pragma unroll
     for (int k = 0; k < KO; ++k) {
       float g = gWoq[k];
       g += ppo_dpp<kDppXor1>(g); g += ppo_dpp<kDppXor2>(g);
       if (uq == k) my_gwo = g;
+      if (A6 && uq + 4 == k) my_gwo2 = g;
     }
     // component (lane % HSL) over the wave's lanes: rotations inside the row, then across the rows
     if (HSL == 4) { gbo_p += ppo_dpp<kDppRor4>(gbo_p); if (NET == 0) gls_p += ppo_dpp<kDppRor4>(gls_p); }
     if (HSL <= 8) { gbo_p += ppo_dpp<kDppRor8>(gbo_p); if (NET == 0) gls_p += ppo_dpp<kDppRor8>(gls_p); }
     gbo_p = ppo_sum_rows(gbo_p);
     if (NET == 0) gls_p = ppo_sum_rows(gls_p);
+    if constexpr (A6) {
+      if (HSL == 4) { gbo_p2 += ppo_dpp<kDppRor4>(gbo_p2); gls_p2 += ppo_dpp<kDppRor4>(gls_p2); }
+      if (HSL <= 8) { gbo_p2 += ppo_dpp<kDppRor8>(gbo_p2); gls_p2 += ppo_dpp<kDppRor8>(gls_p2); }
+      gbo_p2 = ppo_sum_rows(gbo_p2); gls_p2 = ppo_sum_rows(gls_p2);
+    }
     // (no barrier in front: the previous readers of bred / sred are behind the barriers of the norm exchange and of the end of the
     // previous minibatch; H2, which carries dW1's split partials, was last read in the G1 phase, a barrier ago -- H1 is still being
     // read by slower waves' dW1)
     bred[wave * kPH + lane] = gb1p; bred[(4 + wave) * kPH + lane] = gb2p;
-    if (lane < 4) { sred[wave * 8 + lane] = gbo_p; sred[wave * 8 + 4 + lane] = gls_p; }
+    if (lane < 4) { sred[wave * SR + lane] = gbo_p; sred[wave * SR + 4 + lane] = gls_p; }
+    if constexpr (A6) { if (lane < 2) { sred[wave * SR + 8 + lane] = gbo_p2; sred[wave * SR + 12 + lane] = gls_p2; } }
     if (splitW1 && wave >= 2) {                    // the second sample half of dW1's two tiles, to its owners (waves 0, 1) through H2's space
       float* hx = H2 + (wave - 2) * 64 + lane;      // [element][wave][lane]: conflict-free dwords (2048 floats; H2 is not 16-byte aligned for KO = 1)
 #pragma unroll
@@ -957,10 +1060,18 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
       for (int q = 0; q < 4; ++q) { gb1 += bred[q * kPH + t]; gb2 += bred[(4 + q) * kPH + t]; }
     }
     float my_gbo = 0.f, my_gls = 0.f;
-    if (t < 4) {
+    if (NA == 4 && t < 4) {
       if (t < KO) my_gbo = sred[t] + sred[8 + t] + sred[16 + t] + sred[24 + t];
       if (NET == 0) {
         my_gls = sred[4 + t] + sred[12 + t] + sred[20 + t] + sred[28 + t];
+        if (part == 0) my_gls -= H.ent_coef;   // entropy bonus: entropy_loss = -mean(sum_k (c + log_std_k)) -> d/dlog_std_k = -ent_coef (once)
+      }
+    }
+    if (NA == 6 && t < 6) {                       // (component t of the six-action sred layout, see the carve-up)
+      const int ib = t >= 4 ? t + 4 : t, ig = t >= 4 ? t + 8 : 4 + t;
+      if (t < KO) my_gbo = sred[ib] + sred[SR + ib] + sred[2 * SR + ib] + sred[3 * SR + ib];
+      if (NET == 0) {
+        my_gls = sred[ig] + sred[SR + ig] + sred[2 * SR + ig] + sred[3 * SR + ig];
         if (part == 0) my_gls -= H.ent_coef;   // entropy bonus: entropy_loss = -mean(sum_k (c + log_std_k)) -> d/dlog_std_k = -ent_coef (once)
       }
     }
@@ -978,9 +1089,9 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
       // (uniform for the compiler with eight blocks only -- measured on one box, product builds, us per minibatch: (28, 128) 7.79 -> 7.62;
       // with four blocks the burst of fetches it allows costs more elsewhere than it saves: (56, 64) 7.59 -> 7.72, (28, 64) 7.23 -> 7.20;
       // and never for the all-gather, whose readers poll: 7.62 -> 7.71 and 7.72 -> 7.86)
-      float* gxb = A.gx + (size_t)((mb & 1) * 2 + NET) * kPMaxSplit * kPGxSlots;
+      float* gxb = A.gx + (size_t)((mb & 1) * 2 + NET) * kPMaxSplit * GXS;
       if constexpr (NS == 8) gxb = ppo_uniform_ptr(gxb);
-      float* mine = gxb + (size_t)part * kPGxSlots;
+      float* mine = gxb + (size_t)part * GXS;
       unsigned long long* fl = A.xch + kPpoWordFlags + ((mb & 1) * 2 + NET) * kPMaxSplit;
       const int g0 = ppo_gx_tile(0, wave, lane), g1 = ppo_gx_tile(1, wave, lane);
       // Plain vector stores, partner loads past the L1, bracketed by a device-scope release (every storing wave, before the barrier
@@ -993,11 +1104,12 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
       typedef unsigned int ppo_u4 __attribute__((ext_vector_type(4)));
       typedef float ppo_f4 __attribute__((ext_vector_type(4)));
       float qs[NSETS][NSd][4];                     // RS: my sets in every block's partial, in block order
-      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(gxb, 0, kPMaxSplit * kPGxSlots * (int)sizeof(float), 0x00020000);
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(gxb, 0, kPMaxSplit * GXS * (int)sizeof(float), 0x00020000);
       ppo_store_tile(mine + ppo_gx_tile(0, wave, 0), lane, gW2);
       if (hasW1) ppo_store_tile(mine + ppo_gx_tile(1, wave, 0), lane, gW1);
       // (per-thread elements: Wo's by every thread, the biases / log_std -- one float4 -- by threads of the first wave only)
       mine[sqo] = my_gwo;
+      if constexpr (A6) mine[kPGxWo2 + t] = my_gwo2;
       if (wave == 0) *reinterpret_cast<float4*>(mine + sq4) = make_float4(gb1, gb2, my_gbo, my_gls);
       // (the builtin, not inline assembly: the compiler's own wait-count bookkeeping must see that the stores are done, or it waits for
       // them one by one between the loads further down -- and with them, in order, for those loads)
@@ -1038,7 +1150,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
       // assembly with a hand-placed wait; the compiler, not knowing that they were loads, put waits for older operations between
       // them, which -- the counter retires in order -- serialised the partners: 4.3 k cycles for 39 loads.)
       ppo_f4 ta[3][4], tb[3][4];                   // all-to-all form: partner j of 1 (2 blocks) or 3 (4 blocks) = the other blocks in ascending order
-      float vs[5][NSd];                            // per-thread elements {gb1, gb2, gbo, gls, gwo} of every block, in block order (own ones in slot `part`)
+      float vs[A6 ? 6 : 5][NSd];                   // per-thread elements {gb1, gb2, gbo, gls, gwo (, gwo2)} of every block, in block order (own ones in slot `part`)
       const int np = nsplit - 1;
       if (!same_xcd) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
       constexpr int kSc1 = 16;                     // cache-policy bit of the raw buffer loads
@@ -1048,7 +1160,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
           const int o = (ppo_gx_tile(set_kind[s_], tq, lane) + set_q[s_] * 256) * (int)sizeof(float);
           if (set_own[s_]) {                       // (ONE branch around all the loads of a set, never one per load: see the note below)
 #pragma unroll
-            for (int b_ = 0; b_ < NS; ++b_) ppo_ld_sc1(rs, (b_ ^ part) * kPGxSlots * (int)sizeof(float) + o, qs[s_][b_]);      // (own partial included: it comes back from the L2 my stores went to)
+            for (int b_ = 0; b_ < NS; ++b_) ppo_ld_sc1(rs, (b_ ^ part) * GXS * (int)sizeof(float) + o, qs[s_][b_]);      // (own partial included: it comes back from the L2 my stores went to)
           } else {
 #pragma unroll
             for (int b_ = 0; b_ < NS; ++b_)
@@ -1059,7 +1171,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
       } else {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
-          const int base = (j < part ? j : j + 1) * kPGxSlots * (int)sizeof(float);
+          const int base = (j < part ? j : j + 1) * GXS * (int)sizeof(float);
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             if (j < np) {
@@ -1078,12 +1190,16 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
       // not used) and the choice is a select afterwards: a load inside a branch on `part` makes the compiler wait for it at the join,
       // one L2 round trip after the other (measured: loads 3.0 k -> 4.3 k cycles with four blocks, 6.7 k with eight).
       ppo_u4 va[NSd];
-      unsigned vo[NSd];
+      unsigned vo[NSd], vo2[NSd];
 #pragma unroll
-      for (int b_ = 0; b_ < NSd; ++b_) vo[b_] = __builtin_amdgcn_raw_buffer_load_b32(rs, (b_ ^ part) * kPGxSlots * (int)sizeof(float) + sqo * 4, 0, kSc1);      // ALL the loads first ...
+      for (int b_ = 0; b_ < NSd; ++b_) vo[b_] = __builtin_amdgcn_raw_buffer_load_b32(rs, (b_ ^ part) * GXS * (int)sizeof(float) + sqo * 4, 0, kSc1);      // ALL the loads first ...
+      if constexpr (A6) {
+#pragma unroll
+        for (int b_ = 0; b_ < NSd; ++b_) vo2[b_] = __builtin_amdgcn_raw_buffer_load_b32(rs, (b_ ^ part) * GXS * (int)sizeof(float) + (kPGxWo2 + t) * 4, 0, kSc1);
+      }
       if (wave == 0) {                             // (one branch, the last loads of the section: the wait at its join is the wait for everything anyway)
 #pragma unroll
-        for (int b_ = 0; b_ < NSd; ++b_) va[b_] = __builtin_amdgcn_raw_buffer_load_b128(rs, (b_ ^ part) * kPGxSlots * (int)sizeof(float) + sq4 * 4, 0, kSc1);
+        for (int b_ = 0; b_ < NSd; ++b_) va[b_] = __builtin_amdgcn_raw_buffer_load_b128(rs, (b_ ^ part) * GXS * (int)sizeof(float) + sq4 * 4, 0, kSc1);
       } else {
 #pragma unroll
         for (int b_ = 0; b_ < NSd; ++b_) va[b_] = ppo_u4{0u, 0u, 0u, 0u};
@@ -1099,6 +1215,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
         vs[2][b_] = b_ == 0 ? my_gbo : other ? __uint_as_float(va[b_][2]) : 0.f;
         vs[3][b_] = b_ == 0 ? my_gls : other ? __uint_as_float(va[b_][3]) : 0.f;
         vs[4][b_] = b_ == 0 ? my_gwo : other ? __uint_as_float(vo[b_]) : 0.f;
+        if constexpr (A6) vs[A6 ? 5 : 0][b_] = b_ == 0 ? my_gwo2 : other ? __uint_as_float(vo2[b_]) : 0.f;
       }
       PPO_HO(4);
       // WHICH block's partial a slot holds: slot i = block i ^ part.  At every step of the fetch the blocks of a network are then at
@@ -1140,6 +1257,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
         }
       }
       gb1 = tree(vs[0]); gb2 = tree(vs[1]); my_gbo = tree(vs[2]); my_gls = tree(vs[3]); my_gwo = tree(vs[4]);
+      if constexpr (A6) my_gwo2 = tree(vs[A6 ? 5 : 0]);
       PPO_HO(5);
     }
 
@@ -1170,7 +1288,8 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
       if (t < kPH) ss += gb1 * gb1 + gb2 * gb2;
       if (t < KO) ss += my_gbo * my_gbo;
       if (uq < KO) ss += my_gwo * my_gwo;
-      if (NET == 0 && t < 4) ss += my_gls * my_gls;
+      if (A6 && uq < 2) ss += my_gwo2 * my_gwo2;
+      if (NET == 0 && t < NA) ss += my_gls * my_gls;
     }
     const float ss_mine = ppo_block_sum_nb(ss, red);      // (red[0..3] were last read before the previous minibatch's closing barrier)
     float ss_other = 0.f;
@@ -1248,7 +1367,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
 #pragma unroll
       for (int v = 0; v < 16; ++v) *lds_of(v) = wv[v] - upd[v];
     };
-    float* const wxn = A.gx + (size_t)NET * kPMaxSplit * kPGxSlots + (kPGxTile + 2 * kPThreads);      // (RS) this network's weight shares: part p's at + p * kPGxSlots, [set][wave * 64 + lane][4]
+    float* const wxn = A.gx + (size_t)NET * kPMaxSplit * GXS + (kPGxTile + 2 * kPThreads);      // (RS) this network's weight shares: part p's at + p * GXS, [set][wave * 64 + lane][4]
     unsigned long long* const fl2 = A.xch + kPpoWordFlags2 + ((mb & 1) * 2 + NET) * kPMaxSplit;
     if constexpr (RS) {
       // Adam on the share this block owns: 4 elements per set; the new weights go to this block's LDS image and to the exchange
@@ -1279,7 +1398,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
       for (int s_ = 0; s_ < NSETS; ++s_) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) *wp[s_][e] = wv[s_][e];
-        if (!(TAGGED && same_xcd) && set_own[s_]) *reinterpret_cast<float4*>(wxn + (size_t)part * kPGxSlots + (s_ * kPThreads + t) * 4) = make_float4(wv[s_][0], wv[s_][1], wv[s_][2], wv[s_][3]);
+        if (!(TAGGED && same_xcd) && set_own[s_]) *reinterpret_cast<float4*>(wxn + (size_t)part * GXS + (s_ * kPThreads + t) * 4) = make_float4(wv[s_][0], wv[s_][1], wv[s_][2], wv[s_][3]);
       }
       if (TAGGED && same_xcd) {
         // SELF-ANNOUNCING shares (blocks on one XCD): a thread's new weights leave as 16-byte granules of three floats and a TAG (the
@@ -1287,7 +1406,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
         // for the stores, no barrier, no flag, no poll of a flag: one hop between CUs instead of two (the flag's took 0.65 k cycles of
         // waiting behind 0.5 k of draining).  A 16-byte aligned store is one request to the L2: a reader sees all of a granule or
         // none of it; granules nobody needs (W1 shares nobody owns) are written all the same, so that every tag can be waited for.
-        float* gp = wxn + (size_t)part * kPGxSlots + t * 4;
+        float* gp = wxn + (size_t)part * GXS + t * 4;
         const float tagf = __uint_as_float((unsigned)(mb + 1));
         if constexpr (NSETS == 2) {
           *reinterpret_cast<float4*>(gp) = make_float4(wv[0][0], wv[0][1], wv[0][2], tagf);
@@ -1318,7 +1437,8 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
       gs[1] = gb2; ws[1] = t < kPH ? W.b2 + t : nullptr;
       gs[2] = my_gbo; ws[2] = t < KO ? W.bo + t : nullptr;
       gs[3] = my_gwo; ws[3] = uq < KO ? W.Wo + us * KO + uq : nullptr;
-      if (NET == 0) { gs[NQ - 1] = my_gls; ws[NQ - 1] = t < 4 ? log_std + t : nullptr; }
+      if constexpr (A6) { gs[4] = my_gwo2; ws[4] = uq < 2 ? W.Wo + us * KO + 4 + uq : nullptr; }
+      if (NET == 0) { gs[NQ - 1] = my_gls; ws[NQ - 1] = t < NA ? log_std + t : nullptr; }
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
         const float gg = gs[q] * clipc;
@@ -1334,7 +1454,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
     if constexpr (RS) {
       // ---- all-gather of the updated weights: the other NS - 1 shares, from the blocks that own them ----
       float wg[NS - 1][NSETS][4];
-      const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(wxn, 0, kPMaxSplit * kPGxSlots * (int)sizeof(float), 0x00020000);
+      const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(wxn, 0, kPMaxSplit * GXS * (int)sizeof(float), 0x00020000);
       if (TAGGED && same_xcd) {
         // every wave polls the granules it needs itself (no block-wide wait): fetch all of them, look at the tags, again if one is old
         constexpr int NG = NSETS == 2 ? 3 : 2;
@@ -1347,7 +1467,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
           for (int j = 0; j < NS - 1; ++j) {
             const int pj = (j + 1) ^ part;         // (every block at a different partner at every step, as in the reduce-scatter)
 #pragma unroll
-            for (int g = 0; g < NG; ++g) ppo_ld_sc1(rsw, (int)((pj * kPGxSlots + (g * kPThreads + t) * 4) * sizeof(float)), gr[j][g]);
+            for (int g = 0; g < NG; ++g) ppo_ld_sc1(rsw, (int)((pj * GXS + (g * kPThreads + t) * 4) * sizeof(float)), gr[j][g]);
           }
           bool mine = true;
 #pragma unroll
@@ -1383,7 +1503,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
         for (int j = 0; j < NS - 1; ++j) {
           const int pj = (j + 1) ^ part;
 #pragma unroll
-          for (int s_ = 0; s_ < NSETS; ++s_) ppo_ld_sc1(rsw, (int)((pj * kPGxSlots + (s_ * kPThreads + t) * 4) * sizeof(float)), wg[j][s_]);
+          for (int s_ = 0; s_ < NSETS; ++s_) ppo_ld_sc1(rsw, (int)((pj * GXS + (s_ * kPThreads + t) * 4) * sizeof(float)), wg[j][s_]);
         }
       }
       // partner thread (w, l) of block pj wrote what its sets are: the same wave and lane as mine, block pj's tiles and quarters.
@@ -1467,7 +1587,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
     for (int i = t; i < kPH; i += kPThreads) { params[ob1 + i] = W.b1[i]; params[ob2 + i] = W.b2[i]; }
     for (int i = t; i < kPH * kPH; i += kPThreads) params[oW2 + i] = W.W2[(i >> 6) * kPLdh + (i & 63)];
     for (int i = t; i < kPH * KO + KO; i += kPThreads) params[oWo + i] = W.Wo[i];
-    if (NET == 0 && t < 4) params[oLs + t] = log_std[t];
+    if (NET == 0 && t < NA) params[oLs + t] = log_std[t];
   }
   const float lsum = ppo_block_sum(acc_l, red);
   if (t == 0 && A.loss_acc) {
@@ -1485,7 +1605,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
     }
     if (NET == 0 && part == 0) {
       float ent = 0.f;
-      for (int k = 0; k < 4; ++k) ent += 1.4189385332046727f + log_std[k];
+      for (int k = 0; k < NA; ++k) ent += 1.4189385332046727f + log_std[k];
       atomicAdd(&A.loss_acc[2], -ent * (float)n_mb);                  // entropy loss at the final log_std (it is state-independent)
     }
 #ifdef FW_PPO_PROF
@@ -1513,7 +1633,16 @@ __global__ __launch_bounds__(kPThreads) void fw_ppo_update_kernel(PpoArgs A) {
   if (blockIdx.x & 7) return;
   const int i = (int)blockIdx.x >> 3;
   const int part = i >> 1, nsplit = NS ? NS : (int)gridDim.x >> 4;
-  if ((i & 1) == 0) ppo_net_body<0, CH, NS>(A, lds, part, nsplit); else ppo_net_body<1, CH, NS>(A, lds, part, nsplit);
+  if ((i & 1) == 0) ppo_net_body<0, CH, NS, 4>(A, lds, part, nsplit); else ppo_net_body<1, CH, NS, 4>(A, lds, part, nsplit);
+}
+// the same for a six-action policy head (the low-level control task): every cut, the same grid
+template <int CH, int NS>
+__global__ __launch_bounds__(kPThreads) void fw_ppo_update_kernel_a6(PpoArgs A) {
+  extern __shared__ __align__(16) float lds[];
+  if (blockIdx.x & 7) return;
+  const int i = (int)blockIdx.x >> 3;
+  const int part = i >> 1, nsplit = NS ? NS : (int)gridDim.x >> 4;
+  if ((i & 1) == 0) ppo_net_body<0, CH, NS, 6>(A, lds, part, nsplit); else ppo_net_body<1, CH, NS, 6>(A, lds, part, nsplit);
 }
 
 // How a minibatch of B samples is cut: samples per pass (64, 32 or 16) and blocks per network.  The path is sequential, so the
@@ -1532,11 +1661,11 @@ inline PpoSplit ppo_split(int B, int max_blocks = kPMaxSplit) {
   return best;
 }
 
-inline size_t ppo_lds_bytes(int D) {
+inline size_t ppo_lds_bytes(int D, int NA = 4) {
   (void)D;                                          // (sized for the larger of the two forms: W1 as 64 rows of 65)
-  const int ldx = kPLdx;
-  size_t f = (size_t)(kPH * kPLdh + kPH + kPH * kPLdh + kPH + kPH * 4 + 4) + 4 + (size_t)kPChunk * ldx + 64 + 2 * (size_t)kPChunk * kPLdh +
-             3 * (size_t)kPChunk * 4 + 8 * kPH + 8 + 32 + kPThreads + 2 * kPMaxSplit;
+  const int ldx = kPLdx, SA = NA == 6 ? 8 : 4;
+  size_t f = (size_t)(kPH * kPLdh + kPH + kPH * kPLdh + kPH + kPH * NA + NA) + NA + (size_t)kPChunk * ldx + 64 + 2 * (size_t)kPChunk * kPLdh +
+             (2 * (size_t)SA + 4) * kPChunk + 8 * kPH + 8 + 4 * (NA == 6 ? 16 : 8) + kPThreads + 2 * kPMaxSplit;
   return f * sizeof(float);
 }
 

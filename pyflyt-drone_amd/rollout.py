@@ -557,6 +557,8 @@ class PPOConfig:
     image_res: int = 32                    #        side of the rendered image
     cnn_features: int = 32                 #        width of the extractor's output
     cnn_graphs: bool = True                #        replay the CNN rollout / minibatch step as hipGraphs (single process): update 2.4 -> 1.0 ms per 1024-sample minibatch
+    fused_six_actions: bool = False        # six-action policies (the low-level control task) on the fused learner too: fw_ppo_update_a and the
+                                           # three-launch collector (fw_collect_act_a -> fw_step -> fw_collect_stats); off: the torch path
     dist_update: str = "replicated"        # multi-process job: "replicated" = all-gather the rollout shards, every rank runs the same
                                            # minibatch sequence (no per-minibatch collective); "allreduce" = local minibatches + gradient all-reduce
 
@@ -574,13 +576,17 @@ class FusedPpoUpdate:
     def __init__(self, policy: "MlpPolicy", optimizer: torch.optim.Adam, obs_dim: int):
         self.policy, self.opt, self.D = policy, optimizer, obs_dim
         self.Dp = (obs_dim + 1) & ~1
+        self.A = int(policy.action_net.out_features)      # action width: 4, or 6 (the *_a entry points; 4 runs what the plain ones run)
         dev = policy.log_std.device
-        n = _lib.lib().fw_ppo_param_count(obs_dim)
+        L = _lib.lib()
+        n = L.fw_ppo_param_count_a(obs_dim, self.A)
+        if n < 0:
+            _lib.check(n)
         self.flat = torch.zeros(n, dtype=torch.float32, device=dev)
         self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)          # flat order (staging)
-        ns = _lib.lib().fw_ppo_moment_count()
+        ns = L.fw_ppo_moment_count_a(self.A)
         smap = np.empty(ns, dtype=np.int32)
-        _lib.check(_lib.lib().fw_ppo_moment_map(obs_dim, smap.ctypes.data_as(C.c_void_p)))
+        _lib.check(L.fw_ppo_moment_map_a(obs_dim, self.A, smap.ctypes.data_as(C.c_void_p)))
         owned = np.nonzero(smap >= 0)[0]
         self._slot = torch.as_tensor(owned, dtype=torch.long, device=dev)                  # owned slots ...
         self._flat_of_slot = torch.as_tensor(smap[owned], dtype=torch.long, device=dev)    # ... and their flat indices
@@ -596,24 +602,31 @@ class FusedPpoUpdate:
 
     def _workspace(self, n_mb: int, batch_size: int) -> torch.Tensor:
         # exchange words + gradient hand-off buffer + the packed rows of every minibatch (a parallel pre-pass of the call writes them)
-        need = int(_lib.lib().fw_ppo_update_workspace_bytes(n_mb, batch_size, self.D))
+        need = int(_lib.lib().fw_ppo_update_workspace_bytes_a(n_mb, batch_size, self.D, self.A))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.zeros(need, dtype=torch.uint8, device=self.flat.device)
         return self._ws
 
     @staticmethod
-    def fits(policy, obs_dim: int, device) -> bool:
+    def fits(policy, obs_dim: int, device, act_dims=(4,)) -> bool:
         """The kernels are written for the reference's MlpPolicy: two 64-64 tanh nets, 4 actions, obs_dim <= 64 (any number
-        of ranks: a sharded job runs them unchanged on every GPU)."""
+        of ranks: a sharded job runs them unchanged on every GPU).  ``act_dims=(4, 6)`` also admits the six-action head of the
+        low-level control task (PPOConfig.fused_six_actions)."""
         if getattr(policy, "uses_image", False) or not hasattr(policy, "pi_net"):
             return False                   # CNN front end: torch path (the fused kernels are the MlpPolicy's)
         lin = [m for m in list(policy.pi_net) + list(policy.vf_net) if isinstance(m, nn.Linear)]
         return (device.type == "cuda" and obs_dim <= 64 and len(lin) == 4
-                and all(m.out_features == 64 for m in lin) and policy.action_net.out_features == 4)
+                and all(m.out_features == 64 for m in lin) and policy.action_net.out_features in tuple(act_dims))
+
+    @staticmethod
+    def act_dims(cfg) -> tuple:
+        """The action widths the fused kernels take under ``cfg``: 4, and 6 when PPOConfig.fused_six_actions is on."""
+        return (4, 6) if getattr(cfg, "fused_six_actions", False) else (4,)
 
     @staticmethod
     def applies(policy, cfg, obs_dim: int, batch_size: int, device) -> bool:
-        return cfg.fused_update and batch_size % 16 == 0 and FusedPpoUpdate.fits(policy, obs_dim, device)
+        return (cfg.fused_update and batch_size % 16 == 0
+                and FusedPpoUpdate.fits(policy, obs_dim, device, FusedPpoUpdate.act_dims(cfg)))
 
     def _slots(self):
         """(tensor, flat offset, view shape in the flat image, needs transpose) per parameter, in layout order."""
@@ -627,7 +640,7 @@ class FusedPpoUpdate:
             out.append((l2.bias, off, (64,), False)); off += 64
             out.append((head.weight, off, (64, ko), True)); off += 64 * ko
             out.append((head.bias, off, (ko,), False)); off += ko
-        out.append((p.log_std, off, (4,), False)); off += 4
+        out.append((p.log_std, off, (self.A,), False)); off += self.A
         assert off == self.flat.numel()
         return out
 
@@ -717,9 +730,9 @@ class FusedPpoUpdate:
             assert x.dtype == torch.float32 and x.is_contiguous()
         assert perm_i32.dtype == torch.int32 and perm_i32.numel() == n_mb * cfg.batch_size
         ws = self._workspace(n_mb, cfg.batch_size)
-        rc = _lib.lib().fw_ppo_update(_p(self.flat), _p(self.mom_m), _p(self.mom_v), _p(obs), _p(act), _p(old_logp), _p(adv), _p(ret),
-                                      _p(perm_i32), n_mb, cfg.batch_size, self.D, C.byref(H), _p(self.loss), _p(ws), ws.numel(),
-                                      _stream(obs.device))
+        rc = _lib.lib().fw_ppo_update_a(_p(self.flat), _p(self.mom_m), _p(self.mom_v), _p(obs), _p(act), _p(old_logp), _p(adv), _p(ret),
+                                        _p(perm_i32), n_mb, cfg.batch_size, self.D, self.A, C.byref(H), _p(self.loss), _p(ws), ws.numel(),
+                                        _stream(obs.device))
         _lib.check(rc)
         # the workgroups of the launch wait for each other, every wait bounded: a wait that ran out leaves a status word behind and
         # (unless the closing verdict itself was lost) untouched images -- surface it BEFORE anything is written back to the module /
@@ -769,7 +782,7 @@ class PPO:
         # CNN front end: data-parallel minibatches + ONE flattened gradient all-reduce each (the images of a rollout are ~30x
         # the flat observations: gathering every rank's rollout on every rank is the wrong trade there)
         self._replicated = td is not None and cfg.dist_update == "replicated" and not self._img
-        self._fused_collect_ok = (bool(cfg.fused_collect) and FusedPpoUpdate.fits(self.policy, env.obs_dim, self.device)
+        self._fused_collect_ok = (bool(cfg.fused_collect) and FusedPpoUpdate.fits(self.policy, env.obs_dim, self.device, FusedPpoUpdate.act_dims(cfg))
                                   and getattr(env, "use_fused", False) and env.norm_obs and hasattr(env.venv, "step_tensor")
                                   and hasattr(env.venv, "terminal_obs") and hasattr(env.venv, "torch_dtype"))
         # hipGraph replay needs a collective-free body: always on one GPU; in a sharded job when the collector is fused
@@ -789,11 +802,13 @@ class PPO:
             self._fused = FusedPpoUpdate(self.policy, self.optimizer, env.obs_dim)
             self._rng = torch.tensor([cfg.seed * 7919 + 17, 0], dtype=torch.int64, device=self.device)      # seed, draw counter
             # (NaN = "not there yet": fw_collect_step's step waves see their actions replace it and put it back)
-            self._act_env = torch.full((env.num_envs, 4), float("nan"), dtype=env.venv.torch_dtype, device=self.device)
+            self._act_env = torch.full((env.num_envs, self.act_dim), float("nan"), dtype=env.venv.torch_dtype, device=self.device)
             self._tval = torch.zeros(env.num_envs, dtype=torch.float32, device=self.device)
         # one launch per vec-step (fw_collect_step) where the handle's lane mapping has it: 8 lanes per env (either build)
         # (fw_collect_step's act waves take observations of up to 62 features -- wider ones go through fw_collect_act, which takes 64)
+        # (four actions only: fw_collect_step / fw_collect_close have no six-action form -- a six-action policy takes the three launches)
         self._one_launch = (self._collect_fused and bool(cfg.one_launch_collect) and hasattr(env.venv, "_h") and env.obs_dim <= 62
+                            and self.act_dim == 4
                             and getattr(env.venv, "lanes_per_env", 0) == 8 and float(env.gamma) == float(cfg.gamma))
         self._void_recoverable = False
         self.collect_fallbacks = 0         # how many times a void rollout moved this object to the three-launch collector (0 or 1)
@@ -871,7 +886,7 @@ class PPO:
         ba = _p(self.buf_act[t]) if t is not None else None
         bl = _p(self.buf_logp[t]) if t is not None else None
         val = value_out if value_out is not None else (self.buf_val[t] if t is not None else None)
-        _lib.check(L.fw_policy_act(_p(self._fused.flat), _p(obs), env.num_envs, env.obs_dim, nets, 0, _p(self._rng),
+        _lib.check(L.fw_policy_act_a(_p(self._fused.flat), _p(obs), env.num_envs, env.obs_dim, self.act_dim, nets, 0, _p(self._rng),
                                    int(getattr(env.venv, "global_env_offset", 0)), bo, ba, _p(self._act_env),
                                    int(self._act_env.dtype == torch.float64), bl, _p(val), _stream(self.device)))
 
@@ -901,8 +916,8 @@ class PPO:
                 nxt = self.buf_start[prev_t + 1] if prev_t + 1 < T else self.last_starts
                 prev = (_p(venv.rewards), _p(venv.terminated), _p(venv.truncated), _p(venv.terminal_obs), _p(env.ret_rms.var),
                         int(env.norm_reward), float(env.clip_reward), float(env.epsilon), float(cfg.gamma), _p(self.buf_rew[prev_t]), _p(nxt))
-            _lib.check(L.fw_collect_act(_p(self._fused.flat), _p(venv.obs), f64, N, D, _p(env.obs_rms.mean), _p(env.obs_rms.var),
-                                        float(env.clip_obs), float(env.epsilon), nets, 0, _p(self._rng),
+            _lib.check(L.fw_collect_act_a(_p(self._fused.flat), _p(venv.obs), f64, N, D, self.act_dim, _p(env.obs_rms.mean), _p(env.obs_rms.var),
+                                          float(env.clip_obs), float(env.epsilon), nets, 0, _p(self._rng),
                                         int(getattr(venv, "global_env_offset", 0)), bo, ba, _p(self._act_env),
                                         int(self._act_env.dtype == torch.float64), bl, _p(value_out), *prev, st))
 
@@ -963,8 +978,8 @@ class PPO:
                                           _p(env._ret_acc) if track else None, st))
         # V(last observation) for GAE + the finalisation of step T-1 (nothing is sampled; the normalised last observation lands
         # in last_obs for callers that look at it)
-        _lib.check(L.fw_collect_act(_p(self._fused.flat), _p(venv.obs), f64, N, D, _p(env.obs_rms.mean), _p(env.obs_rms.var),
-                                    float(env.clip_obs), float(env.epsilon), 2, 0, _p(self._rng), int(getattr(venv, "global_env_offset", 0)),
+        _lib.check(L.fw_collect_act_a(_p(self._fused.flat), _p(venv.obs), f64, N, D, self.act_dim, _p(env.obs_rms.mean), _p(env.obs_rms.var),
+                                      float(env.clip_obs), float(env.epsilon), 2, 0, _p(self._rng), int(getattr(venv, "global_env_offset", 0)),
                                     None, None, None, 0, None, _p(self.last_values),
                                     _p(venv.rewards), _p(venv.terminated), _p(venv.truncated), _p(venv.terminal_obs), _p(env.ret_rms.var),
                                     int(env.norm_reward), float(env.clip_reward), float(env.epsilon), float(cfg.gamma),
