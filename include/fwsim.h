@@ -388,6 +388,17 @@ int32_t fw_gae(const float* rewards, const float* values, const float* episode_s
 int32_t fw_eval_track(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
                       int32_t info_dim, const int64_t* targets, int64_t* counts, double* cur_rew, int64_t* cur_len, int64_t* step_ctr,
                       double* fin_rew, int64_t* fin_len, int64_t* fin_step, int32_t* fin_info, int32_t N, int32_t E, void* hip_stream);
+/* fw_eval_track for FW_TASK_LOWLEVEL, plus its tracking figures.  Everything fw_eval_track does, and from the
+ * post-step observation row o of env i -- terminal_obs[i] where terminated | truncated, else obs[i]; [N, 21], obs_is_f64 the env
+ * dtype -- with e_psi = wrap(o[18] - o[5]) (to [-pi, pi)), e_h = o[19] - o[11], e_V = o[20] - |o[6:9]|, w = |o[0:3]| it adds
+ * (|e_psi|, e_psi^2, |e_h|, e_h^2, |e_V|, e_V^2, w) in double to cur_track [N, 7]; a recorded episode's seven sums and
+ * survived = !terminated (1.0 / 0.0) go to fin_track [N, E, 8] at its slot, and the sums of finished episodes are cleared.
+ * FW_EINVAL for NULL buffers, obs_dim != 21, N <= 0 or E <= 0.  One launch. */
+int32_t fw_eval_track_ll(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
+                         int32_t info_dim, const void* obs, const void* terminal_obs, int32_t obs_is_f64, int32_t obs_dim,
+                         const int64_t* targets, int64_t* counts, double* cur_rew, int64_t* cur_len, int64_t* step_ctr, double* cur_track,
+                         double* fin_rew, int64_t* fin_len, int64_t* fin_step, int32_t* fin_info, double* fin_track, int32_t N, int32_t E,
+                         void* hip_stream);
 
 /* VecNormalize step (SB3 VecNormalize.step_wait + RunningMeanStd.update, Chan et al. merge),
  * fused: one pass over obs[N,D] (env dtype T_in = double|float per `in_is_f64`) that

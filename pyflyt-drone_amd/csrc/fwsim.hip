@@ -1316,13 +1316,7 @@ void fw_reset_kernel(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict
 // machinery applies, and the other tasks' kernels stay exactly as they were.  The physics is the same inlined Aviary step.
 // The reset is inline (no warm-up, three draws): a wave that contains one runs ~50 more instructions per lane.
 // ------------------------------------------------------------------------------------------
-// wrap to [-pi, pi): Python's (a + pi) % (2 pi) - pi (:158-159), the sign of the modulus taken from the divisor
-template <typename T> __device__ __forceinline__ T ll_wrap_pi(T a) {
-  const T two_pi = (T)(2.0 * kPi);
-  T r = ::fmod(a + (T)kPi, two_pi);
-  r = (r < (T)0) ? r + two_pi : r;
-  return r - (T)kPi;
-}
+// (ll_wrap_pi, the heading wrap, is in fwsim_device.hpp: the evaluation's tracking sums use it too)
 // the episode's target, drawn on a stream of its own keyed on (seed, global env, episode): :86-91
 template <typename T> __device__ __forceinline__ void ll_target(const Params<T>& P, uint32_t genv, uint32_t ep, T tgt[3]) {
   const double k = 1.0 / 9007199254740992.0;
@@ -2397,6 +2391,28 @@ int32_t fw_eval_track(const void* reward, int32_t reward_is_f64, const uint8_t* 
   A.fin_rew = fin_rew; A.fin_len = fin_len; A.fin_step = fin_step; A.fin_info = fin_info; A.N = N; A.E = E;
   DeviceGuard g(device_of(reward));
   hipLaunchKernelGGL(fw_eval_track_kernel, dim3(1), dim3(256), 0, (hipStream_t)hip_stream, A);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+
+int32_t fw_eval_track_ll(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
+                         int32_t info_dim, const void* obs, const void* terminal_obs, int32_t obs_is_f64, int32_t obs_dim,
+                         const int64_t* targets, int64_t* counts, double* cur_rew, int64_t* cur_len, int64_t* step_ctr, double* cur_track,
+                         double* fin_rew, int64_t* fin_len, int64_t* fin_step, int32_t* fin_info, double* fin_track, int32_t N, int32_t E,
+                         void* hip_stream) {
+  if (!reward || !terminated || !truncated || !targets || !counts || !cur_rew || !cur_len || !step_ctr || !fin_rew || !fin_len || !fin_step ||
+      (info && (info_dim <= 0 || !fin_info))) { g_err = "fw_eval_track_ll: bad arguments"; return FW_EINVAL; }
+  if (!obs || !terminal_obs || !cur_track || !fin_track) { g_err = "fw_eval_track_ll: obs, terminal_obs, cur_track and fin_track must be non-NULL"; return FW_EINVAL; }
+  if (obs_dim != 21) { g_err = "fw_eval_track_ll: obs_dim must be 21 (the low-level task's observation), got " + std::to_string(obs_dim); return FW_EINVAL; }
+  if (N <= 0 || E <= 0) { g_err = "fw_eval_track_ll: N and E must be positive, got N=" + std::to_string(N) + ", E=" + std::to_string(E); return FW_EINVAL; }
+  EvalTrackArgs A;
+  A.reward = reward; A.reward_is_f64 = reward_is_f64; A.terminated = terminated; A.truncated = truncated; A.info = info; A.info_dim = info_dim;
+  A.targets = targets; A.counts = counts; A.cur_rew = cur_rew; A.cur_len = cur_len; A.step_ctr = step_ctr;
+  A.fin_rew = fin_rew; A.fin_len = fin_len; A.fin_step = fin_step; A.fin_info = fin_info; A.N = N; A.E = E;
+  EvalTrackLLArgs X;
+  X.obs = obs; X.terminal_obs = terminal_obs; X.obs_is_f64 = obs_is_f64; X.cur_track = cur_track; X.fin_track = fin_track;
+  DeviceGuard g(device_of(reward));
+  hipLaunchKernelGGL(fw_eval_track_ll_kernel, dim3(1), dim3(256), 0, (hipStream_t)hip_stream, A, X);
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }

@@ -134,6 +134,15 @@ __device__ __forceinline__ DevState<T> tile_view(const DevState<T>& G, int blk) 
 
 constexpr double kPi = 3.14159265358979323846;
 
+// FW_TASK_LOWLEVEL's heading wrap to [-pi, pi): Python's (a + pi) % (2 pi) - pi (fixedwing_lowlevel_env.py:158-159), the sign of
+// the modulus taken from the divisor.  The step kernel's reward and the evaluation's tracking sums (fw_eval_track_ll) share it.
+template <typename T> __device__ __forceinline__ T ll_wrap_pi(T a) {
+  const T two_pi = (T)(2.0 * kPi);
+  T r = ::fmod(a + (T)kPi, two_pi);
+  r = (r < (T)0) ? r + two_pi : r;
+  return r - (T)kPi;
+}
+
 // ------------------------------------------------------------------------
 // Launch index kept in DEVICE memory.  The shadow / scenario hand-off compares launch indices; a host counter passed
 // by value is frozen into a captured hipGraph node and repeats on every replay.  Instead every workgroup of the

@@ -44,7 +44,18 @@ struct EvalTrackArgs {
   double* fin_rew; int64_t *fin_len, *fin_step; int32_t* fin_info;      // [N, E] (fin_info [N, E, info_dim])
   int32_t N, E;
 };
-__global__ __launch_bounds__(256) void fw_eval_track_kernel(EvalTrackArgs A) {
+// FW_TASK_LOWLEVEL's tracking sums (fw_eval_track_ll): from the post-step observation row o -- the terminal
+// observation on the step that ends an episode -- e_psi = wrap(o[18] - o[5]), e_h = o[19] - o[11], e_V = o[20] - |o[6:9]|,
+// w = |o[0:3]|; per env the running sums |e_psi|, e_psi^2, |e_h|, e_h^2, |e_V|, e_V^2, w, and for a finished episode those seven
+// plus survived = !terminated.  All in double, whatever the env dtype.
+constexpr int kTrackSums = 7;
+struct EvalTrackLLArgs {
+  const void *obs, *terminal_obs; int32_t obs_is_f64;     // [N, 21], env dtype
+  double* cur_track;                                       // [N, 7]
+  double* fin_track;                                       // [N, E, 8]
+};
+template <bool TRACK>
+__device__ __forceinline__ void eval_track_body(EvalTrackArgs A, EvalTrackLLArgs X) {
   const long long step = A.step_ctr[0] + 1;
   for (int i = threadIdx.x; i < A.N; i += (int)blockDim.x) {
     const double r = A.reward_is_f64 ? reinterpret_cast<const double*>(A.reward)[i] : (double)reinterpret_cast<const float*>(A.reward)[i];
@@ -52,18 +63,43 @@ __global__ __launch_bounds__(256) void fw_eval_track_kernel(EvalTrackArgs A) {
     const long long cl = A.cur_len[i] + 1;
     const bool done = (A.terminated[i] | A.truncated[i]) != 0;
     const long long c = A.counts[i];
+    double ts[kTrackSums];
+    if (TRACK) {
+      const void* src = done ? X.terminal_obs : X.obs;
+      auto o = [&](int k) -> double {
+        const size_t j = (size_t)i * 21 + k;
+        return X.obs_is_f64 ? reinterpret_cast<const double*>(src)[j] : (double)reinterpret_cast<const float*>(src)[j];
+      };
+      const double e_psi = ll_wrap_pi<double>(o(18) - o(5)), e_h = o(19) - o(11);
+      const double e_v = o(20) - ::sqrt(o(6) * o(6) + o(7) * o(7) + o(8) * o(8));
+      const double w = ::sqrt(o(0) * o(0) + o(1) * o(1) + o(2) * o(2));
+      const double add[kTrackSums] = { ::fabs(e_psi), e_psi * e_psi, ::fabs(e_h), e_h * e_h, ::fabs(e_v), e_v * e_v, w };
+#pragma unroll
+      for (int k = 0; k < kTrackSums; ++k) ts[k] = X.cur_track[(size_t)i * kTrackSums + k] + add[k];
+    }
     if (done && c < A.targets[i]) {
       const size_t s = (size_t)i * A.E + (size_t)(c < A.E ? c : A.E - 1);
       A.fin_rew[s] = cr; A.fin_len[s] = cl; A.fin_step[s] = step;
       if (A.info) for (int k = 0; k < A.info_dim; ++k) A.fin_info[s * A.info_dim + k] = A.info[(size_t)i * A.info_dim + k];
+      if (TRACK) {
+#pragma unroll
+        for (int k = 0; k < kTrackSums; ++k) X.fin_track[s * (kTrackSums + 1) + k] = ts[k];
+        X.fin_track[s * (kTrackSums + 1) + kTrackSums] = A.terminated[i] ? 0.0 : 1.0;
+      }
       A.counts[i] = c + 1;
     }
     A.cur_rew[i] = done ? 0.0 : cr;
     A.cur_len[i] = done ? 0 : cl;
+    if (TRACK) {
+#pragma unroll
+      for (int k = 0; k < kTrackSums; ++k) X.cur_track[(size_t)i * kTrackSums + k] = done ? 0.0 : ts[k];
+    }
   }
   __syncthreads();
   if (threadIdx.x == 0) A.step_ctr[0] = step;
 }
+__global__ __launch_bounds__(256) void fw_eval_track_kernel(EvalTrackArgs A) { eval_track_body<false>(A, EvalTrackLLArgs{}); }
+__global__ __launch_bounds__(256) void fw_eval_track_ll_kernel(EvalTrackArgs A, EvalTrackLLArgs X) { eval_track_body<true>(A, X); }
 
 // K4a: per-column batch moments of obs[N,D] (two-pass-free: shifted sums in double), one
 // workgroup per column chunk; K4b merges them into the running statistics (Chan et al.) and

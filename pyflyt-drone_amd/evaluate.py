@@ -14,13 +14,17 @@ Mirrors, for the device-resident envs:
   ``eval/success_rate`` = mean(is_success); the ObjLock scripts add ``duck_strike_rate``
   (train/train_objlock.py:163-167, eval/eval_objlock.py:260-325);
 * ``evaluations.npz`` (timesteps / results / ep_lengths / successes) and ``best_model`` on a
-  new best mean reward (``:172-190, 216-222``).
+  new best mean reward (``:172-190, 216-222``);
+* for the low-level control task, the figures of eval/eval_lowlevel.py: heading / altitude / airspeed
+  tracking error (MAE, RMSE, pooled over every evaluated step), mean angular-rate norm, survival rate
+  (:meth:`EvalResult.tracking_scalars`, definitions in DESIGN.md section 2d).
 
 Everything per step stays on the device; the host reads one small ``dones`` mask per
 vec-step (the episode bookkeeping is host-side like SB3's).
 """
 from __future__ import annotations
 
+import math
 import os
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional
@@ -39,6 +43,21 @@ def sync_envs_normalization(train_env, eval_env) -> None:
     eval_env.ret_rms.load_state_dict(train_env.ret_rms.state_dict())
 
 
+# FW_TASK_LOWLEVEL's per-episode tracking sums, in the column order of fw_eval_track_ll's cur_track / fin_track
+TRACK_SUMS = ("heading_abs", "heading_sq", "altitude_abs", "altitude_sq", "airspeed_abs", "airspeed_sq", "ang_vel")
+
+
+def _track_terms(o: torch.Tensor) -> torch.Tensor:
+    """[N, 7] per-step terms of TRACK_SUMS from post-step observation rows ``o`` [N, 21], in double: the
+    torch statement of what fw_eval_track_ll adds up."""
+    o = o.to(torch.float64)
+    e_psi = torch.remainder(o[:, 18] - o[:, 5] + math.pi, 2 * math.pi) - math.pi      # Python's (a + pi) % (2 pi) - pi
+    e_h = o[:, 19] - o[:, 11]
+    e_v = o[:, 20] - torch.sqrt(o[:, 6] * o[:, 6] + o[:, 7] * o[:, 7] + o[:, 8] * o[:, 8])
+    w = torch.sqrt(o[:, 0] * o[:, 0] + o[:, 1] * o[:, 1] + o[:, 2] * o[:, 2])
+    return torch.stack([e_psi.abs(), e_psi * e_psi, e_h.abs(), e_h * e_h, e_v.abs(), e_v * e_v, w], dim=1)
+
+
 @dataclass
 class EvalResult:
     episode_rewards: List[float]
@@ -46,6 +65,21 @@ class EvalResult:
     num_targets_reached: List[int] = field(default_factory=list)
     is_success: List[bool] = field(default_factory=list)
     duck_strike: List[bool] = field(default_factory=list)
+    # FW_TASK_LOWLEVEL only: per episode, the sums over its steps of |e_psi|, e_psi^2, |e_h|, e_h^2, |e_V|, e_V^2 and the
+    # angular-rate norm (TRACK_SUMS), and survived = not terminated (a truncated episode survived)
+    heading_abs: List[float] = field(default_factory=list)
+    heading_sq: List[float] = field(default_factory=list)
+    altitude_abs: List[float] = field(default_factory=list)
+    altitude_sq: List[float] = field(default_factory=list)
+    airspeed_abs: List[float] = field(default_factory=list)
+    airspeed_sq: List[float] = field(default_factory=list)
+    ang_vel: List[float] = field(default_factory=list)
+    survived: List[bool] = field(default_factory=list)
+
+    def add_tracking(self, sums, survived: bool) -> None:
+        for name, v in zip(TRACK_SUMS, sums):
+            getattr(self, name).append(float(v))
+        self.survived.append(bool(survived))
 
     @property
     def mean_reward(self) -> float: return float(np.mean(self.episode_rewards))
@@ -69,6 +103,21 @@ class EvalResult:
             out["eval/duck_strike_rate"] = float(np.mean(self.duck_strike))
         return out
 
+    def tracking_scalars(self) -> Dict[str, float]:
+        """The low-level controller's figures (eval/eval_lowlevel.py): MAE = sum |e| / sum L and RMSE = sqrt(sum e^2 / sum L), pooled
+        over every evaluated step as the reference's ``extend`` does, the mean angular-rate norm likewise, and the survival rate
+        over episodes.  Empty for the other tasks."""
+        if not self.survived:
+            return {}
+        steps = float(np.sum(self.episode_lengths))
+        out = {}
+        for q in ("heading", "altitude", "airspeed"):
+            out[f"eval/{q}_mae"] = float(np.sum(getattr(self, q + "_abs"))) / steps
+            out[f"eval/{q}_rmse"] = math.sqrt(float(np.sum(getattr(self, q + "_sq"))) / steps)
+        out["eval/ang_vel_mean"] = float(np.sum(self.ang_vel)) / steps
+        out["eval/survival_rate"] = float(np.mean(self.survived))
+        return out
+
 
 @torch.no_grad()
 def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool = True,
@@ -88,7 +137,12 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
     ``use_fused`` (default: whenever possible -- the reference's MlpPolicy on a device env with the 8-lane mapping, an
     evaluation normaliser with frozen statistics): a vec-step of the replayed evaluation is ONE ``fw_collect_step`` launch in
     its deterministic, statistics-frozen form (normalisation, policy forward on the matrix cores, clip, env step) instead of
-    ~20 framework ops; the policy's actions then agree with the torch forward to fp32 rounding, not to the bit."""
+    ~20 framework ops; the policy's actions then agree with the torch forward to fp32 rounding, not to the bit.  The low-level task's
+    six-action MlpPolicy (either lane mapping) keeps the torch forward by default; ``use_fused=True`` makes its vec-step three launches
+    (``fw_collect_act_a`` -> ``fw_step`` -> ``fw_eval_track_ll``).
+
+    For the low-level control task the result also carries the per-episode tracking sums and survival
+    (:meth:`EvalResult.tracking_scalars`): from torch ops in the step-by-step loop, from ``fw_eval_track_ll`` in the replayed one."""
     venv = env.venv
     n = env.num_envs
     targets = np.array([(n_eval_episodes + i) // n for i in range(n)], dtype=np.int64)
@@ -103,6 +157,8 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
     res = EvalResult([], [])
     has_info = hasattr(venv, "info")
     is_objlock = getattr(getattr(venv, "cfg", None), "task", K.FW_TASK_WAYPOINTS) in (K.FW_TASK_OBJLOCK, K.FW_TASK_WAYPOINT_OBJLOCK)
+    track = getattr(getattr(venv, "cfg", None), "task", K.FW_TASK_WAYPOINTS) == K.FW_TASK_LOWLEVEL
+    cur_trk = torch.zeros((n, len(TRACK_SUMS)), dtype=torch.float64, device=env.device) if track else None
     obs = env.reset()
     steps = 0
     while (counts < targets).any():
@@ -111,15 +167,20 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
         obs, _, dones, _, _ = env.step(clipped)
         cur_rew += venv.rewards.to(torch.float64)        # un-normalised reward of the wrapped env
         cur_len += 1
+        if track:                                        # the post-step row: the terminal observation where the episode ended
+            cur_trk += _track_terms(torch.where(dones[:, None], venv.terminal_obs, venv.obs))
         d = dones.cpu().numpy()
         if d.any():
             idx = np.nonzero(d)[0]
             rew_h, len_h = cur_rew.cpu().numpy(), cur_len.cpu().numpy()
             info_h = venv.info.cpu().numpy() if has_info else None
+            trk_h, term_h = (cur_trk.cpu().numpy(), venv.terminated.cpu().numpy()) if track else (None, None)
             for i in idx:
                 if counts[i] < targets[i]:
                     counts[i] += 1
                     res.episode_rewards.append(float(rew_h[i])); res.episode_lengths.append(int(len_h[i]))
+                    if track:
+                        res.add_tracking(trk_h[i], not term_h[i])
                     info = {"episode": {"r": float(rew_h[i]), "l": int(len_h[i])}}
                     if info_h is not None:
                         info["num_targets_reached"] = int(info_h[i, K.INFO_NUM_TARGETS_REACHED])
@@ -138,6 +199,8 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
                         callback(info)
             m = torch.as_tensor(d, device=env.device)
             cur_rew.masked_fill_(m, 0.0); cur_len.masked_fill_(m, 0)
+            if track:
+                cur_trk.masked_fill_(m[:, None], 0.0)
         steps += 1
         if max_vec_steps is not None and steps >= max_vec_steps:
             break
@@ -173,18 +236,27 @@ class ReplayedEvaluation:
     ``launch()`` enqueues the WHOLE evaluation on a side stream -- as many replays as the longest possible episodes need,
     ``episodes per env x (max_steps + 2)`` vec-steps -- and returns at once: the evaluation (a few envs) then runs beside the
     training that continues on the main stream (the PPO update keeps eight of the 256 CUs busy); ``ready()`` / ``result()``
-    collect it.  The policy handed in must not change while it runs (EvalCallback evaluates a copy of the weights)."""
+    collect it.  The policy handed in must not change while it runs (EvalCallback evaluates a copy of the weights).
+
+    The low-level control task's bookkeeping is one ``fw_eval_track_ll`` launch per vec-step, which also sums its tracking figures.
+    ``use_fused=True`` with its six-action MlpPolicy: a vec-step is ``fw_collect_act_a`` (policy only, deterministic, frozen
+    statistics) -> ``fw_step`` -> ``fw_eval_track_ll``, in sequence."""
 
     def __init__(self, policy, env, targets: np.ndarray, callback=None, use_fused: Optional[bool] = None):
         self.policy, self.env, self.callback = policy, env, callback
         venv, n, dev = env.venv, env.num_envs, env.device
         self.fused = self._fused_applies(policy, env) if use_fused is None else bool(use_fused)
-        if self.fused and not self._fused_applies(policy, env):
-            raise ValueError("use_fused=True needs the MlpPolicy, a device env on the 8-lane mapping and an evaluation normaliser (training=False)")
+        # the six-action policy of the low-level task: only on request (the default keeps its torch forward)
+        self.fused6 = self.fused and not self._fused_applies(policy, env) and self._fused6_applies(policy, env)
+        if self.fused and not (self._fused_applies(policy, env) or self.fused6):
+            raise ValueError("use_fused=True needs the MlpPolicy, a device env on the 8-lane mapping (any mapping for the low-level task's "
+                             "six actions) and an evaluation normaliser (training=False)")
         self.venv, self.n, self.dev, self.targets = venv, n, dev, targets
         self.E = E = max(int(targets.max()), 1)
         self.has_info = hasattr(venv, "info")
-        self.is_objlock = getattr(getattr(venv, "cfg", None), "task", K.FW_TASK_WAYPOINTS) in (K.FW_TASK_OBJLOCK, K.FW_TASK_WAYPOINT_OBJLOCK)
+        task = getattr(getattr(venv, "cfg", None), "task", K.FW_TASK_WAYPOINTS)
+        self.is_objlock = task in (K.FW_TASK_OBJLOCK, K.FW_TASK_WAYPOINT_OBJLOCK)
+        self.track = task == K.FW_TASK_LOWLEVEL and hasattr(venv, "terminal_obs")
         self.tg = torch.as_tensor(targets, device=dev)
         self.ar = torch.arange(n, device=dev)
         self.counts = torch.zeros(n, dtype=torch.int64, device=dev)
@@ -195,6 +267,9 @@ class ReplayedEvaluation:
         self.fin_len = torch.zeros((n, E), dtype=torch.int64, device=dev)
         self.fin_step = torch.zeros((n, E), dtype=torch.int64, device=dev)
         self.fin_info = torch.zeros((n, E, venv.info.shape[1]), dtype=venv.info.dtype, device=dev) if self.has_info else None
+        if self.track:
+            self.cur_track = torch.zeros((n, len(TRACK_SUMS)), dtype=torch.float64, device=dev)
+            self.fin_track = torch.zeros((n, E, len(TRACK_SUMS) + 1), dtype=torch.float64, device=dev)      # + survived
         self.obs = None
         self.side = torch.cuda.Stream(device=dev)
         self.done_event = None
@@ -216,6 +291,17 @@ class ReplayedEvaluation:
             return False
         return int(_lib.lib().fw_lanes_per_env(venv._h)) in (8, 16)
 
+    @staticmethod
+    def _fused6_applies(policy, env) -> bool:
+        """the low-level task's six-action MlpPolicy through fw_collect_act_a (either lane mapping)"""
+        from .rollout import FusedPpoUpdate
+        venv = env.venv
+        if not (hasattr(venv, "_h") and hasattr(venv, "step_tensor") and torch.device(env.device).type == "cuda"):
+            return False
+        if env.training or not env.norm_obs or getattr(getattr(venv, "cfg", None), "task", None) != K.FW_TASK_LOWLEVEL:
+            return False
+        return FusedPpoUpdate.fits(policy, env.obs_dim, torch.device(env.device), act_dims=(6,))
+
     def _fused_setup(self) -> None:
         from . import _lib
         from .rollout import FusedPpoUpdate
@@ -224,6 +310,11 @@ class ReplayedEvaluation:
         f = FusedPpoUpdate(self.policy, None, env.obs_dim)
         f.load_params_from_torch()
         self._flat = f.flat                                         # the kernel's parameter image of the policy being evaluated
+        if self.fused6:                                             # fw_collect_act_a's outputs: clipped actions for fw_step, the rest unread
+            self._act_env = torch.zeros((n, 6), dtype=venv.torch_dtype, device=dev)
+            self._act_raw = torch.zeros((n, 6), dtype=torch.float32, device=dev)
+            self._logp = torch.zeros(n, dtype=torch.float32, device=dev)
+            return
         self._act_env = torch.full((n, 4), float("nan"), dtype=venv.torch_dtype, device=dev)      # NaN = "not there yet" (fw_collect_step)
         self._act_raw = torch.zeros((n, 4), dtype=torch.float32, device=dev)                     # rollout-buffer rows the launch fills: not looked at
         self._logp, self._val = torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev)
@@ -232,10 +323,41 @@ class ReplayedEvaluation:
         self._ws = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
         self._ws_ready = False
 
+    def _fused6_step(self) -> None:
+        """a vec-step of the six-action policy: fw_collect_act_a (policy net only, deterministic, frozen statistics, nothing of the
+        previous step to finalise) -> fw_step -> fw_eval_track_ll, one after the other on the stream"""
+        from . import _lib
+        from .rollout import _p, _stream
+        env, venv = self.env, self.venv
+        L, st = _lib.lib(), _stream(self.dev)
+        _lib.check(L.fw_collect_act_a(_p(self._flat), _p(venv.obs), int(venv.obs.dtype == torch.float64), self.n, env.obs_dim, 6,
+                                      _p(env.obs_rms.mean), _p(env.obs_rms.var), float(env.clip_obs), float(env.epsilon), 1, 1, None,
+                                      int(getattr(venv, "global_env_offset", 0)), None, _p(self._act_raw), _p(self._act_env),
+                                      int(self._act_env.dtype == torch.float64), _p(self._logp), None,
+                                      None, None, None, None, None, 0, 0.0, 0.0, 0.0, None, None, st))
+        venv.step_tensor(self._act_env)
+        self._track_step()
+
+    def _track_step(self) -> None:
+        """the low-level task's bookkeeping of a vec-step, tracking sums included: one fw_eval_track_ll launch"""
+        from . import _lib
+        from .rollout import _p, _stream
+        venv, fi = self.venv, self.fin_info
+        _lib.check(_lib.lib().fw_eval_track_ll(
+            _p(venv.rewards), int(venv.rewards.dtype == torch.float64), _p(venv.terminated), _p(venv.truncated),
+            _p(venv.info) if fi is not None else None, int(venv.info.shape[1]) if fi is not None else 0,
+            _p(venv.obs), _p(venv.terminal_obs), int(venv.obs.dtype == torch.float64), int(venv.obs.shape[1]),
+            _p(self.tg), _p(self.counts), _p(self.cur_rew), _p(self.cur_len), _p(self.step_ctr), _p(self.cur_track),
+            _p(self.fin_rew), _p(self.fin_len), _p(self.fin_step), _p(fi) if fi is not None else None, _p(self.fin_track),
+            self.n, self.E, _stream(self.dev)))
+
     def _fused_step(self) -> None:
         import ctypes as C
         from . import _lib
         from .rollout import _stream
+        if self.fused6:
+            self._fused6_step()
+            return
         env, venv = self.env, self.venv
         L, st = _lib.lib(), _stream(self.dev)
         if not self._ws_ready:
@@ -271,7 +393,7 @@ class ReplayedEvaluation:
         import ctypes as C
         from . import _lib
         from .rollout import _stream
-        if not self.fused or not self._ws_ready:
+        if not self.fused or self.fused6 or not self._ws_ready:      # (the six-action path has no fw_collect_step and no status word)
             return
         stw = C.c_uint32(0)
         _lib.check(_lib.lib().fw_collect_status(self.venv._h, self._ws.data_ptr(), self._ws.numel() * 8, C.byref(stw), _stream(self.dev)), self.venv._h)
@@ -287,6 +409,9 @@ class ReplayedEvaluation:
             actions, _, _ = self.policy(self.obs, deterministic=True, generator=None, **policy_inputs(self.policy, self.env))
             o, _, dones, _, _ = self.env.step(actions.clamp(-1.0, 1.0).to(venv.torch_dtype))
             self.obs.copy_(o)
+        if self.track:
+            self._track_step()
+            return
         self.cur_rew.add_(venv.rewards.to(torch.float64))            # un-normalised reward of the wrapped env
         self.cur_len.add_(1); self.step_ctr.add_(1)
         take = dones & (counts < tg)
@@ -344,9 +469,12 @@ class ReplayedEvaluation:
         c_h = torch.minimum(self.counts, self.tg).cpu().numpy()
         rew_h, len_h, step_h = self.fin_rew.cpu().numpy(), self.fin_len.cpu().numpy(), self.fin_step.cpu().numpy()
         info_h = self.fin_info.cpu().numpy() if has_info else None
+        trk_h = self.fin_track.cpu().numpy() if self.track else None
         order = sorted((int(step_h[i, k]), i, k) for i in range(n) for k in range(int(c_h[i])))    # as they ended: by step, then env
         for _, i, k in order:
             res.episode_rewards.append(float(rew_h[i, k])); res.episode_lengths.append(int(len_h[i, k]))
+            if trk_h is not None:
+                res.add_tracking(trk_h[i, k, :len(TRACK_SUMS)], trk_h[i, k, len(TRACK_SUMS)] != 0.0)
             info = _episode_info(res, float(rew_h[i, k]), int(len_h[i, k]), info_h[i, k] if has_info else None, self.is_objlock)
             if self.callback is not None:
                 self.callback(info)
@@ -389,6 +517,7 @@ class EvalCallback:
         self.evaluations_results: List[List[float]] = []
         self.evaluations_length: List[List[int]] = []
         self.evaluations_successes: List[List[bool]] = []
+        self.evaluations_tracking: Dict[str, List[float]] = {}      # the low-level task: figure name -> one value per evaluation
         self.last_scalars: Dict[str, float] = {}
         self._next_eval_calls = self.eval_freq
         self.n_evals = 0
@@ -466,12 +595,16 @@ class EvalCallback:
             kw = {}
             if r.is_success:
                 self.evaluations_successes.append(r.is_success); kw = dict(successes=np.array(self.evaluations_successes, dtype=object))
+            for k, v in r.tracking_scalars().items():              # heading_mae, ..., survival_rate: (n_evals,)
+                self.evaluations_tracking.setdefault(k.split("/", 1)[1], []).append(v)
+            kw.update({k: np.array(v, dtype=np.float64) for k, v in self.evaluations_tracking.items()})
             np.savez(self.log_path, timesteps=self.evaluations_timesteps, results=np.array(self.evaluations_results, dtype=object),
                      ep_lengths=np.array(self.evaluations_length, dtype=object), **kw)
         mean_reward = getattr(r, "mean_reward_override", r.mean_reward)
         self.last_mean_reward = mean_reward
         is_objlock = getattr(getattr(self.eval_env.venv, "cfg", None), "task", 0) in (K.FW_TASK_OBJLOCK, K.FW_TASK_WAYPOINT_OBJLOCK)
         self.last_scalars = r.scalars(self.num_targets_total, has_duck=is_objlock)
+        self.last_scalars.update(r.tracking_scalars())             # (the low-level task's; nothing for the others)
         self.last_scalars["time/total_timesteps"] = timesteps
         if self.verbose and writer:
             print(f"Eval num_timesteps={timesteps}, episode_reward={r.mean_reward:.2f} +/- {r.std_reward:.2f}")
