@@ -400,6 +400,24 @@ int32_t fw_eval_track_ll(const void* reward, int32_t reward_is_f64, const uint8_
                          double* fin_rew, int64_t* fin_len, int64_t* fin_step, int32_t* fin_info, double* fin_track, int32_t N, int32_t E,
                          void* hip_stream);
 
+/* Commanding the low-level controller (FW_TASK_LOWLEVEL; DESIGN.md section 2d "Commanding the controller").
+ * fw_command_ll: cmd is a device [T, N, 3] double schedule of (psi, h, V) commands; env i takes row min(*step_idx, T - 1) (row 0
+ * when step_idx is NULL; step_idx is only read).  In double, as train/train_highlevel_cmd.py:164-166: psi wrapped to [-pi, pi)
+ * (the reward's wrap), h clipped to [0, flight_dome_size], V clipped to [0, 100]; then converted to the handle's dtype and written
+ * to the env's FW_SL_TARGET tail and, when obs is not NULL, to obs[i, 18:21] ([N, 21], the env dtype).  mask (optional, uint8 [N]):
+ * rows with mask[i] == 0 are not touched.  A row with a non-finite component is left unchanged and counted into rejected[0]
+ * (optional; the caller zeroes it).  The command holds until the env's episode ends: the auto-reset draws a new random target.
+ * FW_EUNSUPPORTED for any other task; FW_EINVAL for a NULL cmd or T <= 0.  One thread per env, either lane mapping, f64 / f32. */
+int32_t fw_command_ll(fw_handle h, const double* cmd, int32_t T, const int64_t* step_idx, const uint8_t* mask, void* obs,
+                      int32_t* rejected, void* hip_stream);
+/* fw_trace_ll: with k = *step_idx, and only when 0 <= k < T, the post-step row o of env i -- terminal_obs[i] where terminated |
+ * truncated, else obs[i]; [N, 21], obs_is_f64 the env dtype -- goes to trace[k, i, :] ([T, N, 8] double) as
+ * (o[18], o[5], o[19], o[11], o[20], |o[6:9]|, |o[0:3]|, flag), flag 0 = running, 1 = terminated, 2 = truncated; then *step_idx
+ * advances by one.  terminated / truncated / terminal_obs may be NULL (no env is done).  One workgroup.
+ * FW_EINVAL for NULL obs / trace / step_idx, N <= 0 or T <= 0. */
+int32_t fw_trace_ll(const void* obs, const void* terminal_obs, const uint8_t* terminated, const uint8_t* truncated, int32_t obs_is_f64,
+                    int32_t N, double* trace, int32_t T, int64_t* step_idx, void* hip_stream);
+
 /* VecNormalize step (SB3 VecNormalize.step_wait + RunningMeanStd.update, Chan et al. merge),
  * fused: one pass over obs[N,D] (env dtype T_in = double|float per `in_is_f64`) that
  *   (a) if `update` != 0 merges the batch moments into (mean[D], var[D], count[1]) (double),

@@ -1365,11 +1365,16 @@ __device__ __forceinline__ void ll_write_obs(const Rigid<T>& S, const T act[6], 
   psi = eul[2];
   speed = M<T>::sqrt_(lin_vel[0] * lin_vel[0] + lin_vel[1] * lin_vel[1] + lin_vel[2] * lin_vel[2]);
 }
+// the env's target (component k) in the state tail: the step and reset kernels and fw_command_ll read / write it here
+template <typename T>
+__device__ __forceinline__ T& ll_target_slot(const DevState<T>& D, int env, int k) {
+  return D.r[(size_t)(RF_TASK + FW_SL_TARGET + k) * D.npad + env];
+}
 template <typename T>
 __device__ __forceinline__ void ll_load_tail(const DevState<T>& D, int env, T tgt[3], T act[6]) {
   const size_t n = D.npad;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) tgt[k] = D.r[(size_t)(RF_TASK + FW_SL_TARGET + k) * n + env];
+  for (int k = 0; k < 3; ++k) tgt[k] = ll_target_slot<T>(D, env, k);
 #pragma unroll
   for (int k = 0; k < 6; ++k) act[k] = D.r[(size_t)(RF_TASK + FW_SL_PREV_ACTION + k) * n + env];
 }
@@ -1377,7 +1382,7 @@ template <typename T>
 __device__ __forceinline__ void ll_store_tail(const DevState<T>& D, int env, const T tgt[3], const T act[6]) {
   const size_t n = D.npad;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) D.r[(size_t)(RF_TASK + FW_SL_TARGET + k) * n + env] = tgt[k];
+  for (int k = 0; k < 3; ++k) ll_target_slot<T>(D, env, k) = tgt[k];
 #pragma unroll
   for (int k = 0; k < 6; ++k) D.r[(size_t)(RF_TASK + FW_SL_PREV_ACTION + k) * n + env] = act[k];
 }
@@ -1552,6 +1557,9 @@ __global__ __launch_bounds__(kWave) void fw_reset_kernel_ll(const Params<T>* __r
     flush_obs_tile<T>(tile, ld, obs, env0, EPW, D.n, Dobs);
   }
 }
+
+// the low-level task's command input and trace (fw_command_ll / fw_trace_ll): the target goes to ll_target_slot above
+#include "fwsim_command.hpp"
 
 // ======================================================================
 // host side
@@ -2413,6 +2421,39 @@ int32_t fw_eval_track_ll(const void* reward, int32_t reward_is_f64, const uint8_
   X.obs = obs; X.terminal_obs = terminal_obs; X.obs_is_f64 = obs_is_f64; X.cur_track = cur_track; X.fin_track = fin_track;
   DeviceGuard g(device_of(reward));
   hipLaunchKernelGGL(fw_eval_track_ll_kernel, dim3(1), dim3(256), 0, (hipStream_t)hip_stream, A, X);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+
+int32_t fw_command_ll(fw_handle h, const double* cmd, int32_t T, const int64_t* step_idx, const uint8_t* mask, void* obs,
+                      int32_t* rejected, void* hip_stream) {
+  if (!h) { g_err = "fw_command_ll: NULL handle"; return FW_EINVAL; }
+  if (h->cfg.task != FW_TASK_LOWLEVEL) { h->err = "fw_command_ll: only the low-level task (FW_TASK_LOWLEVEL) takes commands"; return FW_EUNSUPPORTED; }
+  if (!cmd) { h->err = "fw_command_ll: cmd must be non-NULL"; return FW_EINVAL; }
+  if (T <= 0) { h->err = "fw_command_ll: T must be positive, got " + std::to_string(T); return FW_EINVAL; }
+  DeviceGuard g(h->device);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const dim3 grid((unsigned)((h->n + 255) / 256)), block(256);
+  const double dome = h->cfg.flight_dome_size;
+  const bool g8 = h->lanes_per_env == 8;
+  if (h->cfg.dtype == FW_F64) {
+    if (g8) hipLaunchKernelGGL((fw_command_ll_kernel<double, 8>), grid, block, 0, st, dev_state<double>(h), cmd, T, step_idx, mask, (double*)obs, rejected, dome);
+    else hipLaunchKernelGGL((fw_command_ll_kernel<double, 1>), grid, block, 0, st, dev_state<double>(h), cmd, T, step_idx, mask, (double*)obs, rejected, dome);
+  } else {
+    if (g8) hipLaunchKernelGGL((fw_command_ll_kernel<float, 8>), grid, block, 0, st, dev_state<float>(h), cmd, T, step_idx, mask, (float*)obs, rejected, dome);
+    else hipLaunchKernelGGL((fw_command_ll_kernel<float, 1>), grid, block, 0, st, dev_state<float>(h), cmd, T, step_idx, mask, (float*)obs, rejected, dome);
+  }
+  HIP_TRY(h, hipGetLastError());
+  return FW_OK;
+}
+
+int32_t fw_trace_ll(const void* obs, const void* terminal_obs, const uint8_t* terminated, const uint8_t* truncated, int32_t obs_is_f64,
+                    int32_t N, double* trace, int32_t T, int64_t* step_idx, void* hip_stream) {
+  if (!obs || !trace || !step_idx) { g_err = "fw_trace_ll: obs, trace and step_idx must be non-NULL"; return FW_EINVAL; }
+  if (N <= 0 || T <= 0) { g_err = "fw_trace_ll: N and T must be positive, got N=" + std::to_string(N) + ", T=" + std::to_string(T); return FW_EINVAL; }
+  DeviceGuard g(device_of(trace));
+  hipLaunchKernelGGL(fw_trace_ll_kernel, dim3(1), dim3(1024), 0, (hipStream_t)hip_stream, obs, terminal_obs, terminated, truncated,
+                     obs_is_f64, N, trace, T, step_idx);
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }

@@ -179,6 +179,39 @@ class FixedwingVecEnv(_VecEnvBase):
         _lib.check(rc, self._h)
         return self.obs
 
+    def command(self, cmd, mask=None) -> int:
+        """Command the low-level controller (``FW_TASK_LOWLEVEL`` only; any other task raises): (psi, h, V) per env (``cmd`` of
+        shape [N, 3], or [3] for every env), conditioned as the reference's high-level env does it (train/train_highlevel_cmd.py:
+        164-166: psi wrapped to [-pi, pi), h clipped to [0, flight_dome_size], V clipped to [0, 100]) and written, through
+        ``fw_command_ll``, into the target the next step's reward reads and into ``self.obs[:, 18:21]``.  Rows with ``mask == 0`` are untouched; a row with a non-finite component is left as it
+        is and counted.  Returns the number of rejected rows (one host read).
+
+        Persistence: a command holds until the env's episode ends.  The auto-reset then draws a new random target, as without
+        commands; a caller that wants its command to hold issues it again before every act (``command.fly`` does)."""
+        c = torch.as_tensor(cmd, dtype=torch.float64)
+        if c.shape == (3,):
+            c = c.expand(self.num_envs, 3)
+        if c.shape != (self.num_envs, 3):
+            raise ValueError(f"cmd must have shape ({self.num_envs}, 3) or (3,), got {tuple(c.shape)}")
+        c = c.to(device=self.device).contiguous()
+        if mask is not None:
+            mask = torch.as_tensor(mask).to(device=self.device, dtype=torch.uint8).contiguous()
+            if mask.numel() != self.num_envs:
+                raise ValueError("mask must have num_envs elements")
+        rejected = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.command_tensor(c, 1, None, mask=mask, rejected=rejected)
+        return int(rejected.item())
+
+    def command_tensor(self, schedule: torch.Tensor, T: int, step_idx: Optional[torch.Tensor] = None,
+                       mask: Optional[torch.Tensor] = None, rejected: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Device form of :meth:`command` (no host synchronisation, graph-capturable): ``schedule`` a contiguous float64 [T, N, 3]
+        device tensor, env i takes row ``min(step_idx, T - 1)`` (``step_idx`` an int64 device scalar, only read; row 0 without
+        it), ``mask`` uint8 [N], ``rejected`` an int32 device counter the caller zeroes.  Patches and returns ``self.obs``."""
+        rc = _lib.lib().fw_command_ll(self._h, _devptr(schedule), int(T), _devptr(step_idx), _devptr(mask), _devptr(self.obs),
+                                      _devptr(rejected), self._stream())
+        _lib.check(rc, self._h)
+        return self.obs
+
     def render_tensor(self, res: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """FPV image of every env's current pose: float32 ``[N, 2, res, res]`` = (duck mask, depth buffer) of the analytic
         scene the vision features are functionals of (``fw_render``; what ``Camera.capture_image()`` hands the reference env,
