@@ -651,6 +651,10 @@ int32_t fw_lanes_per_env(fw_handle h);
  * FWSIM_CAPTURE_WAVE=1 at fw_create; csrc/fwsim_objlock.hpp "The capture wave"), else 0.  Diagnostic; results agree with the
  * one-wave kernel to rounding. */
 int32_t fw_capture_wave(fw_handle h);
+/* 1 when this handle's fw_step runs the axis-aligned variant of the physics tick (f64 wind-free waypoints on the one-wave 8-lane
+ * build, every surface with forward = e_x and lift = e_y or e_z, diagonal inertia), else 0.  Diagnostic; results are bit-identical
+ * to the general tick. */
+int32_t fw_axis_aligned(fw_handle h);
 const char* fw_last_error(fw_handle h); /* h may be NULL: last create/validate error */
 int32_t fw_destroy(fw_handle h);
 

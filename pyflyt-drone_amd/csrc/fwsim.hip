@@ -297,7 +297,7 @@ enum Phase : int { PH_STEP = 0, PH_WARM = 1, PH_DONE = 2 };
 // COLLECT = the step waves of fw_collect_step (fwsim_fused.hpp): block indices are offset by the act waves in front, the
 // actions are waited for and read coherently, and the epilogue carries the statistics of VecNormalize.step_wait.
 // HELP = the workgroup has a capture wave (fwsim_objlock.hpp, "The capture wave"): camera tasks on the 8-lane mapping.
-template <typename T, bool GENERAL, int G, int TKIND, int WPE = 1, bool COLLECT = false, bool HELP = false>
+template <typename T, bool GENERAL, int G, int TKIND, int WPE = 1, bool COLLECT = false, bool HELP = false, bool AX = false>
 __device__ __forceinline__
 void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp, DevState<T> Dg,
                const T* __restrict__ actions, T* __restrict__ obs, T* __restrict__ reward,
@@ -373,6 +373,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   // (Tried for WPE = 2: this lane's surface constants in LDS, read field by field through a volatile reference -- 54 registers
   // fewer to hold, but the allocator spilled as much elsewhere and the ds_reads sit on the tick's critical path: 40.6 -> 50.9 us
   // at 16 384 envs.  surface_wrench / physics_tick keep the template parameter that made the experiment a four-line change.)
+  if (AX && sub >= FW_NUM_SURFACES) mine_regs.hra = (T)0;    // AX: lanes 5-7 evaluate a zero wrench, no mask (surface_wrench_ax)
   SurfC<T>& mine = mine_regs;
 
   normalize_quat<T>(S.q);
@@ -571,9 +572,9 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
         for (int c = 0; c < FW_NUM_ACTUATORS; ++c) c_eff[c] = stepping ? cmd[c] : (T)0;
         z0 = stepping ? z0 : (T)0; z1 = stepping ? z1 : (T)0;
         LA.cmd = stepping ? cmd_mine : (T)0;
-        contact = aviary_step<T, true, G, HASOBJ>(P, C, OC, D, env, O, S, R, c_eff, tick, z0, z1, wb, wa, gust, mine, wmask, LA);   // :339
+        contact = aviary_step<T, true, G, HASOBJ, AX>(P, C, OC, D, env, O, S, R, c_eff, tick, z0, z1, wb, wa, gust, mine, wmask, LA);   // :339
       } else {
-        contact = aviary_step<T, false, G, HASOBJ>(P, C, OC, D, env, O, S, R, cmd, tick, z0, z1, wb, wa, gust, mine, wmask, LA);    // :339
+        contact = aviary_step<T, false, G, HASOBJ, AX>(P, C, OC, D, env, O, S, R, cmd, tick, z0, z1, wb, wa, gust, mine, wmask, LA);    // :339
       }
     }
     if constexpr (HELP) {
@@ -1065,8 +1066,9 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
 // every step kernel: launch index from the workgroup's own device-side counter, advanced when the workgroup is finished
 #define FW_STEP_RUN(...) do { D.epoch = launch_index(D.lctr); step_body<__VA_ARGS__>(FW_STEP_PASS); launch_done(D.lctr, D.epoch); } while (0)
 // latency mapping (8 lanes per env): one wave per SIMD by construction, let the allocator use the whole file
-template <typename T, bool GENERAL>
-__global__ __launch_bounds__(kWave) void fw_step_kernel_g8(FW_STEP_ARGS) { FW_STEP_RUN(T, GENERAL, 8, FW_TASK_WAYPOINTS); }
+// (AX: the axis-aligned geometry variant of the tick, fw_env::axis_aligned)
+template <typename T, bool GENERAL, bool AX = false>
+__global__ __launch_bounds__(kWave) void fw_step_kernel_g8(FW_STEP_ARGS) { FW_STEP_RUN(T, GENERAL, 8, FW_TASK_WAYPOINTS, 1, false, false, AX); }
 // ... and the same mapping capped at 256 registers: two waves per SIMD (8 192 < N <= 65 536 envs)
 template <typename T, bool GENERAL>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2, 2)))
@@ -1643,6 +1645,24 @@ bool invert3(const double m[9], double inv[9]) {
   return true;
 }
 
+// Geometry of the tick's axis-aligned variant (surface_wrench_ax / physics_tick, AX = true): every lifting surface has fwd = e_x and
+// lift = e_y or e_z, and the inertia tensor (hence its inverse, from invert3) is diagonal.  The shipped airframe is.
+bool axis_aligned_geometry(const fw_config& c) {
+  for (int s = 0; s < FW_NUM_SURFACES; ++s) {
+    const double* F = c.surfaces[s].forward_unit;
+    const double* L = c.surfaces[s].lift_unit;
+    if (!(F[0] == 1.0 && F[1] == 0.0 && F[2] == 0.0)) return false;
+    if (!(L[0] == 0.0 && ((L[1] == 1.0 && L[2] == 0.0) || (L[1] == 0.0 && L[2] == 1.0)))) return false;
+  }
+  const double* I = c.inertia;
+  const double m[9] = { I[0], I[3], I[4], I[3], I[1], I[5], I[4], I[5], I[2] };
+  double mi[9];
+  if (!invert3(m, mi)) return false;
+  for (int k : {1, 2, 3, 5, 6, 7})
+    if (m[k] != 0.0 || mi[k] != 0.0) return false;
+  return true;
+}
+
 // Fold fw_config into the wave-uniform constant block (all derivations in double).
 template <typename T>
 bool build_params(const fw_config& c, uint64_t seed, int64_t env_offset, Params<T>& P, std::string& err) {
@@ -1742,6 +1762,7 @@ struct fw_env {
   int32_t lanes_per_env = 1;    // 1: throughput mapping, 8: latency mapping (see fwsim_device.hpp)
   int32_t g8_waves = 1;         // 8-lane mapping, waypoints task: waves per SIMD the step kernel is built for (1 | 2)
   int32_t capture_wave = 0;     // 8-lane mapping, camera tasks: fw_step workgroups carry a capture wave (fw_step_kernel_obj_g8h)
+  int32_t axis_aligned = 0;     // f64 wind-free waypoints on the 8-lane one-wave build: the tick's axis-aligned variant (axis_aligned_geometry)
   uint64_t seed = 0;
   int64_t env_offset = 0;
   void* params_dev = nullptr;   // Params<T>
@@ -1975,6 +1996,8 @@ int step_T(fw_env* h, const void* actions, void* obs, void* reward, uint8_t* ter
   } else if (h->cfg.task == FW_TASK_WAYPOINT_OBJLOCK) {
     if (g8 && h->capture_wave) FW_LAUNCH_STEP_H((fw_step_kernel_obj_g8h<T, FW_TASK_WAYPOINT_OBJLOCK>));
     else if (g8) FW_LAUNCH_STEP((fw_step_kernel_obj_g8<T, FW_TASK_WAYPOINT_OBJLOCK>)); else FW_LAUNCH_STEP((fw_step_kernel_obj_g1<T, FW_TASK_WAYPOINT_OBJLOCK>));
+  } else if (h->axis_aligned && !general && g8 && h->g8_waves == 1) {   // (axis_aligned implies f64)
+    if constexpr (std::is_same<T, double>::value) FW_LAUNCH_STEP((fw_step_kernel_g8<T, false, true>));
   } else if (general) {
     if (g8 && h->g8_waves == 2) FW_LAUNCH_STEP((fw_step_kernel_g8w2<T, true>));
     else if (g8) FW_LAUNCH_STEP((fw_step_kernel_g8<T, true>)); else FW_LAUNCH_STEP((fw_step_kernel_g1<T, true>));
@@ -2196,6 +2219,10 @@ int32_t fw_create(const fw_config* cfg, int32_t num_envs, int32_t device, uint64
   // combined - 8 %) but not the launch, which lasts as long as its slowest wave (CHANGELOG round 5).
   h->capture_wave = 0;
   if (const char* ev = getenv("FWSIM_CAPTURE_WAVE")) { if (atoi(ev) != 0 && h->lanes_per_env == 8 && camera) h->capture_wave = 1; }
+  // The tick's axis-aligned variant (fw_step_kernel_g8<double, false, true>; bit-identical to the general tick, see
+  // surface_wrench_ax): the f64 wind-free waypoints kernel of the one-wave 8-lane build, when the geometry allows it.
+  h->axis_aligned = (h->lanes_per_env == 8 && h->g8_waves == 1 && wp && !windy && cfg->dtype == FW_F64 &&
+                     axis_aligned_geometry(*cfg)) ? 1 : 0;
   DeviceGuard g(device);
   rc = (cfg->dtype == FW_F64) ? create_T<double>(h) : create_T<float>(h);
   if (rc != FW_OK) {
@@ -2920,6 +2947,7 @@ int32_t fw_rollout_post(const void* reward, int32_t rew_is_f64, const uint8_t* t
 
 int32_t fw_num_envs(fw_handle h) { return h ? h->n : FW_EINVAL; }
 int32_t fw_capture_wave(fw_handle h) { return h ? h->capture_wave : FW_EINVAL; }
+int32_t fw_axis_aligned(fw_handle h) { return h ? h->axis_aligned : FW_EINVAL; }
 int32_t fw_lanes_per_env(fw_handle h) { return h ? (h->lanes_per_env == 8 && h->g8_waves == 2 ? 16 : h->lanes_per_env) : FW_EINVAL; }
 
 const char* fw_last_error(fw_handle h) { return h ? h->err.c_str() : g_err.c_str(); }

@@ -475,6 +475,86 @@ __device__ __forceinline__ void surface_wrench(SC& S, T act, const T v_b[3], con
   tq[0] = rxf[0] + Mq * S.tq[0]; tq[1] = rxf[1] + Mq * S.tq[1]; tq[2] = rxf[2] + Mq * S.tq[2];
 }
 
+// surface_wrench for the axis-aligned geometry of the shipped airframe (fw_create: axis_aligned_geometry -- fwd = e_x, lift = e_y
+// or e_z, diagonal inertia), bit-identical to it:
+//  * When no lane of the wave is stalled (~99 % of the wave-steps under U(-1, 1) actions, tools/stall_fraction.py) the post-stall
+//    arithmetic -- the induced-angle interpolation with its division, the post-stall coefficients and the per-lane selects -- is
+//    skipped: the selects of the general code would all have picked the pre-stall operands.
+//  * This lane's wrench goes into the group sums unmasked: lanes 5-7 carry hra = 0, i.e. an exactly zero wrench (step_body).
+// The dot products with fwd / lift and the general r x f stay as they are: written without their zero terms they were still
+// exact, but the compiler then contracted the surrounding products into FMAs differently and the rounding changed (measured:
+// ~1e-11 relative in the observations after 2100 steps).
+template <typename T>
+__device__ __forceinline__ void surface_wrench_ax(const SurfC<T>& S, T act, const T v_b[3], const T w_b[3],
+                                                  const T wind_b[3], T f[3], T tq[3]) {
+  T wxr[3];
+  const T spos[3] = { S.pos[0], S.pos[1], S.pos[2] };
+  cross(w_b, spos, wxr);
+  T vl0 = v_b[0] + wxr[0] - wind_b[0], vl1 = v_b[1] + wxr[1] - wind_b[1], vl2 = v_b[2] + wxr[2] - wind_b[2];
+  T v_l = vl0 * S.lift[0] + vl1 * S.lift[1] + vl2 * S.lift[2];
+  T v_f = vl0 * S.fwd[0] + vl1 * S.fwd[1] + vl2 * S.fwd[2];
+  T V2 = v_f * v_f + v_l * v_l;
+  T V = M<T>::sqrt_(V2);
+  T alpha = M<T>::atan2_(-v_l, v_f);
+
+  T defl = S.defl_scale * act;
+  T dCl = S.k_dCl * act;
+  T dClmax = S.ftc * dCl;
+  T a0 = S.a0b - dCl * S.inv_Cl3;
+  T asP = a0 + (S.ClmaxPb + dClmax) * S.inv_Cl3;
+  T asN = a0 + (S.ClmaxNb + dClmax) * S.inv_Cl3;
+  bool nostall = (asN < alpha) && (alpha < asP);
+
+  T Cl_lin = S.Cl3 * (alpha - a0);
+  T ai_lin = Cl_lin * S.inv_piAR;
+  T sn, cs, CN, CT, CM, Cl;
+  if (__ballot(!nostall) == 0ull) {                 // wave-uniform: the pre-stall branch alone
+    T ai = ai_lin;
+    asm("" : "+v"(ai));       // as behind the select of the general code: `alpha - a0 - ai` subtracts the rounded product (no FMA)
+    T ae = alpha - a0 - ai;
+    M<T>::sincos_(ae, &sn, &cs);
+    T inv = M<T>::rcp_(cs);
+    CT = S.Cd0 * cs;
+    CN = (Cl_lin + CT * sn) * inv;
+    CM = -CN * ((T)0.25 - (T)0.175 * ((T)1 - ((T)2 * ae) * (T)(1.0 / kPi)));
+    Cl = Cl_lin;
+  } else {                                          // the general code, verbatim
+    const T hpi = (T)(0.5 * kPi);
+    T ai_stP = S.Cl3 * (asP - a0) * S.inv_piAR;
+    T ai_stN = S.Cl3 * (asN - a0) * S.inv_piAR;
+    const bool pos = alpha > (T)0;
+    T ix0 = pos ? asP : -hpi, ix1 = pos ? hpi : asN;
+    T iy0 = pos ? ai_stP : (T)0, iy1 = pos ? (T)0 : ai_stN;
+    T ai_st = interp2<T>(alpha, ix0, ix1, iy0, iy1);
+    T ai = nostall ? ai_lin : ai_st;
+    T ae = alpha - a0 - ai;
+    M<T>::sincos_(ae, &sn, &cs);
+    T asn = M<T>::fabs_(sn);
+    T inv = M<T>::rcp_(nostall ? cs : ((T)0.56 + (T)0.44 * asn));
+    T CT_a = S.Cd0 * cs;
+    T CN_a = (Cl_lin + CT_a * sn) * inv;
+    T CM_a = -CN_a * ((T)0.25 - (T)0.175 * ((T)1 - ((T)2 * ae) * (T)(1.0 / kPi)));
+    T Cd90 = ((T)-4.26e-2 * (defl * defl)) + ((T)2.1e-1 * defl) + (T)1.98;
+    T CN_b = Cd90 * sn * (inv - S.k_exp);
+    T CT_b = (T)0.5 * S.Cd0 * cs;
+    T CM_b = -CN_b * ((T)0.25 - (T)0.175 * ((T)1 - ((T)2 * M<T>::fabs_(ae)) * (T)(1.0 / kPi)));
+    CN = nostall ? CN_a : CN_b;
+    CT = nostall ? CT_a : CT_b;
+    CM = nostall ? CM_a : CM_b;
+    Cl = nostall ? Cl_lin : (CN * cs - CT * sn);
+  }
+  T Cd = CN * sn + CT * cs;
+
+  T hV = S.hra * V;
+  T Fn = hV * (Cl * v_f - Cd * v_l);
+  T Fp = hV * (-Cl * v_l - Cd * v_f);
+  T Mq = S.hra * V2 * CM * S.chord;
+  f[0] = S.lift[0] * Fn + S.fwd[0] * Fp; f[1] = S.lift[1] * Fn + S.fwd[1] * Fp; f[2] = S.lift[2] * Fn + S.fwd[2] * Fp;
+  T rxf[3];
+  cross(spos, f, rxf);
+  tq[0] = rxf[0] + Mq * S.tq[0]; tq[1] = rxf[1] + Mq * S.tq[1]; tq[2] = rxf[2] + Mq * S.tq[2];
+}
+
 // wind vector at time t (envs/fixedwing_envs/fixedwing_base_env.py:145-171)
 template <typename T>
 __device__ __forceinline__ void wind_at(const Params<T>& P, const T wb[3], const T wa[3], T phase, int32_t tick, T w[3]) {
@@ -655,7 +735,10 @@ __device__ __forceinline__ void quat_integrate(const TickC<T>& C, Rigid<T>& S) {
 // G = 1: rolled loop over the 5 surfaces (constants by scalar loads at a wave-uniform index
 //        -- unrolling makes hipcc hoist ~100 constants into SGPRs and spill).
 // G = 8: `mine` holds this lane's surface constants in VGPRs, `wmask` zeroes lanes 5-7.
-template <typename T, bool WIND, int G, typename SC>
+// AX (G = 8, SC = SurfC<T>): axis-aligned geometry -- surface_wrench_ax (lanes 5-7: mine.hra = 0 instead of wmask), and the
+// inertia tensor is diagonal: I w and I^-1 rhs are three products each (the dropped terms are products with an exact 0, and
+// their consumers are products, so the contraction around them does not change).
+template <typename T, bool WIND, int G, bool AX = false, typename SC>
 __device__ __forceinline__ bool physics_tick(const Params<T>& P, const TickC<T>& C, Rigid<T>& S, T R[9],
                                              const T cmd[FW_NUM_ACTUATORS], T noise_z, const T wind[3],
                                              SC& mine, T wmask, LaneAct<T>& LA) {
@@ -676,9 +759,15 @@ __device__ __forceinline__ bool physics_tick(const Params<T>& P, const TickC<T>&
   if (G == 8) {
     const T a_s = LA.a;
     T f[3], tq[3];
-    surface_wrench<T, SC>(mine, a_s, v_b, w_b, wind_b, f, tq);
+    if constexpr (AX) {
+      surface_wrench_ax<T>(mine, a_s, v_b, w_b, wind_b, f, tq);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { F[k] = group_sum<8, T>(f[k] * wmask); Tq[k] = group_sum<8, T>(tq[k] * wmask); }
+      for (int k = 0; k < 3; ++k) { F[k] = group_sum<8, T>(f[k]); Tq[k] = group_sum<8, T>(tq[k]); }
+    } else {
+      surface_wrench<T, SC>(mine, a_s, v_b, w_b, wind_b, f, tq);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { F[k] = group_sum<8, T>(f[k] * wmask); Tq[k] = group_sum<8, T>(tq[k] * wmask); }
+    }
   } else {
 #pragma unroll 1
     for (int s = 0; s < FW_NUM_SURFACES; ++s) {
@@ -704,13 +793,15 @@ __device__ __forceinline__ bool physics_tick(const Params<T>& P, const TickC<T>&
   }
   T acc[3] = { Fw[0] * C.inv_mass, Fw[1] * C.inv_mass, Fw[2] * C.inv_mass - C.gravity };
   T Iw[3], rhs[3] = { Tq[0], Tq[1], Tq[2] }, al_b[3], al_w[3];
-  mv(C.I, w_b, Iw);
+  if (AX) { Iw[0] = C.I[0] * w_b[0]; Iw[1] = C.I[4] * w_b[1]; Iw[2] = C.I[8] * w_b[2]; }
+  else mv(C.I, w_b, Iw);
   if (P.gyroscopic) {
     T g[3];
     cross(w_b, Iw, g);
     rhs[0] -= g[0]; rhs[1] -= g[1]; rhs[2] -= g[2];
   }
-  mv(C.Iinv, rhs, al_b);
+  if (AX) { al_b[0] = C.Iinv[0] * rhs[0]; al_b[1] = C.Iinv[4] * rhs[1]; al_b[2] = C.Iinv[8] * rhs[2]; }
+  else mv(C.Iinv, rhs, al_b);
   mv(R, al_b, al_w);
 #pragma unroll
   for (int k = 0; k < 3; ++k) { S.v[k] += acc[k] * dt; S.w[k] += al_w[k] * dt; }
