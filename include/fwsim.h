@@ -73,7 +73,10 @@ enum {
   FW_TASK_WAYPOINTS = 0,        /* PyFlyt/Fixedwing-Waypoints-v3 (train/train_Fixedwing_Waypoints_v3.py:100-110) */
   FW_TASK_OBJLOCK = 1,          /* envs/fixedwing_objlock_env.py */
   FW_TASK_WAYPOINT_OBJLOCK = 2, /* envs/fixedwing_waypoint_objlock_env.py */
-  FW_TASK_LOWLEVEL = 3          /* envs/fixedwing_envs/fixedwing_lowlevel_env.py: six actuator commands, heading / height / speed tracking */
+  FW_TASK_LOWLEVEL = 3,         /* envs/fixedwing_envs/fixedwing_lowlevel_env.py: six actuator commands, heading / height / speed tracking */
+  /* (4 is not a task: a config that carries it is rejected as "unknown task", as it was before the next id existed) */
+  FW_TASK_WAYPOINTS_DIRECT = 5  /* the waypoints task flown in PyFlyt's mode -1: six actuator commands instead of the four mode-0 actions; the
+                                 * base env of train/train_highlevel_cmd.py's HighLevelCmdEnv */
 };
 
 /* fw_config.dtype */
@@ -259,7 +262,9 @@ enum {
 };
 
 /* low-level tail (offsets from FW_S_TASK): the episode's target and the action its observation shows.  The episode's step
- * count is FW_S_STEP_COUNT, as for every task. */
+ * count is FW_S_STEP_COUNT, as for every task.  FW_TASK_WAYPOINTS_DIRECT uses the same two slots: FW_SL_TARGET holds the last
+ * conditioned command of fw_command_hl, FW_SL_PREV_ACTION the six actuator commands its observation shows (obs[12:18] / [13:19]);
+ * FW_S_ACTION stays zero for it. */
 enum {
   FW_SL_TARGET = 0,        /* 3: psi_ref, h_ref, V_ref            fixedwing_lowlevel_env.py:86-91 */
   FW_SL_PREV_ACTION = 3,   /* 6: the last action (obs[12:18])     :99 */
@@ -299,9 +304,11 @@ int32_t fw_sizeof_config(void);
 int32_t fw_abi_version(void);
 int32_t fw_state_dim(void);      /* FW_STATE_DIM of the canonical state record */
 
-/* Observation width D for a config (22/23 attitude + task part; 21 for FW_TASK_LOWLEVEL); <0 on error. */
+/* Observation width D for a config (22/23 attitude + task part; 21 for FW_TASK_LOWLEVEL; 24/25 + 3 context_length for
+ * FW_TASK_WAYPOINTS_DIRECT, whose action block is six wide); <0 on error. */
 int32_t fw_obs_dim(const fw_config* cfg);
-/* Action width A for a config: 6 for FW_TASK_LOWLEVEL (the actuator commands), 4 otherwise ([roll, pitch, yaw, thrust]); <0 on error. */
+/* Action width A for a config: 6 for FW_TASK_LOWLEVEL and FW_TASK_WAYPOINTS_DIRECT (the actuator commands), 4 otherwise
+ * ([roll, pitch, yaw, thrust]); <0 on error. */
 int32_t fw_act_dim(const fw_config* cfg);
 
 /* Validate a config exactly like the reference constructors do.  On error
@@ -410,6 +417,18 @@ int32_t fw_eval_track_ll(const void* reward, int32_t reward_is_f64, const uint8_
  * FW_EUNSUPPORTED for any other task; FW_EINVAL for a NULL cmd or T <= 0.  One thread per env, either lane mapping, f64 / f32. */
 int32_t fw_command_ll(fw_handle h, const double* cmd, int32_t T, const int64_t* step_idx, const uint8_t* mask, void* obs,
                       int32_t* rejected, void* hip_stream);
+/* The high-level command step (train/train_highlevel_cmd.py:93-101, 158-171), for a FW_TASK_WAYPOINTS_DIRECT
+ * handle with the Euler attitude: `action` is the high-level policy's raw [N, 3] output (heading, altitude, airspeed; double when
+ * action_is_f64, else float).  Per env, in double: clipped to the reference's action Box ([-pi, 0, 0], [pi, flight_dome_size, 30]),
+ * then conditioned as :164-166 (heading wrapped to [-pi, pi), altitude clipped to [0, flight_dome_size], airspeed to [0, 100]),
+ * converted to the handle's dtype and written to low_obs[i] = (obs[i, 0:18], command) ([N, 21], the env dtype: the low-level
+ * controller's raw observation), to the env's FW_SL_TARGET tail and, when not NULL, to cmd_out[i] ([N, 3], the env dtype).  `obs` is
+ * the env's observation buffer ([N, fw_obs_dim]), only read.  mask (optional, uint8 [N]): rows with mask[i] == 0 are not touched,
+ * low_obs and cmd_out included.  A row with a non-finite component keeps the env's stored command (after a reset: 0, start height,
+ * start speed) and is counted into rejected[0] (optional; the caller zeroes it).  FW_EUNSUPPORTED for any other task or the
+ * quaternion attitude; FW_EINVAL for NULL action / obs / low_obs.  One thread per env, either lane mapping, f64 / f32. */
+int32_t fw_command_hl(fw_handle h, const void* action, int32_t action_is_f64, const uint8_t* mask, const void* obs, void* low_obs,
+                      void* cmd_out, int32_t* rejected, void* hip_stream);
 /* fw_trace_ll: with k = *step_idx, and only when 0 <= k < T, the post-step row o of env i -- terminal_obs[i] where terminated |
  * truncated, else obs[i]; [N, 21], obs_is_f64 the env dtype -- goes to trace[k, i, :] ([T, N, 8] double) as
  * (o[18], o[5], o[19], o[11], o[20], |o[6:9]|, |o[0:3]|, flag), flag 0 = running, 1 = terminated, 2 = truncated; then *step_idx

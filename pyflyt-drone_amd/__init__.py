@@ -6,12 +6,14 @@ BASELINE.json: the fixed-wing flight-dynamics step + reward + observation of
 SB3 ``VecEnv`` surface the reference's training scripts consume.
 """
 from . import config
-from .config import (FwConfig, lowlevel_config, train_waypoints_v3_config, waypoints_config)
+from .config import (FwConfig, highlevel_config, lowlevel_config, train_waypoints_v3_config, waypoints_config, waypoints_direct_config)
 from .spaces import Box
 from .vec_env import (FixedwingLowLevelVecEnv, FixedwingObjLockVecEnv, FixedwingVecEnv, FixedwingWaypointObjLockVecEnv,
-                      FixedwingWaypointsVecEnv)
+                      FixedwingWaypointsDirectVecEnv, FixedwingWaypointsVecEnv)
 from . import rollout
-from . import checkpoint, evaluate
+from . import checkpoint, evaluate, highlevel
+from .highlevel import HighLevelCmdVecEnv
 
 __all__ = ["config", "FwConfig", "Box", "FixedwingVecEnv", "FixedwingWaypointsVecEnv", "FixedwingObjLockVecEnv", "FixedwingWaypointObjLockVecEnv",
-           "FixedwingLowLevelVecEnv", "waypoints_config", "train_waypoints_v3_config", "lowlevel_config"]
+           "FixedwingLowLevelVecEnv", "FixedwingWaypointsDirectVecEnv", "HighLevelCmdVecEnv", "waypoints_config",
+           "train_waypoints_v3_config", "lowlevel_config", "waypoints_direct_config", "highlevel_config"]

@@ -30,7 +30,7 @@ FW_STATE_DIM = 176
 FW_INFO_DIM = 8
 
 FW_OK, FW_EINVAL, FW_EHIP, FW_ENOMEM, FW_EVERSION, FW_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
-FW_TASK_WAYPOINTS, FW_TASK_OBJLOCK, FW_TASK_WAYPOINT_OBJLOCK, FW_TASK_LOWLEVEL = 0, 1, 2, 3
+FW_TASK_WAYPOINTS, FW_TASK_OBJLOCK, FW_TASK_WAYPOINT_OBJLOCK, FW_TASK_LOWLEVEL, FW_TASK_WAYPOINTS_DIRECT = 0, 1, 2, 3, 5      # (4 is not a task)
 FW_F64, FW_F32 = 0, 1
 FW_WIND_OFF, FW_WIND_CONSTANT, FW_WIND_GUST_SINE = 0, 1, 2
 FW_WIND_COUPLE_NONE, FW_WIND_COUPLE_FORCE, FW_WIND_COUPLE_AIRSPEED = 0, 1, 2
@@ -364,6 +364,25 @@ def waypoints_config(*, sparse_reward: bool = False, num_targets: int = 4, goal_
     return c
 
 
+def waypoints_direct_config(**kwargs) -> FwConfig:
+    """The waypoints task flown in PyFlyt's mode -1 (``FW_TASK_WAYPOINTS_DIRECT``): the keywords and
+    defaults of :func:`waypoints_config`; the six actions are the actuator commands (surfaces ``a[0..4]`` as given, throttle
+    ``0.5 a[5] + 0.5``, as the low-level task takes them) and the observation's action block is six wide."""
+    c = waypoints_config(**kwargs)
+    c.task = FW_TASK_WAYPOINTS_DIRECT
+    return c
+
+
+def highlevel_config(*, flight_dome_size: float = 200.0, max_duration_seconds: float = 120.0, agent_hz: int = 30,
+                     context_length: int = 2, wind_config: Optional[Mapping[str, Any]] = None, dtype: str = "float64",
+                     motor_noise: bool = True, auto_reset: bool = True) -> FwConfig:
+    """The base env of the reference's ``HighLevelCmdEnv`` (train/train_highlevel_cmd.py:51-62, 78-88: its constructor defaults,
+    euler attitude, the upstream defaults for everything else), flown through six direct actuator commands."""
+    return waypoints_direct_config(flight_dome_size=flight_dome_size, max_duration_seconds=max_duration_seconds, agent_hz=agent_hz,
+                                   context_length=context_length, angle_representation="euler", wind_config=wind_config,
+                                   dtype=dtype, motor_noise=motor_noise, auto_reset=auto_reset)
+
+
 def train_waypoints_v3_config(**overrides) -> FwConfig:
     """TRAIN_CONFIG of train/train_Fixedwing_Waypoints_v3.py:27-55 (the headline config)."""
     kw = dict(sparse_reward=True, num_targets=8, goal_reach_distance=4.0, flight_dome_size=100.0,
@@ -628,15 +647,16 @@ def lowlevel_config_from_reference_kwargs(*, render_mode=None, wind_config: Opti
 def obs_dim(c: FwConfig) -> int:
     if c.task == FW_TASK_LOWLEVEL:
         return 21                                                   # envs/fixedwing_envs/fixedwing_lowlevel_env.py:65-66
-    att = (12 if c.angle_representation == 0 else 13) + 4 + 6
+    att = (12 if c.angle_representation == 0 else 13) + (6 if c.task == FW_TASK_WAYPOINTS_DIRECT else 4) + 6
     if c.task == FW_TASK_OBJLOCK:
         return att + 3 + FW_VISION_FEATS * FW_VISION_HIST + (0 if c.duck_vision_no_deltas else 4)      # (:163-165)
     return att + 3 * c.context_length
 
 
 def act_dim(c: FwConfig) -> int:
-    """Action width (``fw_act_dim``): the low-level task's six actuator commands, [roll, pitch, yaw, thrust] otherwise."""
-    return 6 if c.task == FW_TASK_LOWLEVEL else 4
+    """Action width (``fw_act_dim``): six actuator commands for the low-level task and the direct-command waypoints task,
+    [roll, pitch, yaw, thrust] otherwise."""
+    return 6 if c.task in (FW_TASK_LOWLEVEL, FW_TASK_WAYPOINTS_DIRECT) else 4
 
 
 def max_steps(c: FwConfig) -> int:

@@ -1562,6 +1562,8 @@ __global__ __launch_bounds__(kWave) void fw_reset_kernel_ll(const Params<T>* __r
 
 // the low-level task's command input and trace (fw_command_ll / fw_trace_ll): the target goes to ll_target_slot above
 #include "fwsim_command.hpp"
+// the waypoints task under six direct actuator commands, and the high-level command step in front of it (fw_command_hl)
+#include "fwsim_direct.hpp"
 
 // ======================================================================
 // host side
@@ -1597,7 +1599,7 @@ int validate(const fw_config* c, std::string& msg) {
       if (!(c->gust_amp_enu_mps_range[i][0] <= c->gust_amp_enu_mps_range[i][1])) { snprintf(buf, sizeof buf, "Invalid gust_amp_enu_mps_range"); return fail(FW_EINVAL); }
     }
   }
-  if (c->task < FW_TASK_WAYPOINTS || c->task > FW_TASK_LOWLEVEL) { snprintf(buf, sizeof buf, "unknown task %d", c->task); return fail(FW_EINVAL); }
+  if (c->task < FW_TASK_WAYPOINTS || (c->task > FW_TASK_LOWLEVEL && c->task != FW_TASK_WAYPOINTS_DIRECT)) { snprintf(buf, sizeof buf, "unknown task %d", c->task); return fail(FW_EINVAL); }
   if (c->task == FW_TASK_LOWLEVEL) {
     // fixedwing_lowlevel_env.py:32-33, 46, 137: numpy's uniform(low, high) needs low < high to be a range at all
     if (!(c->lowlevel_speed_range[0] < c->lowlevel_speed_range[1])) {
@@ -1630,7 +1632,7 @@ int validate(const fw_config* c, std::string& msg) {
 
 int obs_dim_of(const fw_config* c) {
   if (c->task == FW_TASK_LOWLEVEL) return 21;       // fixedwing_lowlevel_env.py:65-66
-  int att = (c->angle_representation == 0 ? 12 : 13) + 4 + 6;
+  int att = (c->angle_representation == 0 ? 12 : 13) + (c->task == FW_TASK_WAYPOINTS_DIRECT ? 6 : 4) + 6;      // (direct: the action block is six wide)
   if (c->task == FW_TASK_OBJLOCK) return att + 3 + FW_VISION_FEATS * FW_VISION_HIST + (c->duck_vision_no_deltas ? 0 : 4);
   return att + 3 * c->context_length;
 }
@@ -1735,7 +1737,7 @@ bool build_params(const fw_config& c, uint64_t seed, int64_t env_offset, Params<
   P.wind_mode = c.wind_mode; P.wind_randomize = c.wind_randomize_on_reset; P.wind_randomize_phase = c.wind_randomize_phase;
   P.wind_coupling = (c.wind_mode == FW_WIND_OFF) ? FW_WIND_COUPLE_NONE : c.wind_coupling;
   P.task = c.task; P.angle_repr = c.angle_representation;
-  P.att_dim = (c.angle_representation == 0 ? 12 : 13) + 4 + 6;
+  P.att_dim = (c.angle_representation == 0 ? 12 : 13) + (c.task == FW_TASK_WAYPOINTS_DIRECT ? 6 : 4) + 6;
   P.obs_dim = obs_dim_of(&c); P.ctx = c.context_length;
   P.num_targets = c.num_targets; P.sparse = c.sparse_reward; P.auto_reset = c.auto_reset;
   P.max_steps = (int32_t)(c.agent_hz * c.max_duration_seconds);
@@ -1745,7 +1747,8 @@ bool build_params(const fw_config& c, uint64_t seed, int64_t env_offset, Params<
   // The warm-up is env-independent iff wind cannot act on the dynamics (throttle
   // stays exactly 0 under a zero setpoint, so motor noise multiplies 0).
   // ObjLock: the camera may capture during the warm-up (cadence), so it is always integrated in-kernel.
-  P.warm_valid = (P.wind_coupling == FW_WIND_COUPLE_NONE && c.task == FW_TASK_WAYPOINTS) ? 1 : 0;   // (the duck cannot be in contact during warm-up: it spawns >= start height away only by chance; contacts there are ignored by the reference too)
+  // (direct actuator commands: the same warm-up -- all six commands zero, throttle command zero)
+  P.warm_valid = (P.wind_coupling == FW_WIND_COUPLE_NONE && (c.task == FW_TASK_WAYPOINTS || c.task == FW_TASK_WAYPOINTS_DIRECT)) ? 1 : 0;   // (the duck cannot be in contact during warm-up: it spawns >= start height away only by chance; contacts there are ignored by the reference too)
   P.seed_lo = (uint32_t)seed; P.seed_hi = (uint32_t)(seed >> 32);
   P.env_offset = env_offset;
   for (int k = 0; k < 2; ++k) { P.ll_speed[k] = c.lowlevel_speed_range[k]; P.ll_height[k] = c.lowlevel_height_range[k]; }
@@ -1928,7 +1931,8 @@ int create_T(fw_env* h) {
   // shadow warm-up whenever the reset warm-up cannot be cached (wind acting on the dynamics, camera tasks)
   const bool cached = (h->cfg.task == FW_TASK_WAYPOINTS) &&
                       (h->cfg.wind_mode == FW_WIND_OFF || h->cfg.wind_coupling == FW_WIND_COUPLE_NONE);
-  h->shadow_on = (!cached && h->cfg.auto_reset && h->cfg.task != FW_TASK_LOWLEVEL && !getenv("FWSIM_NO_SHADOW")) ? 1 : 0;   // (low-level: no warm-up to hand off)
+  h->shadow_on = (!cached && h->cfg.auto_reset && h->cfg.task != FW_TASK_LOWLEVEL && h->cfg.task != FW_TASK_WAYPOINTS_DIRECT &&
+                  !getenv("FWSIM_NO_SHADOW")) ? 1 : 0;   // (low-level: no warm-up to hand off; direct waypoints: resets run in the kernel)
   // wind-free waypoints on the latency mapping: workers only pre-sample the next episode's waypoints (scenario_worker)
   if (h->cfg.task == FW_TASK_WAYPOINTS && h->cfg.wind_mode == FW_WIND_OFF && h->cfg.auto_reset && h->lanes_per_env == 8 &&
       !getenv("FWSIM_NO_SHADOW"))
@@ -1990,6 +1994,9 @@ int step_T(fw_env* h, const void* actions, void* obs, void* reward, uint8_t* ter
   if (h->cfg.task == FW_TASK_LOWLEVEL) {
     if (g8) { if (general) FW_LAUNCH_STEP((fw_step_kernel_ll<T, 8, true>)); else FW_LAUNCH_STEP((fw_step_kernel_ll<T, 8, false>)); }
     else { if (general) FW_LAUNCH_STEP((fw_step_kernel_ll<T, 1, true>)); else FW_LAUNCH_STEP((fw_step_kernel_ll<T, 1, false>)); }
+  } else if (h->cfg.task == FW_TASK_WAYPOINTS_DIRECT) {
+    if (g8) { if (general) FW_LAUNCH_STEP((fw_step_kernel_wd<T, 8, true>)); else FW_LAUNCH_STEP((fw_step_kernel_wd<T, 8, false>)); }
+    else { if (general) FW_LAUNCH_STEP((fw_step_kernel_wd<T, 1, true>)); else FW_LAUNCH_STEP((fw_step_kernel_wd<T, 1, false>)); }
   } else if (h->cfg.task == FW_TASK_OBJLOCK) {
     if (g8 && h->capture_wave) FW_LAUNCH_STEP_H((fw_step_kernel_obj_g8h<T, FW_TASK_OBJLOCK>));
     else if (g8) FW_LAUNCH_STEP((fw_step_kernel_obj_g8<T, FW_TASK_OBJLOCK>)); else FW_LAUNCH_STEP((fw_step_kernel_obj_g1<T, FW_TASK_OBJLOCK>));
@@ -2020,6 +2027,8 @@ int reset_T(fw_env* h, const uint8_t* mask, void* obs, int do_reset, hipStream_t
 #define FW_LAUNCH_RESET_LL(KERNEL) hipLaunchKernelGGL((KERNEL), grid_of(h), dim3(kWave), tile_bytes<T>(h), st, (const Params<T>*)h->params_dev, dev_state<T>(h), mask, (T*)obs, do_reset, ov)
     if (g8) FW_LAUNCH_RESET_LL((fw_reset_kernel_ll<T, 8>)); else FW_LAUNCH_RESET_LL((fw_reset_kernel_ll<T, 1>));
 #undef FW_LAUNCH_RESET_LL
+  } else if (h->cfg.task == FW_TASK_WAYPOINTS_DIRECT) {
+    if (g8) FW_LAUNCH_RESET((fw_reset_kernel_wd<T, 8>)); else FW_LAUNCH_RESET((fw_reset_kernel_wd<T, 1>));
   } else if (h->cfg.task == FW_TASK_OBJLOCK) {
     if (g8) FW_LAUNCH_RESET((fw_reset_kernel<T, 8, FW_TASK_OBJLOCK>)); else FW_LAUNCH_RESET((fw_reset_kernel<T, 1, FW_TASK_OBJLOCK>));
   } else if (h->cfg.task == FW_TASK_WAYPOINT_OBJLOCK) {
@@ -2164,7 +2173,7 @@ int32_t fw_sizeof_config(void) { return (int32_t)sizeof(fw_config); }
 int32_t fw_abi_version(void) { return FW_ABI_VERSION; }
 int32_t fw_state_dim(void) { return FW_STATE_DIM; }
 int32_t fw_obs_dim(const fw_config* cfg) { return cfg ? obs_dim_of(cfg) : FW_EINVAL; }
-int32_t fw_act_dim(const fw_config* cfg) { return cfg ? (cfg->task == FW_TASK_LOWLEVEL ? 6 : 4) : FW_EINVAL; }
+int32_t fw_act_dim(const fw_config* cfg) { return cfg ? ((cfg->task == FW_TASK_LOWLEVEL || cfg->task == FW_TASK_WAYPOINTS_DIRECT) ? 6 : 4) : FW_EINVAL; }
 
 int32_t fw_validate_config(const fw_config* cfg, char* msg, int32_t msg_len) {
   std::string m;
@@ -2292,6 +2301,7 @@ int32_t fw_render(fw_handle h, int32_t res, float* out, void* hip_stream) {
   if (!out) { h->err = "fw_render: out is NULL"; return FW_EINVAL; }
   if (h->cfg.task == FW_TASK_WAYPOINTS) { h->err = "fw_render: the waypoints task has no camera"; return FW_EUNSUPPORTED; }
   if (h->cfg.task == FW_TASK_LOWLEVEL) { h->err = "fw_render: the low-level task has no camera"; return FW_EUNSUPPORTED; }
+  if (h->cfg.task == FW_TASK_WAYPOINTS_DIRECT) { h->err = "fw_render: the waypoints task has no camera"; return FW_EUNSUPPORTED; }
   if (res < 1 || res > 1024) { h->err = "fw_render: res must be in [1, 1024]"; return FW_EINVAL; }
   DeviceGuard g(h->device);
   const fw_config& c = h->cfg;
@@ -2470,6 +2480,32 @@ int32_t fw_command_ll(fw_handle h, const double* cmd, int32_t T, const int64_t* 
     if (g8) hipLaunchKernelGGL((fw_command_ll_kernel<float, 8>), grid, block, 0, st, dev_state<float>(h), cmd, T, step_idx, mask, (float*)obs, rejected, dome);
     else hipLaunchKernelGGL((fw_command_ll_kernel<float, 1>), grid, block, 0, st, dev_state<float>(h), cmd, T, step_idx, mask, (float*)obs, rejected, dome);
   }
+  HIP_TRY(h, hipGetLastError());
+  return FW_OK;
+}
+
+int32_t fw_command_hl(fw_handle h, const void* action, int32_t action_is_f64, const uint8_t* mask, const void* obs, void* low_obs,
+                      void* cmd_out, int32_t* rejected, void* hip_stream) {
+  if (!h) { g_err = "fw_command_hl: NULL handle"; return FW_EINVAL; }
+  if (h->cfg.task != FW_TASK_WAYPOINTS_DIRECT) { h->err = "fw_command_hl: only the direct-command waypoints task (FW_TASK_WAYPOINTS_DIRECT) takes high-level commands"; return FW_EUNSUPPORTED; }
+  if (h->cfg.angle_representation != 0) { h->err = "fw_command_hl: the low-level controller's observation needs the euler attitude (angle_representation 0)"; return FW_EUNSUPPORTED; }
+  if (!action || !obs || !low_obs) { h->err = "fw_command_hl: action, obs and low_obs must be non-NULL"; return FW_EINVAL; }
+  DeviceGuard g(h->device);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const dim3 block(256), grid((unsigned)((h->n + 255) / 256));
+  const bool g8 = h->lanes_per_env == 8;
+  const double dome = h->cfg.flight_dome_size;
+  const int32_t D = obs_dim_of(&h->cfg);
+#define FW_LAUNCH_CMD_HL(T, G, TA) hipLaunchKernelGGL((fw_command_hl_kernel<T, G, TA>), grid, block, 0, st, dev_state<T>(h), (const TA*)action, mask, \
+                                                      (const T*)obs, D, (T*)low_obs, (T*)cmd_out, rejected, dome)
+  if (h->cfg.dtype == FW_F64) {
+    if (action_is_f64) { if (g8) FW_LAUNCH_CMD_HL(double, 8, double); else FW_LAUNCH_CMD_HL(double, 1, double); }
+    else { if (g8) FW_LAUNCH_CMD_HL(double, 8, float); else FW_LAUNCH_CMD_HL(double, 1, float); }
+  } else {
+    if (action_is_f64) { if (g8) FW_LAUNCH_CMD_HL(float, 8, double); else FW_LAUNCH_CMD_HL(float, 1, double); }
+    else { if (g8) FW_LAUNCH_CMD_HL(float, 8, float); else FW_LAUNCH_CMD_HL(float, 1, float); }
+  }
+#undef FW_LAUNCH_CMD_HL
   HIP_TRY(h, hipGetLastError());
   return FW_OK;
 }
@@ -2758,6 +2794,10 @@ int64_t fw_collect_step_workspace_bytes(fw_handle h) { return h ? (int64_t)colle
 static int32_t collect_fill(fw_handle h, const fw_collect_args* a, const char* who, bool close, CollectArgs& CA) {
   if (h->cfg.task == FW_TASK_LOWLEVEL) {
     h->err = std::string(who) + " serves the four-action tasks; the low-level task's six actions go through the policy in torch and fw_step";
+    return FW_EUNSUPPORTED;
+  }
+  if (h->cfg.task == FW_TASK_WAYPOINTS_DIRECT) {
+    h->err = std::string(who) + " serves the four-action tasks; the direct-command waypoints task's six actions go through fw_collect_act_a and fw_step";
     return FW_EUNSUPPORTED;
   }
   if (h->lanes_per_env != 8) {

@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 from . import config as K
-from .rollout import policy_inputs
+from .rollout import clip_actions, policy_inputs
 
 
 def sync_envs_normalization(train_env, eval_env) -> None:
@@ -163,7 +163,7 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
     steps = 0
     while (counts < targets).any():
         actions, _, _ = policy(obs, deterministic=deterministic, generator=generator, **policy_inputs(policy, env))
-        clipped = actions.clamp(-1.0, 1.0).to(venv.torch_dtype)
+        clipped = clip_actions(actions, venv).to(venv.torch_dtype)
         obs, _, dones, _, _ = env.step(clipped)
         cur_rew += venv.rewards.to(torch.float64)        # un-normalised reward of the wrapped env
         cur_len += 1
@@ -407,7 +407,7 @@ class ReplayedEvaluation:
             return
         else:
             actions, _, _ = self.policy(self.obs, deterministic=True, generator=None, **policy_inputs(self.policy, self.env))
-            o, _, dones, _, _ = self.env.step(actions.clamp(-1.0, 1.0).to(venv.torch_dtype))
+            o, _, dones, _, _ = self.env.step(clip_actions(actions, venv).to(venv.torch_dtype))
             self.obs.copy_(o)
         if self.track:
             self._track_step()

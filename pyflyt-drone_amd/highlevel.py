@@ -1,0 +1,280 @@
+"""The reference's high-level command task (train/train_highlevel_cmd.py:35-181, ``HighLevelCmdEnv``), vectorised.
+
+A policy outputs (heading, altitude, airspeed) commands; a frozen low-level controller (the six-action ``MlpPolicy`` that
+``examples/train_lowlevel_cmd.py`` trains) turns each command into six actuator commands; the waypoint task runs underneath.
+Which parts of that the reference states and which this build owns is DESIGN.md section 2e.  A vec-step is three launches on the
+env's stream, with no host synchronisation (capturable in a hipGraph):
+
+    fw_command_hl     clip to the action Box, condition (:164-166), low_obs = (obs[:, 0:18], command)
+    fw_collect_act_a  the controller: VecNormalize statistics (frozen), policy net, deterministic, clipped to [-1, 1]
+    fw_step           the waypoints task under six direct actuator commands (FW_TASK_WAYPOINTS_DIRECT)
+
+``condition_command`` restates the first of them in numpy.
+"""
+from __future__ import annotations
+
+import copy
+import ctypes as C
+import os
+from typing import Any, List, Optional
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib
+from . import config as K
+from .spaces import Box
+from .vec_env import FixedwingWaypointsDirectVecEnv, _VecEnvBase, _devptr
+
+LOW_OBS_DIM = 21          # the low-level task's observation: 18 shared columns + (psi, h, V)
+LOW_ACT_DIM = 6
+AIRSPEED_HIGH = 30.0      # the action Box's airspeed bound (train/train_highlevel_cmd.py:96-99)
+
+
+def condition_command(a, dome: float) -> np.ndarray:
+    """The conditioned (heading, altitude, airspeed) command of raw high-level actions ``a[..., 3]``, in double: SB3's clip to the
+    action Box ``[-pi, 0, 0] .. [pi, dome, 30]`` (train/train_highlevel_cmd.py:97-101), then the env's own conditioning (:164-166:
+    heading ``(a + pi) % 2 pi - pi``, altitude clipped to ``[0, dome]``, airspeed clipped to ``[0, 100]``)."""
+    a = np.asarray(a, dtype=np.float64)
+    low, high = np.array([-np.pi, 0.0, 0.0]), np.array([np.pi, float(dome), AIRSPEED_HIGH])
+    b = np.clip(a, low, high)
+    out = np.empty_like(b)
+    out[..., 0] = (b[..., 0] + np.pi) % (2 * np.pi) - np.pi
+    out[..., 1] = np.clip(b[..., 1], 0.0, float(dome))
+    out[..., 2] = np.clip(b[..., 2], 0.0, 100.0)
+    return out
+
+
+def _check_controller(policy) -> None:
+    """The controller the kernels serve: the 21 -> 64 -> 64 -> 6 ``MlpPolicy``."""
+    ok = hasattr(policy, "pi_net") and hasattr(policy, "action_net") and isinstance(policy.action_net, nn.Linear)
+    if ok:
+        lin = [m for m in policy.pi_net if isinstance(m, nn.Linear)]
+        act = [m for m in policy.pi_net if not isinstance(m, nn.Linear)]
+        ok = (len(lin) == 2 and len(act) == 2 and all(isinstance(m, nn.Tanh) for m in act)
+              and (lin[0].in_features, lin[0].out_features) == (LOW_OBS_DIM, 64) and (lin[1].in_features, lin[1].out_features) == (64, 64)
+              and (policy.action_net.in_features, policy.action_net.out_features) == (64, LOW_ACT_DIM))
+    if not ok:
+        raise ValueError("the low-level controller must be the 21 -> 64 -> 64 -> 6 MlpPolicy (rollout.MlpPolicy(21, 6): what "
+                         "examples/train_lowlevel_cmd.py trains)")
+
+
+def _rms_arrays(rms):
+    """(mean, var) as float64 numpy arrays from a RunningMeanStd, a ``{"mean", "var"}`` mapping or a ``(mean, var)`` pair."""
+    if hasattr(rms, "mean") and hasattr(rms, "var"):
+        m, v = rms.mean, rms.var
+    elif isinstance(rms, dict):
+        m, v = rms["mean"], rms["var"]
+    else:
+        m, v = rms
+    m, v = (np.asarray(x.detach().cpu() if torch.is_tensor(x) else x, dtype=np.float64).reshape(-1) for x in (m, v))
+    if m.shape != (LOW_OBS_DIM,) or v.shape != (LOW_OBS_DIM,):
+        raise ValueError(f"the low-level observation statistics must have {LOW_OBS_DIM} entries, got {m.shape[0]} and {v.shape[0]}")
+    return m, v
+
+
+def load_low_checkpoint(path: str):
+    """(policy, (mean, var), clip_obs, epsilon) of a checkpoint written by ``checkpoint.save`` (``examples/train_lowlevel_cmd.py``:
+    ``final_model.pt`` / ``best_model.pt``).  A missing file raises ``FileNotFoundError`` as the reference does (:110-121)."""
+    from .rollout import MlpPolicy
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"low-level controller checkpoint not found: {path}; train the low-level controller first "
+                                "(examples/train_lowlevel_cmd.py)")
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    if "policy" not in sd or "vecnormalize" not in sd:
+        raise ValueError(f"{path} is not a training checkpoint (no policy / vecnormalize entries)")
+    w1, wo = sd["policy"].get("pi_net.0.weight"), sd["policy"].get("action_net.weight")
+    if w1 is None or wo is None or tuple(w1.shape) != (64, LOW_OBS_DIM) or tuple(wo.shape) != (LOW_ACT_DIM, 64):
+        raise ValueError(f"{path} does not hold the 21 -> 64 -> 64 -> 6 MlpPolicy of the low-level task")
+    policy = MlpPolicy(LOW_OBS_DIM, LOW_ACT_DIM)
+    policy.load_state_dict(sd["policy"])
+    vn = sd["vecnormalize"]
+    return policy, _rms_arrays(vn["obs_rms"]), float(vn.get("clip_obs", 10.0)), float(vn.get("epsilon", 1e-8))
+
+
+class HighLevelCmdVecEnv(_VecEnvBase):
+    """``HighLevelCmdEnv`` x N on one MI355X: three actions in the reference's Box (``action_low`` / ``action_high``), the
+    30-value observation of the base env, its reward, termination, truncation and info.
+
+    ``low_policy`` + ``low_obs_rms`` (a ``RunningMeanStd``, a ``{"mean", "var"}`` mapping or a ``(mean, var)`` pair), or
+    ``low_checkpoint`` (a file ``examples/train_lowlevel_cmd.py`` saved), give the frozen controller; the policy is copied.  The other
+    keywords are the reference constructor's.  ``low_action`` holds the controller's clipped output of the last step,
+    ``command`` the conditioned triple, ``low_obs`` the controller's raw observation."""
+
+    metadata = {"render_modes": ["human", "rgb_array"], "render_fps": 30}
+
+    def __init__(self, num_envs: int, low_policy=None, low_obs_rms=None, *, low_checkpoint: Optional[str] = None,
+                 clip_obs: float = 10.0, epsilon: float = 1e-8, render_mode: Optional[str] = None, flight_dome_size: float = 200.0,
+                 max_duration_seconds: float = 120.0, agent_hz: int = 30, context_length: int = 2, wind_config: Optional[dict] = None,
+                 dtype: str = "float64", motor_noise: bool = True, device=None, seed: int = 0, global_env_offset: int = 0):
+        if render_mode is not None:
+            raise ValueError(f"Invalid render mode {render_mode}, rendering is not part of the device env.")
+        # ---- the controller: everything that needs no device first ----
+        if low_checkpoint is not None:
+            if low_policy is not None or low_obs_rms is not None:
+                raise ValueError("give either low_checkpoint or low_policy + low_obs_rms")
+            low_policy, (mean, var), clip_obs, epsilon = load_low_checkpoint(low_checkpoint)
+        else:
+            if low_policy is None or low_obs_rms is None:
+                raise ValueError("HighLevelCmdVecEnv needs the low-level controller: low_policy + low_obs_rms, or low_checkpoint")
+            _check_controller(low_policy)
+            mean, var = _rms_arrays(low_obs_rms)
+        _check_controller(low_policy)
+        if wind_config is not None and not bool(wind_config.get("enabled", False)):
+            wind_config = None                                       # (:86-87)
+        self.base = FixedwingWaypointsDirectVecEnv(
+            num_envs, flight_dome_size=flight_dome_size, max_duration_seconds=max_duration_seconds, agent_hz=agent_hz,
+            context_length=context_length, angle_representation="euler", wind_config=wind_config, dtype=dtype,
+            motor_noise=motor_noise, device=device, seed=seed, global_env_offset=global_env_offset)
+        b = self.base
+        self.device, self.cfg, self.num_envs = b.device, b.cfg, b.num_envs
+        self.obs_dim, self.act_dim = b.obs_dim, 3
+        self.np_dtype, self.torch_dtype = b.np_dtype, b.torch_dtype
+        self.global_env_offset, self.lanes_per_env = b.global_env_offset, b.lanes_per_env
+        self.render_mode = None
+        self.clip_obs, self.epsilon = float(clip_obs), float(epsilon)
+        low = np.array([-np.pi, 0.0, 0.0], dtype=np.float32)
+        high = np.array([np.pi, flight_dome_size, AIRSPEED_HIGH], dtype=np.float32)
+        _VecEnvBase.__init__(self, self.num_envs, Box(-np.inf, np.inf, (self.obs_dim,), self.np_dtype), Box(low, high, (3,), np.float32))
+        dev, n = self.device, self.num_envs
+        self.action_low, self.action_high = torch.as_tensor(low, device=dev), torch.as_tensor(high, device=dev)
+        # the frozen controller: a copy of the module (what the tests' torch forward uses) and the kernels' flat parameter image
+        from .rollout import FusedPpoUpdate
+        self.low_policy = copy.deepcopy(low_policy).to(dev).eval()
+        for p in self.low_policy.parameters():
+            p.requires_grad_(False)
+        f = FusedPpoUpdate(self.low_policy, None, LOW_OBS_DIM)
+        f.load_params_from_torch()
+        self._flat = f.flat
+        self.low_mean = torch.as_tensor(mean, dtype=torch.float64, device=dev)
+        self.low_var = torch.as_tensor(var, dtype=torch.float64, device=dev)
+        self.low_obs = torch.zeros((n, LOW_OBS_DIM), dtype=self.torch_dtype, device=dev)
+        self.low_action = torch.zeros((n, LOW_ACT_DIM), dtype=self.torch_dtype, device=dev)
+        self.command = torch.zeros((n, 3), dtype=self.torch_dtype, device=dev)
+        self.rejected = torch.zeros(1, dtype=torch.int32, device=dev)       # rows with a non-finite action so far (they kept their command)
+        self._act_raw = torch.zeros((n, LOW_ACT_DIM), dtype=torch.float32, device=dev)
+        self._logp = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._actions_dev = torch.zeros((n, 3), dtype=self.torch_dtype, device=dev)
+        self._pending = False
+
+    # the base env's output tensors are this env's
+    obs = property(lambda self: self.base.obs)
+    rewards = property(lambda self: self.base.rewards)
+    terminated = property(lambda self: self.base.terminated)
+    truncated = property(lambda self: self.base.truncated)
+    terminal_obs = property(lambda self: self.base.terminal_obs)
+    info = property(lambda self: self.base.info)
+    seed_value = property(lambda self: self.base.seed_value)
+
+    # ------------------------------------------------------------------ device fast path
+    def reset_tensor(self, mask: Optional[torch.Tensor] = None, scenario: Optional[dict] = None) -> torch.Tensor:
+        return self.base.reset_tensor(mask, scenario)
+
+    def observe_tensor(self) -> torch.Tensor:
+        return self.base.observe_tensor()
+
+    def step_tensor(self, actions: torch.Tensor):
+        """One agent step from raw high-level actions ``[N, 3]`` (float32 or float64 device tensor; anything else is converted to
+        the env dtype): ``fw_command_hl -> fw_collect_act_a -> fw_step`` on the current stream.  Returns the base env's
+        ``(obs, rewards, terminated, truncated)``."""
+        b, L, n = self.base, _lib.lib(), self.num_envs
+        if actions.device != self.device or actions.dtype not in (torch.float32, torch.float64) or not actions.is_contiguous():
+            dt = actions.dtype if actions.dtype in (torch.float32, torch.float64) else self.torch_dtype
+            actions = actions.to(device=self.device, dtype=dt).contiguous()
+        if actions.shape != (n, 3):
+            raise ValueError(f"actions must have shape ({n}, 3), got {tuple(actions.shape)}")
+        st = b._stream()
+        _lib.check(L.fw_command_hl(b._h, _devptr(actions), int(actions.dtype == torch.float64), None, _devptr(b.obs),
+                                   _devptr(self.low_obs), _devptr(self.command), _devptr(self.rejected), st), b._h)
+        f64 = int(self.torch_dtype == torch.float64)
+        # the controller: policy net only, deterministic, frozen statistics, nothing of a previous step to finalise
+        _lib.check(L.fw_collect_act_a(_devptr(self._flat), _devptr(self.low_obs), f64, n, LOW_OBS_DIM, LOW_ACT_DIM,
+                                      _devptr(self.low_mean), _devptr(self.low_var), self.clip_obs, self.epsilon, 1, 1, None,
+                                      int(self.global_env_offset), None, _devptr(self._act_raw), _devptr(self.low_action), f64,
+                                      _devptr(self._logp), None, None, None, None, None, None, 0, 0.0, 0.0, 0.0, None, None, st))
+        return b.step_tensor(self.low_action)
+
+    # ------------------------------------------------------------------ SB3 VecEnv surface (numpy)
+    def reset(self) -> np.ndarray:
+        obs = self.base.reset()
+        self.reset_infos = [{} for _ in range(self.num_envs)]
+        return obs
+
+    def step_async(self, actions: np.ndarray) -> None:
+        a = torch.as_tensor(np.asarray(actions), dtype=self.torch_dtype).reshape(self.num_envs, 3)
+        self._actions_dev.copy_(a, non_blocking=False)
+        self.step_tensor(self._actions_dev)
+        self._pending = True
+
+    def step_wait(self):
+        if not self._pending:
+            raise RuntimeError("step_wait() called without step_async()")
+        self._pending = False
+        self.base._pending = True
+        obs, rewards, dones, infos = self.base.step_wait()
+        cmd = self.command.cpu().numpy().astype(np.float64)
+        for i, d in enumerate(infos):
+            d["command"] = cmd[i].copy()
+        return obs, rewards, dones, infos
+
+    def step(self, actions: np.ndarray):
+        self.step_async(actions)
+        return self.step_wait()
+
+    def seed(self, seed: Optional[int] = None):
+        self._seeds = self.base.seed(seed)
+        return self._seeds
+
+    def close(self) -> None:
+        b = self.__dict__.get("base")
+        if b is not None:
+            b.close()
+
+    def get_attr(self, attr_name: str, indices=None) -> List[Any]:
+        if attr_name == "render_mode":
+            v = self.__dict__.get("render_mode", None)
+        elif attr_name in self.__dict__ or hasattr(type(self), attr_name):
+            v = getattr(self, attr_name)
+        elif "base" in self.__dict__:
+            return self.base.get_attr(attr_name, indices)
+        else:
+            raise AttributeError(f"{type(self).__name__} envs have no attribute {attr_name!r}")
+        return [v for _ in self.base._indices(indices)] if "base" in self.__dict__ else [v for _ in range(self.num_envs)]
+
+    def set_attr(self, attr_name: str, value: Any, indices=None) -> None:
+        if any(attr_name == f[0] for f in type(self.cfg)._fields_):
+            raise AttributeError(f"{attr_name!r} is part of the device-side configuration; build a new env with it")
+        if indices is not None and sorted(self.base._indices(indices)) != list(range(self.num_envs)):
+            raise AttributeError("the envs of a fused device env share their attributes: set them for all envs (indices=None)")
+        setattr(self, attr_name, value)
+
+    def env_method(self, method_name: str, *args, indices=None, **kwargs) -> List[Any]:
+        fn = getattr(self, method_name, None)
+        if not callable(fn) or method_name.startswith("_"):
+            raise AttributeError(f"env_method({method_name!r}) is not available on a fused device env")
+        out = fn(*args, **kwargs)
+        return [out for _ in self.base._indices(indices)]
+
+    def env_is_wrapped(self, wrapper_class, indices=None) -> List[bool]:
+        return [False for _ in self.base._indices(indices)]
+
+    def get_images(self):
+        return [None for _ in range(self.num_envs)]
+
+    def render(self, mode: Optional[str] = None):
+        return None
+
+    @property
+    def unwrapped(self):
+        return self
+
+    # ------------------------------------------------------------------ state access (parity tests / checkpoints)
+    def get_state(self) -> np.ndarray:
+        return self.base.get_state()
+
+    def set_state(self, state: np.ndarray) -> None:
+        self.base.set_state(state)
+
+    def get_counters(self) -> dict:
+        return self.base.get_counters()

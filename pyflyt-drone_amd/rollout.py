@@ -448,6 +448,15 @@ class CnnDetectorPolicy(nn.Module):
         return self.mlp.evaluate_actions(self.features(obs, img, feat), actions)
 
 
+def clip_actions(actions: torch.Tensor, venv) -> torch.Tensor:
+    """SB3's ``np.clip(actions, action_space.low, action_space.high)`` in front of ``env.step``: the bounds an env declares as
+    device tensors ``action_low`` / ``action_high`` (the high-level command env's Box, in physical units), [-1, 1] otherwise."""
+    lo, hi = getattr(venv, "action_low", None), getattr(venv, "action_high", None)
+    if lo is None or hi is None:
+        return actions.clamp(-1.0, 1.0)
+    return torch.clamp(actions, min=lo.to(actions.dtype), max=hi.to(actions.dtype))
+
+
 def policy_inputs(policy, env, out: Optional[torch.Tensor] = None) -> dict:
     """Extra inputs of a policy call besides the flat observation: ``{"img": FPV render of env's current state}`` for a policy
     with a CNN front end (``uses_image``), nothing otherwise."""
@@ -863,7 +872,7 @@ class PPO:
                 kw = {"feat": self.policy.image_features(self.last_img)}
                 self.buf_img[t].copy_(self.last_img)
             actions, values, logp = self.policy(self.last_obs, generator=self.gen, **kw)
-            clipped = actions.clamp(-1.0, 1.0).to(act_dtype)
+            clipped = clip_actions(actions, env.venv).to(act_dtype)
             obs_n, rew_n, dones, timeouts, tobs_n = env.step(clipped)
             # bootstrap truncated episodes with V(terminal_observation).  (CNN front end: the env has already auto-reset, so the
             # terminal pose can no longer be rendered; the image of the step before stands in -- one agent step stale, and only

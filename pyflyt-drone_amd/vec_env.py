@@ -266,7 +266,7 @@ class FixedwingVecEnv(_VecEnvBase):
                 "num_targets_reached": int(info[i, K.INFO_NUM_TARGETS_REACHED]),
                 "TimeLimit.truncated": bool(trunc[i] and not term[i]),
             }
-            if self.cfg.task != K.FW_TASK_WAYPOINTS:
+            if self.cfg.task not in (K.FW_TASK_WAYPOINTS, K.FW_TASK_WAYPOINTS_DIRECT):
                 d["duck_strike"] = bool(info[i, K.INFO_DUCK_STRIKE])
                 d["is_success"] = bool(info[i, K.INFO_IS_SUCCESS])
             if dones[i] and self.cfg.auto_reset:
@@ -405,6 +405,29 @@ class FixedwingWaypointsVecEnv(FixedwingVecEnv):
                                  angle_representation=angle_representation, agent_hz=agent_hz,
                                  context_length=context_length, wind_config=wind_config, dtype=dtype,
                                  motor_noise=motor_noise)
+        super().__init__(cfg, num_envs, device=device, seed=seed, global_env_offset=global_env_offset)
+
+
+class FixedwingWaypointsDirectVecEnv(FixedwingVecEnv):
+    """The waypoints task flown in PyFlyt's mode -1 (``FW_TASK_WAYPOINTS_DIRECT``): six actuator commands in
+    [-1, 1] (surfaces ``a[0..4]`` as given, throttle ``0.5 a[5] + 0.5``) instead of the four mode-0 actions; everything else, and
+    every keyword, as :class:`FixedwingWaypointsVecEnv`.  The observation's action block is six wide (30 values at euler / context 2).
+    The base env of :class:`~.highlevel.HighLevelCmdVecEnv`."""
+
+    def __init__(self, num_envs: int, *, sparse_reward: bool = False, num_targets: int = 4,
+                 goal_reach_distance: float = 2.0, flight_dome_size: float = 100.0,
+                 max_duration_seconds: float = 120.0, angle_representation: str = "quaternion",
+                 agent_hz: int = 30, context_length: int = 2, wind_config: Optional[dict] = None,
+                 render_mode: Optional[str] = None, dtype: str = "float64", motor_noise: bool = True,
+                 device=None, seed: int = 0, global_env_offset: int = 0):
+        if render_mode is not None:
+            raise ValueError(f"Invalid render mode {render_mode}, rendering is not part of the device env.")
+        cfg = K.waypoints_direct_config(sparse_reward=sparse_reward, num_targets=num_targets,
+                                        goal_reach_distance=goal_reach_distance, flight_dome_size=flight_dome_size,
+                                        max_duration_seconds=max_duration_seconds,
+                                        angle_representation=angle_representation, agent_hz=agent_hz,
+                                        context_length=context_length, wind_config=wind_config, dtype=dtype,
+                                        motor_noise=motor_noise)
         super().__init__(cfg, num_envs, device=device, seed=seed, global_env_offset=global_env_offset)
 
 
