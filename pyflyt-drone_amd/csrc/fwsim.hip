@@ -7,6 +7,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <new>
 #include <string>
 #include <type_traits>
@@ -1573,6 +1575,10 @@ namespace {
 constexpr int kG8MaxEnvs = 16384;   // measured crossover on MI355X: 8 lanes/env wins up to 2^14 envs (51 vs 70 us), loses at 2^15 (93 vs 76 us)
 thread_local std::string g_err;
 
+// Task predicates: what the host side asks about a task, in one place (a new task answers them here).
+inline bool has_camera(int task) { return task == FW_TASK_OBJLOCK || task == FW_TASK_WAYPOINT_OBJLOCK; }
+inline bool direct_actions(int task) { return task == FW_TASK_LOWLEVEL || task == FW_TASK_WAYPOINTS_DIRECT; }   // six actuator commands
+
 struct HostDerived {
   double area, aspect, Cl3, a0b, asPb, asNb, theta_f, tau_f, tq[3];
 };
@@ -1623,16 +1629,18 @@ int validate(const fw_config* c, std::string& msg) {
   if (c->task != FW_TASK_OBJLOCK && (c->context_length < 0 || c->context_length > FW_MAX_TARGETS + 1)) { snprintf(buf, sizeof buf, "bad context_length"); return fail(FW_EINVAL); }
   if (c->n_collision_pts < 0 || c->n_collision_pts > FW_MAX_COLLISION_PTS) { snprintf(buf, sizeof buf, "bad n_collision_pts"); return fail(FW_EINVAL); }
   if (c->num_obstacles < 0 || c->num_obstacles > FW_MAX_OBSTACLES) { snprintf(buf, sizeof buf, "bad num_obstacles"); return fail(FW_EINVAL); }
-  if ((c->task == FW_TASK_OBJLOCK || c->task == FW_TASK_WAYPOINT_OBJLOCK) && (c->camera_resolution < 0 || c->camera_resolution > 1024)) { snprintf(buf, sizeof buf, "camera_resolution must be in [1, 1024]"); return fail(FW_EINVAL); }
+  if (has_camera(c->task) && (c->camera_resolution < 0 || c->camera_resolution > 1024)) { snprintf(buf, sizeof buf, "camera_resolution must be in [1, 1024]"); return fail(FW_EINVAL); }
   if (c->physics_hz <= 0 || c->control_hz <= 0 || c->physics_hz % c->control_hz != 0) { snprintf(buf, sizeof buf, "physics_hz must be a multiple of control_hz"); return fail(FW_EINVAL); }
   if (!(c->mass > 0.0)) { snprintf(buf, sizeof buf, "mass must be > 0"); return fail(FW_EINVAL); }
   if (c->wind_coupling < FW_WIND_COUPLE_NONE || c->wind_coupling > FW_WIND_COUPLE_AIRSPEED) { snprintf(buf, sizeof buf, "bad wind_coupling"); return fail(FW_EINVAL); }
   return FW_OK;
 }
 
+// attitude block of the waypoint / camera observations: pose, the last action (direct waypoints: six wide), auxiliary state
+int att_dim_of(const fw_config* c) { return (c->angle_representation == 0 ? 12 : 13) + (c->task == FW_TASK_WAYPOINTS_DIRECT ? 6 : 4) + 6; }
 int obs_dim_of(const fw_config* c) {
   if (c->task == FW_TASK_LOWLEVEL) return 21;       // fixedwing_lowlevel_env.py:65-66
-  int att = (c->angle_representation == 0 ? 12 : 13) + (c->task == FW_TASK_WAYPOINTS_DIRECT ? 6 : 4) + 6;      // (direct: the action block is six wide)
+  const int att = att_dim_of(c);
   if (c->task == FW_TASK_OBJLOCK) return att + 3 + FW_VISION_FEATS * FW_VISION_HIST + (c->duck_vision_no_deltas ? 0 : 4);
   return att + 3 * c->context_length;
 }
@@ -1737,7 +1745,7 @@ bool build_params(const fw_config& c, uint64_t seed, int64_t env_offset, Params<
   P.wind_mode = c.wind_mode; P.wind_randomize = c.wind_randomize_on_reset; P.wind_randomize_phase = c.wind_randomize_phase;
   P.wind_coupling = (c.wind_mode == FW_WIND_OFF) ? FW_WIND_COUPLE_NONE : c.wind_coupling;
   P.task = c.task; P.angle_repr = c.angle_representation;
-  P.att_dim = (c.angle_representation == 0 ? 12 : 13) + (c.task == FW_TASK_WAYPOINTS_DIRECT ? 6 : 4) + 6;
+  P.att_dim = att_dim_of(&c);
   P.obs_dim = obs_dim_of(&c); P.ctx = c.context_length;
   P.num_targets = c.num_targets; P.sparse = c.sparse_reward; P.auto_reset = c.auto_reset;
   P.max_steps = (int32_t)(c.agent_hz * c.max_duration_seconds);
@@ -1757,6 +1765,14 @@ bool build_params(const fw_config& c, uint64_t seed, int64_t env_offset, Params<
   return true;
 }
 
+// One env kernel as a handle launches it (env_kernels_of below): the host function pointer and what of the launch follows the kernel.
+struct EnvKernel {
+  const void* fn = nullptr;
+  unsigned block = kWave;       // 2 * kWave: a capture wave beside every step wave (its LDS carries the mailbox, step_lds_bytes_h)
+  bool worker_half = true;      // step kernels: with shadow_on the second half of the grid are the shadow workers
+  bool takes_objc = true;       // reset kernels: the argument list has the ObjC block (the low-level task's has not)
+};
+
 }  // namespace
 
 struct fw_env {
@@ -1766,6 +1782,7 @@ struct fw_env {
   int32_t g8_waves = 1;         // 8-lane mapping, waypoints task: waves per SIMD the step kernel is built for (1 | 2)
   int32_t capture_wave = 0;     // 8-lane mapping, camera tasks: fw_step workgroups carry a capture wave (fw_step_kernel_obj_g8h)
   int32_t axis_aligned = 0;     // f64 wind-free waypoints on the 8-lane one-wave build: the tick's axis-aligned variant (axis_aligned_geometry)
+  EnvKernel step, reset, collect;   // chosen once by fw_create from the fields above (select_kernels); collect.fn is null where fw_collect_step does not serve
   uint64_t seed = 0;
   int64_t env_offset = 0;
   void* params_dev = nullptr;   // Params<T>
@@ -1815,9 +1832,25 @@ int device_of(const void* p) {
   (void)hipGetLastError();                     // clear the sticky error of a failed query
   return cur;
 }
-// Opt an LDS-resident learner kernel into `bytes` of dynamic LDS: done when a device first sees a size larger than any
-// before (i.e. on the first call per observation width), never again on the launch path.
-int ensure_learner_lds(int dev, int which /*0: fw_ppo_update, 1: fw_policy_act, 2 / 3: their six-action kernels*/, size_t bytes);
+// Opt `kernel` into `bytes` of dynamic LDS where that is more than the 48 KB a workgroup gets without asking.  The attribute belongs
+// to the (device, kernel) pair, not to a handle or a call: keep the maximum ever asked for and only ever raise it, so a later, smaller
+// handle cannot lower the cap under an earlier one.  Set when a pair first sees a larger size, never again on the launch path.
+int ensure_dynamic_lds(fw_env* h, int device, const void* kernel, size_t bytes) {
+  if (bytes <= 48 * 1024) return FW_OK;
+  static std::mutex mu;                         // (one thread per process drives launches today; the lock keeps the map whole if two ever do)
+  static std::map<std::pair<int, const void*>, size_t> caps;
+  std::lock_guard<std::mutex> lock(mu);
+  size_t& cap = caps[{device, kernel}];
+  if (bytes <= cap) return FW_OK;
+  HIP_TRY(h, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  cap = bytes;
+  return FW_OK;
+}
+
+// From a runtime dtype / lane mapping to template arguments: f gets a value of the type, or the lanes per env as a std::integral_constant.
+template <typename F> auto with_real(bool is_f64, F&& f) { return is_f64 ? f(double{}) : f(float{}); }
+template <typename F> auto with_dtype(const fw_env* h, F&& f) { return with_real(h->cfg.dtype == FW_F64, f); }
+template <typename F> auto with_lanes(const fw_env* h, F&& f) { return h->lanes_per_env == 8 ? f(std::integral_constant<int, 8>{}) : f(std::integral_constant<int, 1>{}); }
 
 template <typename T> size_t tile_bytes(const fw_env* h);
 template <typename T> size_t step_lds_bytes(const fw_env* h);
@@ -1854,7 +1887,7 @@ inline int zrow_stride_of(int res) { return ((res + 31) / 32) * 32 + 8; }
 // row buffer of the analytic camera (1 / t of the nearest cylinder fragment per column), 8 envs x zrow_stride words
 template <typename T> size_t tile_bytes(const fw_env* h) {
   size_t b = sizeof(T) * (size_t)(kWave / h->lanes_per_env) * (size_t)(obs_dim_of(&h->cfg) + 1);
-  if ((h->cfg.task == FW_TASK_OBJLOCK || h->cfg.task == FW_TASK_WAYPOINT_OBJLOCK) && h->lanes_per_env == 8) {
+  if (has_camera(h->cfg.task) && h->lanes_per_env == 8) {
     const int res = h->cfg.camera_resolution > 0 ? h->cfg.camera_resolution : 128;
     b = std::max(b, cam_lds(sizeof(T), zrow_stride_of(res), res, h->cfg.num_obstacles > 0).total);   // camera map (fwsim_objlock.hpp): 2 KB without, 48 KB with cylinders at 480 columns
   }
@@ -1916,12 +1949,84 @@ int upload_params(fw_env* h) {
   return FW_OK;
 }
 
+// ---- which kernels a handle launches: one table, looked up once by fw_create (select_kernels) ----
+// A key names the fields of a handle that the choice depends on; kAny in a row matches every value.  The first row that matches
+// wins, so a special case stands above the general one.  A new kernel variant is one new row.
+constexpr int kAny = -1;
+struct KernelKey { int task, lanes, waves, windy, axis_aligned, capture_wave; };
+struct KernelRow { KernelKey key; EnvKernel step, reset, collect; };
+template <typename... A> const void* kfn(void (*kernel)(A...)) { return (const void*)kernel; }      // the host-side pointer hipLaunchKernel takes
+// The argument lists step_T / collect_step_T / reset_T build.  hipLaunchKernel takes them unchecked, so a kernel enters the table
+// through the function of its family: a row whose kernel takes anything else does not compile.
+template <typename T> using StepFn = void (*)(const Params<T>*, const ObjC<T>*, DevState<T>, const T*, T*, T*, uint8_t*, uint8_t*, T*, int32_t*);
+template <typename T> using CollectFn = void (*)(const Params<T>*, const ObjC<T>*, DevState<T>, const T*, T*, T*, uint8_t*, uint8_t*, T*, int32_t*, CollectArgs);
+template <typename T> using ResetFn = void (*)(const Params<T>*, const ObjC<T>*, DevState<T>, const uint8_t*, T*, int, ScenOv);
+template <typename T> using ResetLLFn = void (*)(const Params<T>*, DevState<T>, const uint8_t*, T*, int, ScenOv);
+template <typename T> EnvKernel step_k(StepFn<T> f) { return {kfn(f)}; }
+template <typename T> EnvKernel two_wave(StepFn<T> f) { return {kfn(f), 2 * kWave, false}; }       // step wave + capture wave per workgroup (the capture wave is the worker)
+template <typename T> EnvKernel collect_k(CollectFn<T> f) { return {kfn(f)}; }
+template <typename T> EnvKernel reset_k(ResetFn<T> f) { return {kfn(f)}; }
+template <typename T> EnvKernel no_objc(ResetLLFn<T> f) { return {kfn(f), kWave, true, false}; }
+// The axis-aligned tick exists in f64 only: its float row holds no kernel, and select_kernels refuses a handle that lands on it.
+template <typename T> EnvKernel axis_aligned_step_kernel() {
+  if constexpr (std::is_same<T, double>::value) return step_k<T>(fw_step_kernel_g8<T, false, true>); else return {};
+}
+// (fw_collect_step: the four-action tasks on the 8-lane mapping -- collect_fill says so to the others; general tick, no capture wave)
+template <typename T> const KernelRow* env_kernels_of(const KernelKey& q) {
+  constexpr int LL = FW_TASK_LOWLEVEL, WD = FW_TASK_WAYPOINTS_DIRECT, OBJ = FW_TASK_OBJLOCK, COMB = FW_TASK_WAYPOINT_OBJLOCK, WP = FW_TASK_WAYPOINTS;
+  static const KernelRow rows[] = {
+    // task lanes waves windy axis  capture   fw_step                                               fw_reset / fw_observe                                fw_collect_step
+    {{LL,   8, kAny, 1,    kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 8, true>),         no_objc<T>(fw_reset_kernel_ll<T, 8>),         {}},
+    {{LL,   8, kAny, 0,    kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 8, false>),        no_objc<T>(fw_reset_kernel_ll<T, 8>),         {}},
+    {{LL,   1, kAny, 1,    kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 1, true>),         no_objc<T>(fw_reset_kernel_ll<T, 1>),         {}},
+    {{LL,   1, kAny, 0,    kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 1, false>),        no_objc<T>(fw_reset_kernel_ll<T, 1>),         {}},
+    {{WD,   8, kAny, 1,    kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, true>),         reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
+    {{WD,   8, kAny, 0,    kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, false>),        reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
+    {{WD,   1, kAny, 1,    kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, true>),         reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
+    {{WD,   1, kAny, 0,    kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, false>),        reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
+    {{OBJ,  8, kAny, kAny, kAny, 1},    two_wave<T>(fw_step_kernel_obj_g8h<T, OBJ>),      reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
+    {{OBJ,  8, kAny, kAny, kAny, 0},    step_k<T>(fw_step_kernel_obj_g8<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
+    {{OBJ,  1, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 1, OBJ>),       {}},
+    {{COMB, 8, kAny, kAny, kAny, 1},    two_wave<T>(fw_step_kernel_obj_g8h<T, COMB>),     reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
+    {{COMB, 8, kAny, kAny, kAny, 0},    step_k<T>(fw_step_kernel_obj_g8<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
+    {{COMB, 1, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 1, COMB>),      {}},
+    {{WP,   8, 1,    0,    1,    kAny}, axis_aligned_step_kernel<T>(),                    reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   8, 2,    1,    kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, true>),          reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, true>)},
+    {{WP,   8, 2,    0,    kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, false>),         reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, false>)},
+    {{WP,   8, 1,    1,    kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, true>),            reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, true>)},
+    {{WP,   8, 1,    0,    kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, false>),           reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   1, kAny, 1,    kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, true>),            reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
+    {{WP,   1, kAny, 0,    kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, false>),           reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
+  };
+  auto fits = [](int row, int v) { return row == kAny || row == v; };
+  for (const KernelRow& r : rows)
+    if (const KernelKey& k = r.key; fits(k.task, q.task) && fits(k.lanes, q.lanes) && fits(k.waves, q.waves) && fits(k.windy, q.windy) &&
+                                    fits(k.axis_aligned, q.axis_aligned) && fits(k.capture_wave, q.capture_wave)) return &r;
+  return nullptr;
+}
+
+// The handle's kernels, from the fields fw_create has just fixed.  A combination without a row (or whose row holds no step or
+// reset kernel) is an error here, not a launch that silently does nothing.
+template <typename T> int select_kernels(fw_env* h) {
+  const KernelKey q = { h->cfg.task, h->lanes_per_env, h->g8_waves, h->cfg.wind_mode != FW_WIND_OFF ? 1 : 0, h->axis_aligned, h->capture_wave };
+  const KernelRow* r = env_kernels_of<T>(q);
+  if (!r || !r->step.fn || !r->reset.fn) {
+    h->err = "no kernel is built for (task, dtype, lanes per env, waves per SIMD, wind, axis_aligned, capture_wave) =";
+    for (int x : { q.task, h->cfg.dtype, q.lanes, q.waves, q.windy, q.axis_aligned, q.capture_wave }) h->err += " " + std::to_string(x);
+    return FW_EUNSUPPORTED;
+  }
+  h->step = r->step; h->reset = r->reset; h->collect = r->collect;
+  return FW_OK;
+}
+
 template <typename T>
 int create_T(fw_env* h) {
   const size_t npad = (size_t)h->npad;
+  int rc = select_kernels<T>(h);
+  if (rc != FW_OK) return rc;
   HIP_TRY(h, hipMalloc(&h->r_dev, sizeof(T) * RF_COUNT * npad));
   HIP_TRY(h, hipMalloc((void**)&h->i_dev, sizeof(int32_t) * IF_COUNT * npad));
-  int rc = upload_params<T>(h);
+  rc = upload_params<T>(h);
   if (rc != FW_OK) return rc;
   const size_t nctr = 2 * (size_t)grid_of(h).x;              // step workgroups + (possibly) as many workers
   HIP_TRY(h, hipMalloc((void**)&h->lctr_dev, sizeof(uint32_t) * nctr));
@@ -1931,8 +2036,7 @@ int create_T(fw_env* h) {
   // shadow warm-up whenever the reset warm-up cannot be cached (wind acting on the dynamics, camera tasks)
   const bool cached = (h->cfg.task == FW_TASK_WAYPOINTS) &&
                       (h->cfg.wind_mode == FW_WIND_OFF || h->cfg.wind_coupling == FW_WIND_COUPLE_NONE);
-  h->shadow_on = (!cached && h->cfg.auto_reset && h->cfg.task != FW_TASK_LOWLEVEL && h->cfg.task != FW_TASK_WAYPOINTS_DIRECT &&
-                  !getenv("FWSIM_NO_SHADOW")) ? 1 : 0;   // (low-level: no warm-up to hand off; direct waypoints: resets run in the kernel)
+  h->shadow_on = (!cached && h->cfg.auto_reset && !direct_actions(h->cfg.task) && !getenv("FWSIM_NO_SHADOW")) ? 1 : 0;   // (low-level: no warm-up to hand off; direct waypoints: resets run in the kernel)
   // wind-free waypoints on the latency mapping: workers only pre-sample the next episode's waypoints (scenario_worker)
   if (h->cfg.task == FW_TASK_WAYPOINTS && h->cfg.wind_mode == FW_WIND_OFF && h->cfg.auto_reset && h->lanes_per_env == 8 &&
       !getenv("FWSIM_NO_SHADOW"))
@@ -1948,94 +2052,39 @@ int create_T(fw_env* h) {
     rc = invalidate_shadow(h);
     if (rc != FW_OK) return rc;
   }
-  // the camera's LDS map outgrows what a workgroup gets without asking from ~700 columns on.  The attribute belongs to the
-  // (device, kernel) pair, not to the handle: keep the maximum ever asked for and only ever raise it, so a later, smaller
-  // handle cannot lower the cap under an earlier one
-  if (const size_t lds = step_lds_bytes_h<T>(h); lds > 48 * 1024) {
-    if (lds > 160 * 1024) { h->err = "camera_resolution x num_obstacles needs more LDS than a CU has"; return FW_EINVAL; }
-    const int which = (h->cfg.task == FW_TASK_OBJLOCK ? 0 : 1) + (sizeof(T) == 8 ? 0 : 2);
-    static size_t have[64][4] = {};
-    if (h->device < 64 && lds > have[h->device][which]) {
-      if (h->cfg.task == FW_TASK_OBJLOCK) {
-        HIP_TRY(h, hipFuncSetAttribute((const void*)fw_step_kernel_obj_g8<T, FW_TASK_OBJLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(h, hipFuncSetAttribute((const void*)fw_step_kernel_obj_g8h<T, FW_TASK_OBJLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(h, hipFuncSetAttribute((const void*)fw_reset_kernel<T, 8, FW_TASK_OBJLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      } else {
-        HIP_TRY(h, hipFuncSetAttribute((const void*)fw_step_kernel_obj_g8<T, FW_TASK_WAYPOINT_OBJLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(h, hipFuncSetAttribute((const void*)fw_step_kernel_obj_g8h<T, FW_TASK_WAYPOINT_OBJLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_TRY(h, hipFuncSetAttribute((const void*)fw_reset_kernel<T, 8, FW_TASK_WAYPOINT_OBJLOCK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      }
-      have[h->device][which] = lds;
-    }
-  }
+  // the camera's LDS map outgrows 48 KB from ~480 columns with cylinders on: opt in what this handle launches (the size, for every handle: the largest step launch, with the capture wave's mailbox)
+  const size_t lds = step_lds_bytes_h<T>(h);
+  if (lds > 160 * 1024) { h->err = "camera_resolution x num_obstacles needs more LDS than a CU has"; return FW_EINVAL; }
+  for (const EnvKernel* k : {&h->step, &h->reset}) if ((rc = ensure_dynamic_lds(h, h->device, k->fn, lds)) != FW_OK) return rc;
   hipLaunchKernelGGL(fw_init_kernel<T>, dim3((h->npad + 255) / 256), dim3(256), 0, 0, dev_state<T>(h), kWave / h->lanes_per_env);
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipDeviceSynchronize());
   return FW_OK;
 }
 
-#define FW_LAUNCH_STEP(KERNEL)                                                                                   \
-  hipLaunchKernelGGL((KERNEL), step_grid, dim3(kWave), step_lds_bytes<T>(h), st, (const Params<T>*)h->params_dev,    \
-                     (const ObjC<T>*)h->objc_dev, dev_state<T>(h), (const T*)actions, (T*)obs, (T*)reward, term,  \
-                     trunc, (T*)tobs, info)
-#define FW_LAUNCH_STEP_H(KERNEL)   /* step wave + capture wave per workgroup */                                      \
-  hipLaunchKernelGGL((KERNEL), step_grid, dim3(2 * kWave), step_lds_bytes_h<T>(h), st, (const Params<T>*)h->params_dev, \
-                     (const ObjC<T>*)h->objc_dev, dev_state<T>(h), (const T*)actions, (T*)obs, (T*)reward, term,  \
-                     trunc, (T*)tobs, info)
-
+// The argument lists of the env kernels (FW_STEP_ARGS and the reset kernels' own), launched through the pointer the handle holds.
 template <typename T>
 int step_T(fw_env* h, const void* actions, void* obs, void* reward, uint8_t* term, uint8_t* trunc, void* tobs,
            int32_t* info, hipStream_t st) {
-  const bool general = h->cfg.wind_mode != FW_WIND_OFF;
-  const bool g8 = h->lanes_per_env == 8;
-  dim3 step_grid = grid_of(h);
-  const bool two_wave = g8 && h->capture_wave && h->cfg.task != FW_TASK_WAYPOINTS;
-  if (h->shadow_on && !two_wave) step_grid.x *= 2;          // second half of the grid = shadow workers (two-wave workgroups: the capture wave is the worker)
-  if (h->cfg.task == FW_TASK_LOWLEVEL) {
-    if (g8) { if (general) FW_LAUNCH_STEP((fw_step_kernel_ll<T, 8, true>)); else FW_LAUNCH_STEP((fw_step_kernel_ll<T, 8, false>)); }
-    else { if (general) FW_LAUNCH_STEP((fw_step_kernel_ll<T, 1, true>)); else FW_LAUNCH_STEP((fw_step_kernel_ll<T, 1, false>)); }
-  } else if (h->cfg.task == FW_TASK_WAYPOINTS_DIRECT) {
-    if (g8) { if (general) FW_LAUNCH_STEP((fw_step_kernel_wd<T, 8, true>)); else FW_LAUNCH_STEP((fw_step_kernel_wd<T, 8, false>)); }
-    else { if (general) FW_LAUNCH_STEP((fw_step_kernel_wd<T, 1, true>)); else FW_LAUNCH_STEP((fw_step_kernel_wd<T, 1, false>)); }
-  } else if (h->cfg.task == FW_TASK_OBJLOCK) {
-    if (g8 && h->capture_wave) FW_LAUNCH_STEP_H((fw_step_kernel_obj_g8h<T, FW_TASK_OBJLOCK>));
-    else if (g8) FW_LAUNCH_STEP((fw_step_kernel_obj_g8<T, FW_TASK_OBJLOCK>)); else FW_LAUNCH_STEP((fw_step_kernel_obj_g1<T, FW_TASK_OBJLOCK>));
-  } else if (h->cfg.task == FW_TASK_WAYPOINT_OBJLOCK) {
-    if (g8 && h->capture_wave) FW_LAUNCH_STEP_H((fw_step_kernel_obj_g8h<T, FW_TASK_WAYPOINT_OBJLOCK>));
-    else if (g8) FW_LAUNCH_STEP((fw_step_kernel_obj_g8<T, FW_TASK_WAYPOINT_OBJLOCK>)); else FW_LAUNCH_STEP((fw_step_kernel_obj_g1<T, FW_TASK_WAYPOINT_OBJLOCK>));
-  } else if (h->axis_aligned && !general && g8 && h->g8_waves == 1) {   // (axis_aligned implies f64)
-    if constexpr (std::is_same<T, double>::value) FW_LAUNCH_STEP((fw_step_kernel_g8<T, false, true>));
-  } else if (general) {
-    if (g8 && h->g8_waves == 2) FW_LAUNCH_STEP((fw_step_kernel_g8w2<T, true>));
-    else if (g8) FW_LAUNCH_STEP((fw_step_kernel_g8<T, true>)); else FW_LAUNCH_STEP((fw_step_kernel_g1<T, true>));
-  } else {
-    if (g8 && h->g8_waves == 2) FW_LAUNCH_STEP((fw_step_kernel_g8w2<T, false>));
-    else if (g8) FW_LAUNCH_STEP((fw_step_kernel_g8<T, false>)); else FW_LAUNCH_STEP((fw_step_kernel_g1<T, false>));
-  }
+  const EnvKernel& k = h->step;
+  dim3 grid = grid_of(h);
+  if (h->shadow_on && k.worker_half) grid.x *= 2;          // second half of the grid = shadow workers (two-wave workgroups: the capture wave is the worker)
+  const Params<T>* Pp = (const Params<T>*)h->params_dev; const ObjC<T>* OCp = (const ObjC<T>*)h->objc_dev;
+  DevState<T> D = dev_state<T>(h);
+  void* args[] = { &Pp, &OCp, &D, &actions, &obs, &reward, &term, &trunc, &tobs, &info };
+  (void)hipLaunchKernel(k.fn, grid, dim3(k.block), args, k.block == 2 * kWave ? step_lds_bytes_h<T>(h) : step_lds_bytes<T>(h), st);
   HIP_TRY(h, hipGetLastError());
   return FW_OK;
 }
 
-#define FW_LAUNCH_RESET(KERNEL)                                                                                   \
-  hipLaunchKernelGGL((KERNEL), grid_of(h), dim3(kWave), tile_bytes<T>(h), st, (const Params<T>*)h->params_dev,    \
-                     (const ObjC<T>*)h->objc_dev, dev_state<T>(h), mask, (T*)obs, do_reset, ov)
-
 template <typename T>
 int reset_T(fw_env* h, const uint8_t* mask, void* obs, int do_reset, hipStream_t st, ScenOv ov = ScenOv{}) {
-  const bool g8 = h->lanes_per_env == 8;
-  if (h->cfg.task == FW_TASK_LOWLEVEL) {
-#define FW_LAUNCH_RESET_LL(KERNEL) hipLaunchKernelGGL((KERNEL), grid_of(h), dim3(kWave), tile_bytes<T>(h), st, (const Params<T>*)h->params_dev, dev_state<T>(h), mask, (T*)obs, do_reset, ov)
-    if (g8) FW_LAUNCH_RESET_LL((fw_reset_kernel_ll<T, 8>)); else FW_LAUNCH_RESET_LL((fw_reset_kernel_ll<T, 1>));
-#undef FW_LAUNCH_RESET_LL
-  } else if (h->cfg.task == FW_TASK_WAYPOINTS_DIRECT) {
-    if (g8) FW_LAUNCH_RESET((fw_reset_kernel_wd<T, 8>)); else FW_LAUNCH_RESET((fw_reset_kernel_wd<T, 1>));
-  } else if (h->cfg.task == FW_TASK_OBJLOCK) {
-    if (g8) FW_LAUNCH_RESET((fw_reset_kernel<T, 8, FW_TASK_OBJLOCK>)); else FW_LAUNCH_RESET((fw_reset_kernel<T, 1, FW_TASK_OBJLOCK>));
-  } else if (h->cfg.task == FW_TASK_WAYPOINT_OBJLOCK) {
-    if (g8) FW_LAUNCH_RESET((fw_reset_kernel<T, 8, FW_TASK_WAYPOINT_OBJLOCK>)); else FW_LAUNCH_RESET((fw_reset_kernel<T, 1, FW_TASK_WAYPOINT_OBJLOCK>));
-  } else {
-    if (g8) FW_LAUNCH_RESET((fw_reset_kernel<T, 8, FW_TASK_WAYPOINTS>)); else FW_LAUNCH_RESET((fw_reset_kernel<T, 1, FW_TASK_WAYPOINTS>));
-  }
+  const EnvKernel& k = h->reset;
+  const Params<T>* Pp = (const Params<T>*)h->params_dev; const ObjC<T>* OCp = (const ObjC<T>*)h->objc_dev;
+  DevState<T> D = dev_state<T>(h);
+  void* with_objc[] = { &Pp, &OCp, &D, &mask, &obs, &do_reset, &ov };
+  void* without[] = { &Pp, &D, &mask, &obs, &do_reset, &ov };
+  (void)hipLaunchKernel(k.fn, grid_of(h), dim3(k.block), k.takes_objc ? with_objc : without, tile_bytes<T>(h), st);
   HIP_TRY(h, hipGetLastError());
   return FW_OK;
 }
@@ -2092,25 +2141,28 @@ int set_state_T(fw_env* h, const double* in) {
 }  // namespace
 
 namespace {
-int ensure_learner_lds(int dev, int which, size_t bytes) {
-  static size_t have[64][4] = {};
-  if (dev < 0 || dev >= 64) { g_err = "device index out of range"; return FW_EINVAL; }
-  if (bytes <= have[dev][which]) return FW_OK;
-  if (which == 0) {
-    const void* fns[] = {(const void*)fw_ppo_update_kernel<64, 0>, (const void*)fw_ppo_update_kernel<32, 0>, (const void*)fw_ppo_update_kernel<16, 0>,
-                         (const void*)fw_ppo_update_kernel<64, 4>, (const void*)fw_ppo_update_kernel<32, 4>, (const void*)fw_ppo_update_kernel<16, 4>,
-                         (const void*)fw_ppo_update_kernel<64, 8>, (const void*)fw_ppo_update_kernel<32, 8>, (const void*)fw_ppo_update_kernel<16, 8>};
-    for (const void* fn : fns) HIP_TRY((fw_env*)nullptr, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  } else if (which == 2) {
-    const void* fns[] = {(const void*)fw_ppo_update_kernel_a6<64, 0>, (const void*)fw_ppo_update_kernel_a6<32, 0>, (const void*)fw_ppo_update_kernel_a6<16, 0>,
-                         (const void*)fw_ppo_update_kernel_a6<64, 4>, (const void*)fw_ppo_update_kernel_a6<32, 4>, (const void*)fw_ppo_update_kernel_a6<16, 4>,
-                         (const void*)fw_ppo_update_kernel_a6<64, 8>, (const void*)fw_ppo_update_kernel_a6<32, 8>, (const void*)fw_ppo_update_kernel_a6<16, 8>};
-    for (const void* fn : fns) HIP_TRY((fw_env*)nullptr, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  } else {
-    const void* fn = which == 3 ? (const void*)fw_policy_act_kernel<6> : (const void*)fw_policy_act_kernel<4>;
-    HIP_TRY((fw_env*)nullptr, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  }
-  have[dev][which] = bytes;
+// The learner's kernels: one lookup per family, used by the launch and by the LDS opt-in in front of it.
+const void* ppo_update_kernel(bool a6, int ch /*samples per pass*/, int ns /*blocks per network of the reduce-scatter form, 0: all-to-all*/) {
+  struct Row { int ch, ns; const void* a4; const void* a6; };
+  static const Row rows[] = {
+    {64, 8, kfn(fw_ppo_update_kernel<64, 8>), kfn(fw_ppo_update_kernel_a6<64, 8>)}, {64, 4, kfn(fw_ppo_update_kernel<64, 4>), kfn(fw_ppo_update_kernel_a6<64, 4>)},
+    {64, 0, kfn(fw_ppo_update_kernel<64, 0>), kfn(fw_ppo_update_kernel_a6<64, 0>)}, {32, 8, kfn(fw_ppo_update_kernel<32, 8>), kfn(fw_ppo_update_kernel_a6<32, 8>)},
+    {32, 4, kfn(fw_ppo_update_kernel<32, 4>), kfn(fw_ppo_update_kernel_a6<32, 4>)}, {32, 0, kfn(fw_ppo_update_kernel<32, 0>), kfn(fw_ppo_update_kernel_a6<32, 0>)},
+    {16, 8, kfn(fw_ppo_update_kernel<16, 8>), kfn(fw_ppo_update_kernel_a6<16, 8>)}, {16, 4, kfn(fw_ppo_update_kernel<16, 4>), kfn(fw_ppo_update_kernel_a6<16, 4>)},
+    {16, 0, kfn(fw_ppo_update_kernel<16, 0>), kfn(fw_ppo_update_kernel_a6<16, 0>)},
+  };
+  for (const Row& r : rows) if (r.ch == ch && r.ns == ns) return a6 ? r.a6 : r.a4;
+  return nullptr;
+}
+const void* policy_act_kernel(int act_dim) { return act_dim == 6 ? kfn(fw_policy_act_kernel<6>) : kfn(fw_policy_act_kernel<4>); }
+
+// fw_policy_act, fw_collect_act and fw_policy_terminal_value: the same launch over N rows, under the caller's DeviceGuard for `dev`
+int launch_policy_act(int dev, int act_dim, ActArgs& A, size_t lds, hipStream_t st) {
+  const void* fn = policy_act_kernel(act_dim);
+  if (int rc = ensure_dynamic_lds(nullptr, dev, fn, lds)) return rc;
+  void* args[] = { &A };
+  (void)hipLaunchKernel(fn, dim3((A.N + kPChunk - 1) / kPChunk, 2), dim3(kPThreads), args, lds, st);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }
 }  // namespace
@@ -2135,29 +2187,13 @@ int collect_step_T(fw_env* h, CollectArgs& CA, const void* actions, void* obs, v
                    int32_t* info, hipStream_t st) {
   const size_t lds = std::max(step_lds_bytes<T>(h), collect_act_lds_bytes(CA.A.D));
   if (lds > 160 * 1024) { h->err = "fw_collect_step: the networks do not fit the LDS next to the step kernel's tile"; return FW_EINVAL; }
-  const bool w2 = h->g8_waves == 2, windy = h->cfg.wind_mode != FW_WIND_OFF, f32 = sizeof(T) != 8;       // (w2: waypoints task only, fw_create)
-  const void* fn = h->cfg.task == FW_TASK_OBJLOCK ? (const void*)fw_collect_kernel_obj_g8<T, FW_TASK_OBJLOCK>
-                 : h->cfg.task == FW_TASK_WAYPOINT_OBJLOCK ? (const void*)fw_collect_kernel_obj_g8<T, FW_TASK_WAYPOINT_OBJLOCK>
-                 : windy ? (w2 ? (const void*)fw_collect_kernel_g8w2<T, true> : (const void*)fw_collect_kernel_g8<T, true>)
-                         : (w2 ? (const void*)fw_collect_kernel_g8w2<T, false> : (const void*)fw_collect_kernel_g8<T, false>);
-  if (lds > 48 * 1024) {                       // opt in once per (device, kernel, size class): only ever raised
-    static size_t have[64][12] = {};
-    const int which = w2 ? 8 + (windy ? 0 : 1) + (f32 ? 2 : 0)
-                         : (h->cfg.task == FW_TASK_OBJLOCK ? 0 : h->cfg.task == FW_TASK_WAYPOINT_OBJLOCK ? 1 : windy ? 2 : 3) + (f32 ? 4 : 0);
-    if (h->device < 64 && lds > have[h->device][which]) {
-      HIP_TRY(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      have[h->device][which] = lds;
-    }
-  }
+  if (int rc = ensure_dynamic_lds(h, h->device, h->collect.fn, lds)) return rc;      // (here, not at fw_create: the size follows the policy's width)
   CA.n_workers = (int32_t)(grid_of(h).x * (h->shadow_on ? 2u : 1u));
   dim3 grid((unsigned)(CA.n_act + CA.n_workers + 2 * CA.A.D + 2));          // + one fold wave per partial-sum word
-#define FW_LAUNCH_COLLECT(KERNEL)                                                                                  \
-  hipLaunchKernelGGL((KERNEL), grid, dim3(kWave), lds, st, (const Params<T>*)h->params_dev, (const ObjC<T>*)h->objc_dev, \
-                     dev_state<T>(h), (const T*)actions, (T*)obs, (T*)reward, term, trunc, (T*)tobs, info, CA)
-  if (h->cfg.task == FW_TASK_OBJLOCK) FW_LAUNCH_COLLECT((fw_collect_kernel_obj_g8<T, FW_TASK_OBJLOCK>));
-  else if (h->cfg.task == FW_TASK_WAYPOINT_OBJLOCK) FW_LAUNCH_COLLECT((fw_collect_kernel_obj_g8<T, FW_TASK_WAYPOINT_OBJLOCK>));
-  else if (windy) { if (w2) FW_LAUNCH_COLLECT((fw_collect_kernel_g8w2<T, true>)); else FW_LAUNCH_COLLECT((fw_collect_kernel_g8<T, true>)); }
-  else { if (w2) FW_LAUNCH_COLLECT((fw_collect_kernel_g8w2<T, false>)); else FW_LAUNCH_COLLECT((fw_collect_kernel_g8<T, false>)); }
+  const Params<T>* Pp = (const Params<T>*)h->params_dev; const ObjC<T>* OCp = (const ObjC<T>*)h->objc_dev;
+  DevState<T> D = dev_state<T>(h);
+  void* args[] = { &Pp, &OCp, &D, &actions, &obs, &reward, &term, &trunc, &tobs, &info, &CA };
+  (void)hipLaunchKernel(h->collect.fn, grid, dim3(h->collect.block), args, lds, st);
   HIP_TRY(h, hipGetLastError());
   return FW_OK;
 }
@@ -2173,7 +2209,7 @@ int32_t fw_sizeof_config(void) { return (int32_t)sizeof(fw_config); }
 int32_t fw_abi_version(void) { return FW_ABI_VERSION; }
 int32_t fw_state_dim(void) { return FW_STATE_DIM; }
 int32_t fw_obs_dim(const fw_config* cfg) { return cfg ? obs_dim_of(cfg) : FW_EINVAL; }
-int32_t fw_act_dim(const fw_config* cfg) { return cfg ? ((cfg->task == FW_TASK_LOWLEVEL || cfg->task == FW_TASK_WAYPOINTS_DIRECT) ? 6 : 4) : FW_EINVAL; }
+int32_t fw_act_dim(const fw_config* cfg) { return cfg ? (direct_actions(cfg->task) ? 6 : 4) : FW_EINVAL; }
 
 int32_t fw_validate_config(const fw_config* cfg, char* msg, int32_t msg_len) {
   std::string m;
@@ -2207,7 +2243,7 @@ int32_t fw_create(const fw_config* cfg, int32_t num_envs, int32_t device, uint64
   // Camera tasks with obstacles stay on the 8-lane mapping at every size: there the cylinders are drawn by the wave from LDS
   // work lists; one lane per env tests every pixel against every cylinder (combined, 20 cylinders: 330 us vs 7.8 ms per
   // step at 32 768 envs).
-  const bool camera = cfg->task == FW_TASK_OBJLOCK || cfg->task == FW_TASK_WAYPOINT_OBJLOCK;
+  const bool camera = has_camera(cfg->task);
   const bool cyl_camera = camera && cfg->num_obstacles > 0;
   const bool wp = cfg->task == FW_TASK_WAYPOINTS, windy = wp && cfg->wind_mode != FW_WIND_OFF;
   const int one_wave_max = windy ? 6144 : 8192;                 // up to here the one-wave-per-SIMD build wins
@@ -2233,7 +2269,7 @@ int32_t fw_create(const fw_config* cfg, int32_t num_envs, int32_t device, uint64
   h->axis_aligned = (h->lanes_per_env == 8 && h->g8_waves == 1 && wp && !windy && cfg->dtype == FW_F64 &&
                      axis_aligned_geometry(*cfg)) ? 1 : 0;
   DeviceGuard g(device);
-  rc = (cfg->dtype == FW_F64) ? create_T<double>(h) : create_T<float>(h);
+  rc = with_dtype(h, [&](auto t) { return create_T<decltype(t)>(h); });
   if (rc != FW_OK) {
     g_err = h->err;
     free_device_buffers(h);
@@ -2275,14 +2311,14 @@ int32_t fw_reset(fw_handle h, const uint8_t* mask, const fw_scenario* scenario, 
     ov.targets = dst[0]; ov.duck = dst[1]; ov.obst = dst[2]; ov.nob = dst[3]; ov.wind_base = dst[4]; ov.gust_amp = dst[5]; ov.gust_phase = dst[6];
     if (!ov.obst) ov.nob = nullptr;
   }
-  return (h->cfg.dtype == FW_F64) ? reset_T<double>(h, mask, obs_out, 1, st, ov) : reset_T<float>(h, mask, obs_out, 1, st, ov);
+  return with_dtype(h, [&](auto t) { return reset_T<decltype(t)>(h, mask, obs_out, 1, st, ov); });
 }
 
 int32_t fw_observe(fw_handle h, void* obs_out, void* hip_stream) {
   if (!h || !obs_out) { if (h) h->err = "obs_out is NULL"; return FW_EINVAL; }
   DeviceGuard g(h->device);
   hipStream_t st = (hipStream_t)hip_stream;
-  return (h->cfg.dtype == FW_F64) ? reset_T<double>(h, nullptr, obs_out, 0, st) : reset_T<float>(h, nullptr, obs_out, 0, st);
+  return with_dtype(h, [&](auto t) { return reset_T<decltype(t)>(h, nullptr, obs_out, 0, st); });
 }
 
 int32_t fw_step(fw_handle h, const void* actions, void* obs, void* reward, uint8_t* terminated, uint8_t* truncated,
@@ -2291,17 +2327,14 @@ int32_t fw_step(fw_handle h, const void* actions, void* obs, void* reward, uint8
   if (!actions || !obs || !reward || !terminated || !truncated) { h->err = "actions/obs/reward/terminated/truncated must be non-NULL"; return FW_EINVAL; }
   DeviceGuard g(h->device);
   hipStream_t st = (hipStream_t)hip_stream;
-  return (h->cfg.dtype == FW_F64)
-             ? step_T<double>(h, actions, obs, reward, terminated, truncated, terminal_obs, info_i32, st)
-             : step_T<float>(h, actions, obs, reward, terminated, truncated, terminal_obs, info_i32, st);
+  return with_dtype(h, [&](auto t) { return step_T<decltype(t)>(h, actions, obs, reward, terminated, truncated, terminal_obs, info_i32, st); });
 }
 
 int32_t fw_render(fw_handle h, int32_t res, float* out, void* hip_stream) {
   if (!h) return FW_EINVAL;
   if (!out) { h->err = "fw_render: out is NULL"; return FW_EINVAL; }
-  if (h->cfg.task == FW_TASK_WAYPOINTS) { h->err = "fw_render: the waypoints task has no camera"; return FW_EUNSUPPORTED; }
-  if (h->cfg.task == FW_TASK_LOWLEVEL) { h->err = "fw_render: the low-level task has no camera"; return FW_EUNSUPPORTED; }
-  if (h->cfg.task == FW_TASK_WAYPOINTS_DIRECT) { h->err = "fw_render: the waypoints task has no camera"; return FW_EUNSUPPORTED; }
+  const char* camless = h->cfg.task == FW_TASK_LOWLEVEL ? "fw_render: the low-level task has no camera" : "fw_render: the waypoints task has no camera";
+  if (!has_camera(h->cfg.task)) { h->err = camless; return FW_EUNSUPPORTED; }      // (direct-command waypoints: the waypoints task's words)
   if (res < 1 || res > 1024) { h->err = "fw_render: res must be in [1, 1024]"; return FW_EINVAL; }
   DeviceGuard g(h->device);
   const fw_config& c = h->cfg;
@@ -2332,13 +2365,10 @@ int32_t fw_render(fw_handle h, int32_t res, float* out, void* hip_stream) {
   HIP_TRY(h, hipMemsetAsync(rprof, 0, rp_n * sizeof(long long), st));
   HIP_TRY(h, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_render_prof), &rprof, sizeof(rprof), 0, hipMemcpyHostToDevice, st));
 #endif
-  if (c.dtype == FW_F64) {
-    if (stage_px) hipLaunchKernelGGL((fw_render_kernel<double, true>), dim3((unsigned)h->n), dim3(threads), lds, st, (const double*)h->r_dev, tile, h->n, threads / 64, K, res, out, stage_px);
-    else hipLaunchKernelGGL((fw_render_kernel<double, false>), dim3((unsigned)h->n), dim3(threads), lds, st, (const double*)h->r_dev, tile, h->n, threads / 64, K, res, out, 0);
-  } else {
-    if (stage_px) hipLaunchKernelGGL((fw_render_kernel<float, true>), dim3((unsigned)h->n), dim3(threads), lds, st, (const float*)h->r_dev, tile, h->n, threads / 64, K, res, out, stage_px);
-    else hipLaunchKernelGGL((fw_render_kernel<float, false>), dim3((unsigned)h->n), dim3(threads), lds, st, (const float*)h->r_dev, tile, h->n, threads / 64, K, res, out, 0);
-  }
+  with_dtype(h, [&](auto t) {
+    auto kernel = stage_px ? fw_render_kernel<decltype(t), true> : fw_render_kernel<decltype(t), false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)h->n), dim3(threads), lds, st, (const decltype(t)*)h->r_dev, tile, h->n, threads / 64, K, res, out, stage_px);
+  });
   HIP_TRY(h, hipGetLastError());
 #ifdef FW_RENDER_PROF
   if (std::getenv("FWSIM_RENDER_PROF_DUMP")) {       // per-wave cycle stamps -> mean phase lengths, set-up waves and the others apart
@@ -2374,7 +2404,7 @@ int32_t fw_seed(fw_handle h, uint64_t seed) {
   DeviceGuard g(h->device);
   h->seed = seed;
   HIP_TRY(h, hipDeviceSynchronize());
-  int rc = (h->cfg.dtype == FW_F64) ? upload_params<double>(h) : upload_params<float>(h);
+  int rc = with_dtype(h, [&](auto t) { return upload_params<decltype(t)>(h); });
   if (rc != FW_OK) return rc;
   {
     // episode counters back to -1 (the next reset starts episode 0 of the new seed); rows are tiled, so go through a host copy
@@ -2390,13 +2420,13 @@ int32_t fw_seed(fw_handle h, uint64_t seed) {
 int32_t fw_get_state(fw_handle h, double* state_out) {
   if (!h || !state_out) return FW_EINVAL;
   DeviceGuard g(h->device);
-  return (h->cfg.dtype == FW_F64) ? get_state_T<double>(h, state_out) : get_state_T<float>(h, state_out);
+  return with_dtype(h, [&](auto t) { return get_state_T<decltype(t)>(h, state_out); });
 }
 
 int32_t fw_set_state(fw_handle h, const double* state_in) {
   if (!h || !state_in) return FW_EINVAL;
   DeviceGuard g(h->device);
-  return (h->cfg.dtype == FW_F64) ? set_state_T<double>(h, state_in) : set_state_T<float>(h, state_in);
+  return with_dtype(h, [&](auto t) { return set_state_T<decltype(t)>(h, state_in); });
 }
 
 int32_t fw_get_counters(fw_handle h, uint64_t* out) {
@@ -2472,14 +2502,10 @@ int32_t fw_command_ll(fw_handle h, const double* cmd, int32_t T, const int64_t* 
   hipStream_t st = (hipStream_t)hip_stream;
   const dim3 grid((unsigned)((h->n + 255) / 256)), block(256);
   const double dome = h->cfg.flight_dome_size;
-  const bool g8 = h->lanes_per_env == 8;
-  if (h->cfg.dtype == FW_F64) {
-    if (g8) hipLaunchKernelGGL((fw_command_ll_kernel<double, 8>), grid, block, 0, st, dev_state<double>(h), cmd, T, step_idx, mask, (double*)obs, rejected, dome);
-    else hipLaunchKernelGGL((fw_command_ll_kernel<double, 1>), grid, block, 0, st, dev_state<double>(h), cmd, T, step_idx, mask, (double*)obs, rejected, dome);
-  } else {
-    if (g8) hipLaunchKernelGGL((fw_command_ll_kernel<float, 8>), grid, block, 0, st, dev_state<float>(h), cmd, T, step_idx, mask, (float*)obs, rejected, dome);
-    else hipLaunchKernelGGL((fw_command_ll_kernel<float, 1>), grid, block, 0, st, dev_state<float>(h), cmd, T, step_idx, mask, (float*)obs, rejected, dome);
-  }
+  with_dtype(h, [&](auto t) { with_lanes(h, [&](auto lanes) {
+    using R = decltype(t);
+    hipLaunchKernelGGL((fw_command_ll_kernel<R, decltype(lanes)::value>), grid, block, 0, st, dev_state<R>(h), cmd, T, step_idx, mask, (R*)obs, rejected, dome);
+  }); });
   HIP_TRY(h, hipGetLastError());
   return FW_OK;
 }
@@ -2493,19 +2519,13 @@ int32_t fw_command_hl(fw_handle h, const void* action, int32_t action_is_f64, co
   DeviceGuard g(h->device);
   hipStream_t st = (hipStream_t)hip_stream;
   const dim3 block(256), grid((unsigned)((h->n + 255) / 256));
-  const bool g8 = h->lanes_per_env == 8;
   const double dome = h->cfg.flight_dome_size;
   const int32_t D = obs_dim_of(&h->cfg);
-#define FW_LAUNCH_CMD_HL(T, G, TA) hipLaunchKernelGGL((fw_command_hl_kernel<T, G, TA>), grid, block, 0, st, dev_state<T>(h), (const TA*)action, mask, \
-                                                      (const T*)obs, D, (T*)low_obs, (T*)cmd_out, rejected, dome)
-  if (h->cfg.dtype == FW_F64) {
-    if (action_is_f64) { if (g8) FW_LAUNCH_CMD_HL(double, 8, double); else FW_LAUNCH_CMD_HL(double, 1, double); }
-    else { if (g8) FW_LAUNCH_CMD_HL(double, 8, float); else FW_LAUNCH_CMD_HL(double, 1, float); }
-  } else {
-    if (action_is_f64) { if (g8) FW_LAUNCH_CMD_HL(float, 8, double); else FW_LAUNCH_CMD_HL(float, 1, double); }
-    else { if (g8) FW_LAUNCH_CMD_HL(float, 8, float); else FW_LAUNCH_CMD_HL(float, 1, float); }
-  }
-#undef FW_LAUNCH_CMD_HL
+  with_dtype(h, [&](auto t) { with_lanes(h, [&](auto lanes) { with_real(action_is_f64 != 0, [&](auto ta) {
+    using T = decltype(t); using TA = decltype(ta);
+    hipLaunchKernelGGL((fw_command_hl_kernel<T, decltype(lanes)::value, TA>), grid, block, 0, st, dev_state<T>(h), (const TA*)action, mask,
+                       (const T*)obs, D, (T*)low_obs, (T*)cmd_out, rejected, dome);
+  }); }); });
   HIP_TRY(h, hipGetLastError());
   return FW_OK;
 }
@@ -2534,13 +2554,11 @@ int32_t fw_normalize_obs(const void* obs, int32_t in_is_f64, int32_t N, int32_t 
     // per-block column sums land in the CALLER's workspace: nothing here is shared between callers or streams
     double* scratch = (double*)workspace;
     const int nblocks = N >= 64 * 64 ? 64 : (N + 63) / 64;       // >= 64 rows per block
-    if (in_is_f64) hipLaunchKernelGGL(fw_obs_moments_kernel<double>, dim3(nblocks), dim3(256), 0, st, (const double*)obs, N, D, scratch);
-    else hipLaunchKernelGGL(fw_obs_moments_kernel<float>, dim3(nblocks), dim3(256), 0, st, (const float*)obs, N, D, scratch);
+    with_real(in_is_f64 != 0, [&](auto t) { hipLaunchKernelGGL(fw_obs_moments_kernel<decltype(t)>, dim3(nblocks), dim3(256), 0, st, (const decltype(t)*)obs, N, D, scratch); });
     hipLaunchKernelGGL(fw_obs_merge_kernel, dim3(1), dim3(256), 0, st, scratch, nblocks, N, D, mean, var, count, batch_acc);
   }
   const int total = N * D;
-  if (in_is_f64) hipLaunchKernelGGL(fw_obs_normalize_kernel<double>, dim3((total + 255) / 256), dim3(256), 0, st, (const double*)obs, total, D, mean, var, clip, eps, obs_out);
-  else hipLaunchKernelGGL(fw_obs_normalize_kernel<float>, dim3((total + 255) / 256), dim3(256), 0, st, (const float*)obs, total, D, mean, var, clip, eps, obs_out);
+  with_real(in_is_f64 != 0, [&](auto t) { hipLaunchKernelGGL(fw_obs_normalize_kernel<decltype(t)>, dim3((total + 255) / 256), dim3(256), 0, st, (const decltype(t)*)obs, total, D, mean, var, clip, eps, obs_out); });
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }
@@ -2625,8 +2643,6 @@ static int32_t ppo_update(float* params, float* mom_m, float* mom_v, const float
   hipStream_t st = (hipStream_t)hip_stream;
   const int dev = device_of(params);
   DeviceGuard g(dev);
-  int rc = ensure_learner_lds(dev, a6 ? 2 : 0, lds);
-  if (rc != FW_OK) return rc;
   // everything the blocks exchange lives in the caller's workspace: two learners (or two streams) never share a word
   unsigned long long* xch = (unsigned long long*)workspace;
   float* gx = (float*)((char*)workspace + kPpoWsXch);
@@ -2660,12 +2676,11 @@ static int32_t ppo_update(float* params, float* mom_m, float* mom_v, const float
   }
   const int ns = cut.nsplit >= 4 && rs_env ? cut.nsplit : 0;      // the kernel's NS: 0 = all-to-all swap of whole partials
   const dim3 grid(16 * cut.nsplit);                 // (every 8th block works -- see the kernel)
-#define FW_PPO_LAUNCH(CH_, NS_) do { if (a6) hipLaunchKernelGGL((fw_ppo_update_kernel_a6<CH_, NS_>), grid, dim3(kPThreads), lds, st, A); \
-                                     else hipLaunchKernelGGL((fw_ppo_update_kernel<CH_, NS_>), grid, dim3(kPThreads), lds, st, A); } while (0)
-  if (cut.ch == 64) { if (ns == 8) FW_PPO_LAUNCH(64, 8); else if (ns == 4) FW_PPO_LAUNCH(64, 4); else FW_PPO_LAUNCH(64, 0); }
-  else if (cut.ch == 32) { if (ns == 8) FW_PPO_LAUNCH(32, 8); else if (ns == 4) FW_PPO_LAUNCH(32, 4); else FW_PPO_LAUNCH(32, 0); }
-  else { if (ns == 8) FW_PPO_LAUNCH(16, 8); else if (ns == 4) FW_PPO_LAUNCH(16, 4); else FW_PPO_LAUNCH(16, 0); }
-#undef FW_PPO_LAUNCH
+  const void* fn = ppo_update_kernel(a6, cut.ch, ns);
+  if (!fn) { g_err = w + ": no kernel is built for " + std::to_string(cut.ch) + " samples per pass x " + std::to_string(ns) + " blocks per network"; return FW_EINVAL; }
+  if (int rc = ensure_dynamic_lds(nullptr, dev, fn, lds)) return rc;
+  void* args[] = { &A };
+  (void)hipLaunchKernel(fn, grid, dim3(kPThreads), args, lds, st);
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }
@@ -2706,20 +2721,15 @@ static int32_t policy_act(const float* params, const float* obs, int32_t N, int3
   if (!params || !obs || N <= 0 || obs_dim <= 0 || obs_dim > 64 || (nets & ~3) || !nets) { g_err = w + ": bad arguments"; return FW_EINVAL; }
   if ((nets & 1) && (!act_raw || !act_env || !logp || (!deterministic && !rng))) { g_err = w + ": policy outputs missing"; return FW_EINVAL; }
   if ((nets & 2) && !value) { g_err = w + ": value output missing"; return FW_EINVAL; }
-  const bool a6 = act_dim == 6;
   const size_t lds = act_lds_bytes(obs_dim, act_dim);
   const int dev = device_of(params);
   DeviceGuard g(dev);
-  if (int rc = ensure_learner_lds(dev, a6 ? 3 : 1, lds)) return rc;
   ActArgs A;
   std::memset(&A, 0, sizeof A);
   A.params = params; A.obs = obs; A.N = N; A.D = obs_dim; A.nets = nets; A.deterministic = deterministic; A.act_is_f64 = act_is_f64;
   A.rng = rng; A.env_offset = env_offset; A.obs_copy = obs_copy; A.act_raw = act_raw; A.act_env = act_env; A.logp = logp; A.value = value;
   A.raw = nullptr; A.raw_is_f64 = 0; A.mean = A.var = nullptr; A.clip = A.eps = 0.f; A.terminated = A.truncated = nullptr;
-  if (a6) hipLaunchKernelGGL((fw_policy_act_kernel<6>), dim3((N + kPChunk - 1) / kPChunk, 2), dim3(kPThreads), lds, (hipStream_t)hip_stream, A);
-  else hipLaunchKernelGGL((fw_policy_act_kernel<4>), dim3((N + kPChunk - 1) / kPChunk, 2), dim3(kPThreads), lds, (hipStream_t)hip_stream, A);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return launch_policy_act(dev, act_dim, A, lds, (hipStream_t)hip_stream);
 }
 int32_t fw_policy_act(const float* params, const float* obs, int32_t N, int32_t obs_dim, int32_t nets, int32_t deterministic,
                       const uint64_t* rng, int64_t env_offset, float* obs_copy, float* act_raw, void* act_env, int32_t act_is_f64,
@@ -2748,11 +2758,9 @@ static int32_t collect_act(const float* params, const void* raw_obs, int32_t obs
   if (prev_reward && (!(nets & 2) || !prev_terminated || !prev_truncated || !prev_terminal_obs || !ret_var || !rew_out || !start_out)) {
     g_err = w + ": finalising the previous step needs the value network and all of its buffers"; return FW_EINVAL;
   }
-  const bool a6 = act_dim == 6;
   const size_t lds = act_lds_bytes(obs_dim, act_dim);
   const int dev = device_of(params);
   DeviceGuard g(dev);
-  if (int rc = ensure_learner_lds(dev, a6 ? 3 : 1, lds)) return rc;
   ActArgs A;
   std::memset(&A, 0, sizeof A);
   A.params = params; A.N = N; A.D = obs_dim; A.nets = nets; A.deterministic = deterministic; A.act_is_f64 = act_is_f64;
@@ -2761,10 +2769,7 @@ static int32_t collect_act(const float* params, const void* raw_obs, int32_t obs
   A.prev_reward = prev_reward; A.prev_term = prev_terminated; A.prev_trunc = prev_truncated; A.prev_tobs = prev_terminal_obs;
   A.ret_var = ret_var; A.norm_reward = norm_reward; A.clip_reward = clip_reward; A.rew_eps = eps_reward; A.gamma = gamma;
   A.rew_out = rew_out; A.start_out = start_out;
-  if (a6) hipLaunchKernelGGL((fw_policy_act_kernel<6>), dim3((N + kPChunk - 1) / kPChunk, 2), dim3(kPThreads), lds, (hipStream_t)hip_stream, A);
-  else hipLaunchKernelGGL((fw_policy_act_kernel<4>), dim3((N + kPChunk - 1) / kPChunk, 2), dim3(kPThreads), lds, (hipStream_t)hip_stream, A);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return launch_policy_act(dev, act_dim, A, lds, (hipStream_t)hip_stream);
 }
 int32_t fw_collect_act(const float* params, const void* raw_obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, const double* obs_mean,
                        const double* obs_var, float clip_obs, float eps_obs, int32_t nets, int32_t deterministic, const uint64_t* rng,
@@ -2854,8 +2859,7 @@ int32_t fw_collect_step(fw_handle h, const fw_collect_args* a, void* hip_stream)
     HIP_TRY(h, hipMemsetAsync(a->act_env, 0xFF, bytes, st));      // all-ones words: a NaN in float32 and in float64
     h->collect_act_seen = a->act_env;
   }
-  return h->cfg.dtype == FW_F64 ? collect_step_T<double>(h, CA, a->act_env, a->obs, a->reward, a->terminated, a->truncated, a->terminal_obs, a->info_i32, st)
-                                : collect_step_T<float>(h, CA, a->act_env, a->obs, a->reward, a->terminated, a->truncated, a->terminal_obs, a->info_i32, st);
+  return with_dtype(h, [&](auto t) { return collect_step_T<decltype(t)>(h, CA, a->act_env, a->obs, a->reward, a->terminated, a->truncated, a->terminal_obs, a->info_i32, st); });
 }
 
 int32_t fw_collect_close(fw_handle h, const fw_collect_args* a, const fw_collect_close_args* c, void* hip_stream) {
@@ -2870,8 +2874,7 @@ int32_t fw_collect_close(fw_handle h, const fw_collect_args* a, const fw_collect
   GA.T = c->T; GA.gamma = c->gae_gamma; GA.lam = c->gae_lambda;
   const size_t lds = collect_act_lds_bytes(CA.A.D);
   hipStream_t st = (hipStream_t)hip_stream;
-  if (h->cfg.dtype == FW_F64) hipLaunchKernelGGL(fw_collect_close_kernel<double>, dim3((unsigned)CA.n_chunks + 1), dim3(64), lds, st, CA, GA);
-  else hipLaunchKernelGGL(fw_collect_close_kernel<float>, dim3((unsigned)CA.n_chunks + 1), dim3(64), lds, st, CA, GA);
+  with_dtype(h, [&](auto t) { hipLaunchKernelGGL(fw_collect_close_kernel<decltype(t)>, dim3((unsigned)CA.n_chunks + 1), dim3(64), lds, st, CA, GA); });
   HIP_TRY(h, hipGetLastError());
   return FW_OK;
 }
@@ -2942,8 +2945,7 @@ int32_t fw_collect_stats(const void* obs, int32_t obs_is_f64, int32_t N, int32_t
   A.part = (double*)workspace; A.ticket = (unsigned int*)((char*)workspace + sizeof(double) * 64 * (2 * (size_t)D + 2));
   A.obs_acc = obs_acc; A.ret_acc = ret_acc;
   const int nb = collect_stats_blocks(N);
-  if (obs_is_f64) hipLaunchKernelGGL(fw_collect_stats_kernel<double>, dim3(nb), dim3(256), 0, (hipStream_t)hip_stream, A);
-  else hipLaunchKernelGGL(fw_collect_stats_kernel<float>, dim3(nb), dim3(256), 0, (hipStream_t)hip_stream, A);
+  with_real(obs_is_f64 != 0, [&](auto t) { hipLaunchKernelGGL(fw_collect_stats_kernel<decltype(t)>, dim3(nb), dim3(256), 0, (hipStream_t)hip_stream, A); });
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }
@@ -2957,15 +2959,12 @@ int32_t fw_policy_terminal_value(const float* params, const void* terminal_obs, 
   const size_t lds = act_lds_bytes(obs_dim);
   const int dev = device_of(params);
   DeviceGuard g(dev);
-  if (int rc = ensure_learner_lds(dev, 1, lds)) return rc;
   ActArgs A;
   std::memset(&A, 0, sizeof A);
   A.params = params; A.N = N; A.D = obs_dim; A.nets = 2; A.deterministic = 1; A.value = value;
   A.raw = terminal_obs; A.raw_is_f64 = obs_is_f64; A.mean = mean; A.var = var; A.clip = clip; A.eps = eps;
   A.terminated = terminated; A.truncated = truncated;
-  hipLaunchKernelGGL((fw_policy_act_kernel<4>), dim3((N + kPChunk - 1) / kPChunk, 2), dim3(kPThreads), lds, (hipStream_t)hip_stream, A);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return launch_policy_act(dev, 4, A, lds, (hipStream_t)hip_stream);
 }
 
 int32_t fw_rollout_post(const void* reward, int32_t rew_is_f64, const uint8_t* terminated, const uint8_t* truncated, const float* tvalue,

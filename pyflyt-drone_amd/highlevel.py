@@ -16,7 +16,7 @@ from __future__ import annotations
 import copy
 import ctypes as C
 import os
-from typing import Any, List, Optional
+from typing import Any, Optional
 
 import numpy as np
 import torch
@@ -25,7 +25,7 @@ from torch import nn
 from . import _lib
 from . import config as K
 from .spaces import Box
-from .vec_env import FixedwingWaypointsDirectVecEnv, _VecEnvBase, _devptr
+from .vec_env import FixedwingWaypointsDirectVecEnv, FusedVecEnv, _VecEnvBase, _devptr
 
 LOW_OBS_DIM = 21          # the low-level task's observation: 18 shared columns + (psi, h, V)
 LOW_ACT_DIM = 6
@@ -93,7 +93,7 @@ def load_low_checkpoint(path: str):
     return policy, _rms_arrays(vn["obs_rms"]), float(vn.get("clip_obs", 10.0)), float(vn.get("epsilon", 1e-8))
 
 
-class HighLevelCmdVecEnv(_VecEnvBase):
+class HighLevelCmdVecEnv(FusedVecEnv):
     """``HighLevelCmdEnv`` x N on one MI355X: three actions in the reference's Box (``action_low`` / ``action_high``), the
     30-value observation of the base env, its reward, termination, truncation and info.
 
@@ -156,7 +156,6 @@ class HighLevelCmdVecEnv(_VecEnvBase):
         self._act_raw = torch.zeros((n, LOW_ACT_DIM), dtype=torch.float32, device=dev)
         self._logp = torch.zeros(n, dtype=torch.float32, device=dev)
         self._actions_dev = torch.zeros((n, 3), dtype=self.torch_dtype, device=dev)
-        self._pending = False
 
     # the base env's output tensors are this env's
     obs = property(lambda self: self.base.obs)
@@ -201,26 +200,12 @@ class HighLevelCmdVecEnv(_VecEnvBase):
         self.reset_infos = [{} for _ in range(self.num_envs)]
         return obs
 
-    def step_async(self, actions: np.ndarray) -> None:
-        a = torch.as_tensor(np.asarray(actions), dtype=self.torch_dtype).reshape(self.num_envs, 3)
-        self._actions_dev.copy_(a, non_blocking=False)
-        self.step_tensor(self._actions_dev)
-        self._pending = True
-
-    def step_wait(self):
-        if not self._pending:
-            raise RuntimeError("step_wait() called without step_async()")
-        self._pending = False
-        self.base._pending = True
-        obs, rewards, dones, infos = self.base.step_wait()
+    def _finish_step(self):
+        obs, rewards, dones, infos = self.base._finish_step()
         cmd = self.command.cpu().numpy().astype(np.float64)
         for i, d in enumerate(infos):
             d["command"] = cmd[i].copy()
         return obs, rewards, dones, infos
-
-    def step(self, actions: np.ndarray):
-        self.step_async(actions)
-        return self.step_wait()
 
     def seed(self, seed: Optional[int] = None):
         self._seeds = self.base.seed(seed)
@@ -231,43 +216,11 @@ class HighLevelCmdVecEnv(_VecEnvBase):
         if b is not None:
             b.close()
 
-    def get_attr(self, attr_name: str, indices=None) -> List[Any]:
-        if attr_name == "render_mode":
-            v = self.__dict__.get("render_mode", None)
-        elif attr_name in self.__dict__ or hasattr(type(self), attr_name):
-            v = getattr(self, attr_name)
-        elif "base" in self.__dict__:
-            return self.base.get_attr(attr_name, indices)
-        else:
+    def _inherited_attr(self, attr_name: str) -> Any:
+        """What is not this env's own is the base env's (its attributes, then the fields of its fw_config)."""
+        if "base" not in self.__dict__:
             raise AttributeError(f"{type(self).__name__} envs have no attribute {attr_name!r}")
-        return [v for _ in self.base._indices(indices)] if "base" in self.__dict__ else [v for _ in range(self.num_envs)]
-
-    def set_attr(self, attr_name: str, value: Any, indices=None) -> None:
-        if any(attr_name == f[0] for f in type(self.cfg)._fields_):
-            raise AttributeError(f"{attr_name!r} is part of the device-side configuration; build a new env with it")
-        if indices is not None and sorted(self.base._indices(indices)) != list(range(self.num_envs)):
-            raise AttributeError("the envs of a fused device env share their attributes: set them for all envs (indices=None)")
-        setattr(self, attr_name, value)
-
-    def env_method(self, method_name: str, *args, indices=None, **kwargs) -> List[Any]:
-        fn = getattr(self, method_name, None)
-        if not callable(fn) or method_name.startswith("_"):
-            raise AttributeError(f"env_method({method_name!r}) is not available on a fused device env")
-        out = fn(*args, **kwargs)
-        return [out for _ in self.base._indices(indices)]
-
-    def env_is_wrapped(self, wrapper_class, indices=None) -> List[bool]:
-        return [False for _ in self.base._indices(indices)]
-
-    def get_images(self):
-        return [None for _ in range(self.num_envs)]
-
-    def render(self, mode: Optional[str] = None):
-        return None
-
-    @property
-    def unwrapped(self):
-        return self
+        return self.base.get_attr(attr_name, 0)[0]
 
     # ------------------------------------------------------------------ state access (parity tests / checkpoints)
     def get_state(self) -> np.ndarray:

@@ -87,7 +87,84 @@ except Exception:
             return [indices] if isinstance(indices, int) else indices
 
 
-class FixedwingVecEnv(_VecEnvBase):
+class FusedVecEnv(_VecEnvBase):
+    """The task-independent part of the SB3 ``VecEnv`` surface of a fused device env: the N envs are one object with one
+    config, so "per-env" access (``get_attr`` / ``set_attr`` / ``env_method``) acts on that object once.  A subclass brings
+    ``step_tensor``, the staging tensor ``_actions_dev`` and ``_finish_step`` (the host-side tuple of a finished step), and says in
+    ``_inherited_attr`` where an attribute that is not its own is looked up."""
+
+    _pending = False
+
+    def step_async(self, actions: np.ndarray) -> None:
+        a = torch.as_tensor(np.asarray(actions), dtype=self.torch_dtype).reshape(self.num_envs, self.act_dim)
+        self._actions_dev.copy_(a, non_blocking=False)
+        self.step_tensor(self._actions_dev)
+        self._pending = True
+
+    def step_wait(self):
+        if not self._pending:
+            raise RuntimeError("step_wait() called without step_async()")
+        self._pending = False
+        return self._finish_step()
+
+    def _indices(self, indices) -> List[int]:
+        if indices is None:
+            return list(range(self.num_envs))
+        if isinstance(indices, int):
+            return [indices]
+        return list(indices)
+
+    def _inherited_attr(self, attr_name: str) -> Any:
+        """Where an attribute that is not the env object's own is looked up: the fields of its fw_config (flight_dome_size,
+        num_targets, ...: what the reference env objects carry as attributes)."""
+        if "cfg" in self.__dict__ and any(attr_name == f[0] for f in type(self.cfg)._fields_):
+            return getattr(self.cfg, attr_name)
+        raise AttributeError(f"{type(self).__name__} envs have no attribute {attr_name!r}")
+
+    # Per-env attribute access of the VecEnv API.  The N envs are one kernel launch with one config, so every "per-env"
+    # attribute is the same for all of them: the env object's own attributes first, then _inherited_attr.
+    def get_attr(self, attr_name: str, indices=None) -> List[Any]:
+        if attr_name == "render_mode":
+            v = self.__dict__.get("render_mode", None)
+        elif attr_name in self.__dict__ or hasattr(type(self), attr_name):
+            v = getattr(self, attr_name)
+        else:
+            v = self._inherited_attr(attr_name)
+        return [v for _ in self._indices(indices)]
+
+    def set_attr(self, attr_name: str, value: Any, indices=None) -> None:
+        """Host-side attributes can be set (for all envs at once: they share one object); anything that is compiled into
+        the device-side constants (an ``fw_config`` field) needs a new env."""
+        if "cfg" in self.__dict__ and any(attr_name == f[0] for f in type(self.cfg)._fields_):
+            raise AttributeError(f"{attr_name!r} is part of the device-side configuration; build a new env with it")
+        if indices is not None and sorted(self._indices(indices)) != list(range(self.num_envs)):
+            raise AttributeError("the envs of a fused device env share their attributes: set them for all envs (indices=None)")
+        setattr(self, attr_name, value)
+
+    def env_method(self, method_name: str, *args, indices=None, **kwargs) -> List[Any]:
+        """Call a method "of each env": methods of this object are called ONCE (they already act on all envs) and the
+        result is repeated per requested index, as ``SubprocVecEnv.env_method`` would return it."""
+        fn = getattr(self, method_name, None)
+        if not callable(fn) or method_name.startswith("_"):
+            raise AttributeError(f"env_method({method_name!r}) is not available on a fused device env")
+        out = fn(*args, **kwargs)
+        return [out for _ in self._indices(indices)]
+
+    def env_is_wrapped(self, wrapper_class, indices=None) -> List[bool]:
+        return [False for _ in self._indices(indices)]
+
+    def get_images(self):
+        return [None for _ in range(self.num_envs)]
+
+    def render(self, mode: Optional[str] = None):
+        return None
+
+    @property
+    def unwrapped(self):
+        return self
+
+
+class FixedwingVecEnv(FusedVecEnv):
     """N fixed-wing envs advanced in lockstep by ``fw_step`` on one MI355X.  A ``stable_baselines3`` ``VecEnv``
     (subclass of the real base class when SB3 is importable, of its in-tree mirror otherwise) whose spaces are
     ``gymnasium.spaces.Box`` when gymnasium is importable."""
@@ -139,7 +216,6 @@ class FixedwingVecEnv(_VecEnvBase):
         self.terminal_obs = torch.zeros((n, d), dtype=self.torch_dtype, **kw)
         self.info = torch.zeros((n, K.FW_INFO_DIM), dtype=torch.int32, **kw)
         self._actions_dev = torch.zeros((n, self.act_dim), dtype=self.torch_dtype, **kw)
-        self._pending = False
 
     # ------------------------------------------------------------------ device fast path
     def _stream(self):
@@ -238,16 +314,8 @@ class FixedwingVecEnv(_VecEnvBase):
         want = self.observation_space.dtype
         return a if a.dtype == want else a.astype(want)
 
-    def step_async(self, actions: np.ndarray) -> None:
-        a = torch.as_tensor(np.asarray(actions), dtype=self.torch_dtype).reshape(self.num_envs, self.act_dim)
-        self._actions_dev.copy_(a, non_blocking=False)
-        self.step_tensor(self._actions_dev)
-        self._pending = True
-
-    def step_wait(self):
-        if not self._pending:
-            raise RuntimeError("step_wait() called without step_async()")
-        self._pending = False
+    def _finish_step(self):
+        """``(obs, rewards, dones, infos)`` of the step the output tensors hold, as SB3's workers return it."""
         obs = self._np_obs(self.obs)
         rewards = self.rewards.cpu().numpy()
         term = self.terminated.cpu().numpy().astype(bool)
@@ -289,10 +357,6 @@ class FixedwingVecEnv(_VecEnvBase):
             infos.append(d)
         return infos
 
-    def step(self, actions: np.ndarray):
-        self.step_async(actions)
-        return self.step_wait()
-
     def seed(self, seed: Optional[int] = None) -> Sequence[Optional[int]]:
         s = 0 if seed is None else int(seed)
         _lib.check(_lib.lib().fw_seed(self._h, s & (2**64 - 1)), self._h)
@@ -310,58 +374,6 @@ class FixedwingVecEnv(_VecEnvBase):
             self.close()
         except Exception:
             pass
-
-    def _indices(self, indices) -> List[int]:
-        if indices is None:
-            return list(range(self.num_envs))
-        if isinstance(indices, int):
-            return [indices]
-        return list(indices)
-
-    # Per-env attribute access of the VecEnv API.  The N envs are one kernel launch with one config, so every "per-env"
-    # attribute is the same for all of them: the env object's own attributes first, then the fields of its fw_config
-    # (flight_dome_size, num_targets, ...: what the reference env objects carry as attributes).
-    def get_attr(self, attr_name: str, indices=None) -> List[Any]:
-        if attr_name == "render_mode":
-            v = self.__dict__.get("render_mode", None)
-        elif attr_name in self.__dict__ or hasattr(type(self), attr_name):
-            v = getattr(self, attr_name)
-        elif "cfg" in self.__dict__ and any(attr_name == f[0] for f in type(self.cfg)._fields_):
-            v = getattr(self.cfg, attr_name)
-        else:
-            raise AttributeError(f"{type(self).__name__} envs have no attribute {attr_name!r}")
-        return [v for _ in self._indices(indices)]
-
-    def set_attr(self, attr_name: str, value: Any, indices=None) -> None:
-        """Host-side attributes can be set (for all envs at once: they share one object); anything that is compiled into
-        the device-side constants (an ``fw_config`` field) needs a new env."""
-        if "cfg" in self.__dict__ and any(attr_name == f[0] for f in type(self.cfg)._fields_):
-            raise AttributeError(f"{attr_name!r} is part of the device-side configuration; build a new env with it")
-        if indices is not None and sorted(self._indices(indices)) != list(range(self.num_envs)):
-            raise AttributeError("the envs of a fused device env share their attributes: set them for all envs (indices=None)")
-        setattr(self, attr_name, value)
-
-    def env_method(self, method_name: str, *args, indices=None, **kwargs) -> List[Any]:
-        """Call a method "of each env": methods of this object are called ONCE (they already act on all envs) and the
-        result is repeated per requested index, as ``SubprocVecEnv.env_method`` would return it."""
-        fn = getattr(self, method_name, None)
-        if not callable(fn) or method_name.startswith("_"):
-            raise AttributeError(f"env_method({method_name!r}) is not available on a fused device env")
-        out = fn(*args, **kwargs)
-        return [out for _ in self._indices(indices)]
-
-    def env_is_wrapped(self, wrapper_class, indices=None) -> List[bool]:
-        return [False for _ in self._indices(indices)]
-
-    def get_images(self):
-        return [None for _ in range(self.num_envs)]
-
-    def render(self, mode: Optional[str] = None):
-        return None
-
-    @property
-    def unwrapped(self):
-        return self
 
     # ------------------------------------------------------------------ state access (parity tests / checkpoints)
     def get_state(self) -> np.ndarray:

@@ -12,6 +12,12 @@ check runs on the ISA of every build:
 
 exits 1 and prints the blocks if a spill store to a register that is reloaded later sits between a block label and the exec
 restore of that block.
+
+    python tools/check_isa.py --same-device-code <a.s> <b.s>
+
+compares the device assembly of two builds function by function (a change that means to leave the device code alone, e.g. one
+of the host half of fwsim.hip): the same function names, the same text for each -- its .amdhsa_kernel block included -- up to the
+order of the functions and the function ordinal in local labels, which follow the order of instantiation.  Exits 1 on a difference.
 """
 import re
 import sys
@@ -89,7 +95,30 @@ def scan_ticket(text, kernels=("fw_collect_stats_kernel",)):
     return hits
 
 
+def functions(text):
+    """{name: text} of the functions of a device assembly file, the function ordinal of local labels blanked."""
+    out = {}
+    for m in re.finditer(r"; -- Begin function (\S+)\n(.*?); -- End function", text, re.S):
+        # (the comment behind a label starts at a fixed column: the padding in front of it changes with the ordinal's width)
+        body = re.sub(r"^(\.LBB\d+_\d+:)[ \t]+;", r"\1 ;", m.group(2), flags=re.M)
+        out[m.group(1)] = re.sub(r"(\.LBB|\.LJTI|\.Lfunc_begin|\.Lfunc_end|\bBB)\d+", r"\1#", body)      # (BB12_37: the same labels in comments)
+    return out
+
+
+def compare(a, b):
+    """Names of the functions that only one of two device assembly texts has, or whose text differs; and what was compared."""
+    fa, fb = functions(a), functions(b)
+    diff = sorted(set(fa) ^ set(fb)) + sorted(n for n in set(fa) & set(fb) if fa[n] != fb[n])
+    return diff, len(fa), sum(".amdhsa_kernel " in t for t in fa.values())
+
+
 if __name__ == "__main__":
+    if sys.argv[1] == "--same-device-code":
+        diff, nfn, nk = compare(open(sys.argv[2]).read(), open(sys.argv[3]).read())
+        for name in diff:
+            print(f"differs: {name[:160]}")
+        print(f"{nfn} functions ({nk} kernels) compared, {len(diff)} differing")
+        sys.exit(1 if diff else 0)
     text = open(sys.argv[1]).read()
     h = scan(text) + scan_ticket(text)
     for name, label, spills in h:
