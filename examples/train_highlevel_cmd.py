@@ -4,8 +4,9 @@ The high-level policy of the hierarchical design: it outputs (heading, altitude,
 (what examples/train_lowlevel_cmd.py trains and saves) turns each command into six actuator commands, and the waypoint task runs
 underneath (dome 200 m, 120 s, 30 Hz, euler, context 2).  Same PPO hyper-parameters as the reference's TRAIN_CFG (16 envs, n_steps
 1024, batch 256, 10 epochs, gamma 0.995, lambda 0.95, clip 0.2, no entropy bonus, seed 123).  The three-action policy trains on the
-torch path (the fused learner takes four- and six-action policies); the env's vec-step is three launches
-(fw_command_hl -> fw_collect_act_a -> fw_step).  The actions are the reference's: a raw Gaussian clipped to the Box in physical units.
+torch path by default (the env's vec-step is then three launches, fw_command_hl -> fw_collect_act_a -> fw_step); --fused_learner puts it
+on the fused three-action learner (fw_ppo_update_a3) and collector (fw_collect_act_hl -> fw_step -> fw_collect_stats;
+PPOConfig.fused_three_actions).  The actions are the reference's: a raw Gaussian clipped to the Box in physical units.
 
     python examples/train_lowlevel_cmd.py --total_timesteps 2000000 --out runs/lowlevel_ppo
     python examples/train_highlevel_cmd.py --low_checkpoint runs/lowlevel_ppo/models/final_model.pt --total_timesteps 2000000
@@ -33,6 +34,7 @@ def main():
     ap.add_argument("--total_timesteps", type=int, default=None)
     ap.add_argument("--n_steps", type=int, default=None, help="default: the reference's 16 x 1024 samples per update, split over --num_envs")
     ap.add_argument("--out", type=str, default="runs/highlevel_ppo")
+    ap.add_argument("--fused_learner", action="store_true", help="the fused three-action update / collector kernels instead of the torch path")
     a = ap.parse_args()
     cfg = TRAIN_CFG
     num_envs = a.num_envs if a.num_envs is not None else cfg["num_envs"]
@@ -49,7 +51,8 @@ def main():
     n_steps = a.n_steps if a.n_steps is not None else R.n_steps_for(cfg["num_envs"] * cfg["n_steps"], num_envs)
     model = R.PPO(env, R.PPOConfig(n_steps=n_steps, batch_size=cfg["batch_size"], n_epochs=cfg["n_epochs"], learning_rate=cfg["learning_rate"],
                                    gamma=cfg["gamma"], gae_lambda=cfg["gae_lambda"], clip_range=cfg["clip_range"], ent_coef=cfg["ent_coef"],
-                                   vf_coef=cfg["vf_coef"], max_grad_norm=cfg["max_grad_norm"], seed=cfg["seed"]))
+                                   vf_coef=cfg["vf_coef"], max_grad_norm=cfg["max_grad_norm"], seed=cfg["seed"],
+                                   fused_three_actions=a.fused_learner))
     per_update = n_steps * num_envs
     ev = evaluate.EvalCallback(eval_env, n_eval_episodes=16, eval_freq=max(10 * per_update // num_envs, 1), log_path=log_dir,
                                best_model_save_path=model_dir, num_targets_total=int(venv.cfg.num_targets), verbose=1)
@@ -73,7 +76,8 @@ def main():
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         print(json.dumps({"final": True, "num_envs": num_envs, "n_steps": n_steps, "timesteps": model.num_timesteps, "wall_s": round(dt, 2),
-                          "env_steps_per_s": round(model.num_timesteps / dt), "rejected_actions": int(venv.rejected.item())}), flush=True)
+                          "env_steps_per_s": round(model.num_timesteps / dt), "fused_learner": bool(a.fused_learner),
+                          "rejected_actions": int(venv.rejected.item())}), flush=True)
         checkpoint.save(os.path.join(model_dir, "final_model.pt"), model)
         checkpoint.save_vecnormalize(os.path.join(model_dir, "vecnorm.pt"), env)
         venv.close(); eval_env.venv.close()

@@ -532,6 +532,21 @@ int32_t fw_ppo_update_a(float* params, float* mom_m, float* mom_v, const float* 
                         const float* old_logp, const float* adv, const float* ret, const int32_t* perm,
                         int32_t n_minibatches, int32_t batch_size, int32_t obs_dim, int32_t act_dim, const fw_ppo_hyper* hyper,
                         float* loss_acc, void* workspace, int64_t workspace_bytes, void* hip_stream);
+/* The same learner for a policy head of THREE actions (the high-level command task's heading / altitude / airspeed): the *_a family
+ * with the width fixed -- the *_a entry points themselves keep refusing act_dim = 3.  A three-action instantiation of the same
+ * kernel, every cut and exchange form included; the contracts (status word, results only behind the closing verdict, the FWSIM_PPO_* /
+ * FWSIM_SPIN_LOG2 switches) are those above.  Flat layout as documented with A = 3: Wo[64][3], bo[3], log_std[3]
+ * (fw_ppo_param_count_a3(obs_dim) elements); fw_ppo_moment_count_a3() = fw_ppo_moment_count() slots, mapped by fw_ppo_moment_map_a3 (the
+ * places of a fourth component are padding); act is [S, 3]; the packed rows keep the four-action width, their fourth action float is
+ * written as zero by the pre-pass and reaches no sum. */
+int32_t fw_ppo_param_count_a3(int32_t obs_dim);
+int32_t fw_ppo_moment_count_a3(void);
+int32_t fw_ppo_moment_map_a3(int32_t obs_dim, int32_t* flat_index_of_slot /* host, [fw_ppo_moment_count_a3()] */);
+int64_t fw_ppo_update_workspace_bytes_a3(int32_t n_minibatches, int32_t batch_size, int32_t obs_dim);
+int32_t fw_ppo_update_a3(float* params, float* mom_m, float* mom_v, const float* obs, const float* act /* [S, 3] */,
+                         const float* old_logp, const float* adv, const float* ret, const int32_t* perm,
+                         int32_t n_minibatches, int32_t batch_size, int32_t obs_dim, const fw_ppo_hyper* hyper,
+                         float* loss_acc, void* workspace, int64_t workspace_bytes, void* hip_stream);
 
 /* Rollout collection between two env steps (SB3 OnPolicyAlgorithm.collect_rollouts + VecNormalize reward path,
  * train/train_Fixedwing_Waypoints_v3.py:260,293-310), for the same MlpPolicy / flat parameter image as fw_ppo_update.
@@ -590,6 +605,44 @@ int32_t fw_collect_act_a(const float* params, const void* raw_obs, int32_t obs_i
                          float* value, const void* prev_reward, const uint8_t* prev_terminated, const uint8_t* prev_truncated,
                          const void* prev_terminal_obs, const double* ret_var, int32_t norm_reward, float clip_reward, float eps_reward,
                          float gamma, float* rew_out, float* start_out, void* hip_stream);
+/* The act side of a collected vec-step of the HIGH-LEVEL COMMAND task in one launch (instead of fw_collect_act for the commander,
+ * fw_command_hl, fw_collect_act_a for the controller); a collected vec-step is fw_collect_act_hl -> fw_step -> fw_collect_stats.
+ * `h`: a FW_TASK_WAYPOINTS_DIRECT handle with the euler attitude (fw_command_hl's rule: FW_EUNSUPPORTED otherwise), either dtype,
+ * either lane mapping; N = fw_num_envs(h), the env dtype T = the handle's.  Grid (ceil(N / 64), 2):
+ *   value block  (nets bit 1): what fw_collect_act's value block does with the three-action flat image `params`
+ *     (fw_ppo_param_count_a3(30) floats): value[N] = V(normalised obs), and -- when prev_reward != NULL -- the finalisation of the
+ *     previous step (rew_out, start_out; see fw_collect_act);
+ *   policy block (nets bit 0): obs (the env's raw buffer, T[N, 30]) normalised on load with (obs_mean, obs_var, clip_obs, eps_obs) ->
+ *     obs_copy (may be NULL); the commander 30 -> 64 -> 64 -> 3; act_raw[N, 3] = mean + exp(log_std) z with z = components 0-2 of the
+ *     four-action draw for (rng[0] = seed, rng[1] = draw counter, env_offset + row) (mean if `deterministic`), logp[N]; then
+ *     fw_command_hl's arithmetic on the float32 act_raw row: the conditioned command -> the env's FW_SL_TARGET tail, cmd_out T[N, 3]
+ *     and low_obs T[N, 21] = (obs[:, 0:18], command), a non-finite row keeping the stored command and counted into `rejected`
+ *     (may be NULL); low_obs normalised with the controller's frozen (low_mean, low_var, low_clip, low_eps); the controller
+ *     21 -> 64 -> 64 -> 6 of `low_params` (six-action flat image, fw_ppo_param_count_a(21, 6) floats), deterministic, clipped to
+ *     [-1, 1] -> act_env T[N, 6], the fw_step input.
+ * Given the same act_raw, cmd_out / low_obs / act_env / the tail / rejected are those of fw_command_hl + fw_collect_act_a bit for
+ * bit, and obs_copy is fw_normalize_obs's.  nets = 2 is the closing call of a rollout (value and finalisation only).  No in-grid
+ * wait, no host synchronisation: capturable.  A missing required pointer: FW_EINVAL. */
+typedef struct fw_collect_hl_args {
+  const float *params, *low_params;        /* the commander's and the controller's flat parameter images */
+  const void* obs;                         /* T[N, 30]: the env's raw observation buffer */
+  const double *obs_mean, *obs_var;        /* [30] VecNormalize statistics of the commander's observation */
+  const double *low_mean, *low_var;        /* [21] the controller's frozen statistics */
+  const uint64_t* rng;                     /* [2] seed, draw counter (only read; fw_collect_stats advances it) */
+  int64_t env_offset;                      /* global env id of row 0 */
+  float *obs_copy, *act_raw, *logp, *value;/* rollout-buffer rows of the step being acted */
+  void *low_obs, *cmd_out, *act_env;       /* T[N, 21], T[N, 3], T[N, 6] */
+  int32_t* rejected;                       /* [1] += rows with a non-finite action (may be NULL) */
+  const void* prev_reward;                 /* the previous-step block of fw_collect_act (all NULL / 0: nothing to finalise) */
+  const uint8_t *prev_terminated, *prev_truncated;
+  const void* prev_terminal_obs;
+  const double* ret_var;
+  float *rew_out, *start_out;
+  float clip_obs, eps_obs, low_clip, low_eps, clip_reward, eps_reward, gamma;
+  int32_t nets, deterministic, norm_reward;
+} fw_collect_hl_args;
+int32_t fw_sizeof_collect_hl_args(void);   /* for bindings: the size of the structure this build was compiled with */
+int32_t fw_collect_act_hl(fw_handle h, const fw_collect_hl_args* a, void* hip_stream);
 int64_t fw_collect_stats_workspace_bytes(int32_t D);
 int32_t fw_collect_stats(const void* obs, int32_t obs_is_f64, int32_t N, int32_t D, double* obs_mean, double* obs_var, double* obs_count,
                          int32_t update_obs, const void* reward, int32_t rew_is_f64, const uint8_t* terminated, const uint8_t* truncated,

@@ -23,6 +23,8 @@ EXPORTS = (
     "fw_destroy", "fw_gae", "fw_eval_track", "fw_eval_track_ll", "fw_command_ll", "fw_command_hl", "fw_trace_ll", "fw_normalize_obs", "fw_normalize_obs_workspace_bytes", "fw_ppo_update_workspace_bytes", "fw_ppo_param_count", "fw_ppo_moment_count", "fw_ppo_moment_map", "fw_ppo_update", "fw_policy_act", "fw_policy_terminal_value", "fw_rollout_post", "fw_collect_act", "fw_collect_stats", "fw_collect_stats_workspace_bytes", "fw_collect_step", "fw_collect_finish", "fw_collect_step_workspace_bytes", "fw_collect_workspace_init", "fw_collect_close", "fw_collect_status", "fw_ppo_update_status",
     "fw_ppo_param_count_a", "fw_ppo_moment_count_a", "fw_ppo_moment_map_a", "fw_ppo_update_workspace_bytes_a", "fw_ppo_update_a",
     "fw_policy_act_a", "fw_collect_act_a",
+    "fw_ppo_param_count_a3", "fw_ppo_moment_count_a3", "fw_ppo_moment_map_a3", "fw_ppo_update_workspace_bytes_a3", "fw_ppo_update_a3",
+    "fw_collect_act_hl", "fw_sizeof_collect_hl_args",
 )
 
 
@@ -148,6 +150,15 @@ def lib() -> C.CDLL:
         L.fw_ppo_update_workspace_bytes_a.restype = i64; L.fw_ppo_update_workspace_bytes_a.argtypes = [i32, i32, i32, i32]
         L.fw_ppo_update_a.restype = i32
         L.fw_ppo_update_a.argtypes = [vp] * 9 + [i32, i32, i32, i32, vp, vp, vp, i64, vp]
+        # the three-action learner (the high-level command task): the argument lists of the four-action entry points
+        L.fw_ppo_param_count_a3.restype = i32; L.fw_ppo_param_count_a3.argtypes = [i32]
+        L.fw_ppo_moment_count_a3.restype = i32; L.fw_ppo_moment_count_a3.argtypes = []
+        L.fw_ppo_moment_map_a3.restype = i32; L.fw_ppo_moment_map_a3.argtypes = [i32, vp]
+        L.fw_ppo_update_workspace_bytes_a3.restype = i64; L.fw_ppo_update_workspace_bytes_a3.argtypes = [i32, i32, i32]
+        L.fw_ppo_update_a3.restype = i32
+        L.fw_ppo_update_a3.argtypes = [vp] * 9 + [i32, i32, i32, vp, vp, vp, i64, vp]
+        L.fw_collect_act_hl.restype = i32; L.fw_collect_act_hl.argtypes = [vp, vp, vp]
+        L.fw_sizeof_collect_hl_args.restype = i32; L.fw_sizeof_collect_hl_args.argtypes = []
         L.fw_policy_act_a.restype = i32
         L.fw_policy_act_a.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
         L.fw_collect_act_a.restype = i32
@@ -161,6 +172,8 @@ def lib() -> C.CDLL:
             raise RuntimeError("FW_STATE_DIM mismatch between include/fwsim.h and config.py")
         if L.fw_sizeof_config() != C.sizeof(K.FwConfig):
             raise RuntimeError("fw_config layout mismatch between include/fwsim.h and config.FwConfig")
+        if L.fw_sizeof_collect_hl_args() != C.sizeof(K.FwCollectHlArgs):
+            raise RuntimeError("fw_collect_hl_args layout mismatch between include/fwsim.h and config.FwCollectHlArgs")
         _lib = L
     return _lib
 

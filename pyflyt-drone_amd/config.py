@@ -260,6 +260,16 @@ class FwCollectArgs(C.Structure):
                 + [(n, C.c_int32) for n in ("update_obs", "update_ret", "norm_reward", "deterministic")])
 
 
+class FwCollectHlArgs(C.Structure):
+    """``fw_collect_hl_args`` of include/fwsim.h (the act side of a collected vec-step of the high-level command task)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("params", "low_params", "obs", "obs_mean", "obs_var", "low_mean", "low_var", "rng")]
+                + [("env_offset", C.c_int64)]
+                + [(n, C.c_void_p) for n in ("obs_copy", "act_raw", "logp", "value", "low_obs", "cmd_out", "act_env", "rejected", "prev_reward",
+                                             "prev_terminated", "prev_truncated", "prev_terminal_obs", "ret_var", "rew_out", "start_out")]
+                + [(n, C.c_float) for n in ("clip_obs", "eps_obs", "low_clip", "low_eps", "clip_reward", "eps_reward", "gamma")]
+                + [(n, C.c_int32) for n in ("nets", "deterministic", "norm_reward")])
+
+
 class FwCollectCloseArgs(C.Structure):
     """``fw_collect_close_args`` of include/fwsim.h (GAE buffers of the rollout-closing launch)."""
     _fields_ = ([(n, C.c_void_p) for n in ("rewards", "values", "episode_starts", "adv", "ret")]

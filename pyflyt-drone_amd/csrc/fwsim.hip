@@ -1566,6 +1566,8 @@ __global__ __launch_bounds__(kWave) void fw_reset_kernel_ll(const Params<T>* __r
 #include "fwsim_command.hpp"
 // the waypoints task under six direct actuator commands, and the high-level command step in front of it (fw_command_hl)
 #include "fwsim_direct.hpp"
+// ... and the act side of its collected vec-step in one launch (fw_collect_act_hl)
+#include "fwsim_collect_hl.hpp"
 
 // ======================================================================
 // host side
@@ -2142,16 +2144,26 @@ int set_state_T(fw_env* h, const double* in) {
 
 namespace {
 // The learner's kernels: one lookup per family, used by the launch and by the LDS opt-in in front of it.
-const void* ppo_update_kernel(bool a6, int ch /*samples per pass*/, int ns /*blocks per network of the reduce-scatter form, 0: all-to-all*/) {
-  struct Row { int ch, ns; const void* a4; const void* a6; };
+const void* ppo_update_kernel(int act_dim, int ch /*samples per pass*/, int ns /*blocks per network of the reduce-scatter form, 0: all-to-all*/) {
+  struct Row { int ch, ns; const void* a4; const void* a6; const void* a3; };
+#define FW_PPO_ROW(CH, NS) {CH, NS, kfn(fw_ppo_update_kernel<CH, NS>), kfn(fw_ppo_update_kernel_a6<CH, NS>), kfn(fw_ppo_update_kernel_a3<CH, NS>)}
   static const Row rows[] = {
-    {64, 8, kfn(fw_ppo_update_kernel<64, 8>), kfn(fw_ppo_update_kernel_a6<64, 8>)}, {64, 4, kfn(fw_ppo_update_kernel<64, 4>), kfn(fw_ppo_update_kernel_a6<64, 4>)},
-    {64, 0, kfn(fw_ppo_update_kernel<64, 0>), kfn(fw_ppo_update_kernel_a6<64, 0>)}, {32, 8, kfn(fw_ppo_update_kernel<32, 8>), kfn(fw_ppo_update_kernel_a6<32, 8>)},
-    {32, 4, kfn(fw_ppo_update_kernel<32, 4>), kfn(fw_ppo_update_kernel_a6<32, 4>)}, {32, 0, kfn(fw_ppo_update_kernel<32, 0>), kfn(fw_ppo_update_kernel_a6<32, 0>)},
-    {16, 8, kfn(fw_ppo_update_kernel<16, 8>), kfn(fw_ppo_update_kernel_a6<16, 8>)}, {16, 4, kfn(fw_ppo_update_kernel<16, 4>), kfn(fw_ppo_update_kernel_a6<16, 4>)},
-    {16, 0, kfn(fw_ppo_update_kernel<16, 0>), kfn(fw_ppo_update_kernel_a6<16, 0>)},
+    FW_PPO_ROW(64, 8), FW_PPO_ROW(64, 4), FW_PPO_ROW(64, 0), FW_PPO_ROW(32, 8), FW_PPO_ROW(32, 4), FW_PPO_ROW(32, 0),
+    FW_PPO_ROW(16, 8), FW_PPO_ROW(16, 4), FW_PPO_ROW(16, 0),
   };
-  for (const Row& r : rows) if (r.ch == ch && r.ns == ns) return a6 ? r.a6 : r.a4;
+#undef FW_PPO_ROW
+  for (const Row& r : rows) if (r.ch == ch && r.ns == ns) return act_dim == 6 ? r.a6 : act_dim == 3 ? r.a3 : r.a4;
+  return nullptr;
+}
+// the pre-pass that packs the rows, and the entry point that sizes the workspace (for the message), by action width
+struct PpoWidth { int act_dim; const void* pack; const char* ws_fn; };
+const PpoWidth* ppo_width(int act_dim) {
+  static const PpoWidth rows[] = {
+    {4, kfn(fw_ppo_pack_kernel), "fw_ppo_update_workspace_bytes(n_minibatches, batch_size, obs_dim)"},
+    {6, kfn(fw_ppo_pack_kernel_a6), "fw_ppo_update_workspace_bytes_a(n_minibatches, batch_size, obs_dim, act_dim)"},
+    {3, kfn(fw_ppo_pack_kernel_a3), "fw_ppo_update_workspace_bytes_a3(n_minibatches, batch_size, obs_dim)"},
+  };
+  for (const PpoWidth& r : rows) if (r.act_dim == act_dim) return &r;
   return nullptr;
 }
 const void* policy_act_kernel(int act_dim) { return act_dim == 6 ? kfn(fw_policy_act_kernel<6>) : kfn(fw_policy_act_kernel<4>); }
@@ -2594,6 +2606,18 @@ int32_t fw_ppo_moment_map_a(int32_t obs_dim, int32_t act_dim, int32_t* flat_inde
   for (int i = ns; i < 2 * ns; ++i) flat_index_of_slot[i] = -1;
   return FW_OK;
 }
+int32_t fw_ppo_param_count_a3(int32_t obs_dim) {
+  if (obs_dim <= 0) { g_err = "fw_ppo_param_count_a3: obs_dim must be positive"; return FW_EINVAL; }
+  return ppo_total_params_a((obs_dim + 1) & ~1, 3);
+}
+int32_t fw_ppo_moment_count_a3(void) { return 2 * ppo_moment_slots(3); }      // (the second half unused, as for fw_ppo_moment_count)
+int32_t fw_ppo_moment_map_a3(int32_t obs_dim, int32_t* flat_index_of_slot) {
+  if (obs_dim <= 0 || obs_dim > 64 || !flat_index_of_slot) { g_err = "fw_ppo_moment_map_a3: bad arguments"; return FW_EINVAL; }
+  const int ns = ppo_moment_slots(3);
+  ppo_moment_map(obs_dim, flat_index_of_slot, 3);
+  for (int i = ns; i < 2 * ns; ++i) flat_index_of_slot[i] = -1;
+  return FW_OK;
+}
 
 // Dev knob: FWSIM_SPIN_LOG2=k bounds every in-grid wait (fw_collect_step, fw_ppo_update) to 2^k polls instead of its default --
 // tests use it to provoke the timeout paths and assert that the status words surface on the host side.
@@ -2614,10 +2638,18 @@ int64_t fw_ppo_update_workspace_bytes(int32_t n_minibatches, int32_t batch_size,
   if (n_minibatches <= 0 || batch_size <= 0 || obs_dim <= 0 || obs_dim > 64) return FW_EINVAL;
   return (int64_t)(kPpoWsXch + kPpoWsGx + sizeof(float) * (size_t)n_minibatches * (size_t)batch_size * (size_t)ppo_pack_width(obs_dim));
 }
+static int64_t ppo_workspace_bytes(int32_t n_minibatches, int32_t batch_size, int32_t obs_dim, int32_t act_dim) {
+  return (int64_t)(kPpoWsXch + ppo_ws_gx(act_dim) + sizeof(float) * (size_t)n_minibatches * (size_t)batch_size * (size_t)ppo_pack_width(obs_dim, act_dim));
+}
 int64_t fw_ppo_update_workspace_bytes_a(int32_t n_minibatches, int32_t batch_size, int32_t obs_dim, int32_t act_dim) {
   if (!act_dim_ok(act_dim, "fw_ppo_update_workspace_bytes_a")) return FW_EINVAL;
   if (n_minibatches <= 0 || batch_size <= 0 || obs_dim <= 0 || obs_dim > 64) { g_err = "fw_ppo_update_workspace_bytes_a: bad arguments"; return FW_EINVAL; }
-  return (int64_t)(kPpoWsXch + ppo_ws_gx(act_dim) + sizeof(float) * (size_t)n_minibatches * (size_t)batch_size * (size_t)ppo_pack_width(obs_dim, act_dim));
+  return ppo_workspace_bytes(n_minibatches, batch_size, obs_dim, act_dim);
+}
+// the three-action learner (the high-level command task): the *_a family with the width fixed
+int64_t fw_ppo_update_workspace_bytes_a3(int32_t n_minibatches, int32_t batch_size, int32_t obs_dim) {
+  if (n_minibatches <= 0 || batch_size <= 0 || obs_dim <= 0 || obs_dim > 64) { g_err = "fw_ppo_update_workspace_bytes_a3: bad arguments"; return FW_EINVAL; }
+  return ppo_workspace_bytes(n_minibatches, batch_size, obs_dim, 3);
 }
 
 // fw_ppo_update and fw_ppo_update_a (who: the entry point's name, for the messages)
@@ -2632,10 +2664,10 @@ static int32_t ppo_update(float* params, float* mom_m, float* mom_v, const float
   }
   if (batch_size <= 0 || batch_size % 16 != 0) { g_err = w + ": batch_size must be a multiple of 16"; return FW_EINVAL; }
   if (obs_dim <= 0 || obs_dim > 64) { g_err = w + ": obs_dim must be in [1, 64]"; return FW_EINVAL; }
-  const bool a6 = act_dim == 6;
-  if (!workspace || workspace_bytes < fw_ppo_update_workspace_bytes_a(n_minibatches, batch_size, obs_dim, act_dim)) {
-    g_err = w + (a6 ? ": workspace smaller than fw_ppo_update_workspace_bytes_a(n_minibatches, batch_size, obs_dim, act_dim)"
-                    : ": workspace smaller than fw_ppo_update_workspace_bytes(n_minibatches, batch_size, obs_dim)");
+  const PpoWidth* width = ppo_width(act_dim);
+  if (!width) { g_err = w + ": no learner is built for " + std::to_string(act_dim) + " actions"; return FW_EINVAL; }
+  if (!workspace || workspace_bytes < ppo_workspace_bytes(n_minibatches, batch_size, obs_dim, act_dim)) {
+    g_err = w + ": workspace smaller than " + width->ws_fn;
     return FW_EINVAL;
   }
   const size_t lds = ppo_lds_bytes(obs_dim, act_dim);
@@ -2661,8 +2693,10 @@ static int32_t ppo_update(float* params, float* mom_m, float* mom_v, const float
   PpoPackArgs P;
   P.obs = obs; P.act = act; P.old_logp = old_logp; P.adv = adv; P.ret = ret; P.perm = perm; P.B = batch_size; P.D = obs_dim;
   P.norm_adv = A.H.norm_adv; P.adv_mean = A.H.adv_mean; P.adv_std = A.H.adv_std; P.out = packed;
-  if (a6) hipLaunchKernelGGL(fw_ppo_pack_kernel_a6, dim3(n_minibatches), dim3(256), 0, st, P);
-  else hipLaunchKernelGGL(fw_ppo_pack_kernel, dim3(n_minibatches), dim3(256), 0, st, P);
+  {
+    void* pargs[] = { &P };
+    (void)hipLaunchKernel(width->pack, dim3(n_minibatches), dim3(256), pargs, 0, st);
+  }
   // four / eight blocks per network: gradient tiles by reduce-scatter, updated weights by all-gather (FWSIM_PPO_RS=0: all-to-all, as for two
   // blocks -- written for up to four, so the cut is then chosen among round 4's)
   bool rs_env = true;
@@ -2676,7 +2710,7 @@ static int32_t ppo_update(float* params, float* mom_m, float* mom_v, const float
   }
   const int ns = cut.nsplit >= 4 && rs_env ? cut.nsplit : 0;      // the kernel's NS: 0 = all-to-all swap of whole partials
   const dim3 grid(16 * cut.nsplit);                 // (every 8th block works -- see the kernel)
-  const void* fn = ppo_update_kernel(a6, cut.ch, ns);
+  const void* fn = ppo_update_kernel(act_dim, cut.ch, ns);
   if (!fn) { g_err = w + ": no kernel is built for " + std::to_string(cut.ch) + " samples per pass x " + std::to_string(ns) + " blocks per network"; return FW_EINVAL; }
   if (int rc = ensure_dynamic_lds(nullptr, dev, fn, lds)) return rc;
   void* args[] = { &A };
@@ -2698,6 +2732,13 @@ int32_t fw_ppo_update_a(float* params, float* mom_m, float* mom_v, const float* 
   if (!act_dim_ok(act_dim, "fw_ppo_update_a")) return FW_EINVAL;
   return ppo_update(params, mom_m, mom_v, obs, act, old_logp, adv, ret, perm, n_minibatches, batch_size, obs_dim, act_dim, hyper, loss_acc,
                     workspace, workspace_bytes, hip_stream, "fw_ppo_update_a");
+}
+int32_t fw_ppo_update_a3(float* params, float* mom_m, float* mom_v, const float* obs, const float* act, const float* old_logp,
+                         const float* adv, const float* ret, const int32_t* perm, int32_t n_minibatches, int32_t batch_size,
+                         int32_t obs_dim, const fw_ppo_hyper* hyper, float* loss_acc, void* workspace, int64_t workspace_bytes,
+                         void* hip_stream) {
+  return ppo_update(params, mom_m, mom_v, obs, act, old_logp, adv, ret, perm, n_minibatches, batch_size, obs_dim, 3, hyper, loss_acc,
+                    workspace, workspace_bytes, hip_stream, "fw_ppo_update_a3");
 }
 
 int32_t fw_ppo_update_status(const void* workspace, int64_t workspace_bytes, uint32_t* status_out, uint32_t* paths_out, void* hip_stream) {
@@ -2791,6 +2832,61 @@ int32_t fw_collect_act_a(const float* params, const void* raw_obs, int32_t obs_i
   return collect_act(params, raw_obs, obs_is_f64, N, obs_dim, act_dim, obs_mean, obs_var, clip_obs, eps_obs, nets, deterministic, rng, env_offset,
                      obs_copy, act_raw, act_env, act_is_f64, logp, value, prev_reward, prev_terminated, prev_truncated, prev_terminal_obs,
                      ret_var, norm_reward, clip_reward, eps_reward, gamma, rew_out, start_out, hip_stream, "fw_collect_act_a");
+}
+
+// fw_collect_act_hl's kernel by (dtype, lane mapping): the table the launch and the LDS opt-in look it up in
+static const void* collect_act_hl_kernel(bool f64, int lanes) {
+  struct Row { bool f64; int lanes; const void* fn; };
+  static const Row rows[] = {
+    {true, 8, kfn(fw_collect_act_hl_kernel<double, 8>)}, {true, 1, kfn(fw_collect_act_hl_kernel<double, 1>)},
+    {false, 8, kfn(fw_collect_act_hl_kernel<float, 8>)}, {false, 1, kfn(fw_collect_act_hl_kernel<float, 1>)},
+  };
+  for (const Row& r : rows) if (r.f64 == f64 && r.lanes == lanes) return r.fn;
+  return nullptr;
+}
+int32_t fw_sizeof_collect_hl_args(void) { return (int32_t)sizeof(fw_collect_hl_args); }
+int32_t fw_collect_act_hl(fw_handle h, const fw_collect_hl_args* a, void* hip_stream) {
+  if (!h) { g_err = "fw_collect_act_hl: NULL handle"; return FW_EINVAL; }
+  if (h->cfg.task != FW_TASK_WAYPOINTS_DIRECT) { h->err = "fw_collect_act_hl: only the direct-command waypoints task (FW_TASK_WAYPOINTS_DIRECT) takes high-level commands"; return FW_EUNSUPPORTED; }
+  if (h->cfg.angle_representation != 0) { h->err = "fw_collect_act_hl: the low-level controller's observation needs the euler attitude (angle_representation 0)"; return FW_EUNSUPPORTED; }
+  if (!a) { h->err = "fw_collect_act_hl: NULL arguments"; return FW_EINVAL; }
+  const int32_t nets = a->nets;
+  if (!a->params || !a->obs || !a->obs_mean || !a->obs_var || (nets & ~3) || !nets) { h->err = "fw_collect_act_hl: bad arguments"; return FW_EINVAL; }
+  if ((nets & 1) && (!a->low_params || !a->low_mean || !a->low_var || !a->act_raw || !a->logp || !a->low_obs || !a->cmd_out || !a->act_env ||
+                     (!a->deterministic && !a->rng))) {
+    h->err = "fw_collect_act_hl: the policy block needs low_params, low_mean, low_var, act_raw, logp, low_obs, cmd_out, act_env (and rng unless deterministic)";
+    return FW_EINVAL;
+  }
+  if ((nets & 2) && !a->value) { h->err = "fw_collect_act_hl: value output missing"; return FW_EINVAL; }
+  if (a->prev_reward && (!(nets & 2) || !a->prev_terminated || !a->prev_truncated || !a->prev_terminal_obs || !a->ret_var || !a->rew_out || !a->start_out)) {
+    h->err = "fw_collect_act_hl: finalising the previous step needs the value network and all of its buffers"; return FW_EINVAL;
+  }
+  const int D = obs_dim_of(&h->cfg), f64 = h->cfg.dtype == FW_F64;
+  const size_t lds = hl_act_lds_bytes(D);
+  if (lds > 160 * 1024) { h->err = "fw_collect_act_hl: the two networks do not fit the 160 KB of LDS"; return FW_EINVAL; }
+  DeviceGuard g(h->device);
+  HlActArgs HA;
+  std::memset(&HA, 0, sizeof HA);
+  ActArgs& A = HA.A;
+  A.params = a->params; A.N = h->n; A.D = D; A.nets = nets; A.deterministic = a->deterministic; A.act_is_f64 = f64;
+  A.rng = a->rng; A.env_offset = a->env_offset; A.obs_copy = a->obs_copy; A.act_raw = a->act_raw; A.act_env = a->act_env; A.logp = a->logp; A.value = a->value;
+  A.raw = a->obs; A.raw_is_f64 = f64; A.mean = a->obs_mean; A.var = a->obs_var; A.clip = a->clip_obs; A.eps = a->eps_obs;
+  A.prev_reward = a->prev_reward; A.prev_term = a->prev_terminated; A.prev_trunc = a->prev_truncated; A.prev_tobs = a->prev_terminal_obs;
+  A.ret_var = a->ret_var; A.norm_reward = a->norm_reward; A.clip_reward = a->clip_reward; A.rew_eps = a->eps_reward; A.gamma = a->gamma;
+  A.rew_out = a->rew_out; A.start_out = a->start_out;
+  HA.low_params = a->low_params; HA.low_mean = a->low_mean; HA.low_var = a->low_var; HA.low_clip = a->low_clip; HA.low_eps = a->low_eps;
+  HA.low_obs = a->low_obs; HA.cmd_out = a->cmd_out; HA.rejected = a->rejected; HA.dome = h->cfg.flight_dome_size;
+  const void* fn = collect_act_hl_kernel(f64 != 0, h->lanes_per_env == 8 ? 8 : 1);
+  if (int rc = ensure_dynamic_lds(h, h->device, fn, lds)) return rc;
+  int rc = FW_OK;
+  with_dtype(h, [&](auto t) {
+    using T = decltype(t);
+    DevState<T> Dg = dev_state<T>(h);
+    void* args[] = { &Dg, &HA };
+    (void)hipLaunchKernel(fn, dim3((unsigned)((h->n + kPChunk - 1) / kPChunk), 2), dim3(kPThreads), args, lds, (hipStream_t)hip_stream);
+  });
+  HIP_TRY(h, hipGetLastError());
+  return rc;
 }
 
 int64_t fw_collect_step_workspace_bytes(fw_handle h) { return h ? (int64_t)collect_ws(h).total : FW_EINVAL; }

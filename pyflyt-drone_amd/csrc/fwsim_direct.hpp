@@ -351,17 +351,12 @@ __global__ __launch_bounds__(kWave) void fw_reset_kernel_wd(const Params<T>* __r
 // the reference's Box and conditioned in double, converted once to the handle's dtype and written, behind columns 0:18 of the env's
 // observation, into the low-level controller's raw observation row, into the FW_SL_TARGET tail and (optionally) cmd_out.  A row with
 // a non-finite component takes the command the tail already holds instead and is counted.
-template <typename T, int G, typename TA>
-__global__ __launch_bounds__(256) void fw_command_hl_kernel(DevState<T> Dg, const TA* __restrict__ action, const uint8_t* __restrict__ mask,
-                                                            const T* __restrict__ obs, int32_t obs_dim, T* __restrict__ low_obs,
-                                                            T* __restrict__ cmd_out, int32_t* __restrict__ rejected, double dome) {
-  constexpr int EPW = kWave / G;                     // envs per state tile of this lane mapping (fwsim_device.hpp: tile_index)
-  const int env = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  if (env >= Dg.n) return;
-  if (mask && mask[env] == 0) return;
-  const DevState<T> D = tile_view<T, EPW>(Dg, env / EPW);
-  const double a0 = (double)action[(size_t)env * 3], a1 = (double)action[(size_t)env * 3 + 1], a2 = (double)action[(size_t)env * 3 + 2];
-  T c[3];
+// The command of one env from its raw action (a0, a1, a2), for fw_command_hl_kernel and fw_collect_act_hl_kernel alike: c = the
+// conditioned triple in the handle's dtype, written to the env's FW_SL_TARGET tail -- or, for a non-finite action, the triple the
+// tail already holds, the row counted into `rejected`.  D: the env's state tile.
+template <typename T>
+__device__ __forceinline__ void hl_command(const DevState<T>& D, int env, double a0, double a1, double a2, double dome,
+                                           int32_t* __restrict__ rejected, T (&c)[3]) {
   if (::isfinite(a0) && ::isfinite(a1) && ::isfinite(a2)) {
     // np.clip(x, lo, hi) as numpy computes it for finite x (a -0.0 stays -0.0): the Box first, then :164-166
     auto clip = [](double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); };
@@ -374,6 +369,20 @@ __global__ __launch_bounds__(256) void fw_command_hl_kernel(DevState<T> Dg, cons
 #pragma unroll
     for (int k = 0; k < 3; ++k) c[k] = ll_target_slot<T>(D, env, k);
   }
+}
+
+template <typename T, int G, typename TA>
+__global__ __launch_bounds__(256) void fw_command_hl_kernel(DevState<T> Dg, const TA* __restrict__ action, const uint8_t* __restrict__ mask,
+                                                            const T* __restrict__ obs, int32_t obs_dim, T* __restrict__ low_obs,
+                                                            T* __restrict__ cmd_out, int32_t* __restrict__ rejected, double dome) {
+  constexpr int EPW = kWave / G;                     // envs per state tile of this lane mapping (fwsim_device.hpp: tile_index)
+  const int env = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (env >= Dg.n) return;
+  if (mask && mask[env] == 0) return;
+  const DevState<T> D = tile_view<T, EPW>(Dg, env / EPW);
+  const double a0 = (double)action[(size_t)env * 3], a1 = (double)action[(size_t)env * 3 + 1], a2 = (double)action[(size_t)env * 3 + 2];
+  T c[3];
+  hl_command<T>(D, env, a0, a1, a2, dome, rejected, c);
   const T* o = obs + (size_t)env * obs_dim;
   T* lo = low_obs + (size_t)env * fwsim_cmd::kLLObs;
 #pragma unroll

@@ -17,8 +17,9 @@
 // Flat parameter layout (floats), used for params / exp_avg / exp_avg_sq alike (rollout.py builds it):
 //   for net in (pi, vf):  W1[Dp][64]  b1[64]  W2[64][64]  b2[64]  Wo[64][KO]  bo[KO]     (KO = A / 1)
 //   then log_std[A].       W*[in][out] = torch Linear.weight^T;  Dp = D rounded up to even (zero row).
-// A, the width of the action, is 4 (the reference's tasks) or 6 (the low-level control task's direct actuator commands): a
-// compile-time parameter of the network body (NA), instantiated for both.  The four-action instantiation is the kernel of before.
+// A, the width of the action, is 4 (the reference's tasks), 6 (the low-level control task's direct actuator commands) or 3 (the
+// high-level command task's heading / altitude / airspeed): a compile-time parameter of the network body (NA), instantiated for
+// each.  The four-action instantiation is the kernel of before.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -334,6 +335,48 @@ __global__ __launch_bounds__(256) void fw_ppo_pack_kernel_a6(PpoPackArgs P) {
   }
 }
 
+// ... and for three-action rows (the high-level command task): the packed row keeps the four-action width, the fourth float of the
+// action is written as zero here (act is [S][3]: rows of 12 bytes, read as dwords) -- nothing of the caller's reaches it
+__global__ __launch_bounds__(256) void fw_ppo_pack_kernel_a3(PpoPackArgs P) {
+  __shared__ float st[2];
+  const int32_t* idx = P.perm + (size_t)blockIdx.x * P.B;
+  const int t = threadIdx.x, B = P.B, D = P.D;
+  if (t < 64) {                                      // (the arithmetic of round 3's statistics kernel: one wave, strided sums)
+    float mean = P.adv_mean, sd = P.adv_std;
+    if (P.norm_adv == 1) {
+      float s1 = 0.f;
+      for (int i = t; i < B; i += 64) s1 += P.adv[idx[i]];
+      mean = ppo_wave_sum(s1) / (float)B;
+      float s2 = 0.f;
+      for (int i = t; i < B; i += 64) { const float d = P.adv[idx[i]] - mean; s2 += d * d; }
+      sd = sqrtf(ppo_wave_sum(s2) / (float)(B > 1 ? B - 1 : 1));
+    }
+    if (t == 0) { st[0] = mean; st[1] = sd; }
+  }
+  __syncthreads();
+  const float mean = st[0], sd = st[1];
+  const int Dv4 = (D + 3) >> 2, W4 = Dv4 + 2;      // float4s per row: observation, then action, then scalars
+  float4* out = reinterpret_cast<float4*>(P.out) + (size_t)blockIdx.x * B * W4;
+  const bool vec = (D & 3) == 0;
+  for (int e = t; e < B * W4; e += 256) {
+    const int row = e / W4, q = e - row * W4, si = idx[row];
+    float4 v;
+    if (q < Dv4) {
+      const float* o = P.obs + (size_t)si * D + 4 * q;
+      if (vec) v = *reinterpret_cast<const float4*>(o);
+      else { const int left = D - 4 * q; v = make_float4(o[0], left > 1 ? o[1] : 0.f, left > 2 ? o[2] : 0.f, left > 3 ? o[3] : 0.f); }
+    } else if (q == Dv4) {
+      const float* a = P.act + (size_t)si * 3;
+      v = make_float4(a[0], a[1], a[2], 0.f);
+    } else {
+      float a = P.adv[si];
+      if (P.norm_adv != 0) a = (a - mean) / (sd + 1e-8f);
+      v = make_float4(P.old_logp[si], a, P.ret[si], 0.f);
+    }
+    out[e] = v;
+  }
+}
+
 // The two networks (pi / V) share nothing but the scalar gradient norm that SB3 clips jointly, exchanged once per minibatch
 // through 64-bit words (tag | partial sum of squares).  A minibatch is cut over 1, 2 or 4 workgroups per network (ppo_split),
 // block q running passes q, q + nsplit, ...; per minibatch they exchange gradients through global memory (release / acquire at
@@ -463,9 +506,13 @@ template <int N> __device__ __forceinline__ float ppo_tree_sum(const float (&v)[
 // NA: the width of the action (4, or 6: see the top of the file).  Six actions change the policy head only: the head / loss threads take
 // component hc and, where hc < 2, also component 4 + hc; Wo's thread elements gain a second word (moment slot row 9, exchange slot
 // kPGxWo2); gout / sA rows are 8 floats wide; the packed rows carry two action float4s.
+// Three actions (NA = 3) keep every width of the four-action form -- packed rows, gout / sA rows of four floats, the moment and exchange
+// slots -- and leave the fourth place idle: the head / loss lane hc = 3 of a quad contributes nothing (no log-prob term, no gradient),
+// column 3 of gout / sA is never read into a sum, and the elements uq = 3 of Wo's thread row do not exist (uq < KO).  Rows of Wo are 12
+// bytes: a head thread fetches its HPER rows as one run of 3 HPER floats (16-byte aligned: HPER is a multiple of 4).
 template <int NET, int CH, int NS, int NA>
 __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const int part, const int nsplit) {
-  static_assert(NA == 4 || NA == 6, "action width");
+  static_assert(NA == 3 || NA == 4 || NA == 6, "action width");
   static_assert(NS == 0 || NS == 4 || NS == 8, "blocks per network in the reduce-scatter form");
   constexpr bool RS = NS != 0;
   constexpr int NSd = RS ? NS : 4;                     // (array extents; the divisor where NS may be 0)
@@ -498,7 +545,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
   float* p = lds;
   PpoNetLds W;
   W.W1 = p; p += K1 * ldw1; W.b1 = p; p += kPH; W.W2 = p; p += kPH * kPLdh; W.b2 = p; p += kPH; W.Wo = p; p += kPH * KO; W.bo = p; p += KO;
-  float* log_std = p; p += NA;
+  float* log_std = p; p += NA == 3 ? 5 : NA;      // (three actions: two floats of padding keep what follows 16-byte aligned, as with four)
   float* X = p;  p += CH * ldx + 64;              // (+64: the padded dW1 tile reads a few floats past the last row)
   float* H1 = p; p += CH * kPLdh;
   float* H2 = p; p += CH * kPLdh > 2112 ? CH * kPLdh : 2112;      // (>= 2048 floats: dW1's split partials pass through it)
@@ -683,7 +730,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
     pf_stats += PPO_T() - pf0;
 #endif
     // (policy head: log_std and 1 / sigma^2 of the action component this lane takes -- they only change with the Adam step)
-    const float ls_c = NET == 0 ? log_std[(t % HSL) & 3] : 0.f;
+    const float ls_c = NET == 0 ? log_std[NA == 3 && ((t % HSL) & 3) == 3 ? 0 : (t % HSL) & 3] : 0.f;      // (three actions: lane hc = 3 takes no component)
     const float iv_c = NET == 0 ? expf(-2.0f * ls_c) : 0.f;
     const float ls_c2 = A6 ? log_std[A6 ? 4 + ((t % HSL) & 1) : 0] : 0.f;      // (six actions: component 4 + hc of the lanes with hc < 2)
     const float iv_c2 = A6 ? expf(-2.0f * ls_c2) : 0.f;
@@ -818,9 +865,19 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
             const float2 a = r2[0], b = r2[1];
             w4[j] = make_float4(a.x, a.y, b.x, b.y); w2[j] = r2[2];
           }
-          else w4[j] = make_float4(wo[j], 0.f, 0.f, 0.f);
+          else if (KO == 1) w4[j] = make_float4(wo[j], 0.f, 0.f, 0.f);
         }
-        const float bo_c = W.bo[KO >= 4 ? hc : 0];
+        if constexpr (KO == 3) {                                      // (rows of 12 bytes: the thread's 3 HPER floats as float4s)
+          float wf[3 * HPER];
+#pragma unroll
+          for (int j = 0; j < 3 * HPER / 4; ++j) {
+            const float4 a = reinterpret_cast<const float4*>(wo)[j];
+            wf[4 * j] = a.x; wf[4 * j + 1] = a.y; wf[4 * j + 2] = a.z; wf[4 * j + 3] = a.w;
+          }
+#pragma unroll
+          for (int j = 0; j < HPER; ++j) w4[j] = make_float4(wf[3 * j], wf[3 * j + 1], wf[3 * j + 2], 0.f);
+        }
+        const float bo_c = W.bo[KO >= 4 ? hc : KO == 3 && hc < 3 ? hc : 0];
         const float bo_c2 = A6 ? W.bo[A6 ? 4 + (hc & 1) : 0] : 0.f;
         float act_c = 0.f, act_c2 = 0.f, old_lp = 0.f, adv_s = 0.f, ret_s = 0.f;
         if (NET == 0) { act_c = sA[s * SA + hc]; const float2 sv = *reinterpret_cast<const float2*>(sS + s * 4); old_lp = sv.x; adv_s = sv.y; }
@@ -834,6 +891,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
           o[0] += hv[j] * w4[j].x;
           if (KO >= 4) { o[KO > 1 ? 1 : 0] += hv[j] * w4[j].y; o[KO > 2 ? 2 : 0] += hv[j] * w4[j].z; o[KO > 3 ? 3 : 0] += hv[j] * w4[j].w; }
           if (KO == 6) { o[KO > 4 ? 4 : 0] += hv[j] * w2[j].x; o[KO > 5 ? 5 : 0] += hv[j] * w2[j].y; }
+          if (KO == 3) { o[KO > 1 ? 1 : 0] += hv[j] * w4[j].y; o[KO > 2 ? 2 : 0] += hv[j] * w4[j].z; }
         }
 #pragma unroll
         for (int k = 0; k < KO; ++k) {
@@ -844,7 +902,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
         if (NET == 0) {
           // log pi(a|s), ratio, clipped surrogate (SB3 PPO.train): lane hc of the group's first quad takes action component hc
           // (32- / 16-sample forms: the other quads of a group compute along and contribute nothing)
-          const bool hl = hq < 4;
+          const bool hl = hq < NA && hq < 4;                 // (three actions: lane 3 of the first quad takes no component)
           const float mu = (hc == 0 ? o[0] : hc == 1 ? o[KO > 1 ? 1 : 0] : hc == 2 ? o[KO > 2 ? 2 : 0] : o[KO > 3 ? 3 : 0]) + bo_c;
           const float ls = ls_c, iv = iv_c;                   // log_std and 1 / sigma^2 of component hc: per minibatch (see the top of the loop)
           const float z = act_c - mu;
@@ -855,6 +913,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
             z2 = act_c2 - ((hc & 1 ? o[KO > 5 ? 5 : 0] : o[KO > 4 ? 4 : 0]) + bo_c2);
             if (hc < 2) logp += -0.5f * z2 * z2 * iv_c2 - ls_c2 - 0.9189385332046727f;
           }
+          if constexpr (NA == 3) logp = hc < 3 ? logp : 0.f;              // (the quad's sum below is over three components)
           logp += ppo_dpp<kDppXor1>(logp); logp += ppo_dpp<kDppXor2>(logp);
           const float a = adv_s;
           const float ratio = expf(logp - old_lp);
@@ -897,6 +956,9 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
           if (KO == 4) {
             const float4 g4 = reinterpret_cast<const float4*>(go)[j];
             gWoq[0] += h * g4.x; gWoq[KO > 1 ? 1 : 0] += h * g4.y; gWoq[KO > 2 ? 2 : 0] += h * g4.z; gWoq[KO > 3 ? 3 : 0] += h * g4.w;
+          } else if (KO == 3) {                                       // (column 3 of gout is never written: fetched with the row, not used)
+            const float4 g4 = reinterpret_cast<const float4*>(go)[j];
+            gWoq[0] += h * g4.x; gWoq[KO > 1 ? 1 : 0] += h * g4.y; gWoq[KO > 2 ? 2 : 0] += h * g4.z;
           } else if (KO == 6) {
             const float4 g4 = *reinterpret_cast<const float4*>(go + j * SA);
             const float2 g2 = *reinterpret_cast<const float2*>(go + j * SA + 4);
@@ -1065,6 +1127,13 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
       if (NET == 0) {
         my_gls = sred[4 + t] + sred[12 + t] + sred[20 + t] + sred[28 + t];
         if (part == 0) my_gls -= H.ent_coef;   // entropy bonus: entropy_loss = -mean(sum_k (c + log_std_k)) -> d/dlog_std_k = -ent_coef (once)
+      }
+    }
+    if (NA == 3 && t < 3) {                       // (the four-action sred layout, its fourth component idle)
+      if (t < KO) my_gbo = sred[t] + sred[8 + t] + sred[16 + t] + sred[24 + t];
+      if (NET == 0) {
+        my_gls = sred[4 + t] + sred[12 + t] + sred[20 + t] + sred[28 + t];
+        if (part == 0) my_gls -= H.ent_coef;   // entropy bonus, as above
       }
     }
     if (NA == 6 && t < 6) {                       // (component t of the six-action sred layout, see the carve-up)
@@ -1635,6 +1704,15 @@ __global__ __launch_bounds__(kPThreads) void fw_ppo_update_kernel(PpoArgs A) {
   const int part = i >> 1, nsplit = NS ? NS : (int)gridDim.x >> 4;
   if ((i & 1) == 0) ppo_net_body<0, CH, NS, 4>(A, lds, part, nsplit); else ppo_net_body<1, CH, NS, 4>(A, lds, part, nsplit);
 }
+// the same for a three-action policy head (the high-level command task): every cut, the same grid
+template <int CH, int NS>
+__global__ __launch_bounds__(kPThreads) void fw_ppo_update_kernel_a3(PpoArgs A) {
+  extern __shared__ __align__(16) float lds[];
+  if (blockIdx.x & 7) return;
+  const int i = (int)blockIdx.x >> 3;
+  const int part = i >> 1, nsplit = NS ? NS : (int)gridDim.x >> 4;
+  if ((i & 1) == 0) ppo_net_body<0, CH, NS, 3>(A, lds, part, nsplit); else ppo_net_body<1, CH, NS, 3>(A, lds, part, nsplit);
+}
 // the same for a six-action policy head (the low-level control task): every cut, the same grid
 template <int CH, int NS>
 __global__ __launch_bounds__(kPThreads) void fw_ppo_update_kernel_a6(PpoArgs A) {
@@ -1664,7 +1742,7 @@ inline PpoSplit ppo_split(int B, int max_blocks = kPMaxSplit) {
 inline size_t ppo_lds_bytes(int D, int NA = 4) {
   (void)D;                                          // (sized for the larger of the two forms: W1 as 64 rows of 65)
   const int ldx = kPLdx, SA = NA == 6 ? 8 : 4;
-  size_t f = (size_t)(kPH * kPLdh + kPH + kPH * kPLdh + kPH + kPH * NA + NA) + NA + (size_t)kPChunk * ldx + 64 + 2 * (size_t)kPChunk * kPLdh +
+  size_t f = (size_t)(kPH * kPLdh + kPH + kPH * kPLdh + kPH + kPH * NA + NA) + (NA == 3 ? 5 : NA) + (size_t)kPChunk * ldx + 64 + 2 * (size_t)kPChunk * kPLdh +
              (2 * (size_t)SA + 4) * kPChunk + 8 * kPH + 8 + 4 * (NA == 6 ? 16 : 8) + kPThreads + 2 * kPMaxSplit;
   return f * sizeof(float);
 }

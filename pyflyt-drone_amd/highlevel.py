@@ -9,7 +9,9 @@ env's stream, with no host synchronisation (capturable in a hipGraph):
     fw_collect_act_a  the controller: VecNormalize statistics (frozen), policy net, deterministic, clipped to [-1, 1]
     fw_step           the waypoints task under six direct actuator commands (FW_TASK_WAYPOINTS_DIRECT)
 
-``condition_command`` restates the first of them in numpy.
+``condition_command`` restates the first of them in numpy.  A collected vec-step of ``rollout.PPO`` under
+``PPOConfig.fused_three_actions`` replaces the first two -- and the policy's own forward and sampling in front of them -- by one
+launch, ``fw_collect_act_hl`` (``collect_act_hl``), and steps the base env with ``step_low``.
 """
 from __future__ import annotations
 
@@ -193,6 +195,26 @@ class HighLevelCmdVecEnv(FusedVecEnv):
                                       int(self.global_env_offset), None, _devptr(self._act_raw), _devptr(self.low_action), f64,
                                       _devptr(self._logp), None, None, None, None, None, None, 0, 0.0, 0.0, 0.0, None, None, st))
         return b.step_tensor(self.low_action)
+
+    # ------------------------------------------------------------------ the fused collector (rollout.PPO, fused_three_actions)
+    def collect_act_hl(self, a: "K.FwCollectHlArgs") -> None:
+        """The act side of a collected vec-step in one launch (``fw_collect_act_hl``) on the current stream.  The caller fills the
+        commander's half of ``a`` -- its flat image, the statistics of its observation, ``nets`` / ``deterministic`` / ``rng``, the
+        rollout rows, the previous-step block; the env adds its own: the raw observation buffer, the controller's image and frozen
+        statistics, ``low_obs`` / ``command`` / ``low_action`` / ``rejected``.  ``step_low`` then steps the base env with
+        ``low_action``.  ``nets == 2`` (the end of a rollout) runs the value block only and leaves the env's tensors alone."""
+        b = self.base
+        a.obs, a.env_offset = b.obs.data_ptr(), int(self.global_env_offset)
+        a.low_params, a.low_mean, a.low_var = self._flat.data_ptr(), self.low_mean.data_ptr(), self.low_var.data_ptr()
+        a.low_clip, a.low_eps = self.clip_obs, self.epsilon
+        a.low_obs, a.cmd_out, a.act_env = self.low_obs.data_ptr(), self.command.data_ptr(), self.low_action.data_ptr()
+        a.rejected = self.rejected.data_ptr()
+        _lib.check(_lib.lib().fw_collect_act_hl(b._h, C.byref(a), b._stream()), b._h)
+
+    def step_low(self):
+        """``fw_step`` of the base env with ``low_action`` as it stands (the controller's output of ``collect_act_hl``): the second
+        half of a vec-step whose act side has already run.  Returns the base env's ``(obs, rewards, terminated, truncated)``."""
+        return self.base.step_tensor(self.low_action)
 
     # ------------------------------------------------------------------ SB3 VecEnv surface (numpy)
     def reset(self) -> np.ndarray:

@@ -568,6 +568,8 @@ class PPOConfig:
     cnn_graphs: bool = True                #        replay the CNN rollout / minibatch step as hipGraphs (single process): update 2.4 -> 1.0 ms per 1024-sample minibatch
     fused_six_actions: bool = False        # six-action policies (the low-level control task) on the fused learner too: fw_ppo_update_a and the
                                            # three-launch collector (fw_collect_act_a -> fw_step -> fw_collect_stats); off: the torch path
+    fused_three_actions: bool = False      # the three-action policy of the high-level command task on the fused paths too: fw_ppo_update_a3 and
+                                           # the collector fw_collect_act_hl -> fw_step -> fw_collect_stats (single process); off: the torch path
     dist_update: str = "replicated"        # multi-process job: "replicated" = all-gather the rollout shards, every rank runs the same
                                            # minibatch sequence (no per-minibatch collective); "allreduce" = local minibatches + gradient all-reduce
 
@@ -585,17 +587,27 @@ class FusedPpoUpdate:
     def __init__(self, policy: "MlpPolicy", optimizer: torch.optim.Adam, obs_dim: int):
         self.policy, self.opt, self.D = policy, optimizer, obs_dim
         self.Dp = (obs_dim + 1) & ~1
-        self.A = int(policy.action_net.out_features)      # action width: 4, or 6 (the *_a entry points; 4 runs what the plain ones run)
+        self.A = int(policy.action_net.out_features)      # action width: 4, or 6 (the *_a entry points; 4 runs what the plain ones run), or 3
         dev = policy.log_std.device
         L = _lib.lib()
-        n = L.fw_ppo_param_count_a(obs_dim, self.A)
+        # the entry points of this width: the *_a family takes the width behind obs_dim, the three-action family (*_a3) has it fixed
+        if self.A == 3:
+            self._abi = dict(count=L.fw_ppo_param_count_a3, moments=L.fw_ppo_moment_count_a3, moment_map=L.fw_ppo_moment_map_a3,
+                             workspace=L.fw_ppo_update_workspace_bytes_a3, update=L.fw_ppo_update_a3)
+        else:
+            A = self.A
+            self._abi = dict(count=lambda d: L.fw_ppo_param_count_a(d, A), moments=lambda: L.fw_ppo_moment_count_a(A),
+                             moment_map=lambda d, m: L.fw_ppo_moment_map_a(d, A, m),
+                             workspace=lambda n_mb, bs, d: L.fw_ppo_update_workspace_bytes_a(n_mb, bs, d, A),
+                             update=lambda *a: L.fw_ppo_update_a(*a[:12], A, *a[12:]))
+        n = self._abi["count"](obs_dim)
         if n < 0:
             _lib.check(n)
         self.flat = torch.zeros(n, dtype=torch.float32, device=dev)
         self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)          # flat order (staging)
-        ns = L.fw_ppo_moment_count_a(self.A)
+        ns = self._abi["moments"]()
         smap = np.empty(ns, dtype=np.int32)
-        _lib.check(L.fw_ppo_moment_map_a(obs_dim, self.A, smap.ctypes.data_as(C.c_void_p)))
+        _lib.check(self._abi["moment_map"](obs_dim, smap.ctypes.data_as(C.c_void_p)))
         owned = np.nonzero(smap >= 0)[0]
         self._slot = torch.as_tensor(owned, dtype=torch.long, device=dev)                  # owned slots ...
         self._flat_of_slot = torch.as_tensor(smap[owned], dtype=torch.long, device=dev)    # ... and their flat indices
@@ -611,7 +623,7 @@ class FusedPpoUpdate:
 
     def _workspace(self, n_mb: int, batch_size: int) -> torch.Tensor:
         # exchange words + gradient hand-off buffer + the packed rows of every minibatch (a parallel pre-pass of the call writes them)
-        need = int(_lib.lib().fw_ppo_update_workspace_bytes_a(n_mb, batch_size, self.D, self.A))
+        need = int(self._abi["workspace"](n_mb, batch_size, self.D))
         if self._ws is None or self._ws.numel() < need:
             self._ws = torch.zeros(need, dtype=torch.uint8, device=self.flat.device)
         return self._ws
@@ -620,7 +632,7 @@ class FusedPpoUpdate:
     def fits(policy, obs_dim: int, device, act_dims=(4,)) -> bool:
         """The kernels are written for the reference's MlpPolicy: two 64-64 tanh nets, 4 actions, obs_dim <= 64 (any number
         of ranks: a sharded job runs them unchanged on every GPU).  ``act_dims=(4, 6)`` also admits the six-action head of the
-        low-level control task (PPOConfig.fused_six_actions)."""
+        low-level control task (PPOConfig.fused_six_actions), ``3`` the high-level command task's (PPOConfig.fused_three_actions)."""
         if getattr(policy, "uses_image", False) or not hasattr(policy, "pi_net"):
             return False                   # CNN front end: torch path (the fused kernels are the MlpPolicy's)
         lin = [m for m in list(policy.pi_net) + list(policy.vf_net) if isinstance(m, nn.Linear)]
@@ -629,8 +641,10 @@ class FusedPpoUpdate:
 
     @staticmethod
     def act_dims(cfg) -> tuple:
-        """The action widths the fused kernels take under ``cfg``: 4, and 6 when PPOConfig.fused_six_actions is on."""
-        return (4, 6) if getattr(cfg, "fused_six_actions", False) else (4,)
+        """The action widths the fused kernels take under ``cfg``: 4, 6 when PPOConfig.fused_six_actions is on, 3 when
+        PPOConfig.fused_three_actions is."""
+        return ((4,) + ((6,) if getattr(cfg, "fused_six_actions", False) else ())
+                + ((3,) if getattr(cfg, "fused_three_actions", False) else ()))
 
     @staticmethod
     def applies(policy, cfg, obs_dim: int, batch_size: int, device) -> bool:
@@ -739,9 +753,9 @@ class FusedPpoUpdate:
             assert x.dtype == torch.float32 and x.is_contiguous()
         assert perm_i32.dtype == torch.int32 and perm_i32.numel() == n_mb * cfg.batch_size
         ws = self._workspace(n_mb, cfg.batch_size)
-        rc = _lib.lib().fw_ppo_update_a(_p(self.flat), _p(self.mom_m), _p(self.mom_v), _p(obs), _p(act), _p(old_logp), _p(adv), _p(ret),
-                                        _p(perm_i32), n_mb, cfg.batch_size, self.D, self.A, C.byref(H), _p(self.loss), _p(ws), ws.numel(),
-                                        _stream(obs.device))
+        rc = self._abi["update"](_p(self.flat), _p(self.mom_m), _p(self.mom_v), _p(obs), _p(act), _p(old_logp), _p(adv), _p(ret),
+                                 _p(perm_i32), n_mb, cfg.batch_size, self.D, C.byref(H), _p(self.loss), _p(ws), ws.numel(),
+                                 _stream(obs.device))
         _lib.check(rc)
         # the workgroups of the launch wait for each other, every wait bounded: a wait that ran out leaves a status word behind and
         # (unless the closing verdict itself was lost) untouched images -- surface it BEFORE anything is written back to the module /
@@ -778,6 +792,9 @@ class PPO:
         if policy is None and cfg.detector == "cnn":
             policy = CnnDetectorPolicy(env.obs_dim, image_res=cfg.image_res, cnn_features=cfg.cnn_features)
         self.act_dim = int(getattr(env, "act_dim", 4))      # the env's action width (6 actuator commands on the low-level task)
+        if getattr(cfg, "fused_three_actions", False) and self.act_dim == 3 and _dist() is not None:
+            raise ValueError("PPOConfig.fused_three_actions serves single-process jobs: a sharded job trains the three-action policy with "
+                             "fused_three_actions=False (the torch path)")
         self.policy = (policy or MlpPolicy(env.obs_dim, self.act_dim)).to(self.device)
         self._img = bool(getattr(self.policy, "uses_image", False))
         if self._img and not hasattr(env.venv, "render_tensor"):
@@ -793,7 +810,9 @@ class PPO:
         self._replicated = td is not None and cfg.dist_update == "replicated" and not self._img
         self._fused_collect_ok = (bool(cfg.fused_collect) and FusedPpoUpdate.fits(self.policy, env.obs_dim, self.device, FusedPpoUpdate.act_dims(cfg))
                                   and getattr(env, "use_fused", False) and env.norm_obs and hasattr(env.venv, "step_tensor")
-                                  and hasattr(env.venv, "terminal_obs") and hasattr(env.venv, "torch_dtype"))
+                                  and hasattr(env.venv, "terminal_obs") and hasattr(env.venv, "torch_dtype")
+                                  # (three actions: the collector is the high-level command env's own launch, fw_collect_act_hl)
+                                  and (self.act_dim != 3 or hasattr(env.venv, "collect_act_hl")))
         # hipGraph replay needs a collective-free body: always on one GPU; in a sharded job when the collector is fused
         # (its statistics are exchanged BETWEEN rollouts) and the update is replicated (no gradient all-reduce)
         # (CNN front end: its convolutions are captured like everything else when PPOConfig.cnn_graphs is on -- MIOpen picks its
@@ -817,7 +836,7 @@ class PPO:
         # (fw_collect_step's act waves take observations of up to 62 features -- wider ones go through fw_collect_act, which takes 64)
         # (four actions only: fw_collect_step / fw_collect_close have no six-action form -- a six-action policy takes the three launches)
         self._one_launch = (self._collect_fused and bool(cfg.one_launch_collect) and hasattr(env.venv, "_h") and env.obs_dim <= 62
-                            and self.act_dim == 4
+                            and self.act_dim == 4          # (so _one_launch and _close_gae stay off for six and for three actions)
                             and getattr(env.venv, "lanes_per_env", 0) == 8 and float(env.gamma) == float(cfg.gamma))
         self._void_recoverable = False
         self.collect_fallbacks = 0         # how many times a void rollout moved this object to the three-launch collector (0 or 1)
@@ -906,6 +925,8 @@ class PPO:
         action -- and its value block first finalises step t-1 for its rows (normalised + bootstrapped reward, episode starts),
         while the env's output buffers still hold that step.  fw_collect_stats folds the step's observations and rewards into
         both normalisers.  Same data flow as _rollout_body; SB3 OnPolicyAlgorithm.collect_rollouts + VecNormalize semantics."""
+        if self.act_dim == 3:
+            return self._rollout_body_fused_hl()
         cfg, env, L = self.cfg, self.env, _lib.lib()
         venv, T, N, D = env.venv, cfg.n_steps, env.num_envs, env.obs_dim
         st = _stream(self.device)
@@ -993,6 +1014,48 @@ class PPO:
                                     _p(venv.rewards), _p(venv.terminated), _p(venv.truncated), _p(venv.terminal_obs), _p(env.ret_rms.var),
                                     int(env.norm_reward), float(env.clip_reward), float(env.epsilon), float(cfg.gamma),
                                     _p(self.buf_rew[T - 1]), _p(self.last_starts), st))
+        _lib.check(L.fw_normalize_obs(_p(venv.obs), f64, N, D, _p(env.obs_rms.mean), _p(env.obs_rms.var), _p(env.obs_rms.count), 0,
+                                      float(env.clip_obs), float(env.epsilon), _p(self.last_obs), None, None, st))
+
+    def _rollout_body_fused_hl(self):
+        """collect_rollouts of the high-level command task (three actions; PPOConfig.fused_three_actions) as three launches per
+        vec-step:  fw_collect_act_hl -> fw_step -> fw_collect_stats.  The first is fw_collect_act for the commander, fw_command_hl
+        and the frozen controller's forward in one (HighLevelCmdVecEnv.collect_act_hl); the data flow is _rollout_body_fused's."""
+        from . import config as K
+        cfg, env, L = self.cfg, self.env, _lib.lib()
+        venv, T, N, D = env.venv, cfg.n_steps, env.num_envs, env.obs_dim
+        st = _stream(self.device)
+        f64 = int(venv.obs.dtype == torch.float64)
+        self.buf_start[0].copy_(self.last_starts)
+        track = int(env.training and env.norm_reward)
+
+        def act(t, nets, value_out, prev_t):
+            a = K.FwCollectHlArgs()
+            a.params, a.rng, a.nets, a.deterministic = self._fused.flat.data_ptr(), self._rng.data_ptr(), nets, 0
+            a.obs_mean, a.obs_var = env.obs_rms.mean.data_ptr(), env.obs_rms.var.data_ptr()
+            a.clip_obs, a.eps_obs = float(env.clip_obs), float(env.epsilon)
+            if t is not None:
+                a.obs_copy, a.act_raw, a.logp = self.buf_obs[t].data_ptr(), self.buf_act[t].data_ptr(), self.buf_logp[t].data_ptr()
+            a.value = value_out.data_ptr()
+            if prev_t is not None:               # finalise step prev_t while its outputs are still in the env's buffers
+                nxt = self.buf_start[prev_t + 1] if prev_t + 1 < T else self.last_starts
+                a.prev_reward, a.prev_terminated, a.prev_truncated = venv.rewards.data_ptr(), venv.terminated.data_ptr(), venv.truncated.data_ptr()
+                a.prev_terminal_obs, a.ret_var = venv.terminal_obs.data_ptr(), env.ret_rms.var.data_ptr()
+                a.norm_reward, a.clip_reward, a.eps_reward, a.gamma = int(env.norm_reward), float(env.clip_reward), float(env.epsilon), float(cfg.gamma)
+                a.rew_out, a.start_out = self.buf_rew[prev_t].data_ptr(), nxt.data_ptr()
+            venv.collect_act_hl(a)
+
+        for t in range(T):
+            act(t, 3, self.buf_val[t], t - 1 if t > 0 else None)
+            venv.step_low()
+            _lib.check(L.fw_collect_stats(_p(venv.obs), f64, N, D, _p(env.obs_rms.mean), _p(env.obs_rms.var), _p(env.obs_rms.count),
+                                          int(env.training and env.norm_obs), _p(venv.rewards), int(venv.rewards.dtype == torch.float64),
+                                          _p(venv.terminated), _p(venv.truncated), _p(env.returns), _p(env.ret_rms.mean),
+                                          _p(env.ret_rms.var), _p(env.ret_rms.count), track, float(env.gamma), _p(self._rng),
+                                          _p(env._ws_stats), _p(env._obs_acc) if env.training and env.norm_obs else None,
+                                          _p(env._ret_acc) if track else None, st))
+        # V(last observation) for GAE + the finalisation of step T - 1; the normalised last observation for callers that look at it
+        act(None, 2, self.last_values, T - 1)
         _lib.check(L.fw_normalize_obs(_p(venv.obs), f64, N, D, _p(env.obs_rms.mean), _p(env.obs_rms.var), _p(env.obs_rms.count), 0,
                                       float(env.clip_obs), float(env.epsilon), _p(self.last_obs), None, None, st))
 

@@ -1,6 +1,6 @@
 """Wall time per vec-step of the high-level command task on one GPU.
 
-    python tools/bench_highlevel.py [--legs step highlevel host] [--envs 16 4096] [--steps 2000] [--warmup 100] [--repeats 5]
+    python tools/bench_highlevel.py [--legs step highlevel host act collect update e2e] [--envs 16 4096] [--steps 2000] [--warmup 100] [--repeats 5]
                                     [--out profiles/r10_highlevel_bench.jsonl]
 
 Legs (one JSON line per leg, size and launch mode):
@@ -11,6 +11,15 @@ Legs (one JSON line per leg, size and launch mode):
              the controller is a seeded MlpPolicy(21, 6) with random weights.
   host       the same vec-step composed on the host as tests/test_highlevel_gpu.py composes it: numpy conditioning and normalisation,
              the torch forward of the controller, fw_step of the base env (observation download and action upload every step).
+  act        the act side of a collected vec-step at --envs envs, graph-replayed: fw_collect_act_hl (one launch) beside the three launches
+             it replaces, each alone and as a chain -- fw_collect_act_a (a four-action commander at the same 30 observations stands in
+             for the three-action one, which has no launch of its own), fw_command_hl, fw_collect_act_a (the six-action controller).
+  collect    a collected vec-step of rollout.PPO on the high-level env (PPOConfig.fused_three_actions on: fw_collect_act_hl -> fw_step ->
+             fw_collect_stats; off: the torch path), n_steps 1024, rollouts replayed as hipGraphs: wall time per vec-step.
+  update     one minibatch of the learner at 30 observations, batch 256 (the reference's) and 64: fw_ppo_update_a3 beside
+             fw_ppo_update_a's six- and four-action forms (device time from events, tools/bench_wide_learner.py) and the torch path.
+  e2e        env-steps/s of examples/train_highlevel_cmd.py's configuration (16 envs, n_steps 1024, batch 256, 10 epochs) over
+             --updates updates after a warm-up update, fused beside torch.
 Modes: "graph" replays a captured hipGraph of 64 vec-steps, "eager" launches them one by one.  A timed region is --steps vec-steps
 between two device synchronisations; --repeats regions, the median is reported with the spread.  Under `rocprofv3 --kernel-trace
 --stats` the per-kernel averages of the three launches come out by name (fw_command_hl_kernel, fw_policy_act_kernel, fw_step_kernel_wd).
@@ -28,7 +37,10 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", nargs="+", default=["step", "highlevel", "host"], choices=["step", "highlevel", "host"])
+    ap.add_argument("--legs", nargs="+", default=["step", "highlevel", "host"],
+                    choices=["step", "highlevel", "host", "act", "collect", "update", "e2e"])
+    ap.add_argument("--updates", type=int, default=2)
+    ap.add_argument("--n-steps", type=int, default=1024)
     ap.add_argument("--envs", type=int, nargs="+", default=[16, 4096])
     ap.add_argument("--step-envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=2000)
@@ -133,6 +145,162 @@ def main():
             r = timed(Host(), a.host_steps)
             emit({"leg": "host_composition", "envs": n, "mode": "eager", **r, "env_steps_per_s": round(n / r["us_per_vec_step"] * 1e6)})
             B.close()
+
+    def graph_us(fn, per=64):
+        """us per call of fn() replayed from a hipGraph of `per` calls (median of --repeats regions of --steps calls)"""
+        side = torch.cuda.Stream(); side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            fn()
+        torch.cuda.current_stream().wait_stream(side); torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=side):
+            for _ in range(per):
+                fn()
+
+        class Rep:
+            def run(self, k):
+                for _ in range(max(k // per, 1)):
+                    g.replay()
+        return timed(Rep(), max(a.steps // per, 1) * per)      # (whole replays: the calls timed are the calls counted)
+
+    def hl_ppo(n, fused, n_steps):
+        pol, mean, var = controller()
+        venv = HighLevelCmdVecEnv(n, pol, (mean, var), seed=42)
+        env = R.VecNormalizeDevice(venv, norm_obs=True, norm_reward=True, clip_obs=10.0, gamma=0.995)
+        return R.PPO(env, R.PPOConfig(n_steps=n_steps, batch_size=256, n_epochs=10, learning_rate=3e-4, gamma=0.995, gae_lambda=0.95,
+                                      clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, seed=123, fused_three_actions=fused))
+
+    if "act" in a.legs:
+        import ctypes as C
+        from pyflyt_drone_amd import _lib
+        L = _lib.lib()
+        for n in a.envs:
+            pol, mean, var = controller()
+            env = HighLevelCmdVecEnv(n, pol, (mean, var), seed=42)
+            env.reset_tensor()
+            b = env.base
+            f64 = int(env.torch_dtype == torch.float64)
+            torch.manual_seed(3)
+            flats = {}
+            for A in (3, 4):
+                f = R.FusedPpoUpdate(R.MlpPolicy(30, A).cuda(), None, 30); f.load_params_from_torch(); flats[A] = f.flat
+            om, ov = torch.zeros(30, dtype=torch.float64, device="cuda"), torch.ones(30, dtype=torch.float64, device="cuda")
+            rng = torch.tensor([5, 0], dtype=torch.int64, device="cuda")
+            f32 = dict(dtype=torch.float32, device="cuda")
+            oc, lp, val = torch.zeros((n, 30), **f32), torch.zeros(n, **f32), torch.zeros(n, **f32)
+            ar = {A: torch.zeros((n, A), **f32) for A in (3, 4, 6)}
+            ae4 = torch.zeros((n, 4), dtype=env.torch_dtype, device="cuda")
+            st = lambda: b._stream()
+
+            def fused():
+                h = K.FwCollectHlArgs()
+                h.params, h.rng, h.nets = flats[3].data_ptr(), rng.data_ptr(), 3
+                h.obs_mean, h.obs_var, h.clip_obs, h.eps_obs = om.data_ptr(), ov.data_ptr(), 10.0, 1e-8
+                h.obs_copy, h.act_raw, h.logp, h.value = oc.data_ptr(), ar[3].data_ptr(), lp.data_ptr(), val.data_ptr()
+                env.collect_act_hl(h)
+
+            def commander():
+                _lib.check(L.fw_collect_act_a(R._p(flats[4]), R._p(b.obs), f64, n, 30, 4, R._p(om), R._p(ov), 10.0, 1e-8, 3, 0, R._p(rng), 0,
+                                              R._p(oc), R._p(ar[4]), R._p(ae4), f64, R._p(lp), R._p(val), None, None, None, None, None, 0,
+                                              0.0, 0.0, 0.0, None, None, st()))
+
+            def command():
+                _lib.check(L.fw_command_hl(b._h, R._p(ar[3]), 0, None, R._p(b.obs), R._p(env.low_obs), R._p(env.command), R._p(env.rejected),
+                                           st()), b._h)
+
+            def ctrl():
+                _lib.check(L.fw_collect_act_a(R._p(env._flat), R._p(env.low_obs), f64, n, 21, 6, R._p(env.low_mean), R._p(env.low_var),
+                                              env.clip_obs, env.epsilon, 1, 1, None, 0, None, R._p(ar[6]), R._p(env.low_action), f64, R._p(lp),
+                                              None, None, None, None, None, None, 0, 0.0, 0.0, 0.0, None, None, st()))
+
+            def chain():
+                commander(); command(); ctrl()
+            for name, fn in (("fw_collect_act_hl", fused), ("three_launch_chain", chain), ("fw_collect_act_a_commander4", commander),
+                             ("fw_command_hl", command), ("fw_collect_act_a_controller6", ctrl)):
+                r = graph_us(fn)
+                r["us_per_call"] = r.pop("us_per_vec_step")
+                emit({"leg": "act", "what": name, "envs": n, "mode": "graph", **r})
+            env.close()
+
+    if "collect" in a.legs:
+        for n in a.envs:
+            for fused in (True, False):
+                ppo = hl_ppo(n, fused, a.n_steps)
+                for _ in range(2):                       # eager, then the capture
+                    ppo.collect_rollouts()
+                torch.cuda.synchronize()
+                us = []
+                for _ in range(a.repeats):
+                    t0 = time.perf_counter(); ppo.collect_rollouts(); torch.cuda.synchronize()
+                    us.append((time.perf_counter() - t0) / a.n_steps * 1e6)
+                emit({"leg": "collect", "path": "fused_three_actions" if fused else "torch", "collect_fused": ppo._collect_fused, "envs": n,
+                      "n_steps": a.n_steps, "graph": ppo._g_rollout is not None, "us_per_vec_step": round(float(np.median(us)), 2),
+                      "us_min": round(min(us), 2), "us_max": round(max(us), 2), "repeats": a.repeats})
+                ppo.env.venv.close()
+
+    if "update" in a.legs:
+        import ctypes as C
+        from pyflyt_drone_amd import _lib
+        import bench_wide_learner as W
+        L = _lib.lib()
+
+        def a3_us(B, n_mb, reps):
+            g = torch.Generator(device="cuda"); g.manual_seed(1)
+            S, D = n_mb * B, 30
+            flat0 = torch.randn(L.fw_ppo_param_count_a3(D), device="cuda", generator=g) * 0.1
+            ns = L.fw_ppo_moment_count_a3()
+            obs, act = torch.randn((S, D), device="cuda", generator=g), torch.randn((S, 3), device="cuda", generator=g)
+            lp, adv, ret = (torch.randn(S, device="cuda", generator=g) for _ in range(3))
+            perm = torch.randperm(S, device="cuda", generator=g).to(torch.int32)
+            ws = torch.zeros(int(L.fw_ppo_update_workspace_bytes_a3(n_mb, B, D)), dtype=torch.uint8, device="cuda")
+            loss = torch.zeros(16, device="cuda")
+            H = R._PpoHyper(lr=3e-4, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, beta1=0.9, beta2=0.999, eps=1e-5,
+                            adv_mean=0.0, adv_std=1.0, norm_adv=1, step0=0)
+            times = []
+            for r in range(reps + 1):
+                flat, m, v = flat0.clone(), torch.zeros(ns, device="cuda"), torch.zeros(ns, device="cuda")
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                _lib.check(L.fw_ppo_update_a3(*[R._p(x) for x in (flat, m, v, obs, act, lp, adv, ret, perm)], n_mb, B, D, C.byref(H), R._p(loss),
+                                              R._p(ws), ws.numel(), None))
+                e1.record(); torch.cuda.synchronize()
+                stw = C.c_uint32(0)
+                _lib.check(L.fw_ppo_update_status(R._p(ws), ws.numel(), C.byref(stw), None, None))
+                assert stw.value == 0, stw.value
+                if r:
+                    times.append(e0.elapsed_time(e1) * 1e3 / n_mb)
+            times.sort()
+            return times[len(times) // 2], times
+        for B in (256, 64):
+            n_mb = 640
+            for _ in range(2):                           # alternating: the two forms in the same session, twice
+                med, all_ = a3_us(B, n_mb, a.repeats)
+                emit({"leg": "update", "path": "fw_ppo_update_a3", "act_dim": 3, "obs_dim": 30, "batch": B, "n_mb": n_mb,
+                      "us_per_minibatch": round(med, 3), "all_us": [round(x, 3) for x in all_]})
+                for A in (6, 4):
+                    med, all_ = W.fused_update_us(30, A, B, n_mb, a.repeats)
+                    emit({"leg": "update", "path": "fw_ppo_update_a", "act_dim": A, "obs_dim": 30, "batch": B, "n_mb": n_mb,
+                          "us_per_minibatch": round(med, 3), "all_us": [round(x, 3) for x in all_]})
+            emit({"leg": "update", "path": "torch (autograd + Adam, hipGraph per minibatch)", "act_dim": 3, "obs_dim": 30, "batch": B, "n_mb": 64,
+                  "us_per_minibatch": round(W.torch_update_us(30, 3, B, 64), 3)})
+
+    if "e2e" in a.legs:
+        for fused in (True, False):
+            ppo = hl_ppo(16, fused, a.n_steps)
+            ppo.collect_rollouts(); ppo.train()          # warm-up update (allocations, graph captures)
+            ppo.collect_rollouts(); ppo.train()
+            torch.cuda.synchronize()
+            t_roll = t_upd = 0.0
+            for _ in range(a.updates):
+                t0 = time.perf_counter(); ppo.collect_rollouts(); torch.cuda.synchronize()
+                t1 = time.perf_counter(); ppo.train(); torch.cuda.synchronize()
+                t_roll += t1 - t0; t_upd += time.perf_counter() - t1
+            steps = a.updates * a.n_steps * 16
+            assert all(torch.isfinite(q).all() for q in ppo.policy.parameters())
+            emit({"leg": "e2e", "path": "fused_three_actions" if fused else "torch", "envs": 16, "n_steps": a.n_steps, "updates": a.updates,
+                  "env_steps_per_s": round(steps / (t_roll + t_upd)), "rollout_s_per_update": round(t_roll / a.updates, 4),
+                  "update_s_per_update": round(t_upd / a.updates, 4), "minibatches_per_update": 10 * a.n_steps * 16 // 256})
+            ppo.env.venv.close()
 
     if a.out:
         with open(a.out, "a") as f:

@@ -17,7 +17,8 @@ restore of that block.
 
 compares the device assembly of two builds function by function (a change that means to leave the device code alone, e.g. one
 of the host half of fwsim.hip): the same function names, the same text for each -- its .amdhsa_kernel block included -- up to the
-order of the functions and the function ordinal in local labels, which follow the order of instantiation.  Exits 1 on a difference.
+order of the functions, the function ordinal in local labels, which follows the order of instantiation, and the compiler's names of IR
+blocks in comments (`; %Flow3908`), which are numbered through the module.  Exits 1 on a difference.
 """
 import re
 import sys
@@ -100,7 +101,10 @@ def functions(text):
     out = {}
     for m in re.finditer(r"; -- Begin function (\S+)\n(.*?); -- End function", text, re.S):
         # (the comment behind a label starts at a fixed column: the padding in front of it changes with the ordinal's width)
-        body = re.sub(r"^(\.LBB\d+_\d+:)[ \t]+;", r"\1 ;", m.group(2), flags=re.M)
+        # (the compiler's names of IR blocks, `; %Flow3908` behind a label or a `; %bb.4:` line, are numbered through the whole
+        # module: a template instantiated beside a function renumbers them without touching its code)
+        body = re.sub(r"[ \t]*; %[^\n]*$", "", m.group(2), flags=re.M)
+        body = re.sub(r"^(\.LBB\d+_\d+:)[ \t]+;", r"\1 ;", body, flags=re.M)
         out[m.group(1)] = re.sub(r"(\.LBB|\.LJTI|\.Lfunc_begin|\.Lfunc_end|\bBB)\d+", r"\1#", body)      # (BB12_37: the same labels in comments)
     return out
 
