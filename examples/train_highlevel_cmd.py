@@ -6,7 +6,8 @@ underneath (dome 200 m, 120 s, 30 Hz, euler, context 2).  Same PPO hyper-paramet
 1024, batch 256, 10 epochs, gamma 0.995, lambda 0.95, clip 0.2, no entropy bonus, seed 123).  The three-action policy trains on the
 torch path by default (the env's vec-step is then three launches, fw_command_hl -> fw_collect_act_a -> fw_step); --fused_learner puts it
 on the fused three-action learner (fw_ppo_update_a3) and collector (fw_collect_act_hl -> fw_step -> fw_collect_stats;
-PPOConfig.fused_three_actions).  The actions are the reference's: a raw Gaussian clipped to the Box in physical units.
+PPOConfig.fused_three_actions); --fused_eval puts the evaluations on the fused three-action path as well (fw_collect_act_hl -> fw_step ->
+fw_eval_track_hl; off by default).  The evaluations record the command figures of evaluate.EvalResult.command_scalars.  The actions are the reference's: a raw Gaussian clipped to the Box in physical units.
 
     python examples/train_lowlevel_cmd.py --total_timesteps 2000000 --out runs/lowlevel_ppo
     python examples/train_highlevel_cmd.py --low_checkpoint runs/lowlevel_ppo/models/final_model.pt --total_timesteps 2000000
@@ -35,6 +36,7 @@ def main():
     ap.add_argument("--n_steps", type=int, default=None, help="default: the reference's 16 x 1024 samples per update, split over --num_envs")
     ap.add_argument("--out", type=str, default="runs/highlevel_ppo")
     ap.add_argument("--fused_learner", action="store_true", help="the fused three-action update / collector kernels instead of the torch path")
+    ap.add_argument("--fused_eval", action="store_true", help="the evaluations through the fused three-action kernels (use_fused=True) instead of the torch forward")
     a = ap.parse_args()
     cfg = TRAIN_CFG
     num_envs = a.num_envs if a.num_envs is not None else cfg["num_envs"]
@@ -55,7 +57,8 @@ def main():
                                    fused_three_actions=a.fused_learner))
     per_update = n_steps * num_envs
     ev = evaluate.EvalCallback(eval_env, n_eval_episodes=16, eval_freq=max(10 * per_update // num_envs, 1), log_path=log_dir,
-                               best_model_save_path=model_dir, num_targets_total=int(venv.cfg.num_targets), verbose=1)
+                               best_model_save_path=model_dir, num_targets_total=int(venv.cfg.num_targets), verbose=1,
+                               use_fused=True if a.fused_eval else None)
 
     class Progress:
         t0, last = time.perf_counter(), 0
@@ -76,7 +79,7 @@ def main():
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         print(json.dumps({"final": True, "num_envs": num_envs, "n_steps": n_steps, "timesteps": model.num_timesteps, "wall_s": round(dt, 2),
-                          "env_steps_per_s": round(model.num_timesteps / dt), "fused_learner": bool(a.fused_learner),
+                          "env_steps_per_s": round(model.num_timesteps / dt), "fused_learner": bool(a.fused_learner), "fused_eval": bool(a.fused_eval), "n_evals": ev.n_evals,
                           "rejected_actions": int(venv.rejected.item())}), flush=True)
         checkpoint.save(os.path.join(model_dir, "final_model.pt"), model)
         checkpoint.save_vecnormalize(os.path.join(model_dir, "vecnorm.pt"), env)

@@ -406,6 +406,20 @@ int32_t fw_eval_track_ll(const void* reward, int32_t reward_is_f64, const uint8_
                          const int64_t* targets, int64_t* counts, double* cur_rew, int64_t* cur_len, int64_t* step_ctr, double* cur_track,
                          double* fin_rew, int64_t* fin_len, int64_t* fin_step, int32_t* fin_info, double* fin_track, int32_t N, int32_t E,
                          void* hip_stream);
+/* fw_eval_track for the high-level command task (HighLevelCmdVecEnv; DESIGN.md section 2e "Evaluation").  Everything fw_eval_track
+ * does, and from the post-step observation row o of env i -- terminal_obs[i] where terminated | truncated, else obs[i]; [N, 30],
+ * obs_is_f64 the env dtype -- the conditioned command c = command[i] ([N, 3], the env dtype: the triple in force during the step)
+ * and p = prev_cmd[i] ([N, 3] double, owned by the caller), in double: e_psi = wrap(c0 - o[5]) (to [-pi, pi)), e_h = c1 - o[11],
+ * e_V = c2 - |o[6:9]|, w = |o[0:3]|; d_psi = |wrap(c0 - p0)|, d_h = |c1 - p1|, d_V = |c2 - p2| where cur_len[i] was > 0 before the
+ * step, else 0 (an episode's first step has no previous command); sat = 1 if c1 <= 0, c1 >= alt_high, c2 <= 0 or c2 >= speed_high,
+ * else 0.  It adds (|e_psi|, e_psi^2, |e_h|, e_h^2, |e_V|, e_V^2, w, d_psi, d_h, d_V, sat) to cur_track [N, 11]; a recorded
+ * episode's eleven sums go to fin_track [N, E, 11] at its slot, the sums of finished episodes are cleared, and prev_cmd[i] = c on
+ * every step.  FW_EINVAL for NULL buffers, obs_dim != 30, N <= 0 or E <= 0.  One launch, one workgroup. */
+int32_t fw_eval_track_hl(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
+                         int32_t info_dim, const void* obs, const void* terminal_obs, const void* command, int32_t obs_is_f64,
+                         int32_t obs_dim, double alt_high, double speed_high, const int64_t* targets, int64_t* counts, double* cur_rew,
+                         int64_t* cur_len, int64_t* step_ctr, double* cur_track, double* prev_cmd, double* fin_rew, int64_t* fin_len,
+                         int64_t* fin_step, int32_t* fin_info, double* fin_track, int32_t N, int32_t E, void* hip_stream);
 
 /* Commanding the low-level controller (FW_TASK_LOWLEVEL; DESIGN.md section 2d "Commanding the controller").
  * fw_command_ll: cmd is a device [T, N, 3] double schedule of (psi, h, V) commands; env i takes row min(*step_idx, T - 1) (row 0
@@ -436,6 +450,15 @@ int32_t fw_command_hl(fw_handle h, const void* action, int32_t action_is_f64, co
  * FW_EINVAL for NULL obs / trace / step_idx, N <= 0 or T <= 0. */
 int32_t fw_trace_ll(const void* obs, const void* terminal_obs, const uint8_t* terminated, const uint8_t* truncated, int32_t obs_is_f64,
                     int32_t N, double* trace, int32_t T, int64_t* step_idx, void* hip_stream);
+/* fw_trace_hl: fw_trace_ll for the high-level command task (same step_idx semantics).  With k = *step_idx, and only when
+ * 0 <= k < T, the post-step row o of env i ([N, 30]) and the conditioned command c = command[i] ([N, 3], the env dtype) go to
+ * trace[k, i, :] ([T, N, 11] double) as (c0, o[5], c1, o[11], c2, |o[6:9]|, |o[0:3]|, o[9], o[10],
+ * info[i, FW_INFO_NUM_TARGETS_REACHED] as the step left it (0 when info is NULL; info_dim its row length), flag); then *step_idx
+ * advances by one.  terminated / truncated / terminal_obs may be NULL.  One workgroup.
+ * FW_EINVAL for NULL obs / command / trace / step_idx, N <= 0, T <= 0, or info with info_dim <= 0. */
+int32_t fw_trace_hl(const void* obs, const void* terminal_obs, const uint8_t* terminated, const uint8_t* truncated, const void* command,
+                    const int32_t* info, int32_t info_dim, int32_t obs_is_f64, int32_t N, double* trace, int32_t T, int64_t* step_idx,
+                    void* hip_stream);
 
 /* VecNormalize step (SB3 VecNormalize.step_wait + RunningMeanStd.update, Chan et al. merge),
  * fused: one pass over obs[N,D] (env dtype T_in = double|float per `in_is_f64`) that

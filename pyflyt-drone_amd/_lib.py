@@ -24,7 +24,7 @@ EXPORTS = (
     "fw_ppo_param_count_a", "fw_ppo_moment_count_a", "fw_ppo_moment_map_a", "fw_ppo_update_workspace_bytes_a", "fw_ppo_update_a",
     "fw_policy_act_a", "fw_collect_act_a",
     "fw_ppo_param_count_a3", "fw_ppo_moment_count_a3", "fw_ppo_moment_map_a3", "fw_ppo_update_workspace_bytes_a3", "fw_ppo_update_a3",
-    "fw_collect_act_hl", "fw_sizeof_collect_hl_args",
+    "fw_collect_act_hl", "fw_sizeof_collect_hl_args", "fw_eval_track_hl", "fw_trace_hl",
 )
 
 
@@ -109,6 +109,10 @@ def lib() -> C.CDLL:
         L.fw_eval_track.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
         L.fw_eval_track_ll.restype = i32
         L.fw_eval_track_ll.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
+        L.fw_eval_track_hl.restype = i32
+        L.fw_eval_track_hl.argtypes = ([vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, C.c_double] + [vp] * 12 + [i32, i32, vp])
+        L.fw_trace_hl.restype = i32
+        L.fw_trace_hl.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp]
         L.fw_command_ll.restype = i32
         L.fw_command_ll.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
         L.fw_command_hl.restype = i32

@@ -2504,6 +2504,31 @@ int32_t fw_eval_track_ll(const void* reward, int32_t reward_is_f64, const uint8_
   return FW_OK;
 }
 
+int32_t fw_eval_track_hl(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
+                         int32_t info_dim, const void* obs, const void* terminal_obs, const void* command, int32_t obs_is_f64,
+                         int32_t obs_dim, double alt_high, double speed_high, const int64_t* targets, int64_t* counts, double* cur_rew,
+                         int64_t* cur_len, int64_t* step_ctr, double* cur_track, double* prev_cmd, double* fin_rew, int64_t* fin_len,
+                         int64_t* fin_step, int32_t* fin_info, double* fin_track, int32_t N, int32_t E, void* hip_stream) {
+  if (!reward || !terminated || !truncated || !targets || !counts || !cur_rew || !cur_len || !step_ctr || !fin_rew || !fin_len || !fin_step ||
+      (info && (info_dim <= 0 || !fin_info))) { g_err = "fw_eval_track_hl: bad arguments"; return FW_EINVAL; }
+  if (!obs || !terminal_obs || !cur_track || !fin_track) { g_err = "fw_eval_track_hl: obs, terminal_obs, cur_track and fin_track must be non-NULL"; return FW_EINVAL; }
+  if (!command || !prev_cmd) { g_err = "fw_eval_track_hl: command and prev_cmd must be non-NULL"; return FW_EINVAL; }
+  if (obs_dim != 30) { g_err = "fw_eval_track_hl: obs_dim must be 30 (the high-level command task's observation), got " + std::to_string(obs_dim); return FW_EINVAL; }
+  if (N <= 0 || E <= 0) { g_err = "fw_eval_track_hl: N and E must be positive, got N=" + std::to_string(N) + ", E=" + std::to_string(E); return FW_EINVAL; }
+  EvalTrackArgs A;
+  A.reward = reward; A.reward_is_f64 = reward_is_f64; A.terminated = terminated; A.truncated = truncated; A.info = info; A.info_dim = info_dim;
+  A.targets = targets; A.counts = counts; A.cur_rew = cur_rew; A.cur_len = cur_len; A.step_ctr = step_ctr;
+  A.fin_rew = fin_rew; A.fin_len = fin_len; A.fin_step = fin_step; A.fin_info = fin_info; A.N = N; A.E = E;
+  EvalTrackLLArgs X;
+  X.obs = obs; X.terminal_obs = terminal_obs; X.obs_is_f64 = obs_is_f64; X.cur_track = cur_track; X.fin_track = fin_track;
+  EvalTrackHLArgs H;
+  H.command = command; H.prev_cmd = prev_cmd; H.alt_high = alt_high; H.speed_high = speed_high;
+  DeviceGuard g(device_of(reward));
+  hipLaunchKernelGGL(fw_eval_track_hl_kernel, dim3(1), dim3(256), 0, (hipStream_t)hip_stream, A, X, H);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+
 int32_t fw_command_ll(fw_handle h, const double* cmd, int32_t T, const int64_t* step_idx, const uint8_t* mask, void* obs,
                       int32_t* rejected, void* hip_stream) {
   if (!h) { g_err = "fw_command_ll: NULL handle"; return FW_EINVAL; }
@@ -2549,6 +2574,19 @@ int32_t fw_trace_ll(const void* obs, const void* terminal_obs, const uint8_t* te
   DeviceGuard g(device_of(trace));
   hipLaunchKernelGGL(fw_trace_ll_kernel, dim3(1), dim3(1024), 0, (hipStream_t)hip_stream, obs, terminal_obs, terminated, truncated,
                      obs_is_f64, N, trace, T, step_idx);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+
+int32_t fw_trace_hl(const void* obs, const void* terminal_obs, const uint8_t* terminated, const uint8_t* truncated, const void* command,
+                    const int32_t* info, int32_t info_dim, int32_t obs_is_f64, int32_t N, double* trace, int32_t T, int64_t* step_idx,
+                    void* hip_stream) {
+  if (!obs || !command || !trace || !step_idx) { g_err = "fw_trace_hl: obs, command, trace and step_idx must be non-NULL"; return FW_EINVAL; }
+  if (N <= 0 || T <= 0) { g_err = "fw_trace_hl: N and T must be positive, got N=" + std::to_string(N) + ", T=" + std::to_string(T); return FW_EINVAL; }
+  if (info && info_dim <= FW_INFO_NUM_TARGETS_REACHED) { g_err = "fw_trace_hl: info_dim must cover the num_targets_reached column, got " + std::to_string(info_dim); return FW_EINVAL; }
+  DeviceGuard g(device_of(trace));
+  hipLaunchKernelGGL(fw_trace_hl_kernel, dim3(1), dim3(1024), 0, (hipStream_t)hip_stream, obs, terminal_obs, terminated, truncated,
+                     command, info, info_dim, (int32_t)FW_INFO_NUM_TARGETS_REACHED, obs_is_f64, N, trace, T, step_idx);
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }

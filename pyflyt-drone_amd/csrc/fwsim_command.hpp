@@ -12,12 +12,18 @@
 // terminal_obs where terminated | truncated -- as 8 doubles (o[18], o[5], o[19], o[11], o[20], |o[6:9]|, |o[0:3]|, flag) into
 // trace[k, i, :] for k = *step_idx < T, then k + 1 into *step_idx behind a barrier (no other workgroup reads the counter).
 //
+// fw_trace_hl_kernel: the same for the high-level command task (DESIGN.md section 2e "Evaluation"): the post-step row [30] and the
+// conditioned command c [3] in force during the step, as 11 doubles (c0, o[5], c1, o[11], c2, |o[6:9]|, |o[0:3]|, o[9], o[10],
+// info[i, num_targets_reached] as the step left it, flag) into trace[k, i, :].
+//
 // Included by fwsim.hip behind the low-level task's kernels: the target is written through their accessor ll_target_slot.
 #pragma once
 
 namespace fwsim_cmd {
 constexpr int kTraceCols = 8;
 constexpr int kLLObs = 21;
+constexpr int kTraceColsHL = 11;
+constexpr int kHLObs = 30;
 }
 
 template <typename T, int G>
@@ -72,6 +78,39 @@ __global__ __launch_bounds__(1024) void fw_trace_ll_kernel(const void* __restric
       double* out = trace + ((size_t)k * (size_t)N + (size_t)i) * fwsim_cmd::kTraceCols;
 #pragma unroll
       for (int j = 0; j < fwsim_cmd::kTraceCols; ++j) out[j] = row[j];
+    }
+  }
+  __syncthreads();                                   // every thread has read the counter before it moves
+  if (threadIdx.x == 0) step_idx[0] = k + 1;
+}
+
+__global__ __launch_bounds__(1024) void fw_trace_hl_kernel(const void* __restrict__ obs, const void* __restrict__ terminal_obs,
+                                                          const uint8_t* __restrict__ terminated, const uint8_t* __restrict__ truncated,
+                                                          const void* __restrict__ command, const int32_t* __restrict__ info,
+                                                          int32_t info_dim, int32_t info_col, int32_t obs_is_f64, int32_t N,
+                                                          double* __restrict__ trace, int32_t Tn, int64_t* __restrict__ step_idx) {
+#pragma clang fp contract(off)
+  const long long k = step_idx[0];
+  if (k >= 0 && k < (long long)Tn) {
+    for (int i = threadIdx.x; i < N; i += (int)blockDim.x) {
+      const bool te = terminated && terminated[i] != 0, tr = truncated && truncated[i] != 0;
+      const void* src = ((te || tr) && terminal_obs) ? terminal_obs : obs;
+      auto o = [&](int j) -> double {
+        const size_t q = (size_t)i * fwsim_cmd::kHLObs + j;
+        return obs_is_f64 ? reinterpret_cast<const double*>(src)[q] : (double)reinterpret_cast<const float*>(src)[q];
+      };
+      auto c = [&](int j) -> double {
+        const size_t q = (size_t)i * 3 + j;
+        return obs_is_f64 ? reinterpret_cast<const double*>(command)[q] : (double)reinterpret_cast<const float*>(command)[q];
+      };
+      const double v0 = o(6), v1 = o(7), v2 = o(8), w0 = o(0), w1 = o(1), w2 = o(2);
+      const double reached = info ? (double)info[(size_t)i * info_dim + info_col] : 0.0;
+      const double row[fwsim_cmd::kTraceColsHL] = { c(0), o(5), c(1), o(11), c(2), ::sqrt(v0 * v0 + v1 * v1 + v2 * v2),
+                                                    ::sqrt(w0 * w0 + w1 * w1 + w2 * w2), o(9), o(10), reached,
+                                                    te ? 1.0 : (tr ? 2.0 : 0.0) };
+      double* out = trace + ((size_t)k * (size_t)N + (size_t)i) * fwsim_cmd::kTraceColsHL;
+#pragma unroll
+      for (int j = 0; j < fwsim_cmd::kTraceColsHL; ++j) out[j] = row[j];
     }
   }
   __syncthreads();                                   // every thread has read the counter before it moves

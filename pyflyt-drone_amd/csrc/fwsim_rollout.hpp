@@ -54,8 +54,20 @@ struct EvalTrackLLArgs {
   double* cur_track;                                       // [N, 7]
   double* fin_track;                                       // [N, E, 8]
 };
-template <bool TRACK>
-__device__ __forceinline__ void eval_track_body(EvalTrackArgs A, EvalTrackLLArgs X) {
+// The high-level command task's sums (fw_eval_track_hl, DESIGN.md section 2e "Evaluation"): o is the post-step row [30] (columns 0:18
+// are the low-level observation's), c the conditioned command in force during the step, p the command of the step before.
+// e_psi = wrap(c0 - o[5]), e_h = c1 - o[11], e_V = c2 - |o[6:9]|, w = |o[0:3]|; d = (|wrap(c0 - p0)|, |c1 - p1|, |c2 - p2|), 0 on an
+// episode's first step; sat = c1 or c2 on a bound of the action Box.  Eleven running sums per env, in double; X carries obs /
+// terminal_obs / cur_track [N, 11] / fin_track [N, E, 11] (no survived column).  prev_cmd takes c on every step.
+constexpr int kTrackSumsHL = 11;
+constexpr int kHLObs = 30;
+struct EvalTrackHLArgs {
+  const void* command;                                     // [N, 3], env dtype (X.obs_is_f64)
+  double* prev_cmd;                                        // [N, 3]
+  double alt_high, speed_high;
+};
+template <bool TRACK, bool HL = false>
+__device__ __forceinline__ void eval_track_body(EvalTrackArgs A, EvalTrackLLArgs X, EvalTrackHLArgs H = EvalTrackHLArgs{}) {
   const long long step = A.step_ctr[0] + 1;
   for (int i = threadIdx.x; i < A.N; i += (int)blockDim.x) {
     const double r = A.reward_is_f64 ? reinterpret_cast<const double*>(A.reward)[i] : (double)reinterpret_cast<const float*>(A.reward)[i];
@@ -77,6 +89,35 @@ __device__ __forceinline__ void eval_track_body(EvalTrackArgs A, EvalTrackLLArgs
 #pragma unroll
       for (int k = 0; k < kTrackSums; ++k) ts[k] = X.cur_track[(size_t)i * kTrackSums + k] + add[k];
     }
+    double th[kTrackSumsHL];
+    if (HL) {
+#pragma clang fp contract(off)
+      // (no fused multiply-adds: the norms are the plain sums of squares the torch statement computes)
+      const void* src = done ? X.terminal_obs : X.obs;
+      auto o = [&](int k) -> double {
+        const size_t j = (size_t)i * kHLObs + k;
+        return X.obs_is_f64 ? reinterpret_cast<const double*>(src)[j] : (double)reinterpret_cast<const float*>(src)[j];
+      };
+      double cm[3], pc[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const size_t j = (size_t)i * 3 + k;
+        cm[k] = X.obs_is_f64 ? reinterpret_cast<const double*>(H.command)[j] : (double)reinterpret_cast<const float*>(H.command)[j];
+        pc[k] = H.prev_cmd[j];
+        H.prev_cmd[j] = cm[k];
+      }
+      const bool first = cl == 1;                         // cur_len was 0: the episode has no previous command
+      const double v0 = o(6), v1 = o(7), v2 = o(8), w0 = o(0), w1 = o(1), w2 = o(2);
+      const double e_psi = ll_wrap_pi<double>(cm[0] - o(5)), e_h = cm[1] - o(11);
+      const double e_v = cm[2] - ::sqrt(v0 * v0 + v1 * v1 + v2 * v2);
+      const double w = ::sqrt(w0 * w0 + w1 * w1 + w2 * w2);
+      const double sat = (cm[1] <= 0.0 || cm[1] >= H.alt_high || cm[2] <= 0.0 || cm[2] >= H.speed_high) ? 1.0 : 0.0;
+      const double add[kTrackSumsHL] = { ::fabs(e_psi), e_psi * e_psi, ::fabs(e_h), e_h * e_h, ::fabs(e_v), e_v * e_v, w,
+                                         first ? 0.0 : ::fabs(ll_wrap_pi<double>(cm[0] - pc[0])), first ? 0.0 : ::fabs(cm[1] - pc[1]),
+                                         first ? 0.0 : ::fabs(cm[2] - pc[2]), sat };
+#pragma unroll
+      for (int k = 0; k < kTrackSumsHL; ++k) th[k] = X.cur_track[(size_t)i * kTrackSumsHL + k] + add[k];
+    }
     if (done && c < A.targets[i]) {
       const size_t s = (size_t)i * A.E + (size_t)(c < A.E ? c : A.E - 1);
       A.fin_rew[s] = cr; A.fin_len[s] = cl; A.fin_step[s] = step;
@@ -86,6 +127,10 @@ __device__ __forceinline__ void eval_track_body(EvalTrackArgs A, EvalTrackLLArgs
         for (int k = 0; k < kTrackSums; ++k) X.fin_track[s * (kTrackSums + 1) + k] = ts[k];
         X.fin_track[s * (kTrackSums + 1) + kTrackSums] = A.terminated[i] ? 0.0 : 1.0;
       }
+      if (HL) {
+#pragma unroll
+        for (int k = 0; k < kTrackSumsHL; ++k) X.fin_track[s * kTrackSumsHL + k] = th[k];
+      }
       A.counts[i] = c + 1;
     }
     A.cur_rew[i] = done ? 0.0 : cr;
@@ -94,12 +139,19 @@ __device__ __forceinline__ void eval_track_body(EvalTrackArgs A, EvalTrackLLArgs
 #pragma unroll
       for (int k = 0; k < kTrackSums; ++k) X.cur_track[(size_t)i * kTrackSums + k] = done ? 0.0 : ts[k];
     }
+    if (HL) {
+#pragma unroll
+      for (int k = 0; k < kTrackSumsHL; ++k) X.cur_track[(size_t)i * kTrackSumsHL + k] = done ? 0.0 : th[k];
+    }
   }
   __syncthreads();
   if (threadIdx.x == 0) A.step_ctr[0] = step;
 }
 __global__ __launch_bounds__(256) void fw_eval_track_kernel(EvalTrackArgs A) { eval_track_body<false>(A, EvalTrackLLArgs{}); }
 __global__ __launch_bounds__(256) void fw_eval_track_ll_kernel(EvalTrackArgs A, EvalTrackLLArgs X) { eval_track_body<true>(A, X); }
+__global__ __launch_bounds__(256) void fw_eval_track_hl_kernel(EvalTrackArgs A, EvalTrackLLArgs X, EvalTrackHLArgs H) {
+  eval_track_body<false, true>(A, X, H);
+}
 
 // K4a: per-column batch moments of obs[N,D] (two-pass-free: shifted sums in double), one
 // workgroup per column chunk; K4b merges them into the running statistics (Chan et al.) and

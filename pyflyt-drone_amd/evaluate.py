@@ -17,7 +17,10 @@ Mirrors, for the device-resident envs:
   new best mean reward (``:172-190, 216-222``);
 * for the low-level control task, the figures of eval/eval_lowlevel.py: heading / altitude / airspeed
   tracking error (MAE, RMSE, pooled over every evaluated step), mean angular-rate norm, survival rate
-  (:meth:`EvalResult.tracking_scalars`, definitions in DESIGN.md section 2d).
+  (:meth:`EvalResult.tracking_scalars`, definitions in DESIGN.md section 2d);
+* for the high-level command task, figures the reference has no script for (build-owned, DESIGN.md section 2e "Evaluation"): how
+  the frozen controller follows the commander's commands, how much the commands jump from step to step, how often they sit on a
+  bound of the action Box and how many actions were rejected as non-finite (:meth:`EvalResult.command_scalars`).
 
 Everything per step stays on the device; the host reads one small ``dones`` mask per
 vec-step (the episode bookkeeping is host-side like SB3's).
@@ -58,6 +61,45 @@ def _track_terms(o: torch.Tensor) -> torch.Tensor:
     return torch.stack([e_psi.abs(), e_psi * e_psi, e_h.abs(), e_h * e_h, e_v.abs(), e_v * e_v, w], dim=1)
 
 
+# the high-level command task's per-episode sums, in the column order of fw_eval_track_hl's cur_track / fin_track: the seven of
+# TRACK_SUMS taken against the commander's command, the step-to-step command changes and the steps with a command on a Box bound
+HL_TRACK_SUMS = TRACK_SUMS + ("dcmd_heading", "dcmd_altitude", "dcmd_airspeed", "saturated")
+
+
+def _wrap_pi(a: torch.Tensor) -> torch.Tensor:
+    return torch.remainder(a + math.pi, 2 * math.pi) - math.pi          # Python's (a + pi) % (2 pi) - pi
+
+
+def _track_terms_hl(o: torch.Tensor, c: torch.Tensor, p: torch.Tensor, first: torch.Tensor, alt_high: float,
+                    speed_high: float) -> torch.Tensor:
+    """[N, 11] per-step terms of HL_TRACK_SUMS (DESIGN.md section 2e "Evaluation"), in double: the torch statement of what
+    fw_eval_track_hl adds up.  ``o`` [N, 30] post-step observation rows, ``c`` [N, 3] the conditioned commands in force during the
+    step, ``p`` [N, 3] the commands of the step before, ``first`` [N] bool: the step opens an episode (no previous command: the
+    three changes are 0).  ``alt_high`` / ``speed_high``: the upper bounds of the action Box.  Works on CPU tensors."""
+    o, c, p = o.to(torch.float64), c.to(torch.float64), p.to(torch.float64)
+    e_psi = _wrap_pi(c[:, 0] - o[:, 5])
+    e_h = c[:, 1] - o[:, 11]
+    e_v = c[:, 2] - torch.sqrt(o[:, 6] * o[:, 6] + o[:, 7] * o[:, 7] + o[:, 8] * o[:, 8])
+    w = torch.sqrt(o[:, 0] * o[:, 0] + o[:, 1] * o[:, 1] + o[:, 2] * o[:, 2])
+    zero = torch.zeros_like(w)
+    d_psi = torch.where(first, zero, _wrap_pi(c[:, 0] - p[:, 0]).abs())
+    d_h = torch.where(first, zero, (c[:, 1] - p[:, 1]).abs())
+    d_v = torch.where(first, zero, (c[:, 2] - p[:, 2]).abs())
+    sat = ((c[:, 1] <= 0.0) | (c[:, 1] >= alt_high) | (c[:, 2] <= 0.0) | (c[:, 2] >= speed_high)).to(torch.float64)
+    return torch.stack([e_psi.abs(), e_psi * e_psi, e_h.abs(), e_h * e_h, e_v.abs(), e_v * e_v, w, d_psi, d_h, d_v, sat], dim=1)
+
+
+def _hl_bounds(venv):
+    """(alt_high, speed_high) of a HighLevelCmdVecEnv's action Box when the command figures apply to ``venv`` (its 30-value
+    observation), else None"""
+    if not (hasattr(venv, "command") and hasattr(venv, "step_low") and hasattr(venv, "rejected") and hasattr(venv, "terminal_obs")):
+        return None
+    if int(venv.obs.shape[1]) != 30:
+        return None
+    from .highlevel import AIRSPEED_HIGH
+    return float(venv.cfg.flight_dome_size), float(AIRSPEED_HIGH)
+
+
 @dataclass
 class EvalResult:
     episode_rewards: List[float]
@@ -75,6 +117,18 @@ class EvalResult:
     airspeed_sq: List[float] = field(default_factory=list)
     ang_vel: List[float] = field(default_factory=list)
     survived: List[bool] = field(default_factory=list)
+    # the high-level command task only (HL_TRACK_SUMS): the seven lists above hold the sums against the commander's commands
+    # (survived stays empty); per episode the summed |command change| of each component, the number of steps with the altitude or
+    # airspeed command on a bound of the action Box; and, for the whole evaluation, the actions rejected as non-finite
+    dcmd_heading: List[float] = field(default_factory=list)
+    dcmd_altitude: List[float] = field(default_factory=list)
+    dcmd_airspeed: List[float] = field(default_factory=list)
+    saturated: List[float] = field(default_factory=list)
+    rejected_actions: int = 0
+
+    def add_command(self, sums) -> None:
+        for name, v in zip(HL_TRACK_SUMS, sums):
+            getattr(self, name).append(float(v))
 
     def add_tracking(self, sums, survived: bool) -> None:
         for name, v in zip(TRACK_SUMS, sums):
@@ -118,6 +172,27 @@ class EvalResult:
         out["eval/survival_rate"] = float(np.mean(self.survived))
         return out
 
+    def command_scalars(self) -> Dict[str, float]:
+        """The high-level command task's figures (build-owned, DESIGN.md section 2e "Evaluation"), pooled over every evaluated step
+        as :meth:`tracking_scalars` pools: ``cmd_*_mae`` / ``cmd_*_rmse`` = how far the flight was from the commander's command,
+        ``ang_vel_mean``, ``cmd_*_delta`` = sum |command change| / (sum L - episodes) (0.0 when no episode has a second step),
+        ``cmd_saturation_rate`` = steps with the altitude or airspeed command on a Box bound / sum L, ``rejected_actions``.  Empty for
+        the other tasks."""
+        if not self.saturated:
+            return {}
+        steps = float(np.sum(self.episode_lengths))
+        pairs = steps - float(len(self.episode_lengths))
+        out = {}
+        for q in ("heading", "altitude", "airspeed"):
+            out[f"eval/cmd_{q}_mae"] = float(np.sum(getattr(self, q + "_abs"))) / steps
+            out[f"eval/cmd_{q}_rmse"] = math.sqrt(float(np.sum(getattr(self, q + "_sq"))) / steps)
+        out["eval/ang_vel_mean"] = float(np.sum(self.ang_vel)) / steps
+        for q in ("heading", "altitude", "airspeed"):
+            out[f"eval/cmd_{q}_delta"] = float(np.sum(getattr(self, "dcmd_" + q))) / pairs if pairs > 0 else 0.0
+        out["eval/cmd_saturation_rate"] = float(np.sum(self.saturated)) / steps
+        out["eval/rejected_actions"] = float(self.rejected_actions)
+        return out
+
 
 @torch.no_grad()
 def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool = True,
@@ -142,7 +217,13 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
     (``fw_collect_act_a`` -> ``fw_step`` -> ``fw_eval_track_ll``).
 
     For the low-level control task the result also carries the per-episode tracking sums and survival
-    (:meth:`EvalResult.tracking_scalars`): from torch ops in the step-by-step loop, from ``fw_eval_track_ll`` in the replayed one."""
+    (:meth:`EvalResult.tracking_scalars`): from torch ops in the step-by-step loop, from ``fw_eval_track_ll`` in the replayed one.
+
+    For the high-level command task (``HighLevelCmdVecEnv``) it carries the command figures (:meth:`EvalResult.command_scalars`):
+    from torch ops (``_track_terms_hl``) in the step-by-step loop, from ``fw_eval_track_hl`` in the replayed one.  Its three-action
+    MlpPolicy keeps the torch forward by default; ``use_fused=True`` makes a vec-step ``fw_collect_act_hl`` -> ``fw_step`` ->
+    ``fw_eval_track_hl``.  ``venv.rejected`` is zeroed when the evaluation begins and read once at its end
+    (``EvalResult.rejected_actions``: every env-step the evaluation ran counts, the ones past an env's last wanted episode too)."""
     venv = env.venv
     n = env.num_envs
     targets = np.array([(n_eval_episodes + i) // n for i in range(n)], dtype=np.int64)
@@ -159,6 +240,11 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
     is_objlock = getattr(getattr(venv, "cfg", None), "task", K.FW_TASK_WAYPOINTS) in (K.FW_TASK_OBJLOCK, K.FW_TASK_WAYPOINT_OBJLOCK)
     track = getattr(getattr(venv, "cfg", None), "task", K.FW_TASK_WAYPOINTS) == K.FW_TASK_LOWLEVEL
     cur_trk = torch.zeros((n, len(TRACK_SUMS)), dtype=torch.float64, device=env.device) if track else None
+    hl = _hl_bounds(venv)
+    if hl is not None:
+        cur_hl = torch.zeros((n, len(HL_TRACK_SUMS)), dtype=torch.float64, device=env.device)
+        prev_cmd = torch.zeros((n, 3), dtype=torch.float64, device=env.device)
+        venv.rejected.zero_()
     obs = env.reset()
     steps = 0
     while (counts < targets).any():
@@ -166,6 +252,9 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
         clipped = clip_actions(actions, venv).to(venv.torch_dtype)
         obs, _, dones, _, _ = env.step(clipped)
         cur_rew += venv.rewards.to(torch.float64)        # un-normalised reward of the wrapped env
+        if hl is not None:                               # venv.command: the triple that was in force during the step
+            cur_hl += _track_terms_hl(torch.where(dones[:, None], venv.terminal_obs, venv.obs), venv.command, prev_cmd, cur_len == 0, *hl)
+            prev_cmd = venv.command.to(torch.float64).clone()
         cur_len += 1
         if track:                                        # the post-step row: the terminal observation where the episode ended
             cur_trk += _track_terms(torch.where(dones[:, None], venv.terminal_obs, venv.obs))
@@ -175,12 +264,15 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
             rew_h, len_h = cur_rew.cpu().numpy(), cur_len.cpu().numpy()
             info_h = venv.info.cpu().numpy() if has_info else None
             trk_h, term_h = (cur_trk.cpu().numpy(), venv.terminated.cpu().numpy()) if track else (None, None)
+            hl_h = cur_hl.cpu().numpy() if hl is not None else None
             for i in idx:
                 if counts[i] < targets[i]:
                     counts[i] += 1
                     res.episode_rewards.append(float(rew_h[i])); res.episode_lengths.append(int(len_h[i]))
                     if track:
                         res.add_tracking(trk_h[i], not term_h[i])
+                    if hl_h is not None:
+                        res.add_command(hl_h[i])
                     info = {"episode": {"r": float(rew_h[i]), "l": int(len_h[i])}}
                     if info_h is not None:
                         info["num_targets_reached"] = int(info_h[i, K.INFO_NUM_TARGETS_REACHED])
@@ -201,9 +293,13 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
             cur_rew.masked_fill_(m, 0.0); cur_len.masked_fill_(m, 0)
             if track:
                 cur_trk.masked_fill_(m[:, None], 0.0)
+            if hl is not None:
+                cur_hl.masked_fill_(m[:, None], 0.0)
         steps += 1
         if max_vec_steps is not None and steps >= max_vec_steps:
             break
+    if hl is not None:
+        res.rejected_actions = int(venv.rejected.item())
     return res
 
 
@@ -240,7 +336,11 @@ class ReplayedEvaluation:
 
     The low-level control task's bookkeeping is one ``fw_eval_track_ll`` launch per vec-step, which also sums its tracking figures.
     ``use_fused=True`` with its six-action MlpPolicy: a vec-step is ``fw_collect_act_a`` (policy only, deterministic, frozen
-    statistics) -> ``fw_step`` -> ``fw_eval_track_ll``, in sequence."""
+    statistics) -> ``fw_step`` -> ``fw_eval_track_ll``, in sequence.
+
+    The high-level command task's bookkeeping is one ``fw_eval_track_hl`` launch per vec-step, which also sums its command figures.
+    ``use_fused=True`` with its three-action MlpPolicy (``fused3``): a vec-step is ``fw_collect_act_hl`` (commander and controller,
+    policy nets only, deterministic, frozen statistics) -> ``fw_step`` (``step_low``) -> ``fw_eval_track_hl``, in sequence."""
 
     def __init__(self, policy, env, targets: np.ndarray, callback=None, use_fused: Optional[bool] = None):
         self.policy, self.env, self.callback = policy, env, callback
@@ -248,9 +348,12 @@ class ReplayedEvaluation:
         self.fused = self._fused_applies(policy, env) if use_fused is None else bool(use_fused)
         # the six-action policy of the low-level task: only on request (the default keeps its torch forward)
         self.fused6 = self.fused and not self._fused_applies(policy, env) and self._fused6_applies(policy, env)
-        if self.fused and not (self._fused_applies(policy, env) or self.fused6):
+        # the three-action policy of the high-level command task: only on request, likewise
+        self.fused3 = self.fused and not self._fused_applies(policy, env) and not self.fused6 and self._fused3_applies(policy, env)
+        if self.fused and not (self._fused_applies(policy, env) or self.fused6 or self.fused3):
             raise ValueError("use_fused=True needs the MlpPolicy, a device env on the 8-lane mapping (any mapping for the low-level task's "
-                             "six actions) and an evaluation normaliser (training=False)")
+                             "six actions and for the high-level command task's three actions on its 30-value observation) and an "
+                             "evaluation normaliser (training=False)")
         self.venv, self.n, self.dev, self.targets = venv, n, dev, targets
         self.E = E = max(int(targets.max()), 1)
         self.has_info = hasattr(venv, "info")
@@ -270,6 +373,11 @@ class ReplayedEvaluation:
         if self.track:
             self.cur_track = torch.zeros((n, len(TRACK_SUMS)), dtype=torch.float64, device=dev)
             self.fin_track = torch.zeros((n, E, len(TRACK_SUMS) + 1), dtype=torch.float64, device=dev)      # + survived
+        self.hl = _hl_bounds(venv)
+        if self.hl is not None:
+            self.cur_track = torch.zeros((n, len(HL_TRACK_SUMS)), dtype=torch.float64, device=dev)
+            self.fin_track = torch.zeros((n, E, len(HL_TRACK_SUMS)), dtype=torch.float64, device=dev)
+            self.prev_cmd = torch.zeros((n, 3), dtype=torch.float64, device=dev)
         self.obs = None
         self.side = torch.cuda.Stream(device=dev)
         self.done_event = None
@@ -302,6 +410,17 @@ class ReplayedEvaluation:
             return False
         return FusedPpoUpdate.fits(policy, env.obs_dim, torch.device(env.device), act_dims=(6,))
 
+    @staticmethod
+    def _fused3_applies(policy, env) -> bool:
+        """the high-level command task's three-action MlpPolicy through fw_collect_act_hl (either lane mapping)"""
+        from .rollout import FusedPpoUpdate
+        venv = env.venv
+        if not (hasattr(venv, "collect_act_hl") and _hl_bounds(venv) is not None and torch.device(env.device).type == "cuda"):
+            return False
+        if env.training or not env.norm_obs or env.obs_dim != 30:
+            return False
+        return FusedPpoUpdate.fits(policy, 30, torch.device(env.device), act_dims=(3,))
+
     def _fused_setup(self) -> None:
         from . import _lib
         from .rollout import FusedPpoUpdate
@@ -313,6 +432,10 @@ class ReplayedEvaluation:
         if self.fused6:                                             # fw_collect_act_a's outputs: clipped actions for fw_step, the rest unread
             self._act_env = torch.zeros((n, 6), dtype=venv.torch_dtype, device=dev)
             self._act_raw = torch.zeros((n, 6), dtype=torch.float32, device=dev)
+            self._logp = torch.zeros(n, dtype=torch.float32, device=dev)
+            return
+        if self.fused3:                                             # fw_collect_act_hl's rollout rows: unread (the env owns command / low_action)
+            self._act_raw = torch.zeros((n, 3), dtype=torch.float32, device=dev)
             self._logp = torch.zeros(n, dtype=torch.float32, device=dev)
             return
         self._act_env = torch.full((n, 4), float("nan"), dtype=venv.torch_dtype, device=dev)      # NaN = "not there yet" (fw_collect_step)
@@ -338,6 +461,32 @@ class ReplayedEvaluation:
         venv.step_tensor(self._act_env)
         self._track_step()
 
+    def _fused3_step(self) -> None:
+        """a vec-step of the three-action policy: fw_collect_act_hl (commander and controller, policy nets only, deterministic, frozen
+        statistics, nothing of the previous step to finalise) -> fw_step -> fw_eval_track_hl, one after the other on the stream"""
+        env, venv = self.env, self.venv
+        a = K.FwCollectHlArgs()
+        a.params, a.nets, a.deterministic = self._flat.data_ptr(), 1, 1
+        a.obs_mean, a.obs_var = env.obs_rms.mean.data_ptr(), env.obs_rms.var.data_ptr()
+        a.clip_obs, a.eps_obs = float(env.clip_obs), float(env.epsilon)
+        a.act_raw, a.logp = self._act_raw.data_ptr(), self._logp.data_ptr()
+        venv.collect_act_hl(a)
+        venv.step_low()
+        self._track_hl_step()
+
+    def _track_hl_step(self) -> None:
+        """the high-level command task's bookkeeping of a vec-step, command sums included: one fw_eval_track_hl launch"""
+        from . import _lib
+        from .rollout import _p, _stream
+        venv, fi = self.venv, self.fin_info
+        _lib.check(_lib.lib().fw_eval_track_hl(
+            _p(venv.rewards), int(venv.rewards.dtype == torch.float64), _p(venv.terminated), _p(venv.truncated),
+            _p(venv.info) if fi is not None else None, int(venv.info.shape[1]) if fi is not None else 0,
+            _p(venv.obs), _p(venv.terminal_obs), _p(venv.command), int(venv.obs.dtype == torch.float64), int(venv.obs.shape[1]),
+            self.hl[0], self.hl[1], _p(self.tg), _p(self.counts), _p(self.cur_rew), _p(self.cur_len), _p(self.step_ctr),
+            _p(self.cur_track), _p(self.prev_cmd), _p(self.fin_rew), _p(self.fin_len), _p(self.fin_step),
+            _p(fi) if fi is not None else None, _p(self.fin_track), self.n, self.E, _stream(self.dev)))
+
     def _track_step(self) -> None:
         """the low-level task's bookkeeping of a vec-step, tracking sums included: one fw_eval_track_ll launch"""
         from . import _lib
@@ -357,6 +506,9 @@ class ReplayedEvaluation:
         from .rollout import _stream
         if self.fused6:
             self._fused6_step()
+            return
+        if self.fused3:
+            self._fused3_step()
             return
         env, venv = self.env, self.venv
         L, st = _lib.lib(), _stream(self.dev)
@@ -393,7 +545,7 @@ class ReplayedEvaluation:
         import ctypes as C
         from . import _lib
         from .rollout import _stream
-        if not self.fused or self.fused6 or not self._ws_ready:      # (the six-action path has no fw_collect_step and no status word)
+        if not self.fused or self.fused6 or self.fused3 or not self._ws_ready:      # (the six- and three-action paths have no fw_collect_step and no status word)
             return
         stw = C.c_uint32(0)
         _lib.check(_lib.lib().fw_collect_status(self.venv._h, self._ws.data_ptr(), self._ws.numel() * 8, C.byref(stw), _stream(self.dev)), self.venv._h)
@@ -412,6 +564,9 @@ class ReplayedEvaluation:
         if self.track:
             self._track_step()
             return
+        if self.hl is not None:
+            self._track_hl_step()
+            return
         self.cur_rew.add_(venv.rewards.to(torch.float64))            # un-normalised reward of the wrapped env
         self.cur_len.add_(1); self.step_ctr.add_(1)
         take = dones & (counts < tg)
@@ -428,6 +583,8 @@ class ReplayedEvaluation:
         """reset, two eager steps (they are evaluation steps like any other), capture: on the side stream"""
         self.side.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(self.side):
+            if self.hl is not None:
+                self.venv.rejected.zero_()
             self.obs = self.env.reset().clone()
             for _ in range(2):
                 self._body(); self.steps += 1
@@ -470,24 +627,29 @@ class ReplayedEvaluation:
         rew_h, len_h, step_h = self.fin_rew.cpu().numpy(), self.fin_len.cpu().numpy(), self.fin_step.cpu().numpy()
         info_h = self.fin_info.cpu().numpy() if has_info else None
         trk_h = self.fin_track.cpu().numpy() if self.track else None
+        hl_h = self.fin_track.cpu().numpy() if self.hl is not None else None
+        if self.hl is not None:
+            res.rejected_actions = int(self.venv.rejected.item())
         order = sorted((int(step_h[i, k]), i, k) for i in range(n) for k in range(int(c_h[i])))    # as they ended: by step, then env
         for _, i, k in order:
             res.episode_rewards.append(float(rew_h[i, k])); res.episode_lengths.append(int(len_h[i, k]))
             if trk_h is not None:
                 res.add_tracking(trk_h[i, k, :len(TRACK_SUMS)], trk_h[i, k, len(TRACK_SUMS)] != 0.0)
+            if hl_h is not None:
+                res.add_command(hl_h[i, k])
             info = _episode_info(res, float(rew_h[i, k]), int(len_h[i, k]), info_h[i, k] if has_info else None, self.is_objlock)
             if self.callback is not None:
                 self.callback(info)
         return res
 
 
-def start_evaluation(policy, env, n_eval_episodes: int = 10, callback=None) -> ReplayedEvaluation:
+def start_evaluation(policy, env, n_eval_episodes: int = 10, callback=None, use_fused: Optional[bool] = None) -> ReplayedEvaluation:
     """Asynchronous :func:`evaluate_policy` (deterministic, device envs whose config bounds the episode length): returns a
     running :class:`ReplayedEvaluation`; ``.result()`` waits for it."""
     n = env.num_envs
     targets = np.array([(n_eval_episodes + i) // n for i in range(n)], dtype=np.int64)
     bound = int(targets.max()) * (K.max_steps(env.venv.cfg) + 2)
-    return ReplayedEvaluation(policy, env, targets, callback).launch(bound)
+    return ReplayedEvaluation(policy, env, targets, callback, use_fused=use_fused).launch(bound)
 
 
 class EvalCallback:
@@ -507,7 +669,7 @@ class EvalCallback:
 
     def __init__(self, eval_env, n_eval_episodes: int = 5, eval_freq: int = 10000, log_path: Optional[str] = None,
                  best_model_save_path: Optional[str] = None, deterministic: bool = True, num_targets_total: int = 0,
-                 verbose: int = 0, overlap: Optional[bool] = None):
+                 verbose: int = 0, overlap: Optional[bool] = None, use_fused: Optional[bool] = None):
         self.eval_env, self.n_eval_episodes, self.eval_freq = eval_env, n_eval_episodes, max(int(eval_freq), 1)
         self.log_path = os.path.join(log_path, "evaluations") if log_path else None
         self.best_model_save_path, self.deterministic = best_model_save_path, deterministic
@@ -522,6 +684,7 @@ class EvalCallback:
         self._next_eval_calls = self.eval_freq
         self.n_evals = 0
         self.overlap = overlap
+        self.use_fused = use_fused        # handed to evaluate_policy / start_evaluation (None: fused whenever it is the default there)
         self._pending = None              # (job, num_timesteps at launch, checkpoint snapshot or None)
         self._policy_copy = None
         self._seed0, self._n_launched = None, 0
@@ -562,10 +725,10 @@ class EvalCallback:
                 self._policy_copy = copy.deepcopy(ppo.policy)
             else:
                 self._policy_copy.load_state_dict(ppo.policy.state_dict())
-            job = start_evaluation(self._policy_copy, self.eval_env, self.n_eval_episodes)
+            job = start_evaluation(self._policy_copy, self.eval_env, self.n_eval_episodes, use_fused=self.use_fused)
             self._pending = (job, ppo.num_timesteps, snap)
         else:
-            r = evaluate_policy(ppo.policy, self.eval_env, self.n_eval_episodes, deterministic=self.deterministic)
+            r = evaluate_policy(ppo.policy, self.eval_env, self.n_eval_episodes, deterministic=self.deterministic, use_fused=self.use_fused)
             self._record(ppo, r, ppo.num_timesteps, snap)
         return True
 
@@ -597,6 +760,8 @@ class EvalCallback:
                 self.evaluations_successes.append(r.is_success); kw = dict(successes=np.array(self.evaluations_successes, dtype=object))
             for k, v in r.tracking_scalars().items():              # heading_mae, ..., survival_rate: (n_evals,)
                 self.evaluations_tracking.setdefault(k.split("/", 1)[1], []).append(v)
+            for k, v in r.command_scalars().items():               # the high-level command task: cmd_heading_mae, ...: (n_evals,)
+                self.evaluations_tracking.setdefault(k.split("/", 1)[1], []).append(v)
             kw.update({k: np.array(v, dtype=np.float64) for k, v in self.evaluations_tracking.items()})
             np.savez(self.log_path, timesteps=self.evaluations_timesteps, results=np.array(self.evaluations_results, dtype=object),
                      ep_lengths=np.array(self.evaluations_length, dtype=object), **kw)
@@ -605,6 +770,7 @@ class EvalCallback:
         is_objlock = getattr(getattr(self.eval_env.venv, "cfg", None), "task", 0) in (K.FW_TASK_OBJLOCK, K.FW_TASK_WAYPOINT_OBJLOCK)
         self.last_scalars = r.scalars(self.num_targets_total, has_duck=is_objlock)
         self.last_scalars.update(r.tracking_scalars())             # (the low-level task's; nothing for the others)
+        self.last_scalars.update(r.command_scalars())              # (the high-level command task's; nothing for the others)
         self.last_scalars["time/total_timesteps"] = timesteps
         if self.verbose and writer:
             print(f"Eval num_timesteps={timesteps}, episode_reward={r.mean_reward:.2f} +/- {r.std_reward:.2f}")

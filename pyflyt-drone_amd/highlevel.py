@@ -12,12 +12,16 @@ env's stream, with no host synchronisation (capturable in a hipGraph):
 ``condition_command`` restates the first of them in numpy.  A collected vec-step of ``rollout.PPO`` under
 ``PPOConfig.fused_three_actions`` replaces the first two -- and the policy's own forward and sampling in front of them -- by one
 launch, ``fw_collect_act_hl`` (``collect_act_hl``), and steps the base env with ``step_low``.
+
+:func:`fly` records a flight of a commander, one row per env and vec-step (``fw_trace_hl``, :class:`HighLevelTrace`); the
+evaluation figures of the task are ``evaluate.EvalResult.command_scalars`` (DESIGN.md section 2e "Evaluation").
 """
 from __future__ import annotations
 
 import copy
 import ctypes as C
 import os
+from dataclasses import dataclass
 from typing import Any, Optional
 
 import numpy as np
@@ -253,3 +257,116 @@ class HighLevelCmdVecEnv(FusedVecEnv):
 
     def get_counters(self) -> dict:
         return self.base.get_counters()
+
+
+# ---------------------------------------------------------------------- the flight record (fw_trace_hl)
+# columns of a trace row: commanded / actual heading, altitude, airspeed, angular-rate norm, roll, pitch, waypoints reached, flag
+HL_TRACE_COLS = ("heading_cmd", "heading", "altitude_cmd", "altitude", "airspeed_cmd", "airspeed", "ang_vel", "roll", "pitch",
+                 "targets_reached", "flag")
+FLAG_RUNNING, FLAG_TERMINATED, FLAG_TRUNCATED = 0, 1, 2
+
+
+def trace_rows_hl(obs: torch.Tensor, cmd: torch.Tensor, info: Optional[torch.Tensor] = None,
+                  flag: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[N, 11] trace rows (HL_TRACE_COLS) of observation rows ``obs`` [N, 30] and conditioned commands ``cmd`` [N, 3], in double:
+    the torch statement of one fw_trace_hl row.  ``info`` [N, >= 1] int rows (None: 0 waypoints reached), ``flag`` [N] (None: 0)."""
+    o, c = obs.to(torch.float64), cmd.to(torch.float64)
+    v = torch.sqrt(o[:, 6] * o[:, 6] + o[:, 7] * o[:, 7] + o[:, 8] * o[:, 8])
+    w = torch.sqrt(o[:, 0] * o[:, 0] + o[:, 1] * o[:, 1] + o[:, 2] * o[:, 2])
+    r = torch.zeros_like(v) if info is None else info[:, K.INFO_NUM_TARGETS_REACHED].to(torch.float64)
+    f = torch.zeros_like(v) if flag is None else flag.to(torch.float64)
+    return torch.stack([c[:, 0], o[:, 5], c[:, 1], o[:, 11], c[:, 2], v, w, o[:, 9], o[:, 10], r, f], dim=1)
+
+
+@dataclass
+class HighLevelTrace:
+    """What :func:`fly` recorded.  ``trace [T, N, 11]`` (host, float64): per vec-step and env the post-step row (HL_TRACE_COLS) -- on
+    the step that ends an episode the terminal observation -- with the conditioned command that was in force during the step.
+    ``start [N, 11]``: the rows after ``env.reset()``, their command the one the env holds then (0, start height, start speed).
+    ``dt``: seconds per vec-step.  ``ended_at [N]``: the first step whose row carries a done flag, -1 if the env flew all T steps
+    in one episode (the rows behind it belong to the env's next episodes)."""
+    trace: np.ndarray
+    start: np.ndarray
+    dt: float
+    ended_at: np.ndarray
+
+
+def fly(policy, env, n_steps: int, use_fused: Optional[bool] = None, graph_steps: int = 8) -> HighLevelTrace:
+    """Fly the commander ``policy`` (deterministic, frozen normaliser statistics) for ``n_steps`` vec-steps on ``env``, a
+    ``VecNormalizeDevice(training=False)`` around a :class:`HighLevelCmdVecEnv` with the 30-value observation.  ``env.reset()``
+    first; then per vec-step k: act -> step -> ``fw_trace_hl`` (row k of the trace).  The act is the torch forward followed by
+    ``step_tensor`` (``use_fused`` None / False) or ``fw_collect_act_hl`` followed by ``step_low`` (``use_fused=True``, the launches
+    of ``ReplayedEvaluation._fused3_step``).  With ``graph_steps > 0`` the body is captured as a hipGraph of that many vec-steps and
+    replayed (the trace row is picked on the device); the steps that do not fill a whole graph run eagerly after it.
+    ``graph_steps <= 0`` runs every step eagerly; both give the same trace bit for bit."""
+    from .evaluate import ReplayedEvaluation, _hl_bounds
+    from .rollout import clip_actions
+    venv = getattr(env, "venv", None)
+    if venv is None or _hl_bounds(venv) is None:
+        raise ValueError("fly needs a VecNormalizeDevice around a HighLevelCmdVecEnv with the 30-value observation")
+    if getattr(env, "training", True):
+        raise ValueError("fly needs an evaluation normaliser (training=False): the statistics stay frozen")
+    T = int(n_steps)
+    if T <= 0:
+        raise ValueError(f"n_steps must be positive, got {n_steps}")
+    n, dev = env.num_envs, env.device
+    fused = bool(use_fused)
+    if fused and not ReplayedEvaluation._fused3_applies(policy, env):
+        raise ValueError("use_fused=True needs the three-action MlpPolicy and an evaluation normaliser (training=False) on the GPU")
+    L = _lib.lib()
+    step_idx = torch.zeros((), dtype=torch.int64, device=dev)
+    trace = torch.zeros((T, n, len(HL_TRACE_COLS)), dtype=torch.float64, device=dev)
+    is_f64 = int(venv.obs.dtype == torch.float64)
+    if fused:
+        from .rollout import FusedPpoUpdate
+        f = FusedPpoUpdate(policy, None, env.obs_dim)
+        f.load_params_from_torch()
+        flat = f.flat
+        act_raw = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+        logp = torch.zeros(n, dtype=torch.float32, device=dev)
+
+    def actions():
+        obs_n = env._process_obs(venv.obs, update=False)
+        with torch.no_grad():
+            a, _, _ = policy(obs_n, deterministic=True)
+        return clip_actions(a, venv).to(venv.torch_dtype)
+
+    def body():
+        if fused:
+            a = K.FwCollectHlArgs()
+            a.params, a.nets, a.deterministic = flat.data_ptr(), 1, 1
+            a.obs_mean, a.obs_var = env.obs_rms.mean.data_ptr(), env.obs_rms.var.data_ptr()
+            a.clip_obs, a.eps_obs = float(env.clip_obs), float(env.epsilon)
+            a.act_raw, a.logp = act_raw.data_ptr(), logp.data_ptr()
+            venv.collect_act_hl(a)
+            venv.step_low()
+        else:
+            venv.step_tensor(actions())
+        _lib.check(L.fw_trace_hl(_devptr(venv.obs), _devptr(venv.terminal_obs), _devptr(venv.terminated), _devptr(venv.truncated),
+                                 _devptr(venv.command), _devptr(venv.info), int(venv.info.shape[1]), is_f64, n, _devptr(trace), T,
+                                 _devptr(step_idx), torch.cuda.current_stream(dev).cuda_stream))
+
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        env.reset()
+        side.synchronize()                   # (get_state copies on the default stream)
+        stored = torch.as_tensor(venv.get_state()[:, K.S_TASK:K.S_TASK + 3], dtype=torch.float64, device=dev)   # the FW_SL_TARGET tail
+        start = trace_rows_hl(venv.obs, stored)
+        reps = T // graph_steps if graph_steps and graph_steps > 0 else 0
+        if reps:
+            if not fused:
+                actions()                    # one forward outside the capture warms its libraries up (no env state)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, stream=side):
+                for _ in range(graph_steps):
+                    body()
+            for _ in range(reps):
+                graph.replay()
+        for _ in range(T - reps * (graph_steps if reps else 0)):
+            body()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    tr = trace.cpu().numpy()
+    done = tr[:, :, len(HL_TRACE_COLS) - 1] != FLAG_RUNNING
+    ended_at = np.where(done.any(axis=0), done.argmax(axis=0), -1).astype(np.int64)
+    return HighLevelTrace(trace=tr, start=start.cpu().numpy(), dt=1.0 / float(venv.cfg.agent_hz), ended_at=ended_at)
