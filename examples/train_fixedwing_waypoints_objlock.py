@@ -51,6 +51,8 @@ def main():
     ap.add_argument("--detector", type=str, default="none", choices=["none", "cnn"])
     ap.add_argument("--image_res", type=int, default=32)
     ap.add_argument("--batch_size", type=int, default=None)
+    ap.add_argument("--diagnostics", action="store_true",
+                    help="SB3's train/* figures (approx_kl, clip_fraction, explained_variance, ...) in every printed update line")
     a = ap.parse_args()
     cfg = TRAIN_CONFIG
     model_dir, log_dir = os.path.join(a.out, "models"), os.path.join(a.out, "logs")
@@ -67,7 +69,7 @@ def main():
         checkpoint.load_vecnormalize(vecnorm, env, training=True, norm_reward=True)
     n_steps = R.n_steps_for(cfg["samples_per_update"], a.num_envs, world)
     batch_size = a.batch_size or (1024 if a.detector == "cnn" else cfg["batch_size"])
-    model = R.PPO(env, R.PPOConfig(n_steps=n_steps, batch_size=batch_size, detector=a.detector, image_res=a.image_res, n_epochs=cfg["n_epochs"], learning_rate=cfg["learning_rate"],
+    model = R.PPO(env, R.PPOConfig(diagnostics=a.diagnostics, n_steps=n_steps, batch_size=batch_size, detector=a.detector, image_res=a.image_res, n_epochs=cfg["n_epochs"], learning_rate=cfg["learning_rate"],
                                    gamma=cfg["gamma"], gae_lambda=cfg["gae_lambda"], clip_range=cfg["clip_range"], ent_coef=cfg["ent_coef"],
                                    vf_coef=cfg["vf_coef"], max_grad_norm=cfg["max_grad_norm"], seed=cfg["seed"]))
     if a.pretrained_model:
@@ -81,7 +83,7 @@ def main():
         def on_rollout_end(self, ppo):
             if ppo.num_timesteps - self.last >= 20 * n_steps * a.num_envs * world:
                 dt = time.perf_counter() - self.t0
-                print(json.dumps({"timesteps": ppo.num_timesteps, "fps": round(ppo.num_timesteps / dt), **{k: round(v, 5) for k, v in ppo.logs.items()},
+                print(json.dumps({"timesteps": ppo.num_timesteps, "fps": round(ppo.num_timesteps / dt), **{k: round(v, 5) for k, v in ppo.logs.items()}, **{k: round(v, 6) for k, v in ppo.diagnostics.items()},
                                   **{k: round(float(v), 4) for k, v in ev.last_scalars.items()}}), flush=True)
                 self.last = ppo.num_timesteps
             return True

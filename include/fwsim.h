@@ -571,6 +571,26 @@ int32_t fw_ppo_update_a3(float* params, float* mom_m, float* mom_v, const float*
                          int32_t n_minibatches, int32_t batch_size, int32_t obs_dim, const fw_ppo_hyper* hyper,
                          float* loss_acc, void* workspace, int64_t workspace_bytes, void* hip_stream);
 
+/* The learner with TRAINING DIAGNOSTICS (SB3's train/approx_kl, train/clip_fraction, the per-minibatch losses): the arguments of
+ * fw_ppo_update_a, then `diag` and its size in floats.  act_dim is 3, 4 or 6 (the workspace is sized by the width's own function:
+ * fw_ppo_update_workspace_bytes / _a / _a3); anything else, a NULL `diag` or diag_floats < fw_ppo_diag_floats(n_minibatches): FW_EINVAL.
+ * It runs the diagnostics instantiation of the kernel the plain entry point of that width would run (same cut, same exchanges, same
+ * status word and closing verdict); `params`, `mom_m`, `mom_v` and `loss_acc` end bit-identical to the plain call on the same inputs.
+ * diag: device float32, logically [n_minibatches][2 nets: policy, value][8 parts][4 waves][4] -- one row of four floats per WAVE of
+ * every workgroup, written once per minibatch with a plain 16-byte store (no atomics, no wait):
+ *   policy rows  { sum -min(l1, l2), sum (ratio - 1) - (logp - old_logp), count |ratio - 1| > clip_range, E } each over the samples the
+ *                wave owns and times 1 / batch_size; E = the minibatch's entropy loss -sum_k (0.5 + 0.5 ln 2 pi + log_std_k), at the
+ *                log_std its forward pass used, in the row of part 0 / wave 0 and zero in every other row;
+ *   value rows   { sum (v - return)^2 / batch_size, 0, 0, 0 }.
+ * Rows of parts the cut does not use are not written: the caller zeroes `diag` before the call and sums a minibatch's 32 rows per net
+ * in index order (a fixed order: the same bits in every run).  On a non-zero status `diag` is undefined. */
+int64_t fw_ppo_diag_floats(int32_t n_minibatches);
+int32_t fw_ppo_update_diag(float* params, float* mom_m, float* mom_v, const float* obs, const float* act,
+                           const float* old_logp, const float* adv, const float* ret, const int32_t* perm,
+                           int32_t n_minibatches, int32_t batch_size, int32_t obs_dim, int32_t act_dim, const fw_ppo_hyper* hyper,
+                           float* loss_acc, void* workspace, int64_t workspace_bytes, void* hip_stream,
+                           float* diag, int64_t diag_floats);
+
 /* Rollout collection between two env steps (SB3 OnPolicyAlgorithm.collect_rollouts + VecNormalize reward path,
  * train/train_Fixedwing_Waypoints_v3.py:260,293-310), for the same MlpPolicy / flat parameter image as fw_ppo_update.
  * fw_policy_act: obs[N,obs_dim] (normalised, float32) -> for `nets` bit 0 (policy): act_raw[N,4] = mean + sigma * z

@@ -25,6 +25,7 @@ EXPORTS = (
     "fw_policy_act_a", "fw_collect_act_a",
     "fw_ppo_param_count_a3", "fw_ppo_moment_count_a3", "fw_ppo_moment_map_a3", "fw_ppo_update_workspace_bytes_a3", "fw_ppo_update_a3",
     "fw_collect_act_hl", "fw_sizeof_collect_hl_args", "fw_eval_track_hl", "fw_trace_hl",
+    "fw_ppo_diag_floats", "fw_ppo_update_diag",
 )
 
 
@@ -161,6 +162,10 @@ def lib() -> C.CDLL:
         L.fw_ppo_update_workspace_bytes_a3.restype = i64; L.fw_ppo_update_workspace_bytes_a3.argtypes = [i32, i32, i32]
         L.fw_ppo_update_a3.restype = i32
         L.fw_ppo_update_a3.argtypes = [vp] * 9 + [i32, i32, i32, vp, vp, vp, i64, vp]
+        # the diagnostics form: the *_a argument list (act_dim 3, 4 or 6), then the diagnostics buffer and its size in floats
+        L.fw_ppo_diag_floats.restype = i64; L.fw_ppo_diag_floats.argtypes = [i32]
+        L.fw_ppo_update_diag.restype = i32
+        L.fw_ppo_update_diag.argtypes = [vp] * 9 + [i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, i64]
         L.fw_collect_act_hl.restype = i32; L.fw_collect_act_hl.argtypes = [vp, vp, vp]
         L.fw_sizeof_collect_hl_args.restype = i32; L.fw_sizeof_collect_hl_args.argtypes = []
         L.fw_policy_act_a.restype = i32

@@ -2144,15 +2144,17 @@ int set_state_T(fw_env* h, const double* in) {
 
 namespace {
 // The learner's kernels: one lookup per family, used by the launch and by the LDS opt-in in front of it.
-const void* ppo_update_kernel(int act_dim, int ch /*samples per pass*/, int ns /*blocks per network of the reduce-scatter form, 0: all-to-all*/) {
-  struct Row { int ch, ns; const void* a4; const void* a6; const void* a3; };
-#define FW_PPO_ROW(CH, NS) {CH, NS, kfn(fw_ppo_update_kernel<CH, NS>), kfn(fw_ppo_update_kernel_a6<CH, NS>), kfn(fw_ppo_update_kernel_a3<CH, NS>)}
+// (diag: the diagnostics form of the same row -- fw_ppo_update_diag; the plain entry points never ask for it)
+const void* ppo_update_kernel(int act_dim, int ch /*samples per pass*/, int ns /*blocks per network of the reduce-scatter form, 0: all-to-all*/, bool diag = false) {
+  struct Row { int ch, ns; const void* a4; const void* a6; const void* a3; const void* d4; const void* d6; const void* d3; };
+#define FW_PPO_ROW(CH, NS) {CH, NS, kfn(fw_ppo_update_kernel<CH, NS>), kfn(fw_ppo_update_kernel_a6<CH, NS>), kfn(fw_ppo_update_kernel_a3<CH, NS>), \
+                            kfn(fw_ppo_update_diag_kernel<CH, NS, 4>), kfn(fw_ppo_update_diag_kernel<CH, NS, 6>), kfn(fw_ppo_update_diag_kernel<CH, NS, 3>)}
   static const Row rows[] = {
     FW_PPO_ROW(64, 8), FW_PPO_ROW(64, 4), FW_PPO_ROW(64, 0), FW_PPO_ROW(32, 8), FW_PPO_ROW(32, 4), FW_PPO_ROW(32, 0),
     FW_PPO_ROW(16, 8), FW_PPO_ROW(16, 4), FW_PPO_ROW(16, 0),
   };
 #undef FW_PPO_ROW
-  for (const Row& r : rows) if (r.ch == ch && r.ns == ns) return act_dim == 6 ? r.a6 : act_dim == 3 ? r.a3 : r.a4;
+  for (const Row& r : rows) if (r.ch == ch && r.ns == ns) return diag ? (act_dim == 6 ? r.d6 : act_dim == 3 ? r.d3 : r.d4) : (act_dim == 6 ? r.a6 : act_dim == 3 ? r.a3 : r.a4);
   return nullptr;
 }
 // the pre-pass that packs the rows, and the entry point that sizes the workspace (for the message), by action width
@@ -2694,7 +2696,7 @@ int64_t fw_ppo_update_workspace_bytes_a3(int32_t n_minibatches, int32_t batch_si
 static int32_t ppo_update(float* params, float* mom_m, float* mom_v, const float* obs, const float* act, const float* old_logp,
                           const float* adv, const float* ret, const int32_t* perm, int32_t n_minibatches, int32_t batch_size,
                           int32_t obs_dim, int32_t act_dim, const fw_ppo_hyper* hyper, float* loss_acc, void* workspace, int64_t workspace_bytes,
-                          void* hip_stream, const char* who) {
+                          void* hip_stream, const char* who, float* diag = nullptr /* fw_ppo_update_diag: the diagnostics buffer, checked by the caller */) {
   static_assert(sizeof(fw_ppo_hyper) == sizeof(PpoHyper), "fw_ppo_hyper layout");
   const std::string w = who;
   if (!params || !mom_m || !mom_v || !obs || !act || !old_logp || !adv || !ret || !perm || !hyper || n_minibatches <= 0) {
@@ -2748,11 +2750,12 @@ static int32_t ppo_update(float* params, float* mom_m, float* mom_v, const float
   }
   const int ns = cut.nsplit >= 4 && rs_env ? cut.nsplit : 0;      // the kernel's NS: 0 = all-to-all swap of whole partials
   const dim3 grid(16 * cut.nsplit);                 // (every 8th block works -- see the kernel)
-  const void* fn = ppo_update_kernel(act_dim, cut.ch, ns);
+  const void* fn = ppo_update_kernel(act_dim, cut.ch, ns, diag != nullptr);
   if (!fn) { g_err = w + ": no kernel is built for " + std::to_string(cut.ch) + " samples per pass x " + std::to_string(ns) + " blocks per network"; return FW_EINVAL; }
   if (int rc = ensure_dynamic_lds(nullptr, dev, fn, lds)) return rc;
-  void* args[] = { &A };
-  (void)hipLaunchKernel(fn, grid, dim3(kPThreads), args, lds, st);
+  void* args_plain[] = { &A };
+  void* args_diag[] = { &A, &diag };                // (the diagnostics kernels take the buffer as a second parameter)
+  (void)hipLaunchKernel(fn, grid, dim3(kPThreads), diag ? args_diag : args_plain, lds, st);
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }
@@ -2777,6 +2780,24 @@ int32_t fw_ppo_update_a3(float* params, float* mom_m, float* mom_v, const float*
                          void* hip_stream) {
   return ppo_update(params, mom_m, mom_v, obs, act, old_logp, adv, ret, perm, n_minibatches, batch_size, obs_dim, 3, hyper, loss_acc,
                     workspace, workspace_bytes, hip_stream, "fw_ppo_update_a3");
+}
+// the diagnostics form: the same call on the diagnostics instantiation of the same kernel row
+int64_t fw_ppo_diag_floats(int32_t n_minibatches) {
+  if (n_minibatches <= 0) { g_err = "fw_ppo_diag_floats: n_minibatches must be positive"; return FW_EINVAL; }
+  return (int64_t)ppo_diag_floats(n_minibatches);
+}
+int32_t fw_ppo_update_diag(float* params, float* mom_m, float* mom_v, const float* obs, const float* act, const float* old_logp,
+                           const float* adv, const float* ret, const int32_t* perm, int32_t n_minibatches, int32_t batch_size,
+                           int32_t obs_dim, int32_t act_dim, const fw_ppo_hyper* hyper, float* loss_acc, void* workspace, int64_t workspace_bytes,
+                           void* hip_stream, float* diag, int64_t diag_floats) {
+  if (act_dim != 3 && act_dim != 4 && act_dim != 6) { g_err = "fw_ppo_update_diag: act_dim must be 3, 4 or 6 (got " + std::to_string(act_dim) + ")"; return FW_EINVAL; }
+  if (!diag) { g_err = "fw_ppo_update_diag: diag is NULL"; return FW_EINVAL; }
+  if (n_minibatches <= 0) { g_err = "fw_ppo_update_diag: n_minibatches must be positive"; return FW_EINVAL; }
+  if (diag_floats < (int64_t)ppo_diag_floats(n_minibatches)) {
+    g_err = "fw_ppo_update_diag: diag smaller than fw_ppo_diag_floats(n_minibatches)"; return FW_EINVAL;
+  }
+  return ppo_update(params, mom_m, mom_v, obs, act, old_logp, adv, ret, perm, n_minibatches, batch_size, obs_dim, act_dim, hyper, loss_acc,
+                    workspace, workspace_bytes, hip_stream, "fw_ppo_update_diag", diag);
 }
 
 int32_t fw_ppo_update_status(const void* workspace, int64_t workspace_bytes, uint32_t* status_out, uint32_t* paths_out, void* hip_stream) {

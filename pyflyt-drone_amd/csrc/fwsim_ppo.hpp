@@ -455,6 +455,13 @@ __device__ __forceinline__ bool ppo_wait(const PpoArgs& A, LOAD&& load, DONE&& d
   return false;
 }
 
+// The diagnostics buffer of fw_ppo_update_diag: float32 [n_mb][2 nets][kPMaxSplit parts][4 waves][4], one row per wave (include/fwsim.h)
+constexpr int kPDiagRow = 4, kPDiagMb = 2 * kPMaxSplit * 4 * kPDiagRow;
+__host__ __device__ inline size_t ppo_diag_row(int mb, int net, int part, int wave) {
+  return (size_t)mb * kPDiagMb + (size_t)(((net * kPMaxSplit + part) * 4 + wave) * kPDiagRow);
+}
+__host__ __device__ inline long long ppo_diag_floats(int n_mb) { return (long long)n_mb * kPDiagMb; }
+
 // CH = samples per pass through the network (64: 2 x 2 tiles of 32 x 32 per product; 32 / 16: 2 / 1 x 4 tiles of 16 x 16, see ppo_mfma16_rows);
 // part / nsplit: this block's place among the blocks of its network (chunk c of a minibatch is run by block c % nsplit).
 // NS = 0: the (1, 2 or 4) blocks of a network swap whole partials all to all.  NS = 4 / 8 (then nsplit == NS): the gradient swap is a
@@ -510,8 +517,12 @@ template <int N> __device__ __forceinline__ float ppo_tree_sum(const float (&v)[
 // slots -- and leave the fourth place idle: the head / loss lane hc = 3 of a quad contributes nothing (no log-prob term, no gradient),
 // column 3 of gout / sA is never read into a sum, and the elements uq = 3 of Wo's thread row do not exist (uq < KO).  Rows of Wo are 12
 // bytes: a head thread fetches its HPER rows as one run of 3 HPER floats (16-byte aligned: HPER is a multiple of 4).
-template <int NET, int CH, int NS, int NA>
-__device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const int part, const int nsplit) {
+// DIAG: the diagnostics form (fw_ppo_update_diag): per minibatch every wave leaves one float4 of sums over the samples it owns in its own
+// row of `diag` (layout: include/fwsim.h, ppo_diag_row) -- the values are in registers in the head phase anyway, the wave sum runs on the
+// vector ALU and the row is one plain 16-byte store of lane 0: no barrier, no LDS, no exchange word, no wait.  Nothing of it feeds
+// back: what reaches params / mom_m / mom_v / loss_acc is the arithmetic of the plain form, bit for bit.
+template <int NET, int CH, int NS, int NA, bool DIAG = false>
+__device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const int part, const int nsplit, float* diag = nullptr) {
   static_assert(NA == 3 || NA == 4 || NA == 6, "action width");
   static_assert(NS == 0 || NS == 4 || NS == 8, "blocks per network in the reduce-scatter form");
   constexpr bool RS = NS != 0;
@@ -734,6 +745,13 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
     const float iv_c = NET == 0 ? expf(-2.0f * ls_c) : 0.f;
     const float ls_c2 = A6 ? log_std[A6 ? 4 + ((t % HSL) & 1) : 0] : 0.f;      // (six actions: component 4 + hc of the lanes with hc < 2)
     const float iv_c2 = A6 ? expf(-2.0f * ls_c2) : 0.f;
+    // (diagnostics) this minibatch's sums over the samples of this thread: policy -min(l1, l2), (ratio - 1) - log ratio, 1 where clipped;
+    // value dv^2 -- and the entropy loss at the log_std this minibatch's forward uses (the Adam step below moves it)
+    [[maybe_unused]] float dg_a = 0.f, dg_kl = 0.f, dg_cf = 0.f, dg_ent = 0.f;
+    if constexpr (DIAG && NET == 0) {
+#pragma unroll
+      for (int k = 0; k < NA; ++k) dg_ent -= 1.4189385332046727f + log_std[k];
+    }
     // gradient accumulators of this minibatch (registers)
     f32x16 gW2, gW1;
     float gb1p = 0.f, gb2p = 0.f;                                     // column-sum partials of this thread's 16 rows
@@ -920,6 +938,13 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
           const float rc = fminf(fmaxf(ratio, 1.0f - H.clip_range), 1.0f + H.clip_range);
           const float l1 = a * ratio, l2 = a * rc;
           if (hq == 0) acc_l += -fminf(l1, l2);
+          if constexpr (DIAG) {
+            if (hq == 0) {
+              dg_a += -fminf(l1, l2);
+              dg_kl += (ratio - 1.0f) - (logp - old_lp);
+              dg_cf += fabsf(ratio - 1.0f) > H.clip_range ? 1.0f : 0.f;
+            }
+          }
           // d(-min(l1, l2))/dlogp: through l1 when it is the smaller; on a tie (ratio inside the range: rc == ratio)
           // torch.min halves the gradient between the two branches and the clamp passes its half
           const bool inside = ratio >= 1.0f - H.clip_range && ratio <= 1.0f + H.clip_range;
@@ -940,6 +965,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
         } else {
           const float dv = (o[0] + bo_c) - ret_s;
           if (hq == 0) acc_l += dv * dv;
+          if constexpr (DIAG) { if (hq == 0) dg_a += dv * dv; }
           const float g = H.vf_coef * 2.0f * dv * invB;
           if (hq == 0) { gout[s * SA] = g; gbo_p += g; }
         }
@@ -1079,6 +1105,13 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
 #ifdef FW_PPO_PROF
     const long long pf3 = PPO_T();
 #endif
+    if constexpr (DIAG) {
+      // this wave's row of the minibatch: [loss sum / B, KL sum / B, clipped count / B, entropy loss (first wave of the policy's part 0)]
+      const float s0 = ppo_wave_sum(dg_a), s1 = NET == 0 ? ppo_wave_sum(dg_kl) : 0.f, s2 = NET == 0 ? ppo_wave_sum(dg_cf) : 0.f;
+      if (lane == 0)
+        *reinterpret_cast<float4*>(diag + ppo_diag_row(mb, NET, part, wave)) =
+            make_float4(s0 * invB, s1 * invB, s2 * invB, NET == 0 && part == 0 && wave == 0 ? dg_ent : 0.f);
+    }
     // ---- finish the per-thread gradients: the four row-block partials of the biases; dWo over the quad's sample quarters;
     // dbo / dlog_std component hq over all samples ----
     float my_gwo = 0.f, my_gwo2 = 0.f;                 // Wo[us][uq]; six actions: Wo[us][4 + uq] (uq < 2)
@@ -1721,6 +1754,16 @@ __global__ __launch_bounds__(kPThreads) void fw_ppo_update_kernel_a6(PpoArgs A) 
   const int i = (int)blockIdx.x >> 3;
   const int part = i >> 1, nsplit = NS ? NS : (int)gridDim.x >> 4;
   if ((i & 1) == 0) ppo_net_body<0, CH, NS, 6>(A, lds, part, nsplit); else ppo_net_body<1, CH, NS, 6>(A, lds, part, nsplit);
+}
+
+// the diagnostics form, every action width: the same grid and arguments, plus the caller's diagnostics buffer
+template <int CH, int NS, int NA>
+__global__ __launch_bounds__(kPThreads) void fw_ppo_update_diag_kernel(PpoArgs A, float* diag) {
+  extern __shared__ __align__(16) float lds[];
+  if (blockIdx.x & 7) return;
+  const int i = (int)blockIdx.x >> 3;
+  const int part = i >> 1, nsplit = NS ? NS : (int)gridDim.x >> 4;
+  if ((i & 1) == 0) ppo_net_body<0, CH, NS, NA, true>(A, lds, part, nsplit, diag); else ppo_net_body<1, CH, NS, NA, true>(A, lds, part, nsplit, diag);
 }
 
 // How a minibatch of B samples is cut: samples per pass (64, 32 or 16) and blocks per network.  The path is sequential, so the

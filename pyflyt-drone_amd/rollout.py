@@ -570,6 +570,9 @@ class PPOConfig:
                                            # three-launch collector (fw_collect_act_a -> fw_step -> fw_collect_stats); off: the torch path
     fused_three_actions: bool = False      # the three-action policy of the high-level command task on the fused paths too: fw_ppo_update_a3 and
                                            # the collector fw_collect_act_hl -> fw_step -> fw_collect_stats (single process); off: the torch path
+    diagnostics: bool = False              # SB3's train/* figures after every train(): PPO.diagnostics (approx_kl, clip_fraction, explained_variance,
+                                           # the losses, std, ...) and PPO.diagnostic_series (per minibatch); the fused learner then runs
+                                           # fw_ppo_update_diag; off: nothing changes
     dist_update: str = "replicated"        # multi-process job: "replicated" = all-gather the rollout shards, every rank runs the same
                                            # minibatch sequence (no per-minibatch collective); "allreduce" = local minibatches + gradient all-reduce
 
@@ -577,6 +580,42 @@ class PPOConfig:
 class _PpoHyper(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("lr", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "beta1", "beta2", "eps",
                                          "adv_mean", "adv_std")] + [("norm_adv", C.c_int32), ("step0", C.c_int32)]
+
+
+DIAG_SERIES = ("approx_kl", "clip_fraction", "policy_loss", "value_loss", "entropy_loss")
+
+
+def fused_diag_series(diag: np.ndarray, n_mb: int) -> Dict[str, np.ndarray]:
+    """The per-minibatch figures from the buffer of ``fw_ppo_update_diag`` (include/fwsim.h: float32
+    [n_mb][policy, value][8 parts][4 waves][4]): a minibatch's rows are added in index order, in float64 -- a fixed order, so two runs
+    on the same inputs give the same bits."""
+    d = np.asarray(diag, dtype=np.float32).reshape(n_mb, 2, -1, 4)
+    acc = np.zeros((n_mb, 2, 4), dtype=np.float64)
+    for row in range(d.shape[2]):
+        acc += d[:, :, row, :]
+    return {"approx_kl": acc[:, 0, 1].copy(), "clip_fraction": acc[:, 0, 2].copy(), "policy_loss": acc[:, 0, 0].copy(),
+            "value_loss": acc[:, 1, 0].copy(), "entropy_loss": acc[:, 0, 3].copy()}
+
+
+def explained_variance(values, returns) -> float:
+    """SB3's ``explained_variance(y_pred, y_true)``: ``1 - var(returns - values) / var(returns)``, population variances in float64;
+    NaN when the returns do not vary."""
+    y_pred = np.asarray(values, dtype=np.float64).reshape(-1)
+    y_true = np.asarray(returns, dtype=np.float64).reshape(-1)
+    var_y = np.var(y_true)
+    return float("nan") if var_y == 0 else float(1.0 - np.var(y_true - y_pred) / var_y)
+
+
+def per_epoch(series: Dict[str, np.ndarray], n_epochs: int) -> Dict[str, np.ndarray]:
+    """``PPO.diagnostic_series`` folded to one value per epoch: the mean over the epoch's minibatches (``[n_epochs]`` each) -- how
+    approx_kl and the clip fraction grow as the epochs move the policy away from the one that collected the rollout."""
+    out = {}
+    for k, v in series.items():
+        v = np.asarray(v, dtype=np.float64)
+        if n_epochs <= 0 or v.size % n_epochs:
+            raise ValueError(f"series '{k}' of {v.size} minibatches does not divide into {n_epochs} epochs")
+        out[k] = v.reshape(n_epochs, -1).mean(axis=1)
+    return out
 
 
 class FusedPpoUpdate:
@@ -620,6 +659,8 @@ class FusedPpoUpdate:
         self.last_paths = 0                # fw_ppo_update_status: which exchanges of the last call went through a shared L2
         self._sig = None                   # state_signature() of module + optimiser when the images were last known equal to them (commit())
         self._param_sig = None             # param_signature() when `flat` was last loaded from / stored to the module
+        self._diag = None                  # PPOConfig.diagnostics: the caller-owned buffer of fw_ppo_update_diag (grown here, zeroed per call)
+        self.diag_series = None            # ... and the last successful call's per-minibatch figures (float64 [n_mb] each)
 
     def _workspace(self, n_mb: int, batch_size: int) -> torch.Tensor:
         # exchange words + gradient hand-off buffer + the packed rows of every minibatch (a parallel pre-pass of the call writes them)
@@ -753,9 +794,21 @@ class FusedPpoUpdate:
             assert x.dtype == torch.float32 and x.is_contiguous()
         assert perm_i32.dtype == torch.int32 and perm_i32.numel() == n_mb * cfg.batch_size
         ws = self._workspace(n_mb, cfg.batch_size)
-        rc = self._abi["update"](_p(self.flat), _p(self.mom_m), _p(self.mom_v), _p(obs), _p(act), _p(old_logp), _p(adv), _p(ret),
-                                 _p(perm_i32), n_mb, cfg.batch_size, self.D, C.byref(H), _p(self.loss), _p(ws), ws.numel(),
-                                 _stream(obs.device))
+        diag = bool(getattr(cfg, "diagnostics", False))
+        self.diag_series = None
+        if diag:
+            # the diagnostics instantiation of the same kernel row: one float4 per wave and minibatch into a buffer of ours
+            nd = int(_lib.lib().fw_ppo_diag_floats(n_mb))
+            if self._diag is None or self._diag.numel() < nd:
+                self._diag = torch.empty(nd, dtype=torch.float32, device=self.flat.device)
+            self._diag.zero_()             # (rows of parts the cut does not use stay zero: the sums below take every row)
+            rc = _lib.lib().fw_ppo_update_diag(_p(self.flat), _p(self.mom_m), _p(self.mom_v), _p(obs), _p(act), _p(old_logp), _p(adv),
+                                               _p(ret), _p(perm_i32), n_mb, cfg.batch_size, self.D, self.A, C.byref(H), _p(self.loss),
+                                               _p(ws), ws.numel(), _stream(obs.device), _p(self._diag), self._diag.numel())
+        else:
+            rc = self._abi["update"](_p(self.flat), _p(self.mom_m), _p(self.mom_v), _p(obs), _p(act), _p(old_logp), _p(adv), _p(ret),
+                                     _p(perm_i32), n_mb, cfg.batch_size, self.D, C.byref(H), _p(self.loss), _p(ws), ws.numel(),
+                                     _stream(obs.device))
         _lib.check(rc)
         # the workgroups of the launch wait for each other, every wait bounded: a wait that ran out leaves a status word behind and
         # (unless the closing verdict itself was lost) untouched images -- surface it BEFORE anything is written back to the module /
@@ -770,6 +823,8 @@ class FusedPpoUpdate:
             raise RuntimeError(f"fw_ppo_update gave up inside the launch (status {st.value}: {', '.join(names)} wait ran out); "
                                "the policy and optimiser were left as they were before the call")
         self._pending_step = step0 + n_mb      # commit() moves the result into the module / optimiser
+        if diag:                               # the one device-to-host copy of the diagnostics, behind the status check
+            self.diag_series = fused_diag_series(self._diag[:nd].cpu().numpy(), n_mb)
         return (self.loss[:3] / n_mb).tolist()
 
     def commit(self) -> None:
@@ -878,6 +933,12 @@ class PPO:
         self.last_starts = torch.ones(N, **f32)
         self.num_timesteps = 0
         self.logs: Dict[str, float] = {}
+        # PPOConfig.diagnostics: SB3's train/* scalars of the last train() and their per-minibatch series (not part of a checkpoint)
+        self.diagnostics: Dict[str, float] = {}
+        self.diagnostic_series: Dict[str, np.ndarray] = {}
+        self._n_updates = 0                # SB3's _n_updates: epochs trained so far
+        self._diag_buf = self._diag_i = None      # torch path: [rows, 5] float32 device buffer and the device-side minibatch counter
+        self._g_update_diag = False               # ... and whether the captured update graph books its rows
 
     # ---- SB3 OnPolicyAlgorithm.collect_rollouts ---------------------------------------------
     def _rollout_body(self):
@@ -1228,6 +1289,57 @@ class PPO:
         torch.nn.utils.clip_grad_norm_(params, cfg.max_grad_norm)
         self.optimizer.step()
         self._loss_acc += torch.stack([policy_loss.detach(), value_loss.detach(), entropy_loss.detach()])
+        if cfg.diagnostics:
+            # SB3's per-minibatch figures into row `_diag_i` of a persistent buffer, the counter on the device: no host sync, and the
+            # captured update graph books each replay into the next row (columns: DIAG_SERIES)
+            with torch.no_grad():
+                log_ratio = logp - old_logp[idx]
+                row = torch.stack([((ratio - 1) - log_ratio).mean(), (torch.abs(ratio - 1) > cfg.clip_range).float().mean(),
+                                   policy_loss.detach(), value_loss.detach(), entropy_loss.detach()])
+                self._diag_buf.index_copy_(0, self._diag_i, row.unsqueeze(0))
+                self._diag_i += 1
+
+    def _diag_begin(self, rows: int) -> None:
+        """torch path: room for ``rows`` minibatches (and the warm-up steps of a graph capture), counter at zero."""
+        rows = max(rows, 4)
+        if self._diag_buf is None or self._diag_buf.shape[0] < rows:
+            self._diag_buf = torch.zeros((rows, len(DIAG_SERIES)), dtype=torch.float32, device=self.device)
+            self._diag_i = torch.zeros(1, dtype=torch.long, device=self.device)
+            self._g_update = None          # (a captured graph holds the old buffer's address)
+        self._diag_buf.zero_(); self._diag_i.zero_()
+
+    def _diag_clear(self) -> None:
+        self.diagnostics, self.diagnostic_series = {}, {}
+
+    def _diag_finish(self, series: Dict[str, np.ndarray], adv, ret) -> None:
+        """``diagnostics`` / ``diagnostic_series`` of the update that just ended (SB3 ``PPO.train()``'s logger records)."""
+        cfg = self.cfg
+        # explained variance of the rollout that was consumed: the value predictions against the returns.  A replicated sharded job
+        # looks at the gathered rollout, whose values are ret - adv (the gathered buffers carry no value column)
+        values = (ret - adv) if self._replicated else self.buf_val.reshape(-1)
+        ev = explained_variance(values.detach().cpu().numpy(), ret.detach().cpu().numpy())
+        names = list(DIAG_SERIES)
+        td = _dist()
+        if td is not None and not self._replicated:
+            # "allreduce" mode: every rank walked its own minibatches -- the series (and the explained variance of the rank's own
+            # rollout) become the mean over the ranks, with ONE all-reduce
+            pack = torch.as_tensor(np.concatenate([series[k] for k in names] + [np.array([ev])]), dtype=torch.float64, device=self.device)
+            pack = (all_reduce_sum_(pack) / td.get_world_size()).cpu().numpy()
+            n = series[names[0]].size
+            series = {k: pack[i * n:(i + 1) * n].copy() for i, k in enumerate(names)}
+            ev = float(pack[-1])
+        self.diagnostic_series = {k: np.asarray(series[k], dtype=np.float64) for k in names}
+        s = self.diagnostic_series
+        self.diagnostics = {
+            "train/approx_kl": float(s["approx_kl"].mean()), "train/clip_fraction": float(s["clip_fraction"].mean()),
+            "train/policy_gradient_loss": float(s["policy_loss"].mean()), "train/value_loss": float(s["value_loss"].mean()),
+            "train/entropy_loss": float(s["entropy_loss"].mean()),
+            "train/loss": float(s["policy_loss"][-1] + cfg.ent_coef * s["entropy_loss"][-1] + cfg.vf_coef * s["value_loss"][-1]),
+            "train/explained_variance": ev,
+            "train/std": float(torch.exp(self.policy.log_std.detach()).mean().item()),
+            "train/n_updates": float(self._n_updates), "train/clip_range": float(cfg.clip_range),
+            "train/learning_rate": float(self.optimizer.param_groups[0]["lr"]),
+        }
 
     def _update_buffers(self):
         """``(obs, act, old_logp, adv, ret)`` flattened to [B, ...] as the update walks them: the rank's own rollout, or --
@@ -1270,6 +1382,8 @@ class PPO:
 
     def train(self):
         cfg = self.cfg
+        if cfg.diagnostics or self.diagnostics:
+            self._diag_clear()             # (a train() that raises, or one with the flag switched off, leaves no figures of an earlier update behind)
         st, st_all = self._collect_status_word(wait=True, collective=True)     # a void rollout must not reach the update -- on any rank
         if st_all:
             msg = self._take_back_void_rollout(st, st_all)
@@ -1311,17 +1425,25 @@ class PPO:
             if err is not None:
                 self._flat_current = False     # the flat image holds a result that was not committed
                 self._fused.synced = False
+                self._diag_clear()             # (never the figures of an earlier update next to a failed one)
                 raise err
             self._fused.commit()
             self._g_update = None              # the torch-path graph (if any) holds stale Adam state
             self._flat_current = True          # store_to_torch left flat == the module parameters
             self.logs = {"policy_loss": la[0], "value_loss": la[1], "entropy_loss": la[2],
                          "adv_mean": float(g_mean), "adv_std": float(g_std)}
+            self._n_updates += cfg.n_epochs    # (counted with the flag off too: SB3's figure is the epochs trained, not the epochs watched)
+            if cfg.diagnostics:
+                self._diag_finish(self._fused.diag_series, adv, ret)
             return
         self._flat_current = False             # the torch path below moves the module parameters
         if self._fused is not None:
             self._fused.synced = False
         use_graph = self._graphs and B % bs == 0
+        if cfg.diagnostics:
+            self._diag_begin(cfg.n_epochs * ((B + bs - 1) // bs))
+        if self._g_update is not None and self._g_update_diag != bool(cfg.diagnostics):
+            self._g_update = None              # the captured step books a diagnostics row or not as the flag stood at capture
         if use_graph and self._g_update is None:
             self._idx = torch.zeros(bs, dtype=torch.long, device=self.device)
             self._gm = torch.zeros((), device=self.device); self._gs = torch.ones((), device=self.device)
@@ -1336,6 +1458,7 @@ class PPO:
                     self._minibatch_step(obs, act, old_logp, self._adv_s, self._ret_s, self._idx, self._gm, self._gs, params)
             torch.cuda.current_stream().wait_stream(st); torch.cuda.synchronize()
             self._g_update = torch.cuda.CUDAGraph()
+            self._g_update_diag = bool(cfg.diagnostics)
             with torch.cuda.graph(self._g_update):
                 self._minibatch_step(obs, act, old_logp, self._adv_s, self._ret_s, self._idx, self._gm, self._gs, params)
             with torch.no_grad():                                # undo the warm-up: weights and Adam moments / step
@@ -1349,6 +1472,8 @@ class PPO:
                             else:
                                 v.zero_()
             self._loss_acc.zero_()
+            if cfg.diagnostics:            # (the warm-up steps booked rows too)
+                self._diag_buf.zero_(); self._diag_i.zero_()
         if use_graph:
             self._adv_s.copy_(adv); self._ret_s.copy_(ret); self._gm.copy_(g_mean); self._gs.copy_(g_std)
         for _ in range(cfg.n_epochs):
@@ -1363,6 +1488,10 @@ class PPO:
         la = (self._loss_acc / nb).tolist()                      # the only host sync of the update
         self.logs = {"policy_loss": la[0], "value_loss": la[1], "entropy_loss": la[2],
                      "adv_mean": float(g_mean), "adv_std": float(g_std)}
+        self._n_updates += cfg.n_epochs
+        if cfg.diagnostics:
+            rows = self._diag_buf[:nb].to(torch.float64).cpu().numpy()
+            self._diag_finish({k: rows[:, i].copy() for i, k in enumerate(DIAG_SERIES)}, adv, ret)
 
     # does self._fused.flat hold the current policy parameters?  Clearing it also tells the fused update that its images (parameters
     # AND Adam moments) may be behind the module / optimiser: it then reloads them at its next call instead of reusing them
