@@ -37,6 +37,9 @@ def main():
     ap.add_argument("--total_timesteps", type=int, default=None)
     ap.add_argument("--num_envs", type=int, default=4096)
     ap.add_argument("--out", type=str, default="runs/obj_lock_only_ppo")
+    ap.add_argument("--episode_stats", action="store_true",
+                    help="SB3's rollout/* figures (ep_rew_mean, ep_len_mean, success_rate over the last 100 episodes, and the "
+                         "rollout/interval/* means over all episodes since the last line) in every printed update line")
     ap.add_argument("--diagnostics", action="store_true",
                     help="SB3's train/* figures (approx_kl, clip_fraction, explained_variance, ...) in every printed update line")
     a = ap.parse_args()
@@ -54,7 +57,7 @@ def main():
     if vecnorm:
         checkpoint.load_vecnormalize(vecnorm, env, training=True, norm_reward=True)
     n_steps = R.n_steps_for(cfg["samples_per_update"], a.num_envs, world)      # holds the samples per update: n_steps ~ 1 / (envs x world)
-    model = R.PPO(env, R.PPOConfig(diagnostics=a.diagnostics, n_steps=n_steps, batch_size=cfg["batch_size"], n_epochs=cfg["n_epochs"], learning_rate=cfg["learning_rate"],
+    model = R.PPO(env, R.PPOConfig(diagnostics=a.diagnostics, episode_stats=a.episode_stats, n_steps=n_steps, batch_size=cfg["batch_size"], n_epochs=cfg["n_epochs"], learning_rate=cfg["learning_rate"],
                                    gamma=cfg["gamma"], gae_lambda=cfg["gae_lambda"], clip_range=cfg["clip_range"], ent_coef=cfg["ent_coef"],
                                    vf_coef=cfg["vf_coef"], max_grad_norm=cfg["max_grad_norm"], seed=cfg["seed"]))
     if a.pretrained_model:
@@ -68,7 +71,7 @@ def main():
         def on_rollout_end(self, ppo):
             if ppo.num_timesteps - self.last >= 20 * n_steps * a.num_envs * world:
                 dt = time.perf_counter() - self.t0
-                print(json.dumps({"timesteps": ppo.num_timesteps, "fps": round(ppo.num_timesteps / dt), **{k: round(v, 5) for k, v in ppo.logs.items()}, **{k: round(v, 6) for k, v in ppo.diagnostics.items()},
+                print(json.dumps({"timesteps": ppo.num_timesteps, "fps": round(ppo.num_timesteps / dt), **{k: round(v, 5) for k, v in ppo.logs.items()}, **{k: round(v, 6) for k, v in ppo.diagnostics.items()}, **{k: round(v, 5) for k, v in ppo.rollout_stats.items()},
                                   **{k: round(float(v), 4) for k, v in ev.last_scalars.items()}}), flush=True)
                 self.last = ppo.num_timesteps
             return True

@@ -395,6 +395,24 @@ int32_t fw_gae(const float* rewards, const float* values, const float* episode_s
 int32_t fw_eval_track(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
                       int32_t info_dim, const int64_t* targets, int64_t* counts, double* cur_rew, int64_t* cur_len, int64_t* step_ctr,
                       double* fin_rew, int64_t* fin_len, int64_t* fin_step, int32_t* fin_info, int32_t N, int32_t E, void* hip_stream);
+/* Episode statistics of a training run (monitor.EpisodeMonitor; SB3's Monitor + ep_info_buffer, DESIGN.md section 4b "Episode
+ * statistics").  The state block is the caller's: fw_episode_state_bytes(N, W) bytes of device memory, zeroed once (FW_EINVAL for
+ * N <= 0 or W <= 0), in 8-byte words:
+ *   [0]  episodes finished (int64; the ring's cursor is this mod W)      [1]  vec-steps folded       [2]  truncated episodes
+ *   [3]  sum of lengths     [4..9]  sums of the info columns FW_INFO_NUM_TARGETS_REACHED .. FW_INFO_IS_SUCCESS (all int64, exact)
+ *   [10] sum of returns     [11] sum of squared returns (double)         [12..15] reserved, zero
+ *   then the ring, W words each: return (double), length, vec-step index (1-based), env index, truncated flag (int64), and 4 W
+ *   words of info rows (int32 [W][FW_INFO_DIM]);  then per env, N words each: cur_ret (double), cur_len (int64).
+ * fw_episode_fold folds one vec-step: cur_ret[i] += reward[i] (env dtype, added in double), cur_len[i] += 1; where terminated |
+ * truncated the episode (cur_ret, cur_len, the step's index, i, truncated[i] != 0, the first min(info_dim, FW_INFO_DIM) columns of
+ * its info row -- zeros when info is NULL) is pushed and the accumulators are cleared.  Pushes are ordered by vec-step and inside one
+ * by ascending env index; the slot is the push rank mod W: the ring holds what collections.deque(maxlen=W) holds after extend() in
+ * env order, also when more than W episodes end in one step (only the last W of them are written).  The double sums are reduced in
+ * a fixed order (the same bits in every run).  One launch, one workgroup, graph-capturable: no host reads, fixed addresses.
+ * FW_EINVAL for a NULL reward / terminated / truncated / state, N <= 0, W <= 0, or info with info_dim <= 0. */
+int64_t fw_episode_state_bytes(int32_t N, int32_t W);
+int32_t fw_episode_fold(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
+                        int32_t info_dim, void* state, int32_t N, int32_t W, void* hip_stream);
 /* fw_eval_track for FW_TASK_LOWLEVEL, plus its tracking figures.  Everything fw_eval_track does, and from the
  * post-step observation row o of env i -- terminal_obs[i] where terminated | truncated, else obs[i]; [N, 21], obs_is_f64 the env
  * dtype -- with e_psi = wrap(o[18] - o[5]) (to [-pi, pi)), e_h = o[19] - o[11], e_V = o[20] - |o[6:9]|, w = |o[0:3]| it adds

@@ -26,6 +26,7 @@ EXPORTS = (
     "fw_ppo_param_count_a3", "fw_ppo_moment_count_a3", "fw_ppo_moment_map_a3", "fw_ppo_update_workspace_bytes_a3", "fw_ppo_update_a3",
     "fw_collect_act_hl", "fw_sizeof_collect_hl_args", "fw_eval_track_hl", "fw_trace_hl",
     "fw_ppo_diag_floats", "fw_ppo_update_diag",
+    "fw_episode_state_bytes", "fw_episode_fold",
 )
 
 
@@ -108,6 +109,10 @@ def lib() -> C.CDLL:
         L.fw_gae.restype = i32
         L.fw_eval_track.restype = i32
         L.fw_eval_track.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
+        if hasattr(L, "fw_episode_fold"):      # (an A/B library of an older commit -- FWSIM_LIB, tools/bench_lib.py -- predates the pair; build() insists on it)
+            L.fw_episode_state_bytes.restype = i64; L.fw_episode_state_bytes.argtypes = [i32, i32]
+            L.fw_episode_fold.restype = i32
+            L.fw_episode_fold.argtypes = [vp, i32, vp, vp, vp, i32, vp, i32, i32, vp]
         L.fw_eval_track_ll.restype = i32
         L.fw_eval_track_ll.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
         L.fw_eval_track_hl.restype = i32

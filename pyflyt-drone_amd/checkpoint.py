@@ -89,6 +89,8 @@ def snapshot(ppo, include_env_state: bool = True) -> dict:
         "abi_version": int(K.FW_ABI_VERSION),
         "state_dim": int(K.FW_STATE_DIM),
     }
+    if getattr(ppo, "episode_monitor", None) is not None:
+        sd["episode_stats"] = ppo.episode_monitor.state_dict()      # PPOConfig.episode_stats: window, totals, running episodes
     if include_env_state and hasattr(venv, "get_state"):
         sd["env_state"] = torch.from_numpy(np.ascontiguousarray(venv.get_state()))
         # the episodes that follow are a function of (seed, global env id, episode): record what the state was drawn under

@@ -2484,6 +2484,25 @@ int32_t fw_eval_track(const void* reward, int32_t reward_is_f64, const uint8_t* 
   return FW_OK;
 }
 
+int64_t fw_episode_state_bytes(int32_t N, int32_t W) {
+  if (N <= 0 || W <= 0) { g_err = "fw_episode_state_bytes: N and W must be positive, got N=" + std::to_string(N) + ", W=" + std::to_string(W); return FW_EINVAL; }
+  return 8 * ((int64_t)EP_HEADER_WORDS + (int64_t)W * (5 + kEpInfo / 2) + 2 * (int64_t)N);
+}
+
+int32_t fw_episode_fold(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
+                        int32_t info_dim, void* state, int32_t N, int32_t W, void* hip_stream) {
+  if (!reward || !terminated || !truncated || !state) { g_err = "fw_episode_fold: reward, terminated, truncated and state must be non-NULL"; return FW_EINVAL; }
+  if (N <= 0 || W <= 0) { g_err = "fw_episode_fold: N and W must be positive, got N=" + std::to_string(N) + ", W=" + std::to_string(W); return FW_EINVAL; }
+  if (info && info_dim <= 0) { g_err = "fw_episode_fold: info given with info_dim=" + std::to_string(info_dim); return FW_EINVAL; }
+  EpisodeFoldArgs A;
+  A.reward = reward; A.reward_is_f64 = reward_is_f64; A.terminated = terminated; A.truncated = truncated; A.info = info; A.info_dim = info_dim;
+  A.state = reinterpret_cast<int64_t*>(state); A.N = N; A.W = W;
+  DeviceGuard g(device_of(reward));
+  hipLaunchKernelGGL(fw_episode_fold_kernel, dim3(1), dim3(kEpThreads), 0, (hipStream_t)hip_stream, A);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+
 int32_t fw_eval_track_ll(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
                          int32_t info_dim, const void* obs, const void* terminal_obs, int32_t obs_is_f64, int32_t obs_dim,
                          const int64_t* targets, int64_t* counts, double* cur_rew, int64_t* cur_len, int64_t* step_ctr, double* cur_track,

@@ -153,6 +153,144 @@ __global__ __launch_bounds__(256) void fw_eval_track_hl_kernel(EvalTrackArgs A, 
   eval_track_body<false, true>(A, X, H);
 }
 
+// Episode statistics of a training run (monitor.EpisodeMonitor; SB3's Monitor / ep_info_buffer): one vec-step's rewards and dones into
+// the per-env accumulators, the finished episodes into a ring of W slots in SB3's order (by vec-step, inside one by ascending env
+// index; slot = push rank mod W: what collections.deque(maxlen=W) holds after extend() in env order), and the running totals.
+// The state block, caller-owned and zeroed once, in 8-byte words (fw_episode_state_bytes; the layout of include/fwsim.h):
+//   [0, 16)   header (EpisodeHeader below)
+//   then W words each: ring_ret (double), ring_len, ring_step, ring_env, ring_trunc (int64), 4 W words ring_info (int32 [W][8])
+//   then N words each: cur_ret (double), cur_len (int64)
+// One workgroup, no atomics, no in-grid waits.  More than W episodes may end in one step (all envs meet the time limit together), so
+// the step's dones are counted first (pass 1) and only the last W of them are written (pass 2): consecutive ranks, distinct slots.
+// A done's rank: wave ballot + prefix inside the wave, an LDS scan across the waves, a running base across the passes over N.
+constexpr int kEpThreads = 1024;
+constexpr int kEpWaves = kEpThreads / 64;
+constexpr int kEpInfo = 8;                  // info columns kept per ring entry (FW_INFO_DIM)
+constexpr int kEpInfoSums = 6;              // ... of which the flags and counts are totalled (FW_INFO_NUM_TARGETS_REACHED .. FW_INFO_IS_SUCCESS)
+enum EpisodeHeader { EP_EPISODES = 0, EP_STEPS = 1, EP_TRUNCATED = 2, EP_SUM_LEN = 3, EP_SUM_INFO = 4 /* .. 9 */, EP_SUM_RET = 10,
+                     EP_SUM_RET2 = 11, EP_HEADER_WORDS = 16 };
+struct EpisodeFoldArgs {
+  const void* reward; int32_t reward_is_f64;
+  const uint8_t *terminated, *truncated;
+  const int32_t* info; int32_t info_dim;     // may be NULL: the ring entries then carry a zero info row
+  int64_t* state;
+  int32_t N, W;
+};
+__device__ __forceinline__ long long ep_wave_sum(long long v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+__device__ __forceinline__ double ep_wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);       // a fixed tree: the same bits in every lane, in every run
+  return v;
+}
+__global__ __launch_bounds__(kEpThreads) void fw_episode_fold_kernel(EpisodeFoldArgs A) {
+  __shared__ long long s_cnt[2][kEpWaves];
+  __shared__ long long s_int[kEpWaves][2 + kEpInfoSums];
+  __shared__ double s_dbl[kEpWaves][2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int N = A.N, W = A.W;
+  long long* hdr = reinterpret_cast<long long*>(A.state);
+  double* ring_ret = reinterpret_cast<double*>(hdr + EP_HEADER_WORDS);
+  long long* ring_len = hdr + EP_HEADER_WORDS + (size_t)W;
+  long long* ring_step = ring_len + W;
+  long long* ring_env = ring_step + W;
+  long long* ring_trunc = ring_env + W;
+  int32_t* ring_info = reinterpret_cast<int32_t*>(ring_trunc + W);
+  double* cur_ret = reinterpret_cast<double*>(ring_trunc + W + (size_t)W * (kEpInfo / 2));
+  long long* cur_len = reinterpret_cast<long long*>(cur_ret) + N;
+  const long long pushed0 = hdr[EP_EPISODES], step = hdr[EP_STEPS] + 1;
+  const int passes = (N + kEpThreads - 1) / kEpThreads;
+
+  // pass 1: how many episodes end in this step
+  long long mine = 0;
+  for (int p = 0; p < passes; ++p) {
+    const long long i = (long long)p * kEpThreads + tid;
+    if (i < N) mine += (A.terminated[i] | A.truncated[i]) != 0;
+  }
+  mine = ep_wave_sum(mine);
+  if (lane == 0) s_cnt[0][wave] = mine;
+  __syncthreads();
+  long long D = 0;
+#pragma unroll
+  for (int w = 0; w < kEpWaves; ++w) D += s_cnt[0][w];
+  const long long first_kept = D - W;          // ranks below it would be pushed out of the ring by this very step
+  __syncthreads();
+
+  // pass 2: accumulate, rank the dones, write the last W of them, clear
+  long long base = 0, n_trunc = 0, sum_len = 0, sum_info[kEpInfoSums] = {0, 0, 0, 0, 0, 0};
+  double sum_ret = 0.0, sum_ret2 = 0.0;
+  const int ncol = A.info ? (A.info_dim < kEpInfo ? A.info_dim : kEpInfo) : 0;
+  for (int p = 0; p < passes; ++p) {
+    const long long i = (long long)p * kEpThreads + tid;
+    const bool on = i < N;
+    bool done = false, trunc = false;
+    double cr = 0.0;
+    long long cl = 0;
+    if (on) {
+      const double r = A.reward_is_f64 ? reinterpret_cast<const double*>(A.reward)[i] : (double)reinterpret_cast<const float*>(A.reward)[i];
+      cr = cur_ret[i] + r;
+      cl = cur_len[i] + 1;
+      trunc = A.truncated[i] != 0;
+      done = trunc || A.terminated[i] != 0;
+      cur_ret[i] = done ? 0.0 : cr;
+      cur_len[i] = done ? 0 : cl;
+    }
+    const unsigned long long ballot = __ballot(done);
+    if (lane == 0) s_cnt[p & 1][wave] = __popcll(ballot);
+    __syncthreads();                           // (two buffers: a wave already in pass p + 1 writes the other one)
+    long long before = 0, chunk = 0;
+#pragma unroll
+    for (int w = 0; w < kEpWaves; ++w) { const long long c = s_cnt[p & 1][w]; chunk += c; before += w < wave ? c : 0; }
+    if (done) {
+      const long long rank = base + before + __popcll(ballot & ((1ull << lane) - 1ull));
+      int32_t row[kEpInfo];
+#pragma unroll
+      for (int k = 0; k < kEpInfo; ++k) row[k] = k < ncol ? A.info[(size_t)i * A.info_dim + k] : 0;
+      sum_ret += cr; sum_ret2 += cr * cr; sum_len += cl; n_trunc += trunc;
+#pragma unroll
+      for (int k = 0; k < kEpInfoSums; ++k) sum_info[k] += row[k];
+      if (rank >= first_kept) {
+        const size_t s = (size_t)((pushed0 + rank) % W);
+        ring_ret[s] = cr; ring_len[s] = cl; ring_step[s] = step; ring_env[s] = i; ring_trunc[s] = trunc;
+#pragma unroll
+        for (int k = 0; k < kEpInfo; ++k) ring_info[s * kEpInfo + k] = row[k];
+      }
+    }
+    base += chunk;
+  }
+
+  // the step's sums: lane tree, then the waves in order -- a fixed order for the doubles
+  sum_ret = ep_wave_sum(sum_ret); sum_ret2 = ep_wave_sum(sum_ret2);
+  sum_len = ep_wave_sum(sum_len); n_trunc = ep_wave_sum(n_trunc);
+#pragma unroll
+  for (int k = 0; k < kEpInfoSums; ++k) sum_info[k] = ep_wave_sum(sum_info[k]);
+  if (lane == 0) {
+    s_dbl[wave][0] = sum_ret; s_dbl[wave][1] = sum_ret2;
+    s_int[wave][0] = sum_len; s_int[wave][1] = n_trunc;
+#pragma unroll
+    for (int k = 0; k < kEpInfoSums; ++k) s_int[wave][2 + k] = sum_info[k];
+  }
+  __syncthreads();
+  if (tid < 2 + kEpInfoSums) {
+    long long v = 0;
+    for (int w = 0; w < kEpWaves; ++w) v += s_int[w][tid];
+    const int at = tid == 0 ? EP_SUM_LEN : tid == 1 ? EP_TRUNCATED : EP_SUM_INFO + (tid - 2);
+    hdr[at] += v;
+  } else if (tid < 4 + kEpInfoSums) {
+    const int c = tid - (2 + kEpInfoSums);
+    double v = 0.0;
+    for (int w = 0; w < kEpWaves; ++w) v += s_dbl[w][c];
+    double* tot = reinterpret_cast<double*>(hdr) + (c == 0 ? EP_SUM_RET : EP_SUM_RET2);
+    tot[0] += v;
+  } else if (tid == 4 + kEpInfoSums) {
+    hdr[EP_EPISODES] = pushed0 + D;            // (every thread read both words in front of the first barrier)
+    hdr[EP_STEPS] = step;
+  }
+}
+
 // K4a: per-column batch moments of obs[N,D] (two-pass-free: shifted sums in double), one
 // workgroup per column chunk; K4b merges them into the running statistics (Chan et al.) and
 // K4c normalises.  N*D is small (4096 x 28), so the three launches are latency-trivial and

@@ -573,6 +573,10 @@ class PPOConfig:
     diagnostics: bool = False              # SB3's train/* figures after every train(): PPO.diagnostics (approx_kl, clip_fraction, explained_variance,
                                            # the losses, std, ...) and PPO.diagnostic_series (per minibatch); the fused learner then runs
                                            # fw_ppo_update_diag; off: nothing changes
+    episode_stats: bool = False            # SB3's rollout/* figures after every collect_rollouts(): PPO.rollout_stats (ep_rew_mean, ep_len_mean,
+                                           # success_rate over the last stats_window_size episodes, and the means over all episodes of the
+                                           # interval); one more launch per vec-step (fw_episode_fold, monitor.EpisodeMonitor); off: nothing changes
+    stats_window_size: int = 100           #        SB3's stats_window_size: episodes in the window
     dist_update: str = "replicated"        # multi-process job: "replicated" = all-gather the rollout shards, every rank runs the same
                                            # minibatch sequence (no per-minibatch collective); "allreduce" = local minibatches + gradient all-reduce
 
@@ -937,8 +941,63 @@ class PPO:
         self.diagnostics: Dict[str, float] = {}
         self.diagnostic_series: Dict[str, np.ndarray] = {}
         self._n_updates = 0                # SB3's _n_updates: epochs trained so far
+        # PPOConfig.episode_stats: the device-side episode monitor, folded once per vec-step by every collector
+        self.episode_monitor = None
+        self._stats = {}                   # PPO.rollout_stats of the last rollout, once read
+        self._stats_host = self._stats_event = None      # the monitor's header + ring in pinned memory, and the event behind the copy
+        self._stats_pending, self._stats_figures = False, None
+        if getattr(cfg, "episode_stats", False):
+            from .monitor import EpisodeMonitor
+            missing = [k for k in ("rewards", "terminated", "truncated") if not hasattr(getattr(env, "venv", None), k)]
+            if missing:
+                raise ValueError("PPOConfig.episode_stats reads the env's output buffers after every step: the env has no " + ", ".join(missing))
+            self.episode_monitor = EpisodeMonitor(env.num_envs, int(cfg.stats_window_size), self.device)
         self._diag_buf = self._diag_i = None      # torch path: [rows, 5] float32 device buffer and the device-side minibatch counter
         self._g_update_diag = False               # ... and whether the captured update graph books its rows
+
+    # ---- PPOConfig.episode_stats ------------------------------------------------------------------
+    def _fold_episodes(self) -> None:
+        """Behind a vec-step, on the stream that ran it (inside the captured graph when there is one): the step's raw rewards, done
+        flags and info rows -- still in the env's output buffers -- into the episode monitor.  Nothing when the flag is off."""
+        m = self.episode_monitor
+        if m is not None:
+            v = self.env.venv
+            m.fold(v.rewards, v.terminated, v.truncated, getattr(v, "info", None))
+
+    def _queue_rollout_stats(self) -> None:
+        """Behind a rollout: the monitor's header and ring (16 + 9 W words) on their way to the host.  One small copy, no
+        synchronisation here -- ``rollout_stats`` waits for it when somebody looks.  A sharded job sums the figures over its ranks
+        at once instead (one small all-reduce, next to sync_statistics: a point every rank reaches)."""
+        m = self.episode_monitor
+        self._stats_figures = None
+        if _dist() is not None:
+            self._stats_figures = m.reduced_figures(all_reduce_sum_)
+        elif self.device.type == "cuda":
+            if self._stats_host is None:
+                self._stats_host = torch.zeros(m.head_words, dtype=torch.int64).pin_memory()
+                self._stats_event = torch.cuda.Event()
+            self._stats_host.copy_(m.state[:m.head_words], non_blocking=True)
+            self._stats_event.record(torch.cuda.current_stream(self.device))
+        self._stats_pending = True
+
+    @property
+    def rollout_stats(self) -> Dict[str, float]:
+        """``EpisodeMonitor.scalars()`` of the last ``collect_rollouts()`` (PPOConfig.episode_stats; ``{}`` with the flag off or
+        before the first rollout): SB3's ``rollout/ep_rew_mean`` / ``ep_len_mean`` / ``success_rate`` over the window, the window
+        rates, ``rollout/episodes`` and the ``rollout/interval/*`` means over the episodes finished since the figures were last
+        read.  In a sharded job: totals and interval figures summed over the ranks, window figures over the union of the ranks'
+        windows."""
+        if self._stats_pending:
+            self._stats_pending = False
+            m = self.episode_monitor
+            if self._stats_figures is not None:
+                self._stats = m.scalars(figures=self._stats_figures)
+            elif self.device.type == "cuda":
+                self._stats_event.synchronize()
+                self._stats = m.scalars(head=self._stats_host.numpy().copy())
+            else:
+                self._stats = m.scalars()
+        return self._stats
 
     # ---- SB3 OnPolicyAlgorithm.collect_rollouts ---------------------------------------------
     def _rollout_body(self):
@@ -954,6 +1013,7 @@ class PPO:
             actions, values, logp = self.policy(self.last_obs, generator=self.gen, **kw)
             clipped = clip_actions(actions, env.venv).to(act_dtype)
             obs_n, rew_n, dones, timeouts, tobs_n = env.step(clipped)
+            self._fold_episodes()
             # bootstrap truncated episodes with V(terminal_observation).  (CNN front end: the env has already auto-reset, so the
             # terminal pose can no longer be rendered; the image of the step before stands in -- one agent step stale, and only
             # for the rare episodes that end on the time limit.)
@@ -1043,6 +1103,7 @@ class PPO:
                 a.clip_obs, a.eps_obs, a.clip_reward, a.eps_reward = float(env.clip_obs), float(env.epsilon), float(env.clip_reward), float(env.epsilon)
                 a.update_obs, a.update_ret, a.norm_reward, a.deterministic = upd_obs, track, int(env.norm_reward), 0
                 _lib.check(L.fw_collect_step(venv._h, C.byref(a), st), venv._h)
+                self._fold_episodes()            # (same stream: the env's buffers hold step t until launch t + 1)
             if self._close_gae:
                 # ... and the end of the rollout in one more: the last step's statistics, V(last observation), the finalisation of
                 # step T - 1, the normalised last observation and the GAE scan (fw_collect_close)
@@ -1067,6 +1128,7 @@ class PPO:
                                           _p(env.ret_rms.var), _p(env.ret_rms.count), track, float(env.gamma), _p(self._rng),
                                           _p(env._ws_stats), _p(env._obs_acc) if env.training and env.norm_obs else None,
                                           _p(env._ret_acc) if track else None, st))
+            self._fold_episodes()
         # V(last observation) for GAE + the finalisation of step T-1 (nothing is sampled; the normalised last observation lands
         # in last_obs for callers that look at it)
         _lib.check(L.fw_collect_act_a(_p(self._fused.flat), _p(venv.obs), f64, N, D, self.act_dim, _p(env.obs_rms.mean), _p(env.obs_rms.var),
@@ -1115,6 +1177,7 @@ class PPO:
                                           _p(env.ret_rms.var), _p(env.ret_rms.count), track, float(env.gamma), _p(self._rng),
                                           _p(env._ws_stats), _p(env._obs_acc) if env.training and env.norm_obs else None,
                                           _p(env._ret_acc) if track else None, st))
+            self._fold_episodes()
         # V(last observation) for GAE + the finalisation of step T - 1; the normalised last observation for callers that look at it
         act(None, 2, self.last_values, T - 1)
         _lib.check(L.fw_normalize_obs(_p(venv.obs), f64, N, D, _p(env.obs_rms.mean), _p(env.obs_rms.var), _p(env.obs_rms.count), 0,
@@ -1173,6 +1236,9 @@ class PPO:
         self._warm_rollouts = 0
         self._act_env.fill_(float("nan"))
         restored = self.env.restore_statistics() if hasattr(self.env, "restore_statistics") else False
+        if self.episode_monitor is not None:
+            self.episode_monitor.restore()     # the void rollout's episodes leave the window and the totals too
+            self._stats, self._stats_pending = {}, False
         self.adv = self.ret = None
         self.num_timesteps -= self._void_steps
         self._void_steps = 0
@@ -1231,6 +1297,8 @@ class PPO:
             # the rollout; rollouts queued behind an unread word keep the older base, so that ALL of them can be taken back)
             if hasattr(env, "save_statistics"):
                 env.save_statistics()
+            if self.episode_monitor is not None:
+                self.episode_monitor.snapshot()
             self._void_steps = 0
         body = self._rollout_body
         if self._collect_fused:
@@ -1259,6 +1327,8 @@ class PPO:
         self._status_pending = self._one_launch
         if hasattr(env, "sync_statistics"):
             env.sync_statistics()              # sharded job: one small all-reduce per rollout (no-op on one GPU)
+        if self.episode_monitor is not None:
+            self._queue_rollout_stats()
         if self._collect_fused and self._close_gae:
             self.adv, self.ret = self._adv_buf, self._ret_buf      # written by fw_collect_close inside the rollout
         else:
@@ -1538,8 +1608,11 @@ class PPO:
     # ---- checkpoint (model + normaliser), train/train_Fixedwing_Waypoints_v3.py:340-347 ----------
     def state_dict(self):
         self.check_collect_status()                # never checkpoint behind a void rollout
-        return {"policy": self.policy.state_dict(), "optimizer": self.optimizer.state_dict(),
-                "vecnormalize": self.env.state_dict(), "num_timesteps": self.num_timesteps}
+        sd = {"policy": self.policy.state_dict(), "optimizer": self.optimizer.state_dict(),
+              "vecnormalize": self.env.state_dict(), "num_timesteps": self.num_timesteps}
+        if self.episode_monitor is not None:
+            sd["episode_stats"] = self.episode_monitor.state_dict()
+        return sd
 
     def invalidate_graphs(self) -> None:
         """Drop the captured rollout / update graphs (their kernel arguments froze scalars and state addresses that a
@@ -1554,4 +1627,11 @@ class PPO:
         if self._fused is not None:
             self._fused.synced = False
         self.env.load_state_dict(sd["vecnormalize"])
+        if self.episode_monitor is not None:
+            # (in place: the block keeps its address; a checkpoint written with the flag off leaves a fresh monitor)
+            if sd.get("episode_stats") is not None:
+                self.episode_monitor.load_state_dict(sd["episode_stats"])
+            else:
+                self.episode_monitor.state.zero_(); self.episode_monitor._last = None
+            self._stats, self._stats_pending = {}, False
         self.num_timesteps = 0 if reset_num_timesteps else int(sd["num_timesteps"])
