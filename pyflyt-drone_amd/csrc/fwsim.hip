@@ -136,6 +136,9 @@ __device__ __forceinline__ void shadow_worker(const Params<T>* __restrict__ Pp, 
   const int envc = active ? env : D.n - 1;
   const size_t n = D.npad;
   const int total = P.warmup_aviary_steps + 1;                  // progress 1 = scenario sampled, then one per warm-up step
+  // A warm-up of no steps: the scenario pass leaves progress 0 and the next chunk is the closing pass alone (no Aviary step, only
+  // end_reset()'s compute_state and the first observation), so that progress == total means "closed" for every warm-up length.
+  const int sampled = P.warmup_aviary_steps > 0 ? 1 : 0;
   const unsigned long long req = D.sreq[envc], dn = D.sdone[envc];
   const uint32_t target = (uint32_t)(req >> 32);
   const bool fresh = active && (uint32_t)req != D.epoch && req != ~0ull;     // a request of an earlier launch
@@ -153,7 +156,7 @@ __device__ __forceinline__ void shadow_worker(const Params<T>* __restrict__ Pp, 
       if (OBJ) obj_spawn<T, G>(P, OC, V, env, target, leader, O0); else comb_spawn<T, G>(P, OC, V, env, target, leader, O0);
       if (leader) obj_store<T, OBJ>(V, env, O0);
     }
-    if (leader) { store_rigid<T>(V, env, S0); D.is[env] = 0; D.sdone[env] = pack_done(target, D.epoch, 1); }
+    if (leader) { store_rigid<T>(V, env, S0); D.is[env] = 0; D.sdone[env] = pack_done(target, D.epoch, sampled); }
   }
   if (__ballot(left > 0) == 0ull) return;
   TickC<T> C; SurfC<T> mine; T wmask;
@@ -175,12 +178,13 @@ __device__ __forceinline__ void shadow_worker(const Params<T>* __restrict__ Pp, 
   LaneAct<T> LA; LA.cmd = (T)0; LA.a = (T)0;
   if (G == 8) lane_act_scatter<T>(S, LA);
   const int chunk = left;
+  int steps = sampled ? left : 0;
 #pragma unroll 1
-  while (__ballot(left > 0) != 0ull) {
-    const bool stepped = left > 0;
+  while (__ballot(steps > 0) != 0ull) {
+    const bool stepped = steps > 0;
     if (stepped) {
       (void)aviary_step<T, true, G, HASOBJ>(P, C, OC, V, envc, O, S, R, cmd0, tick, (T)0, (T)0, wb, wa, gust, mine, wmask, LA);
-      left -= 1;
+      steps -= 1;
     }
     if (HASOBJ) obj_capture_step<T, G>(OC, V, stepped, envc, O, S, R, tick);
   }

@@ -19,6 +19,7 @@ import pyflyt_drone_amd  # noqa: E402,F401
 from pyflyt_drone_amd import config as K  # noqa: E402
 from oracle import fw_oracle as O  # noqa: E402
 from helpers import seeded_actions  # noqa: E402
+import fuzz_configs as F  # noqa: E402
 
 GUST = dict(enabled=True, mode="gust_sine", randomize_on_reset=True, randomize_gust_phase=True,
             wind_enu_mps_range=[[-5, 5], [-5, 5], [-0.5, 0.5]], gust_amp_enu_mps_range=[[0, 3], [0, 3], [0, 0.3]],
@@ -42,6 +43,13 @@ def cases():
     nd = K.train_objlock_config(duck_camera_capture_interval_steps=2)
     nd.duck_vision_no_deltas = 1
     yield "objlock_no_deltas", nd, "gentle", 4, 100, 41
+    # off the shipped airframe and rates (tests/fuzz_configs.py; the files store the config bytes beside the trace): general
+    # geometry at 480 / 120 Hz under gust wind, and the combined task with twelve cylinders at 240 / 60 Hz under a constant wind
+    yield FUZZ_WAYPOINTS, F.waypoints(1), "uniform", 4, 100, 51
+    yield FUZZ_COMBINED, F.combined(2), "gentle", 4, 100, 61
+
+
+FUZZ_WAYPOINTS, FUZZ_COMBINED = "fuzz_waypoints_480hz_gust", "fuzz_combined_obstacles"
 
 
 def main(only=None):
@@ -61,7 +69,8 @@ def main(only=None):
         path = os.path.join(HERE, name + ".npz")
         np.savez_compressed(path, seed=seed, obs0=obs0, actions=np.array(A), obs=np.array(OB), reward=np.array(R),
                             terminated=np.array(TE), truncated=np.array(TR), terminal_obs=np.array(TO),
-                            info=np.array(IN), final_state=env.get_state())
+                            info=np.array(IN), final_state=env.get_state(),
+                            **({"fw_config": F.config_bytes(cfg)} if name.startswith("fuzz_") else {}))
         done = int((np.array(TE) | np.array(TR)).sum())
         print(f"{name}: {os.path.getsize(path)/1024:.1f} KiB, {done} episode ends")
 

@@ -21,7 +21,7 @@ from pyflyt_drone_amd import _lib, checkpoint, evaluate
 from pyflyt_drone_amd import config as K
 from pyflyt_drone_amd import rollout as R
 from pyflyt_drone_amd.highlevel import HighLevelCmdVecEnv, condition_command
-from helpers import seeded_actions
+from helpers import as_oracle_obs as _as_oracle_obs, route as _route, seeded_actions, set_routing_mixer
 from oracle import fw_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -53,25 +53,7 @@ def _routed_pair(triple, **kw):
     wd = K.waypoints_direct_config(**BASE_KW, **kw)
     kw.pop("dtype", None)
     wp = K.waypoints_config(**BASE_KW, **kw)
-    for a in range(K.FW_NUM_ACTUATORS):
-        for k in range(4):
-            wp.mixer[a][k] = 0.0
-    for k, s in enumerate(triple):
-        wp.mixer[s][k] = 1.0
-    wp.mixer[5][3] = 1.0
-    return wd, wp
-
-
-def _route(a4, triple):
-    a6 = np.zeros((a4.shape[0], 6), dtype=a4.dtype)
-    a6[:, list(triple)] = a4[:, :3]
-    a6[:, 5] = a4[:, 3]
-    return a6
-
-
-def _as_oracle_obs(o30):
-    """kernel columns 0:12 and 18:30 are the oracle's 0:12 and 16:28"""
-    return np.concatenate([o30[:, 0:12], o30[:, 18:30]], axis=1)
+    return wd, set_routing_mixer(wp, triple)
 
 
 # ------------------------------------------------------------------------------------------------ 1. the base env

@@ -18,6 +18,7 @@ import pyflyt_drone_amd as P
 from pyflyt_drone_amd import checkpoint
 from pyflyt_drone_amd import config as K
 from pyflyt_drone_amd import rollout as R
+from helpers import route, set_routing_mixer
 from oracle import fw_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -92,12 +93,7 @@ def test_physics_matches_the_oracle_through_a_routing_mixer(triple, lanes):
                             angle_representation="euler", agent_hz=120, context_length=1, wind_config=WINDS[wind])
     wp.warmup_aviary_steps = 0
     K._set_vec(wp.start_vel, (15.0, 0.0, 0.0))
-    for a in range(K.FW_NUM_ACTUATORS):
-        for k in range(4):
-            wp.mixer[a][k] = 0.0
-    for k, s in enumerate(triple):
-        wp.mixer[s][k] = 1.0
-    wp.mixer[5][3] = 1.0
+    set_routing_mixer(wp, triple)
     assert wp.motor.noise_ratio > 0 and ll.motor.noise_ratio > 0
     env = P.FixedwingVecEnv(ll, n, seed=seed)
     assert env.lanes_per_env == lanes
@@ -110,9 +106,7 @@ def test_physics_matches_the_oracle_through_a_routing_mixer(triple, lanes):
     for t in range(steps):
         a4 = rng.uniform(-1, 1, size=(n, 4))
         a4[:, :3] *= 0.3
-        a6 = np.zeros((n, 6))
-        a6[:, list(triple)] = a4[:, :3]
-        a6[:, 5] = a4[:, 3]
+        a6 = route(a4, triple)
         _, _, o_term, o_trunc, _, _ = ora.step(a4)
         env.step_tensor(torch.as_tensor(a6, device=env.device))
         done = (o_term | o_trunc).astype(bool) | (env.terminated | env.truncated).cpu().numpy().astype(bool)
