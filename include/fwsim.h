@@ -788,6 +788,11 @@ int32_t fw_capture_wave(fw_handle h);
  * build, every surface with forward = e_x and lift = e_y or e_z, diagonal inertia), else 0.  Diagnostic; results are bit-identical
  * to the general tick. */
 int32_t fw_axis_aligned(fw_handle h);
+/* 1 when this handle's fw_step workgroups carry a noise wave (the axis-aligned kernel with motor noise on and step_ratio <= 8, up to
+ * 4096 envs: a second wave per workgroup draws the launch's motor noise while the step wave is in its prologue; environment variable
+ * FWSIM_AUX_WAVE=0|1 at fw_create overrides where that kernel applies), else 0.  Diagnostic; results are bit-identical to the
+ * one-wave kernel. */
+int32_t fw_aux_wave(fw_handle h);
 const char* fw_last_error(fw_handle h); /* h may be NULL: last create/validate error */
 int32_t fw_destroy(fw_handle h);
 

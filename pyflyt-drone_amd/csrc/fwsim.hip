@@ -303,7 +303,11 @@ enum Phase : int { PH_STEP = 0, PH_WARM = 1, PH_DONE = 2 };
 // COLLECT = the step waves of fw_collect_step (fwsim_fused.hpp): block indices are offset by the act waves in front, the
 // actions are waited for and read coherently, and the epilogue carries the statistics of VecNormalize.step_wait.
 // HELP = the workgroup has a capture wave (fwsim_objlock.hpp, "The capture wave"): camera tasks on the 8-lane mapping.
-template <typename T, bool GENERAL, int G, int TKIND, int WPE = 1, bool COLLECT = false, bool HELP = false, bool AX = false>
+// AUX = the workgroup has a second wave (fw_step_kernel_g8x) that draws the launch's motor noise while the step wave is in its
+// prologue: the draw reads three integers per env and nothing of the launch's physics.  Same lane -> (env, sub) map on both waves;
+// the values cross in LDS ([kWave][2] behind the output stash) and the waves meet at ONE __syncthreads() in front of the sub-step
+// loop, which both execute unconditionally.
+template <typename T, bool GENERAL, int G, int TKIND, int WPE = 1, bool COLLECT = false, bool HELP = false, bool AX = false, bool AUX = false>
 __device__ __forceinline__
 void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp, DevState<T> Dg,
                const T* __restrict__ actions, T* __restrict__ obs, T* __restrict__ reward,
@@ -332,13 +336,14 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   const int blk = (G == 8 && (nblk & 7) == 0) ? (wg & 7) * (nblk >> 3) + (wg >> 3) : wg;
   const DevState<T> D = tile_view<T, EPW>(Dg, blk);  // this wave's tile: row stride EPW (a compile-time constant), global env ids
   if ((GENERAL || DEFER) && bx >= nblk) {
+    if (AUX && threadIdx.x >= kWave) return;         // (a worker workgroup's second wave has nothing to do)
     if (GENERAL) shadow_worker<T, G, TKIND>(Pp, OCp, D, blk); else scenario_worker<T, G>(Pp, D, blk);
     FWP(if (D.prof && threadIdx.x == 0) {
       long long* w = D.prof + ((size_t)(D.epoch % kProfSlots) * 2 * nblk + blockIdx.x) * kProfWords;
       w[0] = FWP_NOW() - p_t0; })
     return;
   }
-  const int lane = threadIdx.x;
+  const int lane = AUX ? (int)(threadIdx.x & (kWave - 1)) : (int)threadIdx.x;
   const int sub = (G == 1) ? 0 : (lane & (G - 1));   // my lane within the env's group
   const int row = lane / G;                          // env slot within the wave
   const bool leader = sub == 0;
@@ -349,6 +354,21 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   const size_t n = D.npad;
   const int Dobs = P.obs_dim;
   const int ld = Dobs + 1;
+
+  // AUX, second wave: the normals of my lane's Aviary step -- the very call the step wave of the one-wave kernel makes below (same
+  // lane map, same arguments, zeros where that wave draws nothing) -- left in LDS for the step wave; then the barrier, and done.
+  T* aux_nz = AUX ? reinterpret_cast<T*>(smem_raw + Dg.mbox_off) : nullptr;     // [kWave][2], behind tile and stash (step_lds_bytes_h)
+  if constexpr (AUX) {
+    if (threadIdx.x >= kWave) {
+      const int32_t a_tick = D.i[IF_TICK * n + envc], a_episode = D.i[IF_EPISODE * n + envc], a_flags = D.i[IF_FLAGS * n + envc];
+      T a_z0 = (T)0, a_z1 = (T)0;
+      if (P.has_noise && P.step_ratio <= G && !(a_flags & (FL_TERM | FL_TRUNC)))
+        rng_normal2<T>(P, (uint32_t)(P.env_offset + envc), (uint32_t)a_episode, (uint32_t)(a_tick / P.ticks_per_aviary) + (uint32_t)sub, a_z0, a_z1);
+      aux_nz[2 * lane] = a_z0; aux_nz[2 * lane + 1] = a_z1;
+      __syncthreads();                               // barrier 1 (the step wave's is in front of its sub-step loop)
+      return;
+    }
+  }
 
   // Loads first, in the order their results are needed (vmcnt retires in order): the counters that feed
   // the RNG and the target window, then the rigid state, then the launch-resident constants.
@@ -459,7 +479,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   const uint32_t astep0 = (uint32_t)(tick / P.ticks_per_aviary);
   const bool pre_noise = (G == 8) && P.has_noise && (P.step_ratio <= G);
   T nz0 = (T)0, nz1 = (T)0;
-  if (pre_noise && !done_at_entry) rng_normal2<T>(P, genv, (uint32_t)episode, astep0 + (uint32_t)sub, nz0, nz1);
+  if (!AUX && pre_noise && !done_at_entry) rng_normal2<T>(P, genv, (uint32_t)episode, astep0 + (uint32_t)sub, nz0, nz1);
 
   int phase = active ? PH_STEP : PH_DONE;
   // STASH: the outputs of the step (reward, flags, info) wait in LDS -- four words per env behind the tile / the camera's map --
@@ -481,6 +501,10 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   T dist_keep = (T)0;
   bool resetting = false;                            // DEFER: auto-reset pending for the epilogue
   bool step_over = active && done_at_entry;          // nothing to simulate: finalise immediately
+  if constexpr (AUX) {                               // barrier 1: every lane of both waves, whatever its env does
+    __syncthreads();
+    nz0 = aux_nz[2 * lane]; nz1 = aux_nz[2 * lane + 1];
+  }
 
   FWP(const long long p_t1 = FWP_NOW();)
 #pragma unroll 1
@@ -1036,7 +1060,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
       ip[1] = make_int4(o_st, OBJ ? o_st : 0, o_sc, 0);
     }
   }
-  if (HELP) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }   // (the capture wave takes no part: no s_barrier)
+  if (HELP || AUX) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }   // (the capture / second wave takes no part: no s_barrier)
   else __syncthreads();
   // (COLLECT: the partial sums first -- the fold waves at the end of the launch are waiting for them, nobody for the observation rows)
   if (COLLECT) collect_stats_tail<T>(*CAp, D.epoch, tile, ld, min(EPW, D.n - env0), wg, nblk, active && leader, latch[4 * row], latch[4 * row + 1] != 0.0, env, c_ret);
@@ -1075,6 +1099,9 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
 // (AX: the axis-aligned geometry variant of the tick, fw_env::axis_aligned)
 template <typename T, bool GENERAL, bool AX = false>
 __global__ __launch_bounds__(kWave) void fw_step_kernel_g8(FW_STEP_ARGS) { FW_STEP_RUN(T, GENERAL, 8, FW_TASK_WAYPOINTS, 1, false, false, AX); }
+// ... with a second wave per workgroup that draws the motor noise (step_body AUX; f64, wind-free, axis-aligned: the headline row)
+template <typename T>
+__global__ __launch_bounds__(2 * kWave) void fw_step_kernel_g8x(FW_STEP_ARGS) { FW_STEP_RUN(T, false, 8, FW_TASK_WAYPOINTS, 1, false, false, true, true); }
 // ... and the same mapping capped at 256 registers: two waves per SIMD (8 192 < N <= 65 536 envs)
 template <typename T, bool GENERAL>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2, 2)))
@@ -1578,6 +1605,7 @@ __global__ __launch_bounds__(kWave) void fw_reset_kernel_ll(const Params<T>* __r
 // ======================================================================
 namespace {
 
+constexpr int kAuxWaveMaxEnvs = 4096;  // noise wave beside every step wave (fw_step_kernel_g8x): 512 two-wave workgroups, one wave per SIMD on 1024 SIMDs
 constexpr int kG8MaxEnvs = 16384;   // measured crossover on MI355X: 8 lanes/env wins up to 2^14 envs (51 vs 70 us), loses at 2^15 (93 vs 76 us)
 thread_local std::string g_err;
 
@@ -1774,7 +1802,7 @@ bool build_params(const fw_config& c, uint64_t seed, int64_t env_offset, Params<
 // One env kernel as a handle launches it (env_kernels_of below): the host function pointer and what of the launch follows the kernel.
 struct EnvKernel {
   const void* fn = nullptr;
-  unsigned block = kWave;       // 2 * kWave: a capture wave beside every step wave (its LDS carries the mailbox, step_lds_bytes_h)
+  unsigned block = kWave;       // 2 * kWave: a capture wave (its LDS carries the mailbox) or a noise wave (its [kWave][2] normals) beside every step wave: step_lds_bytes_h
   bool worker_half = true;      // step kernels: with shadow_on the second half of the grid are the shadow workers
   bool takes_objc = true;       // reset kernels: the argument list has the ObjC block (the low-level task's has not)
 };
@@ -1787,6 +1815,7 @@ struct fw_env {
   int32_t lanes_per_env = 1;    // 1: throughput mapping, 8: latency mapping (see fwsim_device.hpp)
   int32_t g8_waves = 1;         // 8-lane mapping, waypoints task: waves per SIMD the step kernel is built for (1 | 2)
   int32_t capture_wave = 0;     // 8-lane mapping, camera tasks: fw_step workgroups carry a capture wave (fw_step_kernel_obj_g8h)
+  int32_t aux_wave = 0;         // the axis-aligned row with motor noise, up to kAuxWaveMaxEnvs envs: a second wave per step workgroup draws the noise (fw_step_kernel_g8x)
   int32_t axis_aligned = 0;     // f64 wind-free waypoints on the 8-lane one-wave build: the tick's axis-aligned variant (axis_aligned_geometry)
   EnvKernel step, reset, collect;   // chosen once by fw_create from the fields above (select_kernels); collect.fn is null where fw_collect_step does not serve
   uint64_t seed = 0;
@@ -1901,8 +1930,8 @@ template <typename T> size_t tile_bytes(const fw_env* h) {
 }
 // dynamic LDS of a step launch: the tile (or the camera's map) + the output stash of the envs of a wave
 template <typename T> size_t step_lds_bytes(const fw_env* h) { return ((tile_bytes<T>(h) + 15) & ~(size_t)15) + sizeof(double) * 4 * (size_t)(kWave / h->lanes_per_env); }
-// ... of a step launch whose workgroups carry a capture wave: + the mailbox
-template <typename T> size_t step_lds_bytes_h(const fw_env* h) { return ((step_lds_bytes<T>(h) + 15) & ~(size_t)15) + mbox_bytes(sizeof(T)); }
+// ... of a step launch whose workgroups carry a second wave: + the capture mailbox, or the noise wave's [kWave][2] normals in its place (DevState::mbox_off)
+template <typename T> size_t step_lds_bytes_h(const fw_env* h) { return ((step_lds_bytes<T>(h) + 15) & ~(size_t)15) + std::max(mbox_bytes(sizeof(T)), sizeof(T) * 2 * (size_t)kWave); }
 inline dim3 grid_of(const fw_env* h) { return dim3((unsigned)(h->npad / (kWave / h->lanes_per_env))); }
 
 // ObjLock task constants (analytic camera axes, shaping coefficients of envs/fixedwing_objlock_env.py:54-80)
@@ -1959,7 +1988,7 @@ int upload_params(fw_env* h) {
 // A key names the fields of a handle that the choice depends on; kAny in a row matches every value.  The first row that matches
 // wins, so a special case stands above the general one.  A new kernel variant is one new row.
 constexpr int kAny = -1;
-struct KernelKey { int task, lanes, waves, windy, axis_aligned, capture_wave; };
+struct KernelKey { int task, lanes, waves, windy, axis_aligned, capture_wave, aux_wave; };
 struct KernelRow { KernelKey key; EnvKernel step, reset, collect; };
 template <typename... A> const void* kfn(void (*kernel)(A...)) { return (const void*)kernel; }      // the host-side pointer hipLaunchKernel takes
 // The argument lists step_T / collect_step_T / reset_T build.  hipLaunchKernel takes them unchecked, so a kernel enters the table
@@ -1970,6 +1999,7 @@ template <typename T> using ResetFn = void (*)(const Params<T>*, const ObjC<T>*,
 template <typename T> using ResetLLFn = void (*)(const Params<T>*, DevState<T>, const uint8_t*, T*, int, ScenOv);
 template <typename T> EnvKernel step_k(StepFn<T> f) { return {kfn(f)}; }
 template <typename T> EnvKernel two_wave(StepFn<T> f) { return {kfn(f), 2 * kWave, false}; }       // step wave + capture wave per workgroup (the capture wave is the worker)
+template <typename T> EnvKernel noise_wave(StepFn<T> f) { return {kfn(f), 2 * kWave, true}; }       // step wave + noise wave per workgroup; the scenario workers stay the grid's second half
 template <typename T> EnvKernel collect_k(CollectFn<T> f) { return {kfn(f)}; }
 template <typename T> EnvKernel reset_k(ResetFn<T> f) { return {kfn(f)}; }
 template <typename T> EnvKernel no_objc(ResetLLFn<T> f) { return {kfn(f), kWave, true, false}; }
@@ -1977,48 +2007,53 @@ template <typename T> EnvKernel no_objc(ResetLLFn<T> f) { return {kfn(f), kWave,
 template <typename T> EnvKernel axis_aligned_step_kernel() {
   if constexpr (std::is_same<T, double>::value) return step_k<T>(fw_step_kernel_g8<T, false, true>); else return {};
 }
+// ... and so does its build with a noise wave
+template <typename T> EnvKernel aux_wave_step_kernel() {
+  if constexpr (std::is_same<T, double>::value) return noise_wave<T>(fw_step_kernel_g8x<T>); else return {};
+}
 // (fw_collect_step: the four-action tasks on the 8-lane mapping -- collect_fill says so to the others; general tick, no capture wave)
 template <typename T> const KernelRow* env_kernels_of(const KernelKey& q) {
   constexpr int LL = FW_TASK_LOWLEVEL, WD = FW_TASK_WAYPOINTS_DIRECT, OBJ = FW_TASK_OBJLOCK, COMB = FW_TASK_WAYPOINT_OBJLOCK, WP = FW_TASK_WAYPOINTS;
   static const KernelRow rows[] = {
-    // task lanes waves windy axis  capture   fw_step                                               fw_reset / fw_observe                                fw_collect_step
-    {{LL,   8, kAny, 1,    kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 8, true>),         no_objc<T>(fw_reset_kernel_ll<T, 8>),         {}},
-    {{LL,   8, kAny, 0,    kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 8, false>),        no_objc<T>(fw_reset_kernel_ll<T, 8>),         {}},
-    {{LL,   1, kAny, 1,    kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 1, true>),         no_objc<T>(fw_reset_kernel_ll<T, 1>),         {}},
-    {{LL,   1, kAny, 0,    kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 1, false>),        no_objc<T>(fw_reset_kernel_ll<T, 1>),         {}},
-    {{WD,   8, kAny, 1,    kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, true>),         reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
-    {{WD,   8, kAny, 0,    kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, false>),        reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
-    {{WD,   1, kAny, 1,    kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, true>),         reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
-    {{WD,   1, kAny, 0,    kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, false>),        reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
-    {{OBJ,  8, kAny, kAny, kAny, 1},    two_wave<T>(fw_step_kernel_obj_g8h<T, OBJ>),      reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
-    {{OBJ,  8, kAny, kAny, kAny, 0},    step_k<T>(fw_step_kernel_obj_g8<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
-    {{OBJ,  1, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 1, OBJ>),       {}},
-    {{COMB, 8, kAny, kAny, kAny, 1},    two_wave<T>(fw_step_kernel_obj_g8h<T, COMB>),     reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
-    {{COMB, 8, kAny, kAny, kAny, 0},    step_k<T>(fw_step_kernel_obj_g8<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
-    {{COMB, 1, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 1, COMB>),      {}},
-    {{WP,   8, 1,    0,    1,    kAny}, axis_aligned_step_kernel<T>(),                    reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
-    {{WP,   8, 2,    1,    kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, true>),          reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, true>)},
-    {{WP,   8, 2,    0,    kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, false>),         reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, false>)},
-    {{WP,   8, 1,    1,    kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, true>),            reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, true>)},
-    {{WP,   8, 1,    0,    kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, false>),           reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
-    {{WP,   1, kAny, 1,    kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, true>),            reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
-    {{WP,   1, kAny, 0,    kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, false>),           reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
+    // task lanes waves windy axis  capture aux   fw_step                                                     fw_reset / fw_observe                                fw_collect_step
+    {{LL,   8, kAny, 1,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 8, true>),         no_objc<T>(fw_reset_kernel_ll<T, 8>),         {}},
+    {{LL,   8, kAny, 0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 8, false>),        no_objc<T>(fw_reset_kernel_ll<T, 8>),         {}},
+    {{LL,   1, kAny, 1,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 1, true>),         no_objc<T>(fw_reset_kernel_ll<T, 1>),         {}},
+    {{LL,   1, kAny, 0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 1, false>),        no_objc<T>(fw_reset_kernel_ll<T, 1>),         {}},
+    {{WD,   8, kAny, 1,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, true>),         reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
+    {{WD,   8, kAny, 0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, false>),        reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
+    {{WD,   1, kAny, 1,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, true>),         reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
+    {{WD,   1, kAny, 0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, false>),        reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
+    {{OBJ,  8, kAny, kAny, kAny, 1,    kAny}, two_wave<T>(fw_step_kernel_obj_g8h<T, OBJ>),      reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
+    {{OBJ,  8, kAny, kAny, kAny, 0,    kAny}, step_k<T>(fw_step_kernel_obj_g8<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
+    {{OBJ,  1, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 1, OBJ>),       {}},
+    {{COMB, 8, kAny, kAny, kAny, 1,    kAny}, two_wave<T>(fw_step_kernel_obj_g8h<T, COMB>),     reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
+    {{COMB, 8, kAny, kAny, kAny, 0,    kAny}, step_k<T>(fw_step_kernel_obj_g8<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
+    {{COMB, 1, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 1, COMB>),      {}},
+    {{WP,   8, 1,    0,    1,    kAny, 1},    aux_wave_step_kernel<T>(),                        reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   8, 1,    0,    1,    kAny, kAny}, axis_aligned_step_kernel<T>(),                    reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   8, 2,    1,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, true>),          reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, true>)},
+    {{WP,   8, 2,    0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, false>),         reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, false>)},
+    {{WP,   8, 1,    1,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, true>),            reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, true>)},
+    {{WP,   8, 1,    0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, false>),           reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   1, kAny, 1,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, true>),            reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
+    {{WP,   1, kAny, 0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, false>),           reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
   };
   auto fits = [](int row, int v) { return row == kAny || row == v; };
   for (const KernelRow& r : rows)
     if (const KernelKey& k = r.key; fits(k.task, q.task) && fits(k.lanes, q.lanes) && fits(k.waves, q.waves) && fits(k.windy, q.windy) &&
-                                    fits(k.axis_aligned, q.axis_aligned) && fits(k.capture_wave, q.capture_wave)) return &r;
+                                    fits(k.axis_aligned, q.axis_aligned) && fits(k.capture_wave, q.capture_wave) && fits(k.aux_wave, q.aux_wave)) return &r;
   return nullptr;
 }
 
 // The handle's kernels, from the fields fw_create has just fixed.  A combination without a row (or whose row holds no step or
 // reset kernel) is an error here, not a launch that silently does nothing.
 template <typename T> int select_kernels(fw_env* h) {
-  const KernelKey q = { h->cfg.task, h->lanes_per_env, h->g8_waves, h->cfg.wind_mode != FW_WIND_OFF ? 1 : 0, h->axis_aligned, h->capture_wave };
+  const KernelKey q = { h->cfg.task, h->lanes_per_env, h->g8_waves, h->cfg.wind_mode != FW_WIND_OFF ? 1 : 0, h->axis_aligned, h->capture_wave, h->aux_wave };
   const KernelRow* r = env_kernels_of<T>(q);
   if (!r || !r->step.fn || !r->reset.fn) {
-    h->err = "no kernel is built for (task, dtype, lanes per env, waves per SIMD, wind, axis_aligned, capture_wave) =";
-    for (int x : { q.task, h->cfg.dtype, q.lanes, q.waves, q.windy, q.axis_aligned, q.capture_wave }) h->err += " " + std::to_string(x);
+    h->err = "no kernel is built for (task, dtype, lanes per env, waves per SIMD, wind, axis_aligned, capture_wave, aux_wave) =";
+    for (int x : { q.task, h->cfg.dtype, q.lanes, q.waves, q.windy, q.axis_aligned, q.capture_wave, q.aux_wave }) h->err += " " + std::to_string(x);
     return FW_EUNSUPPORTED;
   }
   h->step = r->step; h->reset = r->reset; h->collect = r->collect;
@@ -2286,6 +2321,12 @@ int32_t fw_create(const fw_config* cfg, int32_t num_envs, int32_t device, uint64
   // surface_wrench_ax): the f64 wind-free waypoints kernel of the one-wave 8-lane build, when the geometry allows it.
   h->axis_aligned = (h->lanes_per_env == 8 && h->g8_waves == 1 && wp && !windy && cfg->dtype == FW_F64 &&
                      axis_aligned_geometry(*cfg)) ? 1 : 0;
+  // ... and its build with a noise wave (fw_step_kernel_g8x; bit-identical again): where the step wave pre-draws its motor noise
+  // today (noise on, step_ratio <= 8), up to the size at which every wave of the launch still has a SIMD of its own (512 step
+  // workgroups of two waves on 1024 SIMDs); measured, profiles/r15_aux_wave_ab.txt.  FWSIM_AUX_WAVE=0|1 overrides where the row exists.
+  const bool aux_row = h->axis_aligned && cfg->motor.noise_ratio != 0.0 && 120 / cfg->agent_hz <= 8;      // (Params: has_noise, step_ratio)
+  h->aux_wave = (aux_row && num_envs <= kAuxWaveMaxEnvs) ? 1 : 0;
+  if (const char* ev = getenv("FWSIM_AUX_WAVE")) { if (aux_row) h->aux_wave = atoi(ev) != 0 ? 1 : 0; }
   DeviceGuard g(device);
   rc = with_dtype(h, [&](auto t) { return create_T<decltype(t)>(h); });
   if (rc != FW_OK) {
@@ -3164,6 +3205,7 @@ int32_t fw_rollout_post(const void* reward, int32_t rew_is_f64, const uint8_t* t
 
 int32_t fw_num_envs(fw_handle h) { return h ? h->n : FW_EINVAL; }
 int32_t fw_capture_wave(fw_handle h) { return h ? h->capture_wave : FW_EINVAL; }
+int32_t fw_aux_wave(fw_handle h) { return h ? h->aux_wave : FW_EINVAL; }
 int32_t fw_axis_aligned(fw_handle h) { return h ? h->axis_aligned : FW_EINVAL; }
 int32_t fw_lanes_per_env(fw_handle h) { return h ? (h->lanes_per_env == 8 && h->g8_waves == 2 ? 16 : h->lanes_per_env) : FW_EINVAL; }
 
