@@ -478,6 +478,38 @@ int32_t fw_trace_hl(const void* obs, const void* terminal_obs, const uint8_t* te
                     const int32_t* info, int32_t info_dim, int32_t obs_is_f64, int32_t N, double* trace, int32_t T, int64_t* step_idx,
                     void* hip_stream);
 
+/* fw_trace_rows: the flight recorder of the waypoint and duck tasks (fw_trace_hl's step_idx semantics).  With
+ * k = *step_idx, and only when 0 <= k < T, the post-step row o of env i -- terminal_obs[i] where terminated | truncated, else obs[i];
+ * [N, obs_dim], obs_is_f64 the env dtype -- goes to trace[k, i, :] ([T, N, obs_dim + 2] double) as (o[0 : obs_dim] widened to double,
+ * info[i, FW_INFO_NUM_TARGETS_REACHED] as the step left it (0 when info is NULL; info_dim its row length), flag), flag 0 = running,
+ * 1 = terminated, 2 = truncated (terminated wins); then *step_idx advances by one.  terminated / truncated / terminal_obs / info may
+ * be NULL.  The kernel copies: any observation layout.  One workgroup of 1024 threads, no atomics.
+ * FW_EINVAL for NULL obs / trace / step_idx, N <= 0, T <= 0, obs_dim <= 0, or info with info_dim <= 0. */
+int32_t fw_trace_rows(const void* obs, const void* terminal_obs, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
+                      int32_t info_dim, int32_t obs_is_f64, int32_t N, int32_t obs_dim, double* trace, int32_t T, int64_t* step_idx,
+                      void* hip_stream);
+/* fw_eval_track plus twelve per-episode path sums for the waypoint and duck tasks.  Everything fw_eval_track
+ * does, and from the post-step row o of env i (terminal_obs[i] where terminated | truncated, else obs[i]; [N, obs_dim]) with
+ * omega = o[0:3], v = o[att_dim-6 : att_dim-3], p = o[att_dim-3 : att_dim], a = o[att_dim : att_dim+act_dim],
+ * throttle = o[att_dim+act_dim+5], delta = o[att_dim+act_dim+6 : +3] (present when obs_dim >= att_dim+act_dim+9), r = info[i, 0]
+ * (0 when info is NULL), L = cur_len[i] + 1 and carry[i] = (p_prev[3], p_leg[3], a_prev[6], reached_prev) ([N, 13] double, owned by the
+ * caller, seeded from the reset observation), all in double, cur_path [N, 12]:
+ *   0 path_len += |p - p_prev|      1 speed_sum += |v|      2 alt_sum += p_z      3 alt_min = min(., p_z)      4 ang_vel_sum += |omega|
+ *   5 act_delta_sum += sum_j |a_j - a_prev_j|      6 throttle_sum += throttle
+ *   and where r > reached_prev:  7 first_reach_step = L if still 0,  8 last_reach_step = L,  9 chord_len += |p - p_leg|,
+ *   10 path_at_last_reach = path_len (after this step),  11 miss_dist = +inf;  else 11 miss_dist = min(., |delta|) when delta is present.
+ * On an episode's first step (cur_len[i] == 0) the sums start at 0, alt_min and miss_dist at +inf.  Where the episode goes on:
+ * p_prev = p, a_prev = a, reached_prev = r, and p_leg = p on a reach step.  Where it ended: the twelve sums go to fin_path [N, E, 12] at
+ * the episode's slot (fw_eval_track's recording rule), are cleared, and the carry is re-seeded from the live row obs[i]:
+ * p_prev = p_leg = its p, a_prev = its action block, reached_prev = 0.
+ * FW_EINVAL for NULL buffers, att_dim not 12 or 13, act_dim not 4 or 6, obs_dim < att_dim + act_dim + 6, N <= 0 or E <= 0.
+ * One launch, one workgroup, no atomics. */
+int32_t fw_eval_track_wp(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
+                         int32_t info_dim, const void* obs, const void* terminal_obs, int32_t obs_is_f64, int32_t obs_dim, int32_t att_dim,
+                         int32_t act_dim, const int64_t* targets, int64_t* counts, double* cur_rew, int64_t* cur_len, int64_t* step_ctr,
+                         double* cur_path, double* carry, double* fin_rew, int64_t* fin_len, int64_t* fin_step, int32_t* fin_info,
+                         double* fin_path, int32_t N, int32_t E, void* hip_stream);
+
 /* VecNormalize step (SB3 VecNormalize.step_wait + RunningMeanStd.update, Chan et al. merge),
  * fused: one pass over obs[N,D] (env dtype T_in = double|float per `in_is_f64`) that
  *   (a) if `update` != 0 merges the batch moments into (mean[D], var[D], count[1]) (double),

@@ -11,7 +11,7 @@ from .spaces import Box
 from .vec_env import (FixedwingLowLevelVecEnv, FixedwingObjLockVecEnv, FixedwingVecEnv, FixedwingWaypointObjLockVecEnv,
                       FixedwingWaypointsDirectVecEnv, FixedwingWaypointsVecEnv)
 from . import rollout
-from . import checkpoint, evaluate, highlevel, monitor
+from . import checkpoint, evaluate, flight, highlevel, monitor
 from .highlevel import HighLevelCmdVecEnv
 
 __all__ = ["config", "FwConfig", "Box", "FixedwingVecEnv", "FixedwingWaypointsVecEnv", "FixedwingObjLockVecEnv", "FixedwingWaypointObjLockVecEnv",

@@ -27,6 +27,7 @@ EXPORTS = (
     "fw_collect_act_hl", "fw_sizeof_collect_hl_args", "fw_eval_track_hl", "fw_trace_hl",
     "fw_ppo_diag_floats", "fw_ppo_update_diag",
     "fw_episode_state_bytes", "fw_episode_fold",
+    "fw_trace_rows", "fw_eval_track_wp",
 )
 
 
@@ -121,6 +122,11 @@ def lib() -> C.CDLL:
         L.fw_eval_track_hl.argtypes = ([vp, i32, vp, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, C.c_double] + [vp] * 12 + [i32, i32, vp])
         L.fw_trace_hl.restype = i32
         L.fw_trace_hl.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp]
+        if hasattr(L, "fw_trace_rows"):        # (an A/B library of an older commit predates the pair; build() insists on it)
+            L.fw_trace_rows.restype = i32
+            L.fw_trace_rows.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp]
+            L.fw_eval_track_wp.restype = i32
+            L.fw_eval_track_wp.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32] + [vp] * 12 + [i32, i32, vp]
         L.fw_command_ll.restype = i32
         L.fw_command_ll.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
         L.fw_command_hl.restype = i32

@@ -1595,6 +1595,7 @@ __global__ __launch_bounds__(kWave) void fw_reset_kernel_ll(const Params<T>* __r
 
 // the low-level task's command input and trace (fw_command_ll / fw_trace_ll): the target goes to ll_target_slot above
 #include "fwsim_command.hpp"
+#include "fwsim_flight.hpp"
 // the waypoints task under six direct actuator commands, and the high-level command step in front of it (fw_command_hl)
 #include "fwsim_direct.hpp"
 // ... and the act side of its collected vec-step in one launch (fw_collect_act_hl)
@@ -2653,6 +2654,45 @@ int32_t fw_trace_hl(const void* obs, const void* terminal_obs, const uint8_t* te
   DeviceGuard g(device_of(trace));
   hipLaunchKernelGGL(fw_trace_hl_kernel, dim3(1), dim3(1024), 0, (hipStream_t)hip_stream, obs, terminal_obs, terminated, truncated,
                      command, info, info_dim, (int32_t)FW_INFO_NUM_TARGETS_REACHED, obs_is_f64, N, trace, T, step_idx);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+
+int32_t fw_trace_rows(const void* obs, const void* terminal_obs, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
+                      int32_t info_dim, int32_t obs_is_f64, int32_t N, int32_t obs_dim, double* trace, int32_t T, int64_t* step_idx,
+                      void* hip_stream) {
+  if (!obs || !trace || !step_idx) { g_err = "fw_trace_rows: obs, trace and step_idx must be non-NULL"; return FW_EINVAL; }
+  if (N <= 0 || T <= 0) { g_err = "fw_trace_rows: N and T must be positive, got N=" + std::to_string(N) + ", T=" + std::to_string(T); return FW_EINVAL; }
+  if (obs_dim <= 0) { g_err = "fw_trace_rows: obs_dim must be positive, got " + std::to_string(obs_dim); return FW_EINVAL; }
+  if (info && info_dim <= FW_INFO_NUM_TARGETS_REACHED) { g_err = "fw_trace_rows: info_dim must cover the num_targets_reached column, got " + std::to_string(info_dim); return FW_EINVAL; }
+  DeviceGuard g(device_of(trace));
+  hipLaunchKernelGGL(fw_trace_rows_kernel, dim3(1), dim3(1024), 0, (hipStream_t)hip_stream, obs, terminal_obs, terminated, truncated,
+                     info, info_dim, (int32_t)FW_INFO_NUM_TARGETS_REACHED, obs_is_f64, N, obs_dim, trace, T, step_idx);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+
+int32_t fw_eval_track_wp(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
+                         int32_t info_dim, const void* obs, const void* terminal_obs, int32_t obs_is_f64, int32_t obs_dim, int32_t att_dim,
+                         int32_t act_dim, const int64_t* targets, int64_t* counts, double* cur_rew, int64_t* cur_len, int64_t* step_ctr,
+                         double* cur_path, double* carry, double* fin_rew, int64_t* fin_len, int64_t* fin_step, int32_t* fin_info,
+                         double* fin_path, int32_t N, int32_t E, void* hip_stream) {
+  if (!reward || !terminated || !truncated || !targets || !counts || !cur_rew || !cur_len || !step_ctr || !fin_rew || !fin_len || !fin_step ||
+      (info && (info_dim <= 0 || !fin_info))) { g_err = "fw_eval_track_wp: bad arguments"; return FW_EINVAL; }
+  if (!obs || !terminal_obs || !cur_path || !carry || !fin_path) { g_err = "fw_eval_track_wp: obs, terminal_obs, cur_path, carry and fin_path must be non-NULL"; return FW_EINVAL; }
+  if (att_dim != 12 && att_dim != 13) { g_err = "fw_eval_track_wp: att_dim must be 12 (euler) or 13 (quaternion), got " + std::to_string(att_dim); return FW_EINVAL; }
+  if (act_dim != 4 && act_dim != 6) { g_err = "fw_eval_track_wp: act_dim must be 4 or 6, got " + std::to_string(act_dim); return FW_EINVAL; }
+  if (obs_dim < att_dim + act_dim + 6) { g_err = "fw_eval_track_wp: obs_dim must be at least att_dim + act_dim + 6, got " + std::to_string(obs_dim); return FW_EINVAL; }
+  if (N <= 0 || E <= 0) { g_err = "fw_eval_track_wp: N and E must be positive, got N=" + std::to_string(N) + ", E=" + std::to_string(E); return FW_EINVAL; }
+  EvalTrackArgs A;
+  A.reward = reward; A.reward_is_f64 = reward_is_f64; A.terminated = terminated; A.truncated = truncated; A.info = info; A.info_dim = info_dim;
+  A.targets = targets; A.counts = counts; A.cur_rew = cur_rew; A.cur_len = cur_len; A.step_ctr = step_ctr;
+  A.fin_rew = fin_rew; A.fin_len = fin_len; A.fin_step = fin_step; A.fin_info = fin_info; A.N = N; A.E = E;
+  EvalTrackWPArgs W;
+  W.obs = obs; W.terminal_obs = terminal_obs; W.obs_is_f64 = obs_is_f64; W.obs_dim = obs_dim; W.att_dim = att_dim; W.act_dim = act_dim;
+  W.cur_path = cur_path; W.carry = carry; W.fin_path = fin_path;
+  DeviceGuard g(device_of(reward));
+  hipLaunchKernelGGL(fw_eval_track_wp_kernel, dim3(1), dim3(256), 0, (hipStream_t)hip_stream, A, W);
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }

@@ -20,7 +20,10 @@ Mirrors, for the device-resident envs:
   (:meth:`EvalResult.tracking_scalars`, definitions in DESIGN.md section 2d);
 * for the high-level command task, figures the reference has no script for (build-owned, DESIGN.md section 2e "Evaluation"): how
   the frozen controller follows the commander's commands, how much the commands jump from step to step, how often they sit on a
-  bound of the action Box and how many actions were rejected as non-finite (:meth:`EvalResult.command_scalars`).
+  bound of the action Box and how many actions were rejected as non-finite (:meth:`EvalResult.command_scalars`);
+* for the waypoint, ObjLock and combined tasks, on request (``path_figures=True``), figures of the flight itself (build-owned,
+  DESIGN.md section 2f): path length, airspeed, altitude, control activity, time to the targets, path efficiency and the closest
+  approach to a target that was not reached (:meth:`EvalResult.path_scalars`).
 
 Everything per step stays on the device; the host reads one small ``dones`` mask per
 vec-step (the episode bookkeeping is host-side like SB3's).
@@ -48,6 +51,11 @@ def sync_envs_normalization(train_env, eval_env) -> None:
 
 # FW_TASK_LOWLEVEL's per-episode tracking sums, in the column order of fw_eval_track_ll's cur_track / fin_track
 TRACK_SUMS = ("heading_abs", "heading_sq", "altitude_abs", "altitude_sq", "airspeed_abs", "airspeed_sq", "ang_vel")
+
+
+# the keys of EvalResult.path_scalars (without "eval/"), in the order the evaluation log keeps them
+PATH_SCALARS = ("airspeed_mean", "altitude_mean", "ang_vel_mean", "throttle_mean", "action_delta_mean", "path_length_mean", "altitude_min",
+                "time_to_first_target_s", "time_per_target_s", "path_efficiency", "miss_distance_mean")
 
 
 def _track_terms(o: torch.Tensor) -> torch.Tensor:
@@ -100,6 +108,23 @@ def _hl_bounds(venv):
     return float(venv.cfg.flight_dome_size), float(AIRSPEED_HIGH)
 
 
+def _path_layout(venv):
+    """the row layout of ``venv`` for ``path_figures=True``, or ValueError for an env it is not meant for"""
+    from .flight import RowLayout
+    if _hl_bounds(venv) is not None or hasattr(venv, "step_low"):
+        raise ValueError("path_figures: the high-level command task has its own figures (command_scalars)")
+    cfg = getattr(venv, "cfg", None)
+    if cfg is None or not hasattr(venv, "terminal_obs"):
+        raise ValueError("path_figures needs a waypoints, ObjLock, combined or direct-command waypoints device env")
+    if cfg.task == K.FW_TASK_LOWLEVEL:
+        raise ValueError("path_figures: the low-level task has its own figures (tracking_scalars)")
+    return RowLayout.of(cfg)
+
+
+def _path_complete(info_row) -> bool:
+    return info_row is not None and bool(info_row[K.INFO_ENV_COMPLETE] or info_row[K.INFO_DUCK_STRIKE])
+
+
 @dataclass
 class EvalResult:
     episode_rewards: List[float]
@@ -125,6 +150,27 @@ class EvalResult:
     dcmd_airspeed: List[float] = field(default_factory=list)
     saturated: List[float] = field(default_factory=list)
     rejected_actions: int = 0
+    # path_figures=True only (flight.PATH_SUMS): per episode the twelve path sums, and whether the episode ended
+    # with env_complete or a duck strike (its closest approach then says nothing about a miss)
+    path_len: List[float] = field(default_factory=list)
+    speed_sum: List[float] = field(default_factory=list)
+    alt_sum: List[float] = field(default_factory=list)
+    alt_min: List[float] = field(default_factory=list)
+    ang_vel_sum: List[float] = field(default_factory=list)
+    act_delta_sum: List[float] = field(default_factory=list)
+    throttle_sum: List[float] = field(default_factory=list)
+    first_reach_step: List[float] = field(default_factory=list)
+    last_reach_step: List[float] = field(default_factory=list)
+    chord_len: List[float] = field(default_factory=list)
+    path_at_last_reach: List[float] = field(default_factory=list)
+    miss_dist: List[float] = field(default_factory=list)
+    path_complete: List[bool] = field(default_factory=list)
+
+    def add_path(self, sums, complete: bool = False) -> None:
+        from .flight import PATH_SUMS
+        for name, v in zip(PATH_SUMS, sums):
+            getattr(self, name).append(float(v))
+        self.path_complete.append(bool(complete))
 
     def add_command(self, sums) -> None:
         for name, v in zip(HL_TRACK_SUMS, sums):
@@ -193,12 +239,47 @@ class EvalResult:
         out["eval/rejected_actions"] = float(self.rejected_actions)
         return out
 
+    def path_scalars(self, agent_hz: float, complete=None) -> Dict[str, float]:
+        """The flight's figures (build-owned) from the path sums of ``path_figures=True``; empty without them.
+        Pooled over every evaluated step, as :meth:`tracking_scalars` pools: ``airspeed_mean``, ``altitude_mean``, ``ang_vel_mean``,
+        ``throttle_mean``, ``action_delta_mean`` = sum of the per-step sum / sum L.  Over episodes: ``path_length_mean``;
+        ``altitude_min``, the minimum over episodes; over the episodes that reached a target (absent when none did)
+        ``time_to_first_target_s`` = mean first_reach_step / agent_hz, ``time_per_target_s`` = sum last_reach_step / sum targets reached
+        / agent_hz, ``path_efficiency`` = sum chord_len / sum path_at_last_reach; ``miss_distance_mean`` over the episodes that ended
+        neither with env_complete nor with a duck strike (``complete``: one bool per episode, default what ``add_path`` was told) and
+        whose closest approach is finite (absent when there is none)."""
+        if not self.path_len:
+            return {}
+        hz = float(agent_hz)
+        steps = float(np.sum(self.episode_lengths))
+        out = {"eval/airspeed_mean": float(np.sum(self.speed_sum)) / steps, "eval/altitude_mean": float(np.sum(self.alt_sum)) / steps,
+               "eval/ang_vel_mean": float(np.sum(self.ang_vel_sum)) / steps, "eval/throttle_mean": float(np.sum(self.throttle_sum)) / steps,
+               "eval/action_delta_mean": float(np.sum(self.act_delta_sum)) / steps,
+               "eval/path_length_mean": float(np.mean(self.path_len)), "eval/altitude_min": float(np.min(self.alt_min))}
+        first, last = np.asarray(self.first_reach_step, dtype=np.float64), np.asarray(self.last_reach_step, dtype=np.float64)
+        hit = first > 0
+        if hit.any():
+            out["eval/time_to_first_target_s"] = float(np.mean(first[hit] / hz))
+            if len(self.num_targets_reached) == len(first):
+                n_reached = float(np.asarray(self.num_targets_reached, dtype=np.float64)[hit].sum())
+                if n_reached > 0:
+                    out["eval/time_per_target_s"] = float(last[hit].sum()) / n_reached / hz
+            at = float(np.asarray(self.path_at_last_reach, dtype=np.float64)[hit].sum())
+            if at > 0:
+                out["eval/path_efficiency"] = float(np.asarray(self.chord_len, dtype=np.float64)[hit].sum()) / at
+        comp = np.asarray(self.path_complete if complete is None else complete, dtype=bool)
+        miss = np.asarray(self.miss_dist, dtype=np.float64)
+        keep = ~comp & np.isfinite(miss)
+        if keep.any():
+            out["eval/miss_distance_mean"] = float(np.mean(miss[keep]))
+        return out
+
 
 @torch.no_grad()
 def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool = True,
                     callback: Optional[Callable[[dict], None]] = None, max_vec_steps: Optional[int] = None,
                     generator: Optional[torch.Generator] = None, use_graph: Optional[bool] = None,
-                    use_fused: Optional[bool] = None) -> EvalResult:
+                    use_fused: Optional[bool] = None, path_figures: bool = False) -> EvalResult:
     """Run ``policy`` on ``env`` (a :class:`~.rollout.VecNormalizeDevice` over a device env,
     normally with ``training=False, norm_reward=False``) until ``n_eval_episodes`` episodes are
     complete.  ``callback(info_dict)`` is called for every finished episode with the keys the
@@ -223,15 +304,21 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
     from torch ops (``_track_terms_hl``) in the step-by-step loop, from ``fw_eval_track_hl`` in the replayed one.  Its three-action
     MlpPolicy keeps the torch forward by default; ``use_fused=True`` makes a vec-step ``fw_collect_act_hl`` -> ``fw_step`` ->
     ``fw_eval_track_hl``.  ``venv.rejected`` is zeroed when the evaluation begins and read once at its end
-    (``EvalResult.rejected_actions``: every env-step the evaluation ran counts, the ones past an env's last wanted episode too)."""
+    (``EvalResult.rejected_actions``: every env-step the evaluation ran counts, the ones past an env's last wanted episode too).
+
+    ``path_figures=True`` (the waypoint, ObjLock, combined and direct-command waypoints tasks; ``ValueError`` for the low- and
+    high-level tasks): the result also carries the twelve path sums of every episode (:meth:`EvalResult.path_scalars`, DESIGN.md
+    section 2f): from torch ops (``flight.path_step``) in the step-by-step loop, from ``fw_eval_track_wp`` -- in place of
+    ``fw_eval_track`` / the framework ops -- in the replayed one, on its torch-forward and on its ``fw_collect_step`` body."""
     venv = env.venv
     n = env.num_envs
+    path_layout = _path_layout(venv) if path_figures else None
     targets = np.array([(n_eval_episodes + i) // n for i in range(n)], dtype=np.int64)
     if use_graph is None:
         use_graph = (deterministic and generator is None and torch.device(env.device).type == "cuda" and hasattr(venv, "step_tensor")
                      and not getattr(policy, "uses_image", False))        # (a CNN front end keeps MIOpen out of captures)
     if use_graph:
-        return ReplayedEvaluation(policy, env, targets, callback, use_fused=use_fused).run(max_vec_steps)
+        return ReplayedEvaluation(policy, env, targets, callback, use_fused=use_fused, path_figures=path_figures).run(max_vec_steps)
     counts = np.zeros(n, dtype=np.int64)
     cur_rew = torch.zeros(n, dtype=torch.float64, device=env.device)
     cur_len = torch.zeros(n, dtype=torch.int64, device=env.device)
@@ -246,6 +333,9 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
         prev_cmd = torch.zeros((n, 3), dtype=torch.float64, device=env.device)
         venv.rejected.zero_()
     obs = env.reset()
+    if path_layout is not None:
+        from . import flight
+        cur_path, carry = flight.path_init(n, env.device), flight.seed_carry(venv.obs, path_layout)
     steps = 0
     while (counts < targets).any():
         actions, _, _ = policy(obs, deterministic=deterministic, generator=generator, **policy_inputs(policy, env))
@@ -255,6 +345,11 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
         if hl is not None:                               # venv.command: the triple that was in force during the step
             cur_hl += _track_terms_hl(torch.where(dones[:, None], venv.terminal_obs, venv.obs), venv.command, prev_cmd, cur_len == 0, *hl)
             prev_cmd = venv.command.to(torch.float64).clone()
+        if path_layout is not None:                      # the post-step row; where the episode ended the live row seeds the next one
+            cur_path, carry = flight.path_step(torch.where(dones[:, None], venv.terminal_obs, venv.obs),
+                                               venv.info[:, K.INFO_NUM_TARGETS_REACHED] if has_info else None, cur_len == 0, cur_path,
+                                               carry, path_layout, cur_len + 1)
+            carry = torch.where(dones[:, None], flight.seed_carry(venv.obs, path_layout), carry)
         cur_len += 1
         if track:                                        # the post-step row: the terminal observation where the episode ended
             cur_trk += _track_terms(torch.where(dones[:, None], venv.terminal_obs, venv.obs))
@@ -265,6 +360,7 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
             info_h = venv.info.cpu().numpy() if has_info else None
             trk_h, term_h = (cur_trk.cpu().numpy(), venv.terminated.cpu().numpy()) if track else (None, None)
             hl_h = cur_hl.cpu().numpy() if hl is not None else None
+            path_h = cur_path.cpu().numpy() if path_layout is not None else None
             for i in idx:
                 if counts[i] < targets[i]:
                     counts[i] += 1
@@ -273,6 +369,8 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
                         res.add_tracking(trk_h[i], not term_h[i])
                     if hl_h is not None:
                         res.add_command(hl_h[i])
+                    if path_h is not None:
+                        res.add_path(path_h[i], _path_complete(info_h[i] if info_h is not None else None))
                     info = {"episode": {"r": float(rew_h[i]), "l": int(len_h[i])}}
                     if info_h is not None:
                         info["num_targets_reached"] = int(info_h[i, K.INFO_NUM_TARGETS_REACHED])
@@ -295,6 +393,8 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
                 cur_trk.masked_fill_(m[:, None], 0.0)
             if hl is not None:
                 cur_hl.masked_fill_(m[:, None], 0.0)
+            if path_layout is not None:
+                cur_path = torch.where(m[:, None], flight.path_init(n, env.device), cur_path)
         steps += 1
         if max_vec_steps is not None and steps >= max_vec_steps:
             break
@@ -340,11 +440,16 @@ class ReplayedEvaluation:
 
     The high-level command task's bookkeeping is one ``fw_eval_track_hl`` launch per vec-step, which also sums its command figures.
     ``use_fused=True`` with its three-action MlpPolicy (``fused3``): a vec-step is ``fw_collect_act_hl`` (commander and controller,
-    policy nets only, deterministic, frozen statistics) -> ``fw_step`` (``step_low``) -> ``fw_eval_track_hl``, in sequence."""
+    policy nets only, deterministic, frozen statistics) -> ``fw_step`` (``step_low``) -> ``fw_eval_track_hl``, in sequence.
 
-    def __init__(self, policy, env, targets: np.ndarray, callback=None, use_fused: Optional[bool] = None):
+    ``path_figures=True`` (the waypoint, ObjLock, combined and direct-command waypoints tasks): the bookkeeping of a vec-step is one
+    ``fw_eval_track_wp`` launch -- in place of the framework ops behind the torch forward, and of ``fw_eval_track`` behind
+    ``fw_collect_step`` -- which also carries the twelve path sums of ``flight.PATH_SUMS``.  Off, nothing is launched that was not."""
+
+    def __init__(self, policy, env, targets: np.ndarray, callback=None, use_fused: Optional[bool] = None, path_figures: bool = False):
         self.policy, self.env, self.callback = policy, env, callback
         venv, n, dev = env.venv, env.num_envs, env.device
+        self.path_layout = _path_layout(venv) if path_figures else None
         self.fused = self._fused_applies(policy, env) if use_fused is None else bool(use_fused)
         # the six-action policy of the low-level task: only on request (the default keeps its torch forward)
         self.fused6 = self.fused and not self._fused_applies(policy, env) and self._fused6_applies(policy, env)
@@ -378,6 +483,11 @@ class ReplayedEvaluation:
             self.cur_track = torch.zeros((n, len(HL_TRACK_SUMS)), dtype=torch.float64, device=dev)
             self.fin_track = torch.zeros((n, E, len(HL_TRACK_SUMS)), dtype=torch.float64, device=dev)
             self.prev_cmd = torch.zeros((n, 3), dtype=torch.float64, device=dev)
+        if self.path_layout is not None:
+            from . import flight
+            self.cur_path = flight.path_init(n, dev)
+            self.carry = torch.zeros((n, flight.CARRY_DIM), dtype=torch.float64, device=dev)      # seeded behind the reset (_begin)
+            self.fin_path = torch.zeros((n, E, len(flight.PATH_SUMS)), dtype=torch.float64, device=dev)
         self.obs = None
         self.side = torch.cuda.Stream(device=dev)
         self.done_event = None
@@ -500,8 +610,29 @@ class ReplayedEvaluation:
             _p(self.fin_rew), _p(self.fin_len), _p(self.fin_step), _p(fi) if fi is not None else None, _p(self.fin_track),
             self.n, self.E, _stream(self.dev)))
 
+    def _track_wp_step(self) -> None:
+        """the bookkeeping of a vec-step with the path sums: one fw_eval_track_wp launch (path_figures=True)"""
+        from . import _lib
+        from .rollout import _p, _stream
+        venv, fi, lay = self.venv, self.fin_info, self.path_layout
+        _lib.check(_lib.lib().fw_eval_track_wp(
+            _p(venv.rewards), int(venv.rewards.dtype == torch.float64), _p(venv.terminated), _p(venv.truncated),
+            _p(venv.info) if fi is not None else None, int(venv.info.shape[1]) if fi is not None else 0,
+            _p(venv.obs), _p(venv.terminal_obs), int(venv.obs.dtype == torch.float64), int(venv.obs.shape[1]), lay.att_dim, lay.act_dim,
+            _p(self.tg), _p(self.counts), _p(self.cur_rew), _p(self.cur_len), _p(self.step_ctr), _p(self.cur_path), _p(self.carry),
+            _p(self.fin_rew), _p(self.fin_len), _p(self.fin_step), _p(fi) if fi is not None else None, _p(self.fin_path),
+            self.n, self.E, _stream(self.dev)))
+
+    def _collect_prepare(self) -> None:
+        """fw_collect_step's workspace, initialised once (in front of the first launch, outside any capture)"""
+        from . import _lib
+        from .rollout import _stream
+        if not self._ws_ready:
+            venv = self.venv
+            _lib.check(_lib.lib().fw_collect_workspace_init(venv._h, self._ws.data_ptr(), self._ws.numel() * 8, _stream(self.dev)), venv._h)
+            self._ws_ready = True
+
     def _fused_step(self) -> None:
-        import ctypes as C
         from . import _lib
         from .rollout import _stream
         if self.fused6:
@@ -510,11 +641,28 @@ class ReplayedEvaluation:
         if self.fused3:
             self._fused3_step()
             return
+        self._collect_step()
+        if self.path_layout is not None:
+            self._track_wp_step()
+            return
+        # ... and the episode bookkeeping of the step in one more (fw_eval_track)
+        venv, L, st = self.venv, _lib.lib(), _stream(self.dev)
+        fi = self.fin_info
+        _lib.check(L.fw_eval_track(venv.rewards.data_ptr(), int(venv.rewards.dtype == torch.float64), venv.terminated.data_ptr(),
+                                   venv.truncated.data_ptr(), venv.info.data_ptr() if fi is not None else None,
+                                   int(venv.info.shape[1]) if fi is not None else 0, self.tg.data_ptr(), self.counts.data_ptr(),
+                                   self.cur_rew.data_ptr(), self.cur_len.data_ptr(), self.step_ctr.data_ptr(), self.fin_rew.data_ptr(),
+                                   self.fin_len.data_ptr(), self.fin_step.data_ptr(), fi.data_ptr() if fi is not None else None,
+                                   self.n, self.E, st))
+
+    def _collect_step(self) -> None:
+        """act + env step of the four-action policy as ONE fw_collect_step launch (deterministic, statistics frozen)"""
+        import ctypes as C
+        from . import _lib
+        from .rollout import _stream
         env, venv = self.env, self.venv
         L, st = _lib.lib(), _stream(self.dev)
-        if not self._ws_ready:
-            _lib.check(L.fw_collect_workspace_init(venv._h, self._ws.data_ptr(), self._ws.numel() * 8, st), venv._h)
-            self._ws_ready = True
+        self._collect_prepare()
         a = K.FwCollectArgs()
         a.params = self._flat.data_ptr()
         a.obs_mean, a.obs_var, a.obs_count = env.obs_rms.mean.data_ptr(), env.obs_rms.var.data_ptr(), env.obs_rms.count.data_ptr()
@@ -531,14 +679,6 @@ class ReplayedEvaluation:
         a.clip_obs, a.eps_obs, a.clip_reward, a.eps_reward = float(env.clip_obs), float(env.epsilon), float(env.clip_reward), float(env.epsilon)
         a.update_obs, a.update_ret, a.norm_reward, a.deterministic = 0, 0, 0, 1
         _lib.check(L.fw_collect_step(venv._h, C.byref(a), st), venv._h)
-        # ... and the episode bookkeeping of the step in one more (fw_eval_track)
-        fi = self.fin_info
-        _lib.check(L.fw_eval_track(venv.rewards.data_ptr(), int(venv.rewards.dtype == torch.float64), venv.terminated.data_ptr(),
-                                   venv.truncated.data_ptr(), venv.info.data_ptr() if fi is not None else None,
-                                   int(venv.info.shape[1]) if fi is not None else 0, self.tg.data_ptr(), self.counts.data_ptr(),
-                                   self.cur_rew.data_ptr(), self.cur_len.data_ptr(), self.step_ctr.data_ptr(), self.fin_rew.data_ptr(),
-                                   self.fin_len.data_ptr(), self.fin_step.data_ptr(), fi.data_ptr() if fi is not None else None,
-                                   self.n, self.E, st))
 
     def _fused_check(self) -> None:
         """fw_collect_step's status word: a wait inside one of the launches ran out -> the evaluation is void ("returns or raises")"""
@@ -567,6 +707,9 @@ class ReplayedEvaluation:
         if self.hl is not None:
             self._track_hl_step()
             return
+        if self.path_layout is not None:
+            self._track_wp_step()
+            return
         self.cur_rew.add_(venv.rewards.to(torch.float64))            # un-normalised reward of the wrapped env
         self.cur_len.add_(1); self.step_ctr.add_(1)
         take = dones & (counts < tg)
@@ -586,6 +729,9 @@ class ReplayedEvaluation:
             if self.hl is not None:
                 self.venv.rejected.zero_()
             self.obs = self.env.reset().clone()
+            if self.path_layout is not None:
+                from . import flight
+                self.carry.copy_(flight.seed_carry(self.venv.obs, self.path_layout))
             for _ in range(2):
                 self._body(); self.steps += 1
             self.graph = torch.cuda.CUDAGraph()
@@ -628,6 +774,7 @@ class ReplayedEvaluation:
         info_h = self.fin_info.cpu().numpy() if has_info else None
         trk_h = self.fin_track.cpu().numpy() if self.track else None
         hl_h = self.fin_track.cpu().numpy() if self.hl is not None else None
+        path_h = self.fin_path.cpu().numpy() if self.path_layout is not None else None
         if self.hl is not None:
             res.rejected_actions = int(self.venv.rejected.item())
         order = sorted((int(step_h[i, k]), i, k) for i in range(n) for k in range(int(c_h[i])))    # as they ended: by step, then env
@@ -637,19 +784,22 @@ class ReplayedEvaluation:
                 res.add_tracking(trk_h[i, k, :len(TRACK_SUMS)], trk_h[i, k, len(TRACK_SUMS)] != 0.0)
             if hl_h is not None:
                 res.add_command(hl_h[i, k])
+            if path_h is not None:
+                res.add_path(path_h[i, k], _path_complete(info_h[i, k] if has_info else None))
             info = _episode_info(res, float(rew_h[i, k]), int(len_h[i, k]), info_h[i, k] if has_info else None, self.is_objlock)
             if self.callback is not None:
                 self.callback(info)
         return res
 
 
-def start_evaluation(policy, env, n_eval_episodes: int = 10, callback=None, use_fused: Optional[bool] = None) -> ReplayedEvaluation:
+def start_evaluation(policy, env, n_eval_episodes: int = 10, callback=None, use_fused: Optional[bool] = None,
+                     path_figures: bool = False) -> ReplayedEvaluation:
     """Asynchronous :func:`evaluate_policy` (deterministic, device envs whose config bounds the episode length): returns a
     running :class:`ReplayedEvaluation`; ``.result()`` waits for it."""
     n = env.num_envs
     targets = np.array([(n_eval_episodes + i) // n for i in range(n)], dtype=np.int64)
     bound = int(targets.max()) * (K.max_steps(env.venv.cfg) + 2)
-    return ReplayedEvaluation(policy, env, targets, callback, use_fused=use_fused).launch(bound)
+    return ReplayedEvaluation(policy, env, targets, callback, use_fused=use_fused, path_figures=path_figures).launch(bound)
 
 
 class EvalCallback:
@@ -669,7 +819,8 @@ class EvalCallback:
 
     def __init__(self, eval_env, n_eval_episodes: int = 5, eval_freq: int = 10000, log_path: Optional[str] = None,
                  best_model_save_path: Optional[str] = None, deterministic: bool = True, num_targets_total: int = 0,
-                 verbose: int = 0, overlap: Optional[bool] = None, use_fused: Optional[bool] = None):
+                 verbose: int = 0, overlap: Optional[bool] = None, use_fused: Optional[bool] = None,
+                 path_figures: bool = False):
         self.eval_env, self.n_eval_episodes, self.eval_freq = eval_env, n_eval_episodes, max(int(eval_freq), 1)
         self.log_path = os.path.join(log_path, "evaluations") if log_path else None
         self.best_model_save_path, self.deterministic = best_model_save_path, deterministic
@@ -684,10 +835,16 @@ class EvalCallback:
         self._next_eval_calls = self.eval_freq
         self.n_evals = 0
         self.overlap = overlap
+        self.path_figures = bool(path_figures)      # the flight's figures as well (EvalResult.path_scalars; not for the low- / high-level tasks)
+        if self.path_figures:
+            _path_layout(eval_env.venv)
         self.use_fused = use_fused        # handed to evaluate_policy / start_evaluation (None: fused whenever it is the default there)
         self._pending = None              # (job, num_timesteps at launch, checkpoint snapshot or None)
         self._policy_copy = None
         self._seed0, self._n_launched = None, 0
+
+    def _agent_hz(self) -> float:
+        return float(self.eval_env.venv.cfg.agent_hz)
 
     def _can_overlap(self, ppo) -> bool:
         if not self.overlap:
@@ -725,10 +882,12 @@ class EvalCallback:
                 self._policy_copy = copy.deepcopy(ppo.policy)
             else:
                 self._policy_copy.load_state_dict(ppo.policy.state_dict())
-            job = start_evaluation(self._policy_copy, self.eval_env, self.n_eval_episodes, use_fused=self.use_fused)
+            job = start_evaluation(self._policy_copy, self.eval_env, self.n_eval_episodes, use_fused=self.use_fused,
+                                   path_figures=self.path_figures)
             self._pending = (job, ppo.num_timesteps, snap)
         else:
-            r = evaluate_policy(ppo.policy, self.eval_env, self.n_eval_episodes, deterministic=self.deterministic, use_fused=self.use_fused)
+            r = evaluate_policy(ppo.policy, self.eval_env, self.n_eval_episodes, deterministic=self.deterministic, use_fused=self.use_fused,
+                                path_figures=self.path_figures)
             self._record(ppo, r, ppo.num_timesteps, snap)
         return True
 
@@ -762,6 +921,10 @@ class EvalCallback:
                 self.evaluations_tracking.setdefault(k.split("/", 1)[1], []).append(v)
             for k, v in r.command_scalars().items():               # the high-level command task: cmd_heading_mae, ...: (n_evals,)
                 self.evaluations_tracking.setdefault(k.split("/", 1)[1], []).append(v)
+            if self.path_figures:                                  # path_length_mean, ...: (n_evals,), NaN where a key was absent
+                ps = r.path_scalars(self._agent_hz())
+                for name in PATH_SCALARS:
+                    self.evaluations_tracking.setdefault(name, []).append(ps.get("eval/" + name, float("nan")))
             kw.update({k: np.array(v, dtype=np.float64) for k, v in self.evaluations_tracking.items()})
             np.savez(self.log_path, timesteps=self.evaluations_timesteps, results=np.array(self.evaluations_results, dtype=object),
                      ep_lengths=np.array(self.evaluations_length, dtype=object), **kw)
@@ -771,6 +934,8 @@ class EvalCallback:
         self.last_scalars = r.scalars(self.num_targets_total, has_duck=is_objlock)
         self.last_scalars.update(r.tracking_scalars())             # (the low-level task's; nothing for the others)
         self.last_scalars.update(r.command_scalars())              # (the high-level command task's; nothing for the others)
+        if self.path_figures:
+            self.last_scalars.update(r.path_scalars(self._agent_hz()))
         self.last_scalars["time/total_timesteps"] = timesteps
         if self.verbose and writer:
             print(f"Eval num_timesteps={timesteps}, episode_reward={r.mean_reward:.2f} +/- {r.std_reward:.2f}")
