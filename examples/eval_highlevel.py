@@ -29,6 +29,8 @@ def main():
     ap.add_argument("--num_envs", type=int, default=16)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fused", action="store_true", help="commander and controller in the fused kernel (fw_collect_act_hl)")
+    ap.add_argument("--controller_hz", type=int, default=None,
+                    help="the rate the frozen controller runs at: 30 (default, once per agent step) or 120 (once per Aviary step, inside the step kernel)")
     ap.add_argument("--trace_steps", type=int, default=0, help="also record a flight of this many vec-steps (trace.npz)")
     ap.add_argument("--out", type=str, default=None, help="directory for evaluation.json and trace.npz")
     a = ap.parse_args()
@@ -42,7 +44,7 @@ def main():
 
     def make():
         venv = P.HighLevelCmdVecEnv(a.num_envs, low_checkpoint=a.low_checkpoint, flight_dome_size=200.0, max_duration_seconds=120.0,
-                                    agent_hz=30, context_length=2, seed=a.seed)
+                                    agent_hz=30, context_length=2, seed=a.seed, controller_hz=a.controller_hz)
         env = R.VecNormalizeDevice(venv, training=False, norm_reward=False, clip_obs=10.0)
         vecnorm = checkpoint.infer_vecnorm_path(a.checkpoint, a.vecnorm_path)
         if vecnorm:
@@ -77,7 +79,7 @@ def main():
     if a.out:
         os.makedirs(a.out, exist_ok=True)
         with open(os.path.join(a.out, "evaluation.json"), "w") as f:
-            json.dump({"checkpoint": a.checkpoint, "low_checkpoint": a.low_checkpoint, "episodes": len(r.episode_lengths), "fused": bool(a.fused),
+            json.dump({"checkpoint": a.checkpoint, "low_checkpoint": a.low_checkpoint, "episodes": len(r.episode_lengths), "fused": bool(a.fused), "controller_hz": a.controller_hz or 30,
                        "episode_rewards": r.episode_rewards, "episode_lengths": r.episode_lengths,
                        **{k.split("/", 1)[1]: v for k, v in {**sc, **cs}.items()}}, f, indent=1)
     if a.trace_steps > 0:

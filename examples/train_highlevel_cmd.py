@@ -36,6 +36,9 @@ def main():
     ap.add_argument("--n_steps", type=int, default=None, help="default: the reference's 16 x 1024 samples per update, split over --num_envs")
     ap.add_argument("--out", type=str, default="runs/highlevel_ppo")
     ap.add_argument("--fused_learner", action="store_true", help="the fused three-action update / collector kernels instead of the torch path")
+    ap.add_argument("--controller_hz", type=int, default=None,
+                    help="the rate the frozen controller runs at: 30 (default, once per agent step, the reference's behaviour) or 120 "
+                         "(once per Aviary step inside the step kernel: the rate it was trained at)")
     ap.add_argument("--fused_eval", action="store_true", help="the evaluations through the fused three-action kernels (use_fused=True) instead of the torch forward")
     ap.add_argument("--episode_stats", action="store_true",
                     help="SB3's rollout/* figures (ep_rew_mean, ep_len_mean, success_rate over the last 100 episodes, and the "
@@ -49,7 +52,7 @@ def main():
 
     def make(n, seed):                      # a missing checkpoint raises FileNotFoundError here, as the reference does (:110-121)
         return P.HighLevelCmdVecEnv(n, low_checkpoint=a.low_checkpoint, flight_dome_size=200.0, max_duration_seconds=120.0, agent_hz=30,
-                                    context_length=2, wind_config=cfg["wind"], seed=seed)
+                                    context_length=2, wind_config=cfg["wind"], seed=seed, controller_hz=a.controller_hz)
 
     venv = make(num_envs, cfg["seed"])
     os.makedirs(model_dir, exist_ok=True); os.makedirs(log_dir, exist_ok=True)

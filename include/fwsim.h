@@ -736,6 +736,35 @@ typedef struct fw_collect_hl_args {
 } fw_collect_hl_args;
 int32_t fw_sizeof_collect_hl_args(void);   /* for bindings: the size of the structure this build was compiled with */
 int32_t fw_collect_act_hl(fw_handle h, const fw_collect_hl_args* a, void* hip_stream);
+
+/* The high-level command task with the frozen controller at the control rate (controller_hz = control_hz): ONE agent step of a
+ * FW_TASK_WAYPOINTS_DIRECT handle with the euler attitude (anything else: FW_EUNSUPPORTED, fw_command_hl's rule) in which the
+ * controller runs in front of every Aviary step of the agent step, inside the step kernel, instead of once per agent step in front
+ * of fw_step.  There is no action input: the command in force is the env's FW_SL_TARGET tail, written by fw_command_hl /
+ * fw_collect_act_hl (after an auto-reset: level flight at the start height and speed).  Per Aviary step the controller's raw row is
+ * (columns 0:12 of the observation of the current rigid state, the six actuator commands last issued -- the tail's on the first
+ * Aviary step, zeros after a reset -- and the command), normalised as fw_collect_act_a normalises (low_mean / low_var / low_clip /
+ * low_eps, frozen); the policy net of the six-action flat image low_params (fw_ppo_param_count_a(21, 6) floats) gives the mean
+ * action, clipped to [-1, 1]: fw_controller_forward's arithmetic, bit for bit.  Warm-up steps of an in-kernel reset and envs that
+ * are done at entry run no controller.  The output buffers are fw_step's; low_action (T[N, 6], may be NULL) receives the
+ * controller's output that was in force when the step ended.  The observation and the tail show the same six values (zeros after
+ * an auto-reset).  No in-grid wait, no host synchronisation: capturable.  A missing required pointer: FW_EINVAL. */
+typedef struct fw_step_hl_args {
+  const float* low_params;                 /* the controller's flat parameter image */
+  const double *low_mean, *low_var;        /* [21] its frozen observation statistics */
+  void *obs, *reward;                      /* the output buffers of fw_step */
+  uint8_t *terminated, *truncated;
+  void* terminal_obs;                      /* may be NULL */
+  int32_t* info_i32;                       /* may be NULL */
+  void* low_action;                        /* T[N, 6], may be NULL */
+  float low_clip, low_eps;
+} fw_step_hl_args;
+int32_t fw_sizeof_step_hl_args(void);      /* for bindings: the size of the structure this build was compiled with */
+int32_t fw_step_hl(fw_handle h, const fw_step_hl_args* a, void* hip_stream);
+/* The controller as fw_step_hl's kernel computes it, on raw rows [N, 21] (float64 or float32), one thread per env:
+ * act_out[i] (float64 or float32 [N, 6]) = clip(policy_net(clip((raw_obs[i] - mean) / sqrt(var + eps), +-clip)), +-1). */
+int32_t fw_controller_forward(const float* params, const void* raw_obs, int32_t obs_is_f64, int32_t N, const double* mean, const double* var,
+                              float clip, float eps, void* act_out, int32_t act_is_f64, void* hip_stream);
 int64_t fw_collect_stats_workspace_bytes(int32_t D);
 int32_t fw_collect_stats(const void* obs, int32_t obs_is_f64, int32_t N, int32_t D, double* obs_mean, double* obs_var, double* obs_count,
                          int32_t update_obs, const void* reward, int32_t rew_is_f64, const uint8_t* terminated, const uint8_t* truncated,

@@ -28,6 +28,7 @@ EXPORTS = (
     "fw_ppo_diag_floats", "fw_ppo_update_diag",
     "fw_episode_state_bytes", "fw_episode_fold",
     "fw_trace_rows", "fw_eval_track_wp",
+    "fw_step_hl", "fw_sizeof_step_hl_args", "fw_controller_forward",
 )
 
 
@@ -181,6 +182,13 @@ def lib() -> C.CDLL:
         L.fw_ppo_update_diag.argtypes = [vp] * 9 + [i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, i64]
         L.fw_collect_act_hl.restype = i32; L.fw_collect_act_hl.argtypes = [vp, vp, vp]
         L.fw_sizeof_collect_hl_args.restype = i32; L.fw_sizeof_collect_hl_args.argtypes = []
+        if hasattr(L, "fw_step_hl"):           # (an A/B library of an older commit predates the pair; build() insists on it)
+            L.fw_step_hl.restype = i32; L.fw_step_hl.argtypes = [vp, vp, vp]
+            L.fw_sizeof_step_hl_args.restype = i32; L.fw_sizeof_step_hl_args.argtypes = []
+            L.fw_controller_forward.restype = i32
+            L.fw_controller_forward.argtypes = [vp, vp, i32, i32, vp, vp, f32, f32, vp, i32, vp]
+            if L.fw_sizeof_step_hl_args() != C.sizeof(K.FwStepHlArgs):
+                raise RuntimeError("fw_step_hl_args layout mismatch between include/fwsim.h and config.FwStepHlArgs")
         L.fw_policy_act_a.restype = i32
         L.fw_policy_act_a.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
         L.fw_collect_act_a.restype = i32

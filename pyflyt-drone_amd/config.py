@@ -270,6 +270,13 @@ class FwCollectHlArgs(C.Structure):
                 + [(n, C.c_int32) for n in ("nets", "deterministic", "norm_reward")])
 
 
+class FwStepHlArgs(C.Structure):
+    """``fw_step_hl_args`` of include/fwsim.h (an agent step with the frozen controller at the control rate inside the kernel)."""
+    _fields_ = ([(n, C.c_void_p) for n in ("low_params", "low_mean", "low_var", "obs", "reward", "terminated", "truncated", "terminal_obs",
+                                             "info_i32", "low_action")]
+                + [(n, C.c_float) for n in ("low_clip", "low_eps")])
+
+
 class FwCollectCloseArgs(C.Structure):
     """``fw_collect_close_args`` of include/fwsim.h (GAE buffers of the rollout-closing launch)."""
     _fields_ = ([(n, C.c_void_p) for n in ("rewards", "values", "episode_starts", "adv", "ret")]

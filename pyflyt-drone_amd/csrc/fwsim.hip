@@ -1600,6 +1600,8 @@ __global__ __launch_bounds__(kWave) void fw_reset_kernel_ll(const Params<T>* __r
 #include "fwsim_direct.hpp"
 // ... and the act side of its collected vec-step in one launch (fw_collect_act_hl)
 #include "fwsim_collect_hl.hpp"
+// ... and its step with the frozen controller at the control rate inside the kernel (fw_step_hl, fw_controller_forward)
+#include "fwsim_hl_step.hpp"
 
 // ======================================================================
 // host side
@@ -1819,6 +1821,7 @@ struct fw_env {
   int32_t aux_wave = 0;         // the axis-aligned row with motor noise, up to kAuxWaveMaxEnvs envs: a second wave per step workgroup draws the noise (fw_step_kernel_g8x)
   int32_t axis_aligned = 0;     // f64 wind-free waypoints on the 8-lane one-wave build: the tick's axis-aligned variant (axis_aligned_geometry)
   EnvKernel step, reset, collect;   // chosen once by fw_create from the fields above (select_kernels); collect.fn is null where fw_collect_step does not serve
+  EnvKernel step_hl;                // fw_step_hl's kernel (hl_step_kernel_of); null where fw_step_hl does not serve
   uint64_t seed = 0;
   int64_t env_offset = 0;
   void* params_dev = nullptr;   // Params<T>
@@ -2061,11 +2064,34 @@ template <typename T> int select_kernels(fw_env* h) {
   return FW_OK;
 }
 
+// fw_step_hl's kernels, a table of their own: the direct-command waypoints task with the euler attitude (fw_command_hl's rule), by
+// lane mapping and wind.  Any other handle holds no kernel, and fw_step_hl says so.
+struct HlStepRow { int lanes, windy; EnvKernel step; };
+template <typename T> using HlStepFn = void (*)(const Params<T>*, const ObjC<T>*, DevState<T>, fwsim_ctl::CtlArgs, T*, T*, uint8_t*, uint8_t*, T*, int32_t*);
+template <typename T> EnvKernel hl_step_k(HlStepFn<T> f) { return {kfn(f)}; }
+template <typename T> EnvKernel hl_step_kernel_of(const fw_env* h) {
+  static const HlStepRow rows[] = {
+    {8, 1, hl_step_k<T>(fw_step_kernel_wdc<T, 8, true>)}, {8, 0, hl_step_k<T>(fw_step_kernel_wdc<T, 8, false>)},
+    {1, 1, hl_step_k<T>(fw_step_kernel_wdc<T, 1, true>)}, {1, 0, hl_step_k<T>(fw_step_kernel_wdc<T, 1, false>)},
+  };
+  if (h->cfg.task != FW_TASK_WAYPOINTS_DIRECT || h->cfg.angle_representation != 0) return {};
+  const int windy = h->cfg.wind_mode != FW_WIND_OFF ? 1 : 0;
+  for (const HlStepRow& r : rows) if (r.lanes == h->lanes_per_env && r.windy == windy) return r.step;
+  return {};
+}
+// dynamic LDS of an fw_step_hl launch: the observation tile, then the controller's statistics, (8 lanes per env) its policy net, and
+// one activation row per env of the wave
+template <typename T> size_t hl_step_lds_bytes(const fw_env* h) {
+  return ((tile_bytes<T>(h) + 15) & ~(size_t)15) + fwsim_ctl::ctl_lds_bytes(kWave / h->lanes_per_env, h->lanes_per_env == 8);
+}
+
 template <typename T>
 int create_T(fw_env* h) {
   const size_t npad = (size_t)h->npad;
   int rc = select_kernels<T>(h);
   if (rc != FW_OK) return rc;
+  h->step_hl = hl_step_kernel_of<T>(h);
+  if (h->step_hl.fn && (rc = ensure_dynamic_lds(h, h->device, h->step_hl.fn, hl_step_lds_bytes<T>(h))) != FW_OK) return rc;
   HIP_TRY(h, hipMalloc(&h->r_dev, sizeof(T) * RF_COUNT * npad));
   HIP_TRY(h, hipMalloc((void**)&h->i_dev, sizeof(int32_t) * IF_COUNT * npad));
   rc = upload_params<T>(h);
@@ -2631,6 +2657,49 @@ int32_t fw_command_hl(fw_handle h, const void* action, int32_t action_is_f64, co
                        (const T*)obs, D, (T*)low_obs, (T*)cmd_out, rejected, dome);
   }); }); });
   HIP_TRY(h, hipGetLastError());
+  return FW_OK;
+}
+
+int32_t fw_sizeof_step_hl_args(void) { return (int32_t)sizeof(fw_step_hl_args); }
+int32_t fw_step_hl(fw_handle h, const fw_step_hl_args* a, void* hip_stream) {
+  if (!h) { g_err = "fw_step_hl: NULL handle"; return FW_EINVAL; }
+  if (h->cfg.task != FW_TASK_WAYPOINTS_DIRECT) { h->err = "fw_step_hl: only the direct-command waypoints task (FW_TASK_WAYPOINTS_DIRECT) takes high-level commands"; return FW_EUNSUPPORTED; }
+  if (h->cfg.angle_representation != 0) { h->err = "fw_step_hl: the low-level controller's observation needs the euler attitude (angle_representation 0)"; return FW_EUNSUPPORTED; }
+  if (!h->step_hl.fn) { h->err = "fw_step_hl: no kernel is built for this handle"; return FW_EUNSUPPORTED; }
+  if (!a) { h->err = "fw_step_hl: NULL arguments"; return FW_EINVAL; }
+  if (!a->low_params || !a->low_mean || !a->low_var || !a->obs || !a->reward || !a->terminated || !a->truncated) {
+    h->err = "fw_step_hl: low_params, low_mean, low_var, obs, reward, terminated and truncated must be non-NULL"; return FW_EINVAL;
+  }
+  DeviceGuard g(h->device);
+  hipStream_t st = (hipStream_t)hip_stream;
+  fwsim_ctl::CtlArgs CA;
+  CA.params = a->low_params; CA.mean = a->low_mean; CA.var = a->low_var; CA.clip = a->low_clip; CA.eps = a->low_eps; CA.low_action = a->low_action;
+  void* obs = a->obs; void* reward = a->reward; uint8_t* term = a->terminated; uint8_t* trunc = a->truncated; void* tobs = a->terminal_obs;
+  int32_t* info = a->info_i32;
+  with_dtype(h, [&](auto t) {
+    using T = decltype(t);
+    const Params<T>* Pp = (const Params<T>*)h->params_dev; const ObjC<T>* OCp = (const ObjC<T>*)h->objc_dev;
+    DevState<T> D = dev_state<T>(h);
+    void* args[] = { &Pp, &OCp, &D, &CA, &obs, &reward, &term, &trunc, &tobs, &info };
+    (void)hipLaunchKernel(h->step_hl.fn, grid_of(h), dim3(h->step_hl.block), args, hl_step_lds_bytes<T>(h), st);
+  });
+  HIP_TRY(h, hipGetLastError());
+  return FW_OK;
+}
+
+int32_t fw_controller_forward(const float* params, const void* raw_obs, int32_t obs_is_f64, int32_t N, const double* mean, const double* var,
+                              float clip, float eps, void* act_out, int32_t act_is_f64, void* hip_stream) {
+  if (!params || !raw_obs || !mean || !var || !act_out) { g_err = "fw_controller_forward: params, raw_obs, mean, var and act_out must be non-NULL"; return FW_EINVAL; }
+  if (N <= 0) { g_err = "fw_controller_forward: N must be positive, got " + std::to_string(N); return FW_EINVAL; }
+  DeviceGuard g(device_of(params));
+  const dim3 grid((unsigned)((N + kWave - 1) / kWave)), block(kWave);
+  const size_t lds = fwsim_ctl::ctl_lds_bytes(kWave, false);
+  with_real(obs_is_f64 != 0, [&](auto t) { with_real(act_is_f64 != 0, [&](auto to) {
+    using T = decltype(t); using TO = decltype(to);
+    hipLaunchKernelGGL((fw_controller_forward_kernel<T, TO>), grid, block, lds, (hipStream_t)hip_stream, params, (const T*)raw_obs, N, mean, var,
+                       clip, eps, (TO*)act_out);
+  }); });
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }
 

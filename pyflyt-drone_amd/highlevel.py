@@ -9,6 +9,12 @@ env's stream, with no host synchronisation (capturable in a hipGraph):
     fw_collect_act_a  the controller: VecNormalize statistics (frozen), policy net, deterministic, clipped to [-1, 1]
     fw_step           the waypoints task under six direct actuator commands (FW_TASK_WAYPOINTS_DIRECT)
 
+With ``controller_hz=120`` (the config's ``control_hz``, the rate the controller was trained at) a vec-step is two launches: the
+controller runs inside the step kernel, in front of every Aviary step of the agent step, on the state of that moment:
+
+    fw_command_hl     as above
+    fw_step_hl        the same task; per Aviary step the controller's row (attitude, last actuator commands, command) and forward
+
 ``condition_command`` restates the first of them in numpy.  A collected vec-step of ``rollout.PPO`` under
 ``PPOConfig.fused_three_actions`` replaces the first two -- and the policy's own forward and sampling in front of them -- by one
 launch, ``fw_collect_act_hl`` (``collect_act_hl``), and steps the base env with ``step_low``.
@@ -99,6 +105,23 @@ def load_low_checkpoint(path: str):
     return policy, _rms_arrays(vn["obs_rms"]), float(vn.get("clip_obs", 10.0)), float(vn.get("epsilon", 1e-8))
 
 
+CONTROL_HZ = 120          # the config's control_hz: one Aviary step, the rate the low-level task runs its controller at
+
+
+def check_controller_hz(controller_hz: Optional[int], agent_hz: int) -> bool:
+    """True when the controller runs at the control rate inside the step (``controller_hz == 120 != agent_hz``), False for the
+    reference's once-per-agent-step controller (``None`` or ``agent_hz``); any other rate raises ``ValueError``."""
+    if controller_hz is None:
+        return False
+    if isinstance(controller_hz, bool) or int(controller_hz) != controller_hz:
+        raise ValueError(f"controller_hz must be None, agent_hz ({agent_hz}) or {CONTROL_HZ}, got {controller_hz!r}")
+    if int(controller_hz) == int(agent_hz):
+        return False
+    if int(controller_hz) == CONTROL_HZ:
+        return True
+    raise ValueError(f"controller_hz must be None, agent_hz ({agent_hz}) or {CONTROL_HZ}, got {controller_hz!r}")
+
+
 class HighLevelCmdVecEnv(FusedVecEnv):
     """``HighLevelCmdEnv`` x N on one MI355X: three actions in the reference's Box (``action_low`` / ``action_high``), the
     30-value observation of the base env, its reward, termination, truncation and info.
@@ -106,16 +129,24 @@ class HighLevelCmdVecEnv(FusedVecEnv):
     ``low_policy`` + ``low_obs_rms`` (a ``RunningMeanStd``, a ``{"mean", "var"}`` mapping or a ``(mean, var)`` pair), or
     ``low_checkpoint`` (a file ``examples/train_lowlevel_cmd.py`` saved), give the frozen controller; the policy is copied.  The other
     keywords are the reference constructor's.  ``low_action`` holds the controller's clipped output of the last step,
-    ``command`` the conditioned triple, ``low_obs`` the controller's raw observation."""
+    ``command`` the conditioned triple, ``low_obs`` the controller's raw observation.
+
+    ``controller_hz``: the rate the controller runs at.  ``None`` or ``agent_hz``: once per agent step, its six commands held for
+    the Aviary steps of the agent step (the reference's behaviour).  ``120`` (the config's ``control_hz``): once per Aviary step,
+    inside the step kernel (``fw_step_hl``) -- the rate ``examples/train_lowlevel_cmd.py`` trains it at; ``low_action`` is then the
+    output of the last Aviary step, ``low_obs`` the row ``fw_command_hl`` wrote.  Anything else raises ``ValueError``.  The knob is a
+    constructor argument, not state: a checkpoint moves across it."""
 
     metadata = {"render_modes": ["human", "rgb_array"], "render_fps": 30}
 
     def __init__(self, num_envs: int, low_policy=None, low_obs_rms=None, *, low_checkpoint: Optional[str] = None,
                  clip_obs: float = 10.0, epsilon: float = 1e-8, render_mode: Optional[str] = None, flight_dome_size: float = 200.0,
                  max_duration_seconds: float = 120.0, agent_hz: int = 30, context_length: int = 2, wind_config: Optional[dict] = None,
-                 dtype: str = "float64", motor_noise: bool = True, device=None, seed: int = 0, global_env_offset: int = 0):
+                 dtype: str = "float64", motor_noise: bool = True, device=None, seed: int = 0, global_env_offset: int = 0,
+                 controller_hz: Optional[int] = None):
         if render_mode is not None:
             raise ValueError(f"Invalid render mode {render_mode}, rendering is not part of the device env.")
+        self.controller_in_step = check_controller_hz(controller_hz, agent_hz)
         # ---- the controller: everything that needs no device first ----
         if low_checkpoint is not None:
             if low_policy is not None or low_obs_rms is not None:
@@ -162,6 +193,7 @@ class HighLevelCmdVecEnv(FusedVecEnv):
         self._act_raw = torch.zeros((n, LOW_ACT_DIM), dtype=torch.float32, device=dev)
         self._logp = torch.zeros(n, dtype=torch.float32, device=dev)
         self._actions_dev = torch.zeros((n, 3), dtype=self.torch_dtype, device=dev)
+        self.controller_hz = CONTROL_HZ if self.controller_in_step else int(agent_hz)
 
     # the base env's output tensors are this env's
     obs = property(lambda self: self.base.obs)
@@ -181,8 +213,8 @@ class HighLevelCmdVecEnv(FusedVecEnv):
 
     def step_tensor(self, actions: torch.Tensor):
         """One agent step from raw high-level actions ``[N, 3]`` (float32 or float64 device tensor; anything else is converted to
-        the env dtype): ``fw_command_hl -> fw_collect_act_a -> fw_step`` on the current stream.  Returns the base env's
-        ``(obs, rewards, terminated, truncated)``."""
+        the env dtype): ``fw_command_hl -> fw_collect_act_a -> fw_step`` on the current stream (``controller_hz=120``:
+        ``fw_command_hl -> fw_step_hl``).  Returns the base env's ``(obs, rewards, terminated, truncated)``."""
         b, L, n = self.base, _lib.lib(), self.num_envs
         if actions.device != self.device or actions.dtype not in (torch.float32, torch.float64) or not actions.is_contiguous():
             dt = actions.dtype if actions.dtype in (torch.float32, torch.float64) else self.torch_dtype
@@ -192,6 +224,8 @@ class HighLevelCmdVecEnv(FusedVecEnv):
         st = b._stream()
         _lib.check(L.fw_command_hl(b._h, _devptr(actions), int(actions.dtype == torch.float64), None, _devptr(b.obs),
                                    _devptr(self.low_obs), _devptr(self.command), _devptr(self.rejected), st), b._h)
+        if self.controller_in_step:
+            return self.step_low()
         f64 = int(self.torch_dtype == torch.float64)
         # the controller: policy net only, deterministic, frozen statistics, nothing of a previous step to finalise
         _lib.check(L.fw_collect_act_a(_devptr(self._flat), _devptr(self.low_obs), f64, n, LOW_OBS_DIM, LOW_ACT_DIM,
@@ -217,8 +251,19 @@ class HighLevelCmdVecEnv(FusedVecEnv):
 
     def step_low(self):
         """``fw_step`` of the base env with ``low_action`` as it stands (the controller's output of ``collect_act_hl``): the second
-        half of a vec-step whose act side has already run.  Returns the base env's ``(obs, rewards, terminated, truncated)``."""
-        return self.base.step_tensor(self.low_action)
+        half of a vec-step whose act side has already run.  With ``controller_hz=120`` it is ``fw_step_hl``: the command the act
+        side left in the env's tail is flown with the controller inside the kernel, and ``low_action`` is an output.  Returns the
+        base env's ``(obs, rewards, terminated, truncated)``."""
+        b = self.base
+        if not self.controller_in_step:
+            return b.step_tensor(self.low_action)
+        a = K.FwStepHlArgs()
+        a.low_params, a.low_mean, a.low_var = self._flat.data_ptr(), self.low_mean.data_ptr(), self.low_var.data_ptr()
+        a.low_clip, a.low_eps = self.clip_obs, self.epsilon
+        a.obs, a.reward, a.terminated, a.truncated = b.obs.data_ptr(), b.rewards.data_ptr(), b.terminated.data_ptr(), b.truncated.data_ptr()
+        a.terminal_obs, a.info_i32, a.low_action = b.terminal_obs.data_ptr(), b.info.data_ptr(), self.low_action.data_ptr()
+        _lib.check(_lib.lib().fw_step_hl(b._h, C.byref(a), b._stream()), b._h)
+        return b.obs, b.rewards, b.terminated, b.truncated
 
     # ------------------------------------------------------------------ SB3 VecEnv surface (numpy)
     def reset(self) -> np.ndarray:

@@ -1,7 +1,7 @@
 """Wall time per vec-step of the high-level command task on one GPU.
 
-    python tools/bench_highlevel.py [--legs step highlevel host act collect update e2e] [--envs 16 4096] [--steps 2000] [--warmup 100] [--repeats 5]
-                                    [--out profiles/r10_highlevel_bench.jsonl]
+    python tools/bench_highlevel.py [--legs step highlevel host act collect update e2e hz] [--envs 16 4096] [--steps 2000] [--warmup 100] [--repeats 5]
+                                    [--controller_hz 30 120] [--out profiles/r10_highlevel_bench.jsonl]
 
 Legs (one JSON line per leg, size and launch mode):
   step       the direct-command step kernel (FW_TASK_WAYPOINTS_DIRECT) beside the four-action waypoint kernel of the same build: the headline
@@ -20,6 +20,10 @@ Legs (one JSON line per leg, size and launch mode):
              fw_ppo_update_a's six- and four-action forms (device time from events, tools/bench_wide_learner.py) and the torch path.
   e2e        env-steps/s of examples/train_highlevel_cmd.py's configuration (16 envs, n_steps 1024, batch 256, 10 epochs) over
              --updates updates after a warm-up update, fused beside torch.
+  hz         the controller rate (HighLevelCmdVecEnv(controller_hz=...)), every rate of --controller_hz in the same session, f64,
+             graph-replayed: the vec-step (30: fw_command_hl -> fw_collect_act_a -> fw_step; 120: fw_command_hl -> fw_step_hl), the
+             step launch alone (fw_step with low_action as it stands / fw_step_hl) and the fused collected vec-step of rollout.PPO
+             (fw_collect_act_hl -> step_low -> fw_collect_stats).  Each line carries its ratio to the 30 Hz line of the same session.
 Modes: "graph" replays a captured hipGraph of 64 vec-steps, "eager" launches them one by one.  A timed region is --steps vec-steps
 between two device synchronisations; --repeats regions, the median is reported with the spread.  Under `rocprofv3 --kernel-trace
 --stats` the per-kernel averages of the three launches come out by name (fw_command_hl_kernel, fw_policy_act_kernel, fw_step_kernel_wd).
@@ -38,7 +42,8 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", nargs="+", default=["step", "highlevel", "host"],
-                    choices=["step", "highlevel", "host", "act", "collect", "update", "e2e"])
+                    choices=["step", "highlevel", "host", "act", "collect", "update", "e2e", "hz"])
+    ap.add_argument("--controller_hz", type=int, nargs="+", default=[30, 120])
     ap.add_argument("--updates", type=int, default=2)
     ap.add_argument("--n-steps", type=int, default=1024)
     ap.add_argument("--envs", type=int, nargs="+", default=[16, 4096])
@@ -163,9 +168,9 @@ def main():
                     g.replay()
         return timed(Rep(), max(a.steps // per, 1) * per)      # (whole replays: the calls timed are the calls counted)
 
-    def hl_ppo(n, fused, n_steps):
+    def hl_ppo(n, fused, n_steps, controller_hz=None):
         pol, mean, var = controller()
-        venv = HighLevelCmdVecEnv(n, pol, (mean, var), seed=42)
+        venv = HighLevelCmdVecEnv(n, pol, (mean, var), seed=42, controller_hz=controller_hz)
         env = R.VecNormalizeDevice(venv, norm_obs=True, norm_reward=True, clip_obs=10.0, gamma=0.995)
         return R.PPO(env, R.PPOConfig(n_steps=n_steps, batch_size=256, n_epochs=10, learning_rate=3e-4, gamma=0.995, gae_lambda=0.95,
                                       clip_range=0.2, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5, seed=123, fused_three_actions=fused))
@@ -301,6 +306,42 @@ def main():
                   "env_steps_per_s": round(steps / (t_roll + t_upd)), "rollout_s_per_update": round(t_roll / a.updates, 4),
                   "update_s_per_update": round(t_upd / a.updates, 4), "minibatches_per_update": 10 * a.n_steps * 16 // 256})
             ppo.env.venv.close()
+
+    if "hz" in a.legs:
+        for n in a.envs:
+            base = {}
+
+            def emit_hz(what, hz, r, **more):
+                key = "us_per_call" if "us_per_call" in r else "us_per_vec_step"
+                if hz == 30:
+                    base.setdefault(what, r[key])
+                ratio = round(r[key] / base[what], 3) if what in base else None
+                emit({"leg": "hz", "what": what, "controller_hz": hz, "envs": n, "dtype": "float64", "mode": "graph", **r,
+                      "ratio_to_30hz": ratio, **more})
+            for hz in a.controller_hz:
+                pol, mean, var = controller()
+                env = HighLevelCmdVecEnv(n, pol, (mean, var), seed=42, controller_hz=hz)
+                env.reset_tensor()
+                r = timed(bench.Stepper(env, pool_of(n, 3, hl_scale, hl_shift), use_graph=True), a.steps)
+                emit_hz("vec_step", hz, r, lanes_per_env=env.lanes_per_env, launches=2 if env.controller_in_step else 3,
+                        resets=env.get_counters()["resets"], rejected=int(env.rejected.item()))
+                r = graph_us(env.step_low)
+                r["us_per_call"] = r.pop("us_per_vec_step")
+                emit_hz("step_launch_alone", hz, r, kernel="fw_step_kernel_wdc" if env.controller_in_step else "fw_step_kernel_wd")
+                env.close()
+            for hz in a.controller_hz:
+                ppo = hl_ppo(n, True, a.n_steps, controller_hz=hz)
+                for _ in range(2):                       # eager, then the capture
+                    ppo.collect_rollouts()
+                torch.cuda.synchronize()
+                us = []
+                for _ in range(a.repeats):
+                    t0 = time.perf_counter(); ppo.collect_rollouts(); torch.cuda.synchronize()
+                    us.append((time.perf_counter() - t0) / a.n_steps * 1e6)
+                emit_hz("collected_vec_step_fused", hz, {"us_per_vec_step": round(float(np.median(us)), 2), "us_min": round(min(us), 2),
+                                                         "us_max": round(max(us), 2), "repeats": a.repeats, "n_steps": a.n_steps},
+                        collect_fused=ppo._collect_fused, graph=ppo._g_rollout is not None)
+                ppo.env.venv.close()
 
     if a.out:
         with open(a.out, "a") as f:
