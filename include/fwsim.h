@@ -854,6 +854,39 @@ int32_t fw_axis_aligned(fw_handle h);
  * FWSIM_AUX_WAVE=0|1 at fw_create overrides where that kernel applies), else 0.  Diagnostic; results are bit-identical to the
  * one-wave kernel. */
 int32_t fw_aux_wave(fw_handle h);
+/* TEST HOOK, not used by the product: evaluates ONE device building block (a __device__ function of csrc/fwsim_device.hpp, called,
+ * not copied) on n rows.  `in` [n, in_cols] and `out` [n, out_cols] are DEVICE buffers of doubles; the constants (Params / TickC /
+ * SurfC as fw_create folded them) and the dtype are the handle's: a row is converted to the handle's dtype inside the kernel and
+ * the results are widened back.  Rows map to lanes one to one, or (8-lane forms, marked "group") to groups of 8 consecutive lanes
+ * that all get the row's inputs.  Stream-ordered, no host synchronisation.  An unknown op / variant, a NULL pointer, n <= 0 or
+ * n > 2^24, or column counts other than the table's: FW_EINVAL; a variant this handle has no kernel for: FW_EUNSUPPORTED.
+ *
+ *   op          variant              in columns                                    out columns
+ *   MATH1       0                    x                                             rcp, sqrt, sin, sincos.s, sincos.c, asin, log
+ *   MATH2       0                    a, b                                          div(a, b), atan2(a, b)
+ *   ROT         0                    q[4], d                                       rot_from_quat[9], rot_from_unit_quat[9], normalize_quat[4], two_over_norm2(d)
+ *   EULER       LANE | LANES8(group) q[4]                                          euler[3], gimbal guard taken (0 | 1); LANES8: per lane, [8][4]
+ *               INVERSE              euler[3]                                      quat_from_euler[4]
+ *   QUAT_STEP   0                    w[3], q[4]                                    quat_integrate: q[4] after one physics tick
+ *   SURFACE     SCALAR | REGS(group) surface, actuation, v_b[3], w_b[3], wind_b[3] force[3], torque about the COM[3]
+ *               | LDS(group) | AX(group: float64 and an axis-aligned airframe only)
+ *   GROUP       0 (group)            v[8], b[8]: one of each per lane              per lane [10]: group_sum v, group_min v, group_or (uint32) b,
+ *                                                                                  group_any (b odd), lane_pick5 of v[0..4], act[0..4] after
+ *                                                                                  lane_act_scatter, + 1000 * lane, lane_act_gather
+ *   RNG         PHILOX               counter[4], key[2]  (uint32 values)           philox4x32_10[4]
+ *               UNIFORM              env, episode, j, lo, hi                       rng_uniform (the handle's seed, scenario stream)
+ *               NORMAL2              a.hi, a.lo, b.hi, b.lo  (uint32 values)       the two normals of the Box-Muller half of rng_normal2
+ *   WIND        0                    base[3], amp[3], phase, tick, k (0..64)       gust_init(tick) + k x gust_advance + wind_from_phase [3], wind_at(tick + k) [3]
+ */
+enum {
+  FW_PROBE_MATH1 = 0, FW_PROBE_MATH2 = 1, FW_PROBE_ROT = 2, FW_PROBE_EULER = 3, FW_PROBE_QUAT_STEP = 4, FW_PROBE_SURFACE = 5,
+  FW_PROBE_GROUP = 6, FW_PROBE_RNG = 7, FW_PROBE_WIND = 8
+};
+enum { FW_PROBE_EULER_LANE = 0, FW_PROBE_EULER_LANES8 = 1, FW_PROBE_EULER_INVERSE = 2 };
+enum { FW_PROBE_SURFACE_SCALAR = 0, FW_PROBE_SURFACE_REGS = 1, FW_PROBE_SURFACE_LDS = 2, FW_PROBE_SURFACE_AX = 3 };
+enum { FW_PROBE_RNG_PHILOX = 0, FW_PROBE_RNG_UNIFORM = 1, FW_PROBE_RNG_NORMAL2 = 2 };
+int32_t fw_probe(fw_handle h, int32_t op, int32_t variant, const double* in, int32_t in_cols, double* out, int32_t out_cols,
+                 int32_t n, void* hip_stream);
 const char* fw_last_error(fw_handle h); /* h may be NULL: last create/validate error */
 int32_t fw_destroy(fw_handle h);
 

@@ -29,6 +29,7 @@ EXPORTS = (
     "fw_episode_state_bytes", "fw_episode_fold",
     "fw_trace_rows", "fw_eval_track_wp",
     "fw_step_hl", "fw_sizeof_step_hl_args", "fw_controller_forward",
+    "fw_probe",
 )
 
 
@@ -189,6 +190,8 @@ def lib() -> C.CDLL:
             L.fw_controller_forward.argtypes = [vp, vp, i32, i32, vp, vp, f32, f32, vp, i32, vp]
             if L.fw_sizeof_step_hl_args() != C.sizeof(K.FwStepHlArgs):
                 raise RuntimeError("fw_step_hl_args layout mismatch between include/fwsim.h and config.FwStepHlArgs")
+        if hasattr(L, "fw_probe"):             # the test hook (an A/B library of an older commit predates it; build() insists on it)
+            L.fw_probe.restype = i32; L.fw_probe.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, vp]
         L.fw_policy_act_a.restype = i32
         L.fw_policy_act_a.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
         L.fw_collect_act_a.restype = i32

@@ -1602,6 +1602,8 @@ __global__ __launch_bounds__(kWave) void fw_reset_kernel_ll(const Params<T>* __r
 #include "fwsim_collect_hl.hpp"
 // ... and its step with the frozen controller at the control rate inside the kernel (fw_step_hl, fw_controller_forward)
 #include "fwsim_hl_step.hpp"
+// ... and the test hook that evaluates the device building blocks one at a time (fw_probe)
+#include "fwsim_probe.hpp"
 
 // ======================================================================
 // host side
@@ -3309,6 +3311,29 @@ int32_t fw_rollout_post(const void* reward, int32_t rew_is_f64, const uint8_t* t
   A.gamma = gamma; A.clip_reward = clip_reward; A.epsilon = epsilon; A.rew_out = rew_out; A.start_out = start_out; A.rng = rng; A.ret_acc = ret_acc;
   hipLaunchKernelGGL(fw_rollout_post_kernel, dim3(1), dim3(1024), 0, (hipStream_t)hip_stream, A);
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+
+int32_t fw_probe(fw_handle h, int32_t op, int32_t variant, const double* in, int32_t in_cols, double* out, int32_t out_cols,
+                 int32_t n, void* hip_stream) {
+  if (!h) { g_err = "fw_probe: the handle must be non-NULL"; return FW_EINVAL; }
+  if (!in || !out) { h->err = "fw_probe: in and out must be non-NULL"; return FW_EINVAL; }
+  if (n <= 0 || n > (1 << 24)) { h->err = "fw_probe: n must be in [1, 2^24], got " + std::to_string(n); return FW_EINVAL; }
+  const probe::Shape sh = probe::shape_of(op, variant);
+  if (sh.in_cols == 0) { h->err = "fw_probe: unknown (op, variant) = (" + std::to_string(op) + ", " + std::to_string(variant) + ")"; return FW_EINVAL; }
+  if (in_cols != sh.in_cols || out_cols != sh.out_cols) {
+    h->err = "fw_probe: (op, variant) = (" + std::to_string(op) + ", " + std::to_string(variant) + ") takes " + std::to_string(sh.in_cols) +
+             " input and " + std::to_string(sh.out_cols) + " output columns, got " + std::to_string(in_cols) + " and " + std::to_string(out_cols);
+    return FW_EINVAL;
+  }
+  DeviceGuard g(h->device);
+  hipError_t herr = hipSuccess;
+  const bool axis_ok = axis_aligned_geometry(h->cfg);
+  const int rc = with_dtype(h, [&](auto t) {
+    return probe::dispatch<decltype(t)>(op, variant, axis_ok, h->params_dev, in, out, n, (hipStream_t)hip_stream, herr, h->err);
+  });
+  if (rc != FW_OK) return rc;
+  HIP_TRY(h, herr);
   return FW_OK;
 }
 

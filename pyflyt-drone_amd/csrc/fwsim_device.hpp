@@ -166,8 +166,16 @@ __device__ __forceinline__ void stat_add(unsigned long long* stats, int which) {
 // fp64 op, tools/microbench_math.hip), so what matters is the DEPTH of each function:
 // v_rcp/v_rsq seeds + Newton steps instead of the IEEE division / sqrt sequences,
 // bounded-range Cody-Waite sincos and a single-division atan2, all with Estrin-scheme
-// polynomials (log depth instead of Horner's linear chain).  Each is accurate to ~1 ulp
-// (prototyped against numpy: <= 4.5e-16 absolute).
+// polynomials (log depth instead of Horner's linear chain).  Each is accurate to ~1 ulp:
+// rcp_ / div_ / sqrt_ within 1 ulp; sincos_ / sin_ / atan2_ / asin_ within 4.5e-16 absolute and,
+// where the result is below 0.25, within 4 ulp of it.  sincos_ beyond |x| = 2 pi: its two-word
+// Cody-Waite reduction leaves 1.5e-33 of pi/2 out, so the reduced argument of quadrant count
+// k = rint(x * 2/pi) is off by |k| * 1.5e-33 and a result below 0.25 is within 4 ulp + |k| * 1.5e-33
+// (measured to |x| = 1e9: 9 ulp at worst, where the result is ~1e-9); the 4.5e-16 absolute holds for
+// every |x| < 3.3e9 (k must fit an int).  The one far-domain caller is the gust clock, which scales
+// the sine by an amplitude of metres per second and needs the absolute figure alone: the relative
+// one costs the 1e-7 parity nothing.  Held function by function by tests/test_device_functions_gpu.py
+// through fw_probe.
 template <typename T> struct M;
 template <> struct M<double> {
   static __device__ __forceinline__ double rcp_(double d) {
@@ -240,7 +248,7 @@ template <> struct M<double> {
     double r = fma(z, p, tc);
     r = (ay > ax) ? (0.5 * kPi - r) : r;
     r = (x < 0.0) ? (kPi - r) : r;
-    return (y < 0.0) ? -r : r;
+    return ::copysign(r, y);                     // the sign BIT of y, as libm: atan2(-0, x < 0) = -pi (r >= 0 here)
   }
   static __device__ __forceinline__ double asin_(double s) { return atan2_(s, sqrt_((1.0 - s) * (1.0 + s))); }
   static __device__ __forceinline__ double fabs_(double x) { return ::fabs(x); }
@@ -336,18 +344,23 @@ __device__ __forceinline__ double rng_uniform(const Params<T>& P, uint32_t genv,
   double u = (double)(rng_u64(P, genv, ep, STREAM_SCENARIO, j) >> 11) * (1.0 / 9007199254740992.0);
   return lo + (hi - lo) * u;
 }
-// two N(0,1) for Aviary step `astep`; both 64-bit words come from ONE Philox block
+// Box-Muller on two raw 64-bit words: u1 in (0, 1] from the top 53 bits of `a` (+1: the log stays finite), u2 in [0, 1) from `b`
 template <typename T>
-__device__ __forceinline__ void rng_normal2(const Params<T>& P, uint32_t genv, uint32_t ep, uint32_t astep, T& z0, T& z1) {
-  uint32_t o[4];
-  philox4x32_10(astep, ep, genv, STREAM_NOISE, P.seed_lo, P.seed_hi, o);
-  uint64_t a = ((uint64_t)o[1] << 32) | o[0], b = ((uint64_t)o[3] << 32) | o[2];
+__device__ __forceinline__ void normal2_from_words(uint64_t a, uint64_t b, T& z0, T& z1) {
   double u1 = (double)((a >> 11) + 1) * (1.0 / 9007199254740992.0);
   double u2 = (double)(b >> 11) * (1.0 / 9007199254740992.0);
   T r = M<T>::sqrt_((T)-2.0 * M<T>::log_((T)u1));
   T s, c;
   M<T>::sincos_((T)(2.0 * kPi * u2), &s, &c);
   z0 = r * c; z1 = r * s;
+}
+// two N(0,1) for Aviary step `astep`; both 64-bit words come from ONE Philox block
+template <typename T>
+__device__ __forceinline__ void rng_normal2(const Params<T>& P, uint32_t genv, uint32_t ep, uint32_t astep, T& z0, T& z1) {
+  uint32_t o[4];
+  philox4x32_10(astep, ep, genv, STREAM_NOISE, P.seed_lo, P.seed_hi, o);
+  uint64_t a = ((uint64_t)o[1] << 32) | o[0], b = ((uint64_t)o[3] << 32) | o[2];
+  normal2_from_words<T>(a, b, z0, z1);
 }
 
 // ------------------------------------------------------------------------
