@@ -1,0 +1,85 @@
+"""Device-resident counterpart of the reference's examples/lowlevel.py: the low-level controller trained with SAC instead of PPO.
+
+Same hyper-parameters (SB3 ``SAC("MlpPolicy")``: net_arch [256, 256], buffer 200 000, batch 256, gamma 0.99, tau 0.02, lr 3e-4, one
+gradient step per env step, automatic entropy coefficient, no VecNormalize, 100 000 steps) on the low-level env this project has
+(``FW_TASK_LOWLEVEL``: 21 observations, six actuator commands); the script's own reward / termination / reset variant of the env is
+not built.  A vec-step -- act, env step, store, ``gradient_steps`` x (sample, update) -- is one captured graph
+(pyflyt_drone_amd/sac.py); ``--no-fused_update`` runs the gradient steps in torch on the same act / store / sample / noise kernels.
+
+    python examples/train_lowlevel_sac.py --out runs/lowlevel_sac
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import pyflyt_drone_amd as P  # noqa: E402
+from pyflyt_drone_amd import evaluate, rollout as R, sac as S  # noqa: E402
+
+TRAIN_CONFIG = dict(total_timesteps=100_000, learning_rate=3e-4, buffer_size=200_000, batch_size=256, gamma=0.99, tau=0.02,
+                    target_update_interval=1, learning_starts=100, net_arch=(256, 256), seed=0, n_eval_episodes=16, eval_freq=10_000)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--total_timesteps", type=int, default=TRAIN_CONFIG["total_timesteps"])
+    ap.add_argument("--num_envs", type=int, default=16)
+    ap.add_argument("--gradient_steps", type=int, default=-1, help="per vec-step; -1: one per env (update-to-data 1, as the reference)")
+    ap.add_argument("--fused_update", action=argparse.BooleanOptionalAction, default=True,
+                    help="fw_sac_update (default) or the torch gradient step")
+    ap.add_argument("--use_graphs", action=argparse.BooleanOptionalAction, default=True)
+    ap.add_argument("--eval_freq", type=int, default=TRAIN_CONFIG["eval_freq"], help="env steps between evaluations")
+    ap.add_argument("--eval_max_steps", type=int, default=1800, help="time limit of an evaluation episode (agent steps)")
+    ap.add_argument("--out", type=str, default="runs/lowlevel_sac")
+    a = ap.parse_args()
+    c = TRAIN_CONFIG
+    os.makedirs(a.out, exist_ok=True)
+    env = P.FixedwingLowLevelVecEnv(num_envs=a.num_envs, seed=c["seed"])
+    from pyflyt_drone_amd import config as K
+    eval_env = R.VecNormalizeDevice(P.FixedwingVecEnv(K.lowlevel_config(max_episode_steps=a.eval_max_steps), 16, seed=c["seed"],
+                                                      global_env_offset=a.num_envs),
+                                    training=False, norm_obs=False, norm_reward=False)
+    model = S.SAC(env, S.SACConfig(learning_rate=c["learning_rate"], buffer_size=c["buffer_size"], batch_size=c["batch_size"],
+                                   gamma=c["gamma"], tau=c["tau"], gradient_steps=a.gradient_steps,
+                                   target_update_interval=c["target_update_interval"], learning_starts=c["learning_starts"],
+                                   net_arch=c["net_arch"], seed=c["seed"], use_graphs=a.use_graphs, fused_update=a.fused_update))
+    t0 = time.perf_counter()
+    state = {"next_eval": a.eval_freq, "train_s": 0.0, "mark": t0}
+
+    def evaluate_now(sac):
+        torch.cuda.synchronize()
+        state["train_s"] += time.perf_counter() - state["mark"]
+        r = evaluate.evaluate_policy(sac.policy, eval_env, c["n_eval_episodes"], deterministic=True)
+        logs = sac.read_logs()
+        line = {"timesteps": sac.num_timesteps, "n_updates": sac.n_updates,
+                "env_steps_per_s": round(sac.num_timesteps / max(state["train_s"], 1e-9), 1),
+                "eval_ep_rew_mean": round(float(sum(r.episode_rewards) / len(r.episode_rewards)), 3),
+                "eval_ep_len_mean": round(float(sum(r.episode_lengths) / len(r.episode_lengths)), 1),
+                **{k: round(float(v), 5) for k, v in r.tracking_scalars().items()},
+                **{k: round(float(logs[k]), 5) for k in S.SCALARS}}
+        print(json.dumps(line), flush=True)
+        state["mark"] = time.perf_counter()
+
+    def on_step(sac):
+        if sac.num_timesteps >= state["next_eval"]:
+            evaluate_now(sac)
+            state["next_eval"] += a.eval_freq
+        return True
+
+    print(json.dumps({"config": {**{k: v for k, v in c.items()}, "num_envs": a.num_envs, "gradient_steps": model.G,
+                                 "fused_update": a.fused_update, "use_graphs": a.use_graphs}}), flush=True)
+    evaluate_now(model)                      # the untrained actor: the line later evaluations are read against
+    try:
+        model.learn(a.total_timesteps, callbacks=[on_step])
+    finally:
+        torch.save(model.state_dict(include_buffer=False), os.path.join(a.out, "final_model.pt"))
+        env.close(); eval_env.venv.close()
+    print(json.dumps({"done": model.num_timesteps, "wall_s": round(time.perf_counter() - t0, 1), "checkpoint": os.path.join(a.out, "final_model.pt")}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -887,6 +887,51 @@ enum { FW_PROBE_SURFACE_SCALAR = 0, FW_PROBE_SURFACE_REGS = 1, FW_PROBE_SURFACE_
 enum { FW_PROBE_RNG_PHILOX = 0, FW_PROBE_RNG_UNIFORM = 1, FW_PROBE_RNG_NORMAL2 = 2 };
 int32_t fw_probe(fw_handle h, int32_t op, int32_t variant, const double* in, int32_t in_cols, double* out, int32_t out_cols,
                  int32_t n, void* hip_stream);
+/* ---- Soft actor-critic for the low-level task (csrc/fwsim_sac.hpp; SB3 `SAC("MlpPolicy")`, one gradient step of `SAC.train()`) ----
+ * ReLU MLPs in fp32: the actor obs_dim -> hidden -> hidden -> 2 act_dim (mean | log_std, clamped to [-20, 2]), two critics and their two
+ * targets (obs_dim + act_dim) -> hidden -> hidden -> 1.  Built for obs_dim <= 64, act_dim <= 8, hidden 64 or 256 and batches that are
+ * multiples of 16 in [16, 512]: anything else FW_EUNSUPPORTED; NULL pointers and non-positive sizes FW_EINVAL.  No handle: every
+ * buffer is a device buffer of the caller, everything is stream-ordered, nothing allocates, synchronises or reads device state on the
+ * host, so all five entry points can be captured into a graph.
+ *
+ * Flat image (floats, fw_sac_param_count of them), W[in][out] = torch Linear.weight^T:
+ *   actor | q1 | q2 | log_ent_coef | q1 target | q2 target | exp_avg[T] | exp_avg_sq[T] | tail[4]
+ *   one network: W1[in][hidden] b1 W2[hidden][hidden] b2 W3[hidden][out] b3;  T = actor + 2 critics + 1;  tail[0] = Adam step count (int32).
+ * Device counters (int64[4]): [0] ring cursor (rows), [1] rows filled, [2] vec-steps stored, [3] gradient steps.
+ * Ring / batch rows (floats): obs[obs_dim] | action[act_dim] | reward | next_obs[obs_dim] | done. */
+typedef struct fw_sac_hyper {
+  float lr, gamma, tau, beta1, beta2, eps, target_entropy, ent_coef;   /* ent_coef: the fixed coefficient when auto_ent == 0 */
+  int32_t auto_ent, target_update_interval;   /* Polyak when the Adam step count after the step is a multiple of the interval */
+  uint64_t seed;                              /* of the step's noise (fw_sac_noise's) */
+} fw_sac_hyper;
+int32_t fw_sizeof_sac_hyper(void);
+int32_t fw_sac_param_count(int32_t obs_dim, int32_t act_dim, int32_t hidden);
+int64_t fw_sac_update_workspace_bytes(int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch);
+/* One launch per vec-step: the actor on obs [N, obs_dim] (the env's dtype, read as fp32), eps from Philox keyed by (seed, env_offset +
+ * row, counters[2]), action = tanh(mean + exp(log_std) eps) (mode 0), tanh(mean) (mode 1) or uniform in [-1, 1) without a forward
+ * (mode 2, SB3's learning_starts).  Writes the action as fp32 (act_f32) and in the env's dtype (act_env, fw_step's input), the fp32
+ * copy of obs (obs_stage: the step overwrites the env's buffer) and, where non-NULL, logp [N] and eps [N, act_dim]. */
+int32_t fw_sac_act(const float* image, const void* obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t mode,
+                   uint64_t seed, int64_t env_offset, const int64_t* counters, float* act_f32, void* act_env, float* obs_stage, float* logp,
+                   float* eps, void* hip_stream);
+/* After fw_step: appends N rows at counters[0] of the ring (capacity rows, a multiple of N): next_obs is terminal_obs where the episode
+ * ended and the new obs otherwise, done is `terminated` alone (a pure time-limit end bootstraps).  A closing one-lane launch advances
+ * cursor, fill and step counter. */
+int32_t fw_replay_store(float* ring, int64_t capacity, int64_t* counters, const float* obs_stage, const float* act_f32, const void* reward,
+                        const void* next_obs, const void* terminal_obs, const uint8_t* terminated, const uint8_t* truncated, int32_t env_is_f64,
+                        int32_t N, int32_t obs_dim, int32_t act_dim, void* hip_stream);
+/* `batch` uniform row indices in [0, counters[1]) from Philox keyed by (seed, counters[3]); gathers the rows into out [batch, row_floats]
+ * and writes the indices to idx_out (optional). */
+int32_t fw_replay_sample(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
+                         float* out, int32_t* idx_out, void* hip_stream);
+/* eps and eps' [2][batch][act_dim] of gradient step counters[3]: the values fw_sac_update draws inside. */
+int32_t fw_sac_noise(uint64_t seed, const int64_t* counters, int32_t batch, int32_t act_dim, float* out, void* hip_stream);
+/* One gradient step on the image from batch_rows [batch, 2 obs_dim + act_dim + 2]: a fixed sequence of 24 launches, kernel boundaries
+ * the only synchronisation between workgroups, every weight gradient summed over the batch by one workgroup in a fixed order (two runs
+ * give the same bits).  out (optional) [5]: critic loss, actor loss, ent-coef loss, alpha (before the step), mean logp.  Increments
+ * tail[0] and counters[3]. */
+int32_t fw_sac_update(float* image, const float* batch_rows, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch, const fw_sac_hyper* hyper,
+                      int64_t* counters, float* out, void* workspace, int64_t workspace_bytes, void* hip_stream);
 const char* fw_last_error(fw_handle h); /* h may be NULL: last create/validate error */
 int32_t fw_destroy(fw_handle h);
 

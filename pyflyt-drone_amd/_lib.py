@@ -30,6 +30,8 @@ EXPORTS = (
     "fw_trace_rows", "fw_eval_track_wp",
     "fw_step_hl", "fw_sizeof_step_hl_args", "fw_controller_forward",
     "fw_probe",
+    "fw_sizeof_sac_hyper", "fw_sac_param_count", "fw_sac_update_workspace_bytes", "fw_sac_act", "fw_replay_store", "fw_replay_sample",
+    "fw_sac_noise", "fw_sac_update",
 )
 
 
@@ -192,6 +194,17 @@ def lib() -> C.CDLL:
                 raise RuntimeError("fw_step_hl_args layout mismatch between include/fwsim.h and config.FwStepHlArgs")
         if hasattr(L, "fw_probe"):             # the test hook (an A/B library of an older commit predates it; build() insists on it)
             L.fw_probe.restype = i32; L.fw_probe.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, vp]
+        if hasattr(L, "fw_sac_update"):        # the off-policy learner (an A/B library of an older commit predates it; build() insists on it)
+            L.fw_sizeof_sac_hyper.restype = i32; L.fw_sizeof_sac_hyper.argtypes = []
+            L.fw_sac_param_count.restype = i32; L.fw_sac_param_count.argtypes = [i32, i32, i32]
+            L.fw_sac_update_workspace_bytes.restype = i64; L.fw_sac_update_workspace_bytes.argtypes = [i32, i32, i32, i32]
+            L.fw_sac_act.restype = i32
+            L.fw_sac_act.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp]
+            L.fw_replay_store.restype = i32
+            L.fw_replay_store.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
+            L.fw_replay_sample.restype = i32; L.fw_replay_sample.argtypes = [vp, i64, vp, u64, i32, i32, vp, vp, vp]
+            L.fw_sac_noise.restype = i32; L.fw_sac_noise.argtypes = [u64, vp, i32, i32, vp, vp]
+            L.fw_sac_update.restype = i32; L.fw_sac_update.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]
         L.fw_policy_act_a.restype = i32
         L.fw_policy_act_a.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
         L.fw_collect_act_a.restype = i32

@@ -1604,6 +1604,8 @@ __global__ __launch_bounds__(kWave) void fw_reset_kernel_ll(const Params<T>* __r
 #include "fwsim_hl_step.hpp"
 // ... and the test hook that evaluates the device building blocks one at a time (fw_probe)
 #include "fwsim_probe.hpp"
+// ... and the off-policy learner of the low-level task (fw_sac_act, fw_replay_store / _sample, fw_sac_noise, fw_sac_update)
+#include "fwsim_sac.hpp"
 
 // ======================================================================
 // host side
@@ -3351,6 +3353,103 @@ int32_t fw_destroy(fw_handle h) {
   (void)hipDeviceSynchronize();
   free_device_buffers(h);
   delete h;
+  return FW_OK;
+}
+
+// ---- soft actor-critic (csrc/fwsim_sac.hpp) ----
+static int32_t sac_check_shape(const char* who, int32_t d, int32_t A, int32_t H) {
+  if (d <= 0 || A <= 0 || H <= 0) { g_err = std::string(who) + ": obs_dim, act_dim and hidden must be positive"; return FW_EINVAL; }
+  if (!sac_shape_ok(d, A, H)) {
+    g_err = std::string(who) + ": built for obs_dim <= 64, act_dim <= 8 and hidden 64 or 256, got (" + std::to_string(d) + ", " + std::to_string(A) + ", " + std::to_string(H) + ")";
+    return FW_EUNSUPPORTED;
+  }
+  return FW_OK;
+}
+static int32_t sac_check_batch(const char* who, int32_t B) {
+  if (B <= 0) { g_err = std::string(who) + ": the batch size must be positive"; return FW_EINVAL; }
+  if (!sac_batch_ok(B)) { g_err = std::string(who) + ": built for batch sizes that are multiples of 16 in [16, 512], got " + std::to_string(B); return FW_EUNSUPPORTED; }
+  return FW_OK;
+}
+int32_t fw_sizeof_sac_hyper(void) { return (int32_t)sizeof(fw_sac_hyper); }
+int32_t fw_sac_param_count(int32_t obs_dim, int32_t act_dim, int32_t hidden) {
+  const int32_t rc = sac_check_shape("fw_sac_param_count", obs_dim, act_dim, hidden);
+  return rc != FW_OK ? rc : sac_layout(obs_dim, act_dim, hidden).total;
+}
+int64_t fw_sac_update_workspace_bytes(int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch) {
+  int32_t rc = sac_check_shape("fw_sac_update_workspace_bytes", obs_dim, act_dim, hidden);
+  if (rc == FW_OK) rc = sac_check_batch("fw_sac_update_workspace_bytes", batch);
+  return rc != FW_OK ? rc : (int64_t)sac_ws(obs_dim, act_dim, hidden, batch).total * (int64_t)sizeof(float);
+}
+int32_t fw_sac_act(const float* image, const void* obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t mode,
+                   uint64_t seed, int64_t env_offset, const int64_t* counters, float* act_f32, void* act_env, float* obs_stage, float* logp,
+                   float* eps, void* hip_stream) {
+  if (!image || !obs || !counters || !act_f32 || !act_env || !obs_stage) { g_err = "fw_sac_act: image, obs, counters, act_f32, act_env and obs_stage must be non-NULL"; return FW_EINVAL; }
+  if (N <= 0 || mode < 0 || mode > 2 || env_offset < 0) { g_err = "fw_sac_act: N must be positive, mode 0, 1 or 2 and env_offset non-negative"; return FW_EINVAL; }
+  const int32_t rc = sac_check_shape("fw_sac_act", obs_dim, act_dim, hidden);
+  if (rc != FW_OK) return rc;
+  DeviceGuard g(device_of(image));
+  SacActArgs a{image, obs, N, obs_dim, act_dim, mode, seed, env_offset, counters, act_f32, act_env, obs_stage, logp, eps};
+  const dim3 grid((unsigned)((N + 15) / 16)), block(256);
+  with_real(obs_is_f64 != 0, [&](auto t) {
+    using T = decltype(t);
+    if (hidden == 64) hipLaunchKernelGGL((fw_sac_act_kernel<T, 64>), grid, block, 0, (hipStream_t)hip_stream, a);
+    else hipLaunchKernelGGL((fw_sac_act_kernel<T, 256>), grid, block, 0, (hipStream_t)hip_stream, a);
+  });
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+int32_t fw_replay_store(float* ring, int64_t capacity, int64_t* counters, const float* obs_stage, const float* act_f32, const void* reward,
+                        const void* next_obs, const void* terminal_obs, const uint8_t* terminated, const uint8_t* truncated, int32_t env_is_f64,
+                        int32_t N, int32_t obs_dim, int32_t act_dim, void* hip_stream) {
+  if (!ring || !counters || !obs_stage || !act_f32 || !reward || !next_obs || !terminal_obs || !terminated || !truncated) { g_err = "fw_replay_store: every pointer must be non-NULL"; return FW_EINVAL; }
+  if (N <= 0 || obs_dim <= 0 || act_dim <= 0 || capacity < N || capacity % N != 0) { g_err = "fw_replay_store: N, obs_dim and act_dim must be positive and capacity a positive multiple of N"; return FW_EINVAL; }
+  if (obs_dim > kSacMaxD || act_dim > kSacMaxA) { g_err = "fw_replay_store: built for obs_dim <= 64 and act_dim <= 8"; return FW_EUNSUPPORTED; }
+  DeviceGuard g(device_of(ring));
+  SacStoreArgs s{ring, capacity, counters, obs_stage, act_f32, reward, next_obs, terminal_obs, terminated, truncated, N, obs_dim, act_dim};
+  const long long elems = (long long)N * (2 * obs_dim + act_dim + 2);
+  with_real(env_is_f64 != 0, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((fw_replay_store_kernel<T>), dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, s);
+  });
+  hipLaunchKernelGGL(fw_replay_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, counters, capacity, N);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+int32_t fw_replay_sample(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
+                         float* out, int32_t* idx_out, void* hip_stream) {
+  if (!ring || !counters || !out) { g_err = "fw_replay_sample: ring, counters and out must be non-NULL"; return FW_EINVAL; }
+  if (capacity <= 0 || capacity > 0x7fffffffLL || row_floats <= 0 || batch <= 0) { g_err = "fw_replay_sample: capacity (below 2^31), row_floats and batch must be positive"; return FW_EINVAL; }
+  DeviceGuard g(device_of(ring));
+  hipLaunchKernelGGL(fw_replay_sample_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, ring, capacity, counters, seed,
+                     row_floats, batch, out, idx_out);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+int32_t fw_sac_noise(uint64_t seed, const int64_t* counters, int32_t batch, int32_t act_dim, float* out, void* hip_stream) {
+  if (!counters || !out) { g_err = "fw_sac_noise: counters and out must be non-NULL"; return FW_EINVAL; }
+  if (batch <= 0 || act_dim <= 0) { g_err = "fw_sac_noise: batch and act_dim must be positive"; return FW_EINVAL; }
+  if (act_dim > kSacMaxA) { g_err = "fw_sac_noise: built for act_dim <= 8"; return FW_EUNSUPPORTED; }
+  DeviceGuard g(device_of(out));
+  hipLaunchKernelGGL(fw_sac_noise_kernel, dim3((unsigned)((2 * batch * ((act_dim + 3) / 4) + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, seed,
+                     counters, batch, act_dim, out);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+int32_t fw_sac_update(float* image, const float* batch_rows, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch, const fw_sac_hyper* hyper,
+                      int64_t* counters, float* out, void* workspace, int64_t workspace_bytes, void* hip_stream) {
+  if (!image || !batch_rows || !hyper || !counters || !workspace) { g_err = "fw_sac_update: image, batch_rows, hyper, counters and workspace must be non-NULL"; return FW_EINVAL; }
+  int32_t rc = sac_check_shape("fw_sac_update", obs_dim, act_dim, hidden);
+  if (rc == FW_OK) rc = sac_check_batch("fw_sac_update", batch);
+  if (rc != FW_OK) return rc;
+  if (workspace_bytes < (int64_t)sac_ws(obs_dim, act_dim, hidden, batch).total * (int64_t)sizeof(float)) { g_err = "fw_sac_update: the workspace is smaller than fw_sac_update_workspace_bytes asks for"; return FW_EINVAL; }
+  static_assert(sizeof(fw_sac_hyper) == sizeof(SacHyper), "fw_sac_hyper and SacHyper must agree");
+  DeviceGuard g(device_of(image));
+  SacStepArgs S{};
+  S.image = image; S.batch = batch_rows; S.ws = (float*)workspace; S.ctr = counters; S.out = out;
+  S.d = obs_dim; S.A = act_dim; S.H = hidden; S.B = batch;
+  std::memcpy(&S.hp, hyper, sizeof(SacHyper));
+  sac_update_launch((hipStream_t)hip_stream, S);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }
 

@@ -1,0 +1,597 @@
+"""Soft actor-critic for the low-level control task (the reference's ``examples/lowlevel.py``: SB3 ``SAC("MlpPolicy")`` with
+``net_arch=[256, 256]``, a 200 000-row buffer, batches of 256, ``gamma=0.99``, ``tau=0.02``, one gradient step per env step, an
+automatic entropy coefficient and no ``VecNormalize``).
+
+Everything between two env steps runs on the device (csrc/fwsim_sac.hpp, include/fwsim.h):
+
+* ``fw_sac_act``       the actor on the env's observations, the squashed-Gaussian sample (or SB3's uniform ``learning_starts``
+                       actions), the fp32 staging copy of the observation the step is about to overwrite;
+* ``fw_replay_store``  appends the N transitions to a flat fp32 ring at a device-resident cursor;
+* ``fw_replay_sample`` draws a batch from the ring by a counter-based generator;
+* ``fw_sac_noise``     the two noise blocks of a gradient step;
+* ``fw_sac_update``    one gradient step of SB3's ``SAC.train()`` on a flat image of all five networks and their Adam moments.
+
+:func:`sac_update_torch` is the same gradient step in plain torch (CPU tensors too): the reference the kernels are tested against
+and the ``fused_update=False`` path.
+
+Two departures from SB3, both only visible away from the reference's settings: the Polyak step is taken when the *total* number of
+gradient steps is a multiple of ``target_update_interval`` (SB3 counts inside one ``train()`` call), and a vec-step is a warm-up step
+-- uniform actions, no gradient step -- exactly while ``num_timesteps < learning_starts`` (SB3 starts training one vec-step later
+when ``learning_starts`` is not a multiple of the env count).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import time
+from dataclasses import dataclass, asdict
+from typing import Dict, Optional, Sequence, Tuple
+
+import torch
+from torch import nn
+
+from . import _lib
+
+LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
+MAX_OBS_DIM, MAX_ACT_DIM, HIDDEN_WIDTHS, MAX_BATCH = 64, 8, (64, 256), 512
+CTR_CURSOR, CTR_SIZE, CTR_STEPS, CTR_GRAD = 0, 1, 2, 3          # the device counters (int64[4])
+
+
+def _p(t: Optional[torch.Tensor]):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _stream(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+@dataclass
+class SACConfig:
+    """The reference's hyper-parameters (examples/lowlevel.py) as defaults."""
+    learning_rate: float = 3e-4
+    buffer_size: int = 200_000
+    batch_size: int = 256
+    gamma: float = 0.99
+    tau: float = 0.02
+    gradient_steps: int = 1              # per vec-step; -1: one per env (update-to-data 1, SB3's meaning)
+    target_update_interval: int = 1
+    learning_starts: int = 100
+    ent_coef: object = "auto"            # or a fixed float
+    net_arch: Tuple[int, int] = (256, 256)
+    seed: int = 0
+    use_graphs: bool = True
+    fused_update: bool = True
+
+    def __post_init__(self):
+        self.net_arch = tuple(int(h) for h in self.net_arch)
+        if len(self.net_arch) != 2 or self.net_arch[0] != self.net_arch[1] or self.net_arch[0] <= 0:
+            raise ValueError(f"net_arch must be two equal positive widths, got {self.net_arch}")
+        if self.gradient_steps != -1 and self.gradient_steps < 0:
+            raise ValueError("gradient_steps must be non-negative, or -1 for one per env")
+        if self.batch_size <= 0 or self.buffer_size <= 0 or self.target_update_interval <= 0 or self.learning_starts < 0:
+            raise ValueError("batch_size, buffer_size and target_update_interval must be positive, learning_starts non-negative")
+        if not (0.0 <= self.gamma <= 1.0 and 0.0 < self.tau <= 1.0 and self.learning_rate > 0.0):
+            raise ValueError("gamma must be in [0, 1], tau in (0, 1] and learning_rate positive")
+        if self.ent_coef != "auto":
+            self.ent_coef = float(self.ent_coef)
+            if self.ent_coef < 0.0:
+                raise ValueError("a fixed ent_coef must be non-negative")
+
+    @property
+    def hidden(self) -> int:
+        return self.net_arch[0]
+
+    @property
+    def auto_ent(self) -> bool:
+        return self.ent_coef == "auto"
+
+    def resolved_gradient_steps(self, num_envs: int) -> int:
+        return int(num_envs) if self.gradient_steps == -1 else int(self.gradient_steps)
+
+
+def fits(obs_dim: int, act_dim: int, hidden: int, batch_size: int) -> bool:
+    """What the kernels are built for (include/fwsim.h): anything else is ``FW_EUNSUPPORTED``."""
+    return (1 <= obs_dim <= MAX_OBS_DIM and 1 <= act_dim <= MAX_ACT_DIM and hidden in HIDDEN_WIDTHS
+            and 16 <= batch_size <= MAX_BATCH and batch_size % 16 == 0)
+
+
+def ring_capacity(buffer_size: int, num_envs: int) -> int:
+    """Rows of the ring: whole vec-steps only, so a store never wraps inside itself."""
+    cap = (int(buffer_size) // int(num_envs)) * int(num_envs)
+    if cap <= 0:
+        raise ValueError(f"buffer_size {buffer_size} holds no vec-step of {num_envs} envs")
+    return cap
+
+
+def row_floats(obs_dim: int, act_dim: int) -> int:
+    return 2 * obs_dim + act_dim + 2
+
+
+def split_rows(rows: torch.Tensor, obs_dim: int, act_dim: int):
+    """(s, a, r, s', done) views of ring / batch rows ``[obs | action | reward | next_obs | done]``."""
+    d, a = obs_dim, act_dim
+    return rows[:, :d], rows[:, d:d + a], rows[:, d + a], rows[:, d + a + 1:2 * d + a + 1], rows[:, 2 * d + a + 1]
+
+
+# ---------------------------------------------------------------------------------------------
+# the torch modules
+# ---------------------------------------------------------------------------------------------
+def _mlp(n_in: int, hidden: int, n_out: int) -> nn.Sequential:
+    return nn.Sequential(nn.Linear(n_in, hidden), nn.ReLU(), nn.Linear(hidden, hidden), nn.ReLU(), nn.Linear(hidden, n_out))
+
+
+class SacPolicy(nn.Module):
+    """Actor ``d -> H -> H -> 2A`` (mean | log_std, clamped to [-20, 2]), two critics ``(d + A) -> H -> H -> 1`` on
+    ``cat(obs, action)`` and their targets (copies at construction), ``log_ent_coef`` (log 1.0): ReLU MLPs, torch's default
+    initialisation."""
+
+    def __init__(self, obs_dim: int, act_dim: int, hidden: int = 256):
+        super().__init__()
+        self.obs_dim, self.act_dim, self.hidden = int(obs_dim), int(act_dim), int(hidden)
+        self.actor = _mlp(obs_dim, hidden, 2 * act_dim)
+        self.q1, self.q2 = _mlp(obs_dim + act_dim, hidden, 1), _mlp(obs_dim + act_dim, hidden, 1)
+        self.q1_target, self.q2_target = _mlp(obs_dim + act_dim, hidden, 1), _mlp(obs_dim + act_dim, hidden, 1)
+        self.q1_target.load_state_dict(self.q1.state_dict()); self.q2_target.load_state_dict(self.q2.state_dict())
+        for q in list(self.q1_target.parameters()) + list(self.q2_target.parameters()):
+            q.requires_grad_(False)
+        self.log_ent_coef = nn.Parameter(torch.zeros(()))
+        self.n_updates = 0               # gradient steps taken (the Polyak schedule counts them)
+
+    def dist(self, obs):
+        out = self.actor(obs)
+        return out[..., :self.act_dim], out[..., self.act_dim:].clamp(LOG_STD_MIN, LOG_STD_MAX)
+
+    def sample(self, obs, eps):
+        """a = tanh(mean + exp(log_std) eps) and its log-probability."""
+        mean, log_std = self.dist(obs)
+        a = torch.tanh(mean + torch.exp(log_std) * eps)
+        logp = (-0.5 * eps * eps - log_std - 0.5 * math.log(2.0 * math.pi)).sum(-1) - torch.log(1.0 - a * a + 1e-6).sum(-1)
+        return a, logp
+
+    def q_min(self, obs, act, target: bool = False):
+        x = torch.cat([obs, act], dim=-1)
+        q1, q2 = (self.q1_target, self.q2_target) if target else (self.q1, self.q2)
+        return torch.min(torch.cat([q1(x), q2(x)], dim=-1), dim=-1).values
+
+    def forward(self, obs, deterministic: bool = False, generator=None):
+        """``(actions, values, log_prob)`` like :class:`~.rollout.MlpPolicy`: values are min(Q1, Q2)(obs, action)."""
+        p = self.actor[0].weight
+        obs = obs.to(dtype=p.dtype)
+        mean, _ = self.dist(obs)
+        eps = (torch.zeros_like(mean) if deterministic
+               else torch.randn(mean.shape, device=mean.device, dtype=mean.dtype, generator=generator))
+        a, logp = self.sample(obs, eps)
+        return a, self.q_min(obs, a), logp
+
+
+def make_optimizers(policy: SacPolicy, cfg: SACConfig, capturable: bool = False) -> Dict[str, Optional[torch.optim.Adam]]:
+    """SB3's three optimisers: Adam(eps 1e-8, betas (0.9, 0.999)) for the actor, for both critics together and for log_ent_coef."""
+    kw = dict(lr=cfg.learning_rate, eps=1e-8, betas=(0.9, 0.999), capturable=capturable)
+    return {"actor": torch.optim.Adam(policy.actor.parameters(), **kw),
+            "critic": torch.optim.Adam(list(policy.q1.parameters()) + list(policy.q2.parameters()), **kw),
+            "ent": torch.optim.Adam([policy.log_ent_coef], **kw) if cfg.auto_ent else None}
+
+
+def sac_update_torch(policy: SacPolicy, optimizers, batch, eps, eps_next, cfg: SACConfig) -> Dict[str, torch.Tensor]:
+    """One gradient step of SB3's ``SAC.train()`` in the order DESIGN.md section 4c spells out (the numbers at the right).  ``batch``: ``(s, a, r, s', done)`` or
+    rows ``[B, 2d + A + 2]``; ``eps`` / ``eps_next``: N(0, 1) of shape ``[B, A]``.  Returns the five scalars ``fw_sac_update``
+    reports (tensors, no host read)."""
+    if torch.is_tensor(batch):
+        batch = split_rows(batch, policy.obs_dim, policy.act_dim)
+    s, a, r, s2, done = batch
+    a_pi, logp = policy.sample(s, eps)                                                          # 1, 2
+    if cfg.auto_ent:
+        alpha = torch.exp(policy.log_ent_coef.detach())                                        # 3: the value before this step
+        ent_loss = -(policy.log_ent_coef * (logp.detach() + float(-policy.act_dim))).mean()    # 4
+        optimizers["ent"].zero_grad(set_to_none=True); ent_loss.backward(); optimizers["ent"].step()
+    else:
+        alpha = torch.as_tensor(float(cfg.ent_coef), dtype=s.dtype, device=s.device)
+        ent_loss = torch.zeros((), dtype=s.dtype, device=s.device)
+    with torch.no_grad():
+        a2, logp2 = policy.sample(s2, eps_next)                                                # 5
+        y = r + (1.0 - done) * cfg.gamma * (policy.q_min(s2, a2, target=True) - alpha * logp2)   # 6
+    x = torch.cat([s, a], dim=-1)
+    q1, q2 = policy.q1(x).squeeze(-1), policy.q2(x).squeeze(-1)
+    critic_loss = 0.5 * (((q1 - y) ** 2).mean() + ((q2 - y) ** 2).mean())                       # 7
+    optimizers["critic"].zero_grad(set_to_none=True); critic_loss.backward(); optimizers["critic"].step()
+    actor_loss = (alpha * logp - policy.q_min(s, a_pi)).mean()                                 # 8: the critics after their step
+    optimizers["actor"].zero_grad(set_to_none=True); actor_loss.backward(); optimizers["actor"].step()
+    optimizers["critic"].zero_grad(set_to_none=True)      # (the actor loss left gradients in the critics: they are not theirs)
+    policy.n_updates += 1
+    if policy.n_updates % cfg.target_update_interval == 0:                                      # 9
+        with torch.no_grad():
+            for net, tgt in ((policy.q1, policy.q1_target), (policy.q2, policy.q2_target)):
+                for p, t in zip(net.parameters(), tgt.parameters()):
+                    t.mul_(1.0 - cfg.tau).add_(p, alpha=cfg.tau)
+    return {"critic_loss": critic_loss.detach(), "actor_loss": actor_loss.detach(), "ent_coef_loss": ent_loss.detach(),
+            "ent_coef": alpha.detach(), "mean_logp": logp.detach().mean()}
+
+
+SCALARS = ("critic_loss", "actor_loss", "ent_coef_loss", "ent_coef", "mean_logp")
+
+
+# ---------------------------------------------------------------------------------------------
+# the flat image of fw_sac_update
+# ---------------------------------------------------------------------------------------------
+class _SacHyper(C.Structure):
+    _fields_ = [("lr", C.c_float), ("gamma", C.c_float), ("tau", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float), ("target_entropy", C.c_float), ("ent_coef", C.c_float), ("auto_ent", C.c_int32),
+                ("target_update_interval", C.c_int32), ("seed", C.c_uint64)]
+
+
+def net_floats(n_in: int, hidden: int, n_out: int) -> int:
+    return n_in * hidden + hidden + hidden * hidden + hidden + hidden * n_out + n_out
+
+
+def image_layout(obs_dim: int, act_dim: int, hidden: int) -> Dict[str, int]:
+    """Offsets (floats) of the blocks of the flat image (include/fwsim.h)."""
+    na, nc = net_floats(obs_dim, hidden, 2 * act_dim), net_floats(obs_dim + act_dim, hidden, 1)
+    L = {"actor": 0, "q1": na, "q2": na + nc, "log_ent_coef": na + 2 * nc}
+    L["q1_target"] = L["log_ent_coef"] + 1
+    L["q2_target"] = L["q1_target"] + nc
+    L["params"] = L["q2_target"] + nc
+    L["trained"] = L["log_ent_coef"] + 1
+    L["exp_avg"], L["exp_avg_sq"] = L["params"], L["params"] + L["trained"]
+    L["tail"] = L["params"] + 2 * L["trained"]
+    L["total"] = L["tail"] + 4
+    return L
+
+
+class FusedSacUpdate:
+    """Host side of ``fw_sac_update``: the flat float32 image of the five networks, ``log_ent_coef``, the Adam moments and the step
+    count, and its pack / unpack against the modules and the three optimisers (CPU tensors too).  The image is a cache of them,
+    guarded by the tensors' version counters as :class:`~.rollout.FusedPpoUpdate` does."""
+
+    def __init__(self, policy: SacPolicy, optimizers, cfg: SACConfig):
+        self.policy, self.opts, self.cfg = policy, optimizers, cfg
+        self.d, self.A, self.H = policy.obs_dim, policy.act_dim, policy.hidden
+        self.L = image_layout(self.d, self.A, self.H)
+        dev = policy.log_ent_coef.device
+        self.image = torch.zeros(self.L["total"], dtype=torch.float32, device=dev)
+        self.out = torch.zeros(8, dtype=torch.float32, device=dev)
+        self._ws = None
+        self._sig = None
+        self.ahead = 0                   # gradient steps the image has taken since it was last equal to modules and optimisers
+
+    def _slots(self):
+        """(tensor, offset in the image, needs transpose, optimiser or None) per parameter, in layout order."""
+        p, out = self.policy, []
+        for name, net, opt in (("actor", p.actor, self.opts["actor"]), ("q1", p.q1, self.opts["critic"]), ("q2", p.q2, self.opts["critic"]),
+                               ("q1_target", p.q1_target, None), ("q2_target", p.q2_target, None)):
+            off = self.L[name]
+            for lin in (net[0], net[2], net[4]):
+                out.append((lin.weight, off, True, opt)); off += lin.weight.numel()
+                out.append((lin.bias, off, False, opt)); off += lin.bias.numel()
+        out.append((p.log_ent_coef, self.L["log_ent_coef"], False, self.opts.get("ent")))
+        return out
+
+    def signature(self):
+        sig = [self.policy.n_updates]
+        for t, _, _, opt in self._slots():
+            sig.append((t.data_ptr(), t._version))
+            st = opt.state.get(t) if opt is not None else None
+            if st:
+                sig += [(st[k].data_ptr(), st[k]._version) if torch.is_tensor(st[k]) else (k, st[k]) for k in ("exp_avg", "exp_avg_sq", "step")]
+        return tuple(sig)
+
+    def current(self) -> bool:
+        return self._sig is not None and self._sig == self.signature()
+
+    @torch.no_grad()
+    def pack(self) -> None:
+        """Modules and optimisers -> image."""
+        img, L = self.image, self.L
+        img.zero_()
+        for t, off, tr, opt in self._slots():
+            n = t.numel()
+            img[off:off + n].copy_((t.t() if tr else t).reshape(-1))
+            st = opt.state.get(t) if opt is not None else None
+            if st:
+                for key in ("exp_avg", "exp_avg_sq"):
+                    img[L[key] + off:L[key] + off + n].copy_((st[key].t() if tr else st[key]).reshape(-1))
+        img[L["tail"]:].view(torch.int32)[0] = int(self.policy.n_updates)
+        self._sig, self.ahead = self.signature(), 0
+
+    @torch.no_grad()
+    def unpack(self, n_updates: Optional[int] = None) -> None:
+        """Image -> modules and optimisers.  ``n_updates``: the step count when the caller already knows it (no host read)."""
+        img, L = self.image, self.L
+        step = int(img[L["tail"]:].view(torch.int32)[0].item()) if n_updates is None else int(n_updates)
+        for t, off, tr, opt in self._slots():
+            n = t.numel()
+            shape = (t.shape[1], t.shape[0]) if tr else t.shape
+
+            def get(base):
+                v = img[base + off:base + off + n].view(shape)
+                return v.t() if tr else v
+            t.data.copy_(get(0))
+            if opt is None or (step == 0 and not opt.state.get(t)):
+                continue
+            st = opt.state[t]
+            if not st:
+                cap = bool(opt.param_groups[0].get("capturable", False))
+                st["step"] = torch.zeros((), dtype=torch.float32, device=t.device if cap else "cpu")
+                st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(t), torch.zeros_like(t)
+            st["exp_avg"].copy_(get(L["exp_avg"])); st["exp_avg_sq"].copy_(get(L["exp_avg_sq"]))
+            if torch.is_tensor(st["step"]):
+                st["step"].fill_(float(step))
+            else:
+                st["step"] = step
+        self.policy.n_updates = step
+        self._sig, self.ahead = self.signature(), 0
+
+    def hyper(self) -> _SacHyper:
+        pg = self.opts["actor"].param_groups[0]
+        cfg = self.cfg
+        return _SacHyper(lr=pg["lr"], gamma=cfg.gamma, tau=cfg.tau, beta1=pg["betas"][0], beta2=pg["betas"][1], eps=pg["eps"],
+                         target_entropy=float(-self.A), ent_coef=0.0 if cfg.auto_ent else float(cfg.ent_coef),
+                         auto_ent=int(cfg.auto_ent), target_update_interval=cfg.target_update_interval, seed=int(cfg.seed) & (2**64 - 1))
+
+    def workspace(self, batch: int) -> torch.Tensor:
+        need = int(_lib.lib().fw_sac_update_workspace_bytes(self.d, self.A, self.H, batch))
+        if need < 0:
+            _lib.check(need)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.zeros(need, dtype=torch.uint8, device=self.image.device)
+        return self._ws
+
+    def run(self, rows: torch.Tensor, counters: torch.Tensor) -> None:
+        """One gradient step on the image (the caller packs before, counts the step in ``ahead`` and unpacks when the modules are
+        wanted; nothing here reads the device)."""
+        assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.shape[1] == row_floats(self.d, self.A)
+        B = rows.shape[0]
+        ws = self.workspace(B) if fits(self.d, self.A, self.H, B) else self.out          # (an unsupported shape: let the ABI say so)
+        H = self.hyper()
+        _lib.check(_lib.lib().fw_sac_update(_p(self.image), _p(rows), self.d, self.A, self.H, B, C.byref(H), _p(counters), _p(self.out),
+                                            _p(ws), ws.numel(), _stream(rows.device)))
+
+    def scalars(self) -> Dict[str, float]:
+        return dict(zip(SCALARS, self.out[:5].tolist()))
+
+
+# ---------------------------------------------------------------------------------------------
+# the replay ring
+# ---------------------------------------------------------------------------------------------
+class ReplayBufferDevice:
+    """Flat fp32 ring ``[capacity, 2d + A + 2]`` and the device counters (cursor, rows filled, vec-steps stored, gradient steps):
+    the host reads none of them on the training path."""
+
+    def __init__(self, buffer_size: int, num_envs: int, obs_dim: int, act_dim: int, device):
+        self.num_envs, self.obs_dim, self.act_dim = int(num_envs), int(obs_dim), int(act_dim)
+        self.capacity = ring_capacity(buffer_size, num_envs)
+        self.row = row_floats(obs_dim, act_dim)
+        self.ring = torch.zeros((self.capacity, self.row), dtype=torch.float32, device=device)
+        self.counters = torch.zeros(4, dtype=torch.int64, device=device)
+
+    def store(self, obs_stage, act_f32, reward, next_obs, terminal_obs, terminated, truncated) -> None:
+        _lib.check(_lib.lib().fw_replay_store(_p(self.ring), self.capacity, _p(self.counters), _p(obs_stage), _p(act_f32), _p(reward),
+                                              _p(next_obs), _p(terminal_obs), _p(terminated), _p(truncated),
+                                              int(reward.dtype == torch.float64), self.num_envs, self.obs_dim, self.act_dim,
+                                              _stream(self.ring.device)))
+
+    def sample(self, seed: int, out: torch.Tensor, idx_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        _lib.check(_lib.lib().fw_replay_sample(_p(self.ring), self.capacity, _p(self.counters), int(seed) & (2**64 - 1), self.row,
+                                               out.shape[0], _p(out), _p(idx_out), _stream(self.ring.device)))
+        return out
+
+    @property
+    def size(self) -> int:
+        return int(self.counters[CTR_SIZE].item())
+
+    @property
+    def cursor(self) -> int:
+        return int(self.counters[CTR_CURSOR].item())
+
+    def state_dict(self, include_buffer: bool = False):
+        sd = {"counters": self.counters.cpu().clone(), "capacity": self.capacity}
+        if include_buffer:
+            sd["ring"] = self.ring.cpu().clone()
+        return sd
+
+    def load_state_dict(self, sd) -> None:
+        if int(sd["capacity"]) != self.capacity:
+            raise ValueError(f"the checkpoint's ring has {sd['capacity']} rows, this one {self.capacity}")
+        self.counters.copy_(sd["counters"])
+        if "ring" in sd:
+            self.ring.copy_(sd["ring"])
+        else:                            # no rows came along: the ring starts empty, the step and gradient counters go on
+            self.ring.zero_()
+            self.counters[CTR_CURSOR] = 0; self.counters[CTR_SIZE] = 0
+
+
+def sac_noise(seed: int, counters: torch.Tensor, batch: int, act_dim: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """eps and eps' ``[2, B, A]`` of the gradient step ``counters[3]`` (``fw_sac_noise``): the values ``fw_sac_update`` draws inside."""
+    if out is None:
+        out = torch.empty((2, batch, act_dim), dtype=torch.float32, device=counters.device)
+    _lib.check(_lib.lib().fw_sac_noise(int(seed) & (2**64 - 1), _p(counters), batch, act_dim, _p(out), _stream(counters.device)))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# the learner
+# ---------------------------------------------------------------------------------------------
+ACT_STOCHASTIC, ACT_DETERMINISTIC, ACT_WARMUP = 0, 1, 2
+
+
+class SAC:
+    """SAC on a bare device env (``FixedwingLowLevelVecEnv``; the reference uses no normaliser).  A vec-step is act -> ``env.step_tensor``
+    -> store -> G x (sample -> update); with ``use_graphs`` and the fused update it is one captured graph, with a second one for the
+    warm-up steps (with the torch update the graph ends behind the store and the gradient steps run eagerly)."""
+
+    def __init__(self, env, cfg: SACConfig = SACConfig(), policy: Optional[SacPolicy] = None):
+        self.env, self.cfg = env, cfg
+        self.device = torch.device(env.device)
+        self.N, self.d, self.A = env.num_envs, env.obs_dim, env.act_dim
+        if policy is None:
+            with torch.random.fork_rng(devices=[]):
+                torch.manual_seed(int(cfg.seed))
+                policy = SacPolicy(self.d, self.A, cfg.hidden)
+        self._policy = policy.to(self.device)
+        self.optimizers = make_optimizers(self._policy, cfg)
+        self.G = cfg.resolved_gradient_steps(self.N)
+        if not fits(self.d, self.A, cfg.hidden, cfg.batch_size):
+            raise ValueError(f"the SAC kernels take obs_dim <= {MAX_OBS_DIM}, act_dim <= {MAX_ACT_DIM}, hidden in {HIDDEN_WIDTHS} and batch "
+                             f"sizes that are multiples of 16 up to {MAX_BATCH}; got ({self.d}, {self.A}, {cfg.hidden}, {cfg.batch_size})")
+        self.buffer = ReplayBufferDevice(cfg.buffer_size, self.N, self.d, self.A, self.device)
+        self.fused = FusedSacUpdate(self._policy, self.optimizers, cfg)
+        kw = dict(dtype=torch.float32, device=self.device)
+        self.obs_stage, self.act_f32 = torch.zeros((self.N, self.d), **kw), torch.zeros((self.N, self.A), **kw)
+        self.act_env = torch.zeros((self.N, self.A), dtype=env.torch_dtype, device=self.device)
+        self.batch = torch.zeros((cfg.batch_size, self.buffer.row), **kw)
+        self.batch_idx = torch.zeros(cfg.batch_size, dtype=torch.int32, device=self.device)
+        self.noise = torch.zeros((2, cfg.batch_size, self.A), **kw)
+        self.scal = torch.zeros(5, **kw)          # the torch path's last scalars
+        self.num_timesteps = 0
+        self.env_offset = int(getattr(env, "global_env_offset", 0))
+        self._started = False
+        self._graphs = {}
+        self.logs: Dict[str, float] = {}
+
+    @property
+    def policy(self) -> SacPolicy:
+        """The torch modules, brought up to date with the image first: the fused gradient steps train the image and leave the
+        modules (and the optimisers) alone until somebody asks for them."""
+        self.sync_policy()
+        return self._policy
+
+    def sync_policy(self) -> None:
+        if self.fused.ahead:
+            self.fused.unpack(self._policy.n_updates + self.fused.ahead)
+
+    @property
+    def n_updates(self) -> int:
+        return self._policy.n_updates + self.fused.ahead
+
+    # ------------------------------------------------------------------ the pieces of a vec-step
+    def _ensure_started(self) -> None:
+        if not self._started:
+            self.env.reset_tensor()
+            self._started = True
+
+    def _image_for_act(self) -> torch.Tensor:
+        if not self.fused.current():
+            self.fused.pack()
+        return self.fused.image
+
+    def act(self, mode: int = ACT_STOCHASTIC, logp: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
+        env = self.env
+        _lib.check(_lib.lib().fw_sac_act(_p(self._image_for_act()), _p(env.obs), int(env.torch_dtype == torch.float64), self.N, self.d,
+                                         self.A, self.cfg.hidden, int(mode), int(self.cfg.seed) & (2**64 - 1), self.env_offset,
+                                         _p(self.buffer.counters), _p(self.act_f32), _p(self.act_env), _p(self.obs_stage), _p(logp), _p(eps),
+                                         _stream(self.device)))
+        return self.act_env
+
+    def _store(self) -> None:
+        e = self.env
+        self.buffer.store(self.obs_stage, self.act_f32, e.rewards, e.obs, e.terminal_obs, e.terminated, e.truncated)
+
+    def _gradient_step_fused(self) -> None:
+        self.buffer.sample(self.cfg.seed, self.batch, self.batch_idx)
+        self.fused.run(self.batch, self.buffer.counters)
+
+    def _gradient_step_torch(self) -> None:
+        self.buffer.sample(self.cfg.seed, self.batch, self.batch_idx)
+        sac_noise(self.cfg.seed, self.buffer.counters, self.cfg.batch_size, self.A, out=self.noise)
+        s = sac_update_torch(self._policy, self.optimizers, self.batch, self.noise[0], self.noise[1], self.cfg)
+        self.scal.copy_(torch.stack([s[k].float() for k in SCALARS]))
+        self.buffer.counters[CTR_GRAD] += 1
+
+    def _vec_step_body(self, warm: bool, with_train: bool) -> None:
+        self.act(ACT_WARMUP if warm else ACT_STOCHASTIC)
+        self.env.step_tensor(self.act_env)
+        self._store()
+        if with_train:
+            for _ in range(self.G):
+                self._gradient_step_fused()
+
+    def _replay(self, key, warm: bool, with_train: bool) -> None:
+        """The vec-step of this form as a graph replay.  Its first call runs eagerly (it loads the kernels and is the vec-step
+        itself), its second call captures -- a capture runs nothing -- and replays."""
+        g = self._graphs.get(key)
+        if g is None:
+            self._vec_step_body(warm, with_train)
+            self._graphs[key] = "ran"
+            return
+        if g == "ran":
+            torch.cuda.synchronize(self.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._vec_step_body(warm, with_train)
+            self._graphs[key] = g
+        g.replay()
+
+    def collect_step(self, train: bool = True) -> None:
+        """One vec-step: act (uniform while ``num_timesteps < learning_starts``) -> env step -> store, then -- unless it was a warm-up
+        step or ``train`` is off -- the configured number of gradient steps."""
+        self._ensure_started()
+        warm = self.num_timesteps < self.cfg.learning_starts
+        do_train = train and not warm and self.G > 0
+        fused_train = do_train and self.cfg.fused_update
+        if fused_train and not self.fused.current():
+            self.fused.pack()
+        if self.cfg.use_graphs:
+            if not warm:
+                self._image_for_act()
+            self._replay((warm, fused_train), warm, fused_train)
+        else:
+            self._vec_step_body(warm, fused_train)
+        if fused_train:
+            self.fused.ahead += self.G
+        elif do_train:
+            self.train(self.G)
+        self.num_timesteps += self.N
+
+    def train(self, gradient_steps: int) -> None:
+        """``gradient_steps`` x (sample -> update) on the current buffer."""
+        if gradient_steps <= 0:
+            return
+        if self.cfg.fused_update:
+            if not self.fused.current():
+                self.fused.pack()
+            for _ in range(gradient_steps):
+                self._gradient_step_fused()
+            self.fused.ahead += gradient_steps
+        else:
+            self.sync_policy()
+            for _ in range(gradient_steps):
+                self._gradient_step_torch()
+
+    def read_logs(self) -> Dict[str, float]:
+        """The last gradient step's scalars (one host read)."""
+        src = self.fused.out[:5] if self.cfg.fused_update else self.scal
+        self.logs = dict(zip(SCALARS, src.tolist()))
+        self.logs["n_updates"] = self.n_updates
+        self.logs["num_timesteps"] = self.num_timesteps
+        return self.logs
+
+    def learn(self, total_timesteps: int, callbacks: Sequence = ()):
+        """Vec-steps until ``num_timesteps`` has grown by ``total_timesteps``; every callback is called as ``cb(self)`` after each
+        vec-step and stops the run by returning ``False``."""
+        end = self.num_timesteps + int(total_timesteps)
+        t0, n0 = time.perf_counter(), self.num_timesteps
+        while self.num_timesteps < end:
+            self.collect_step()
+            if any(cb(self) is False for cb in callbacks):
+                break
+        torch.cuda.synchronize(self.device)
+        self.read_logs()
+        self.logs["env_steps_per_s"] = (self.num_timesteps - n0) / max(time.perf_counter() - t0, 1e-9)
+        return self
+
+    # ------------------------------------------------------------------ checkpoints
+    def state_dict(self, include_buffer: bool = False):
+        self.sync_policy()
+        return {"policy": self._policy.state_dict(), "n_updates": self._policy.n_updates,
+                "optimizers": {k: (o.state_dict() if o is not None else None) for k, o in self.optimizers.items()},
+                "buffer": self.buffer.state_dict(include_buffer), "num_timesteps": self.num_timesteps, "config": asdict(self.cfg)}
+
+    def load_state_dict(self, sd) -> None:
+        self.fused.ahead = 0
+        self._policy.load_state_dict(sd["policy"])
+        self._policy.n_updates = int(sd["n_updates"])
+        for k, o in self.optimizers.items():
+            if o is not None and sd["optimizers"].get(k) is not None:
+                o.load_state_dict(sd["optimizers"][k])
+        self.buffer.load_state_dict(sd["buffer"])
+        self.num_timesteps = int(sd["num_timesteps"])
+        self.fused._sig = None
