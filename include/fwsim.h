@@ -854,6 +854,11 @@ int32_t fw_axis_aligned(fw_handle h);
  * FWSIM_AUX_WAVE=0|1 at fw_create overrides where that kernel applies), else 0.  Diagnostic; results are bit-identical to the
  * one-wave kernel. */
 int32_t fw_aux_wave(fw_handle h);
+/* 1 when this handle's fw_step runs the noise-wave kernel compiled for the shape of the headline training config (30 Hz agent steps
+ * of four 2-tick control steps, 2 of 8 waypoints in a 28-word euler observation, sparse reward, motor noise, gyroscopic term: those
+ * integers are constants of the kernel instead of loads; environment variable FWSIM_STEP_SHAPE=0 at fw_create turns it off, no value
+ * turns it on for another config), else 0.  Diagnostic; results are bit-identical to the noise-wave kernel. */
+int32_t fw_step_shape(fw_handle h);
 /* TEST HOOK, not used by the product: evaluates ONE device building block (a __device__ function of csrc/fwsim_device.hpp, called,
  * not copied) on n rows.  `in` [n, in_cols] and `out` [n, out_cols] are DEVICE buffers of doubles; the constants (Params / TickC /
  * SurfC as fw_create folded them) and the dtype are the handle's: a row is converted to the handle's dtype inside the kernel and

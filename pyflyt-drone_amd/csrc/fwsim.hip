@@ -307,7 +307,13 @@ enum Phase : int { PH_STEP = 0, PH_WARM = 1, PH_DONE = 2 };
 // prologue: the draw reads three integers per env and nothing of the launch's physics.  Same lane -> (env, sub) map on both waves;
 // the values cross in LDS ([kWave][2] behind the output stash) and the waves meet at ONE __syncthreads() in front of the sub-step
 // loop, which both execute unconditionally.
-template <typename T, bool GENERAL, int G, int TKIND, int WPE = 1, bool COLLECT = false, bool HELP = false, bool AX = false, bool AUX = false>
+// SH = the shape the instantiation is compiled for (fwsim_device.hpp: ShapeOfParams reads Params, as every kernel but one does;
+// ShapeTrainWaypoints is the headline config's, fw_step_kernel_g8xs): trip counts, row lengths and the reward / attitude / noise
+// variants become constants, and the four numbers of the task logic that stay run-time values (max_steps, auto_reset, dome, reach) are
+// loaded once in front of the sub-step loop.  Integers only: the floating-point results are those of the run-time shape, bit for
+// bit (sum_squares_fma pins the two sums of squares whose FMA contraction would otherwise follow the shape of the loop around them).
+template <typename T, bool GENERAL, int G, int TKIND, int WPE = 1, bool COLLECT = false, bool HELP = false, bool AX = false, bool AUX = false,
+          typename SH = ShapeOfParams>
 __device__ __forceinline__
 void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp, DevState<T> Dg,
                const T* __restrict__ actions, T* __restrict__ obs, T* __restrict__ reward,
@@ -325,6 +331,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   // observation is the cached attitude block + the deltas of the freshly sampled waypoints.  No second obs pass, no
   // sampling inside the step loop, and the waves that contain a reset finish with the others.
   constexpr bool DEFER = !GENERAL && TKIND == FW_TASK_WAYPOINTS;
+  static_assert(!SH::kFixed || (std::is_same<T, double>::value && DEFER && G == 8 && !COLLECT && !HELP), "a fixed shape is threaded through the wind-free 8-lane waypoints path only");
   const int nblk = (Dg.npad + EPW - 1) / EPW;        // step blocks; blocks beyond are shadow workers
   FWP(const long long p_t0 = FWP_NOW(); long long p_reset = 0, p_avi = 0, p_task = 0, p_r1 = 0, p_r2 = 0, p_r3 = 0; int p_nreset = 0, p_nhit = 0;)
   // XCD-aware block -> env-block map (G = 8): a wave touches 64 B of every SoA row, i.e. half a 128-B L2 line, and
@@ -352,7 +359,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   const bool active = env < D.n;
   const int envc = active ? env : D.n - 1;           // inactive lanes shadow the last env and never store
   const size_t n = D.npad;
-  const int Dobs = P.obs_dim;
+  const int Dobs = FW_SH(obs_dim);
   const int ld = Dobs + 1;
 
   // AUX, second wave: the normals of my lane's Aviary step -- the very call the step wave of the one-wave kernel makes below (same
@@ -362,8 +369,8 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
     if (threadIdx.x >= kWave) {
       const int32_t a_tick = D.i[IF_TICK * n + envc], a_episode = D.i[IF_EPISODE * n + envc], a_flags = D.i[IF_FLAGS * n + envc];
       T a_z0 = (T)0, a_z1 = (T)0;
-      if (P.has_noise && P.step_ratio <= G && !(a_flags & (FL_TERM | FL_TRUNC)))
-        rng_normal2<T>(P, (uint32_t)(P.env_offset + envc), (uint32_t)a_episode, (uint32_t)(a_tick / P.ticks_per_aviary) + (uint32_t)sub, a_z0, a_z1);
+      if (FW_SH(has_noise) && FW_SH(step_ratio) <= G && !(a_flags & (FL_TERM | FL_TRUNC)))
+        rng_normal2<T>(P, (uint32_t)(P.env_offset + envc), (uint32_t)a_episode, (uint32_t)(a_tick / FW_SH(ticks_per_aviary)) + (uint32_t)sub, a_z0, a_z1);
       aux_nz[2 * lane] = a_z0; aux_nz[2 * lane + 1] = a_z1;
       __syncthreads();                               // barrier 1 (the step wave's is in front of its sub-step loop)
       return;
@@ -383,7 +390,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   T tmine[3] = {(T)0, (T)0, (T)0};
   T a_keep = (T)0;
   if (LANE_T) {
-    if (sub < P.num_targets) {
+    if (sub < FW_SH(num_targets)) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) tmine[k] = D.r[(size_t)(RF_TARGETS + 3 * sub + k) * n + envc];
     }
@@ -476,8 +483,8 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
 
   // Motor noise.  G = 8: lane j of the group draws the normals of the step's j-th Aviary
   // step up front (8 lanes -> up to 8 sub-steps, in parallel); they are fetched by shuffle.
-  const uint32_t astep0 = (uint32_t)(tick / P.ticks_per_aviary);
-  const bool pre_noise = (G == 8) && P.has_noise && (P.step_ratio <= G);
+  const uint32_t astep0 = (uint32_t)(tick / FW_SH(ticks_per_aviary));
+  const bool pre_noise = (G == 8) && FW_SH(has_noise) && (FW_SH(step_ratio) <= G);
   T nz0 = (T)0, nz1 = (T)0;
   if (!AUX && pre_noise && !done_at_entry) rng_normal2<T>(P, genv, (uint32_t)episode, astep0 + (uint32_t)sub, nz0, nz1);
 
@@ -501,6 +508,14 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   T dist_keep = (T)0;
   bool resetting = false;                            // DEFER: auto-reset pending for the epilogue
   bool step_over = active && done_at_entry;          // nothing to simulate: finalise immediately
+  // A fixed shape: what the task logic of a sub-step still reads from Params, fetched here once.  The scalar file is full in this
+  // kernel and the allocator would rather load a Params field again (a round trip with its own wait, in every sub-step) than keep
+  // it; a value that went through an empty asm cannot be re-derived from memory, so it is kept (or parked in a lane).
+  int32_t k_max_steps = 0, k_auto_reset = 0; T k_dome = (T)0, k_reach = (T)0;
+  if constexpr (SH::kFixed) {
+    k_max_steps = P.max_steps; k_auto_reset = P.auto_reset; k_dome = P.dome; k_reach = P.reach;
+    asm("" : "+s"(k_max_steps)); asm("" : "+s"(k_auto_reset)); asm("" : "+s"(k_dome)); asm("" : "+s"(k_reach));
+  }
   if constexpr (AUX) {                               // barrier 1: every lane of both waves, whatever its env does
     __syncthreads();
     nz0 = aux_nz[2 * lane]; nz1 = aux_nz[2 * lane + 1];
@@ -530,7 +545,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
           ip[1] = make_int4(out_strike, OBJ ? out_strike : 0, step_count, 0);
         }
       }
-      if (DEFER) { resetting = (flags & (FL_TERM | FL_TRUNC)) && P.auto_reset; FWP(if (resetting) p_nreset += 1;) }
+      if (DEFER) { resetting = (flags & (FL_TERM | FL_TRUNC)) && (SH::kFixed ? k_auto_reset : P.auto_reset); FWP(if (resetting) p_nreset += 1;) }
       // GENERAL: a reset whose pre-simulated episode is ready is a copy, done in the epilogue (the observation pass there writes
       // the terminal observation); only a reset without one runs here, with its warm-up in the loop
       const bool take_shadow = GENERAL && (flags & (FL_TERM | FL_TRUNC)) && P.auto_reset && D.shadow_on &&
@@ -594,17 +609,17 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
     const bool stepping = stepped && (!GENERAL || phase == PH_STEP);
     bool contact = false;
     if (stepped) {
-      if (P.has_noise && !pre_noise && stepping)
-        rng_normal2<T>(P, genv, (uint32_t)episode, (uint32_t)(tick / P.ticks_per_aviary), z0, z1);
+      if (FW_SH(has_noise) && !pre_noise && stepping)
+        rng_normal2<T>(P, genv, (uint32_t)episode, (uint32_t)(tick / FW_SH(ticks_per_aviary)), z0, z1);
       if (GENERAL) {
         T c_eff[FW_NUM_ACTUATORS];
 #pragma unroll
         for (int c = 0; c < FW_NUM_ACTUATORS; ++c) c_eff[c] = stepping ? cmd[c] : (T)0;
         z0 = stepping ? z0 : (T)0; z1 = stepping ? z1 : (T)0;
         LA.cmd = stepping ? cmd_mine : (T)0;
-        contact = aviary_step<T, true, G, HASOBJ, AX>(P, C, OC, D, env, O, S, R, c_eff, tick, z0, z1, wb, wa, gust, mine, wmask, LA);   // :339
+        contact = aviary_step<T, true, G, HASOBJ, AX, SH>(P, C, OC, D, env, O, S, R, c_eff, tick, z0, z1, wb, wa, gust, mine, wmask, LA);   // :339
       } else {
-        contact = aviary_step<T, false, G, HASOBJ, AX>(P, C, OC, D, env, O, S, R, cmd, tick, z0, z1, wb, wa, gust, mine, wmask, LA);    // :339
+        contact = aviary_step<T, false, G, HASOBJ, AX, SH>(P, C, OC, D, env, O, S, R, cmd, tick, z0, z1, wb, wa, gust, mine, wmask, LA);    // :339
       }
     }
     if constexpr (HELP) {
@@ -782,28 +797,32 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
         step_over = (it + 1 >= P.step_ratio) || (flags & (FL_TERM | FL_TRUNC));
       } else if (stepping) {
         // compute_state(): WaypointHandler.distance_to_targets side effects
-        const int nleft = P.num_targets - num_reached;
+        const int nleft = FW_SH(num_targets) - num_reached;
         const T old_dist = new_dist;
-        if (P.task != FW_TASK_OBJLOCK && nleft > 0) {
+        if (FW_SH(task) != FW_TASK_OBJLOCK && nleft > 0) {
           T dx = tcur[0] - S.p[0], dy = tcur[1] - S.p[1], dz = tcur[2] - S.p[2];
-          new_dist = M<T>::sqrt_(dx * dx + dy * dy + dz * dz);
+          if constexpr (SH::kFixed) new_dist = M<T>::sqrt_(sum_squares_fma(dx, dy, dz));
+          else new_dist = M<T>::sqrt_(dx * dx + dy * dy + dz * dz);
         }
         tgt_obs = num_reached;
         // compute_base_term_trunc_reward(): :296-312
-        if (step_count > P.max_steps) flags |= FL_TRUNC;
+        if (step_count > (SH::kFixed ? k_max_steps : P.max_steps)) flags |= FL_TRUNC;
         if (contact) { rew = (T)-100; flags |= FL_COLLISION | FL_TERM; }
-        if (S.p[0] * S.p[0] + S.p[1] * S.p[1] + S.p[2] * S.p[2] > P.dome * P.dome) { rew = (T)-100; flags |= FL_OOB | FL_TERM; }
+        bool oob;
+        if constexpr (SH::kFixed) oob = sum_squares_fma(S.p[0], S.p[1], S.p[2]) > k_dome * k_dome;
+        else oob = S.p[0] * S.p[0] + S.p[1] * S.p[1] + S.p[2] * S.p[2] > P.dome * P.dome;
+        if (oob) { rew = (T)-100; flags |= FL_OOB | FL_TERM; }
         // waypoint reward (upstream FixedwingWaypointsEnv; mirrored at fixedwing_waypoint_objlock_env.py:286-294)
-        if (P.task != FW_TASK_OBJLOCK && nleft > 0) {
-          if (!P.sparse) {
+        if (FW_SH(task) != FW_TASK_OBJLOCK && nleft > 0) {
+          if (!FW_SH(sparse)) {
             T progress = (old_dist != (T)0) ? (old_dist - new_dist) : (T)0;
             rew += M<T>::fmax_((T)3 * progress, (T)0);
             rew += M<T>::rcp_(new_dist);
           }
-          if (new_dist < P.reach) {
+          if (new_dist < (SH::kFixed ? k_reach : P.reach)) {
             rew = (T)100;
             num_reached += 1;
-            if (num_reached == P.num_targets) flags |= FL_TRUNC | FL_COMPLETE;
+            if (num_reached == FW_SH(num_targets)) flags |= FL_TRUNC | FL_COMPLETE;
             if (LANE_T) {                                                   // advance_targets(): the next waypoint's lane hands it over
 #pragma unroll
               for (int k = 0; k < 3; ++k) tcur[k] = __shfl(tmine[k], gbase | (num_reached & (G - 1)), kWave);
@@ -814,7 +833,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
             }
           }
         }
-        step_over = (it + 1 >= P.step_ratio) || (flags & (FL_TERM | FL_TRUNC));     // :334-337
+        step_over = (it + 1 >= FW_SH(step_ratio)) || (flags & (FL_TERM | FL_TRUNC));     // :334-337
       } else {
         warm_left -= 1;
         if (warm_left == 0) {
@@ -847,7 +866,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   T wo[kWO];
   if (WO && resetting) {
 #pragma unroll
-    for (int j = 0; j < kWO; ++j) { const int k = sub + j * G; wo[j] = (k < P.att_dim) ? vload(&Pp->warm_obs[k]) : (T)0; }
+    for (int j = 0; j < kWO; ++j) { const int k = sub + j * G; wo[j] = (k < FW_SH(att_dim)) ? vload(&Pp->warm_obs[k]) : (T)0; }
   }
 
   // (pre: the worker also left the first observation row and the first distance: requested here as well)
@@ -898,14 +917,14 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
       for (int k = 0; k < 4; ++k) act_obs[k] = D.r[(size_t)(RF_ACTION + k) * n + envc];
     }
     T Ro[9];
-    int o = write_obs_attitude<T, true>(P, S, act_obs, Ro, [&](int k, T v) { if (leader) tile[row * ld + k] = v; });
-#pragma unroll 1
-    for (int i = 0; i < P.ctx; ++i) {
+    int o = write_obs_attitude<T, true, SH>(P, S, act_obs, Ro, [&](int k, T v) { if (leader) tile[row * ld + k] = v; });
+#pragma unroll SH::kCtxUnroll
+    for (int i = 0; i < FW_SH(ctx); ++i) {
       const int t = tgt_obs + i;
       T tw[3], d[3], b[3] = {(T)0, (T)0, (T)0};
 #pragma unroll
       for (int k = 0; k < 3; ++k) tw[k] = __shfl(tmine[k], gbase | (t & (G - 1)), kWave);
-      if (t < P.num_targets) {
+      if (t < FW_SH(num_targets)) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) d[k] = tw[k] - S.p[k];
         mtv(Ro, d, b);
@@ -942,14 +961,14 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
     if (pre) {                                         // sampled ahead of time by a worker block of an earlier launch
 #pragma unroll
       for (int k = 0; k < 3; ++k) sc.t_mine[k] = tpre[k];
-      if (sub < P.num_targets) {
+      if (sub < FW_SH(num_targets)) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) D.r[(size_t)(RF_TARGETS + 3 * sub + k) * n + env] = tpre[k];
       }
     } else {
       sample_scenario_inl<T, G>(Pp, D.r, n, env, (uint32_t)episode, &sc);
     }
-    const int nt = min(P.ctx, P.num_targets);
+    const int nt = min(FW_SH(ctx), FW_SH(num_targets));
     T t0[3] = {(T)0, (T)0, (T)0};
     const bool copied = WO && pre && Dobs <= kDOW * G;    // the worker left the whole first observation row: nothing to compute
     if (copied) {
@@ -957,7 +976,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
       for (int j = 0; j < kDOW; ++j) { const int k = sub + j * G; if (k < Dobs) tile[row * ld + k] = dow[j]; }
     }
 #pragma unroll 1
-    for (int i = 0; i < (copied ? 0 : P.ctx); ++i) {
+    for (int i = 0; i < (copied ? 0 : FW_SH(ctx)); ++i) {
       T tw[3] = {(T)0, (T)0, (T)0};
       if (G > 1) {
 #pragma unroll
@@ -973,14 +992,14 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
         mtv(P.warm_R, d, b);
         if (i == 0) { t0[0] = tw[0]; t0[1] = tw[1]; t0[2] = tw[2]; }
       }
-      if (leader) { tile[row * ld + P.att_dim + 3 * i] = b[0]; tile[row * ld + P.att_dim + 3 * i + 1] = b[1]; tile[row * ld + P.att_dim + 3 * i + 2] = b[2]; }
+      if (leader) { tile[row * ld + FW_SH(att_dim) + 3 * i] = b[0]; tile[row * ld + FW_SH(att_dim) + 3 * i + 1] = b[1]; tile[row * ld + FW_SH(att_dim) + 3 * i + 2] = b[2]; }
     }
     FWP(const long long p_e2 = FWP_NOW(); p_r2 = p_e2 - p_e1;)      // new waypoints stored, their deltas in the tile
     if (WO && !copied) {
 #pragma unroll
-      for (int j = 0; j < kWO; ++j) { const int k = sub + j * G; if (k < P.att_dim) tile[row * ld + k] = wo[j]; }   // the env's lanes share the cached attitude block
+      for (int j = 0; j < kWO; ++j) { const int k = sub + j * G; if (k < FW_SH(att_dim)) tile[row * ld + k] = wo[j]; }   // the env's lanes share the cached attitude block
     }
-    if (!copied) for (int k = sub + (WO ? kWO * G : 0); k < P.att_dim; k += G) tile[row * ld + k] = Pp->warm_obs[k];
+    if (!copied) for (int k = sub + (WO ? kWO * G : 0); k < FW_SH(att_dim); k += G) tile[row * ld + k] = Pp->warm_obs[k];
 #pragma unroll
     for (int k = 0; k < 3; ++k) { S.p[k] = P.warm[k]; S.v[k] = P.warm[7 + k]; S.w[k] = P.warm[10 + k]; }
 #pragma unroll
@@ -990,7 +1009,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
     tick = P.warm_ticks;
     step_count = 0; flags = 0; ep_return = (T)0; tgt_obs = 0; num_reached = 0;
     new_dist = copied ? dnd : (T)0;
-    if (P.num_targets > 0 && !copied) {
+    if (FW_SH(num_targets) > 0 && !copied) {
       if (G == 1 && nt == 0) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) t0[k] = D.r[(size_t)(RF_TARGETS + k) * n + env];
@@ -1102,6 +1121,9 @@ __global__ __launch_bounds__(kWave) void fw_step_kernel_g8(FW_STEP_ARGS) { FW_ST
 // ... with a second wave per workgroup that draws the motor noise (step_body AUX; f64, wind-free, axis-aligned: the headline row)
 template <typename T>
 __global__ __launch_bounds__(2 * kWave) void fw_step_kernel_g8x(FW_STEP_ARGS) { FW_STEP_RUN(T, false, 8, FW_TASK_WAYPOINTS, 1, false, false, true, true); }
+// ... and that kernel compiled for the shape of the headline training config (step_body SH; fw_env::step_shape)
+template <typename T>
+__global__ __launch_bounds__(2 * kWave) void fw_step_kernel_g8xs(FW_STEP_ARGS) { FW_STEP_RUN(T, false, 8, FW_TASK_WAYPOINTS, 1, false, false, true, true, ShapeTrainWaypoints); }
 // ... and the same mapping capped at 256 registers: two waves per SIMD (8 192 < N <= 65 536 envs)
 template <typename T, bool GENERAL>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2, 2)))
@@ -1714,6 +1736,15 @@ bool axis_aligned_geometry(const fw_config& c) {
   return true;
 }
 
+// Host twin of ShapeTrainWaypoints (fwsim_device.hpp): 1 when fill_params() gives every field that shape compiles in exactly the
+// value it compiles in -- the same expressions as there.  Only fields that no call changes after fw_create are in a shape
+// (auto_reset is one too, but the kernel reads it once per launch, outside the sub-step loop, and both settings are in use).
+int step_shape_of(const fw_config& c) {
+  return (c.task == FW_TASK_WAYPOINTS && 120 / c.agent_hz == 4 && c.physics_hz / c.control_hz == 2 && c.context_length == 2 &&
+          c.num_targets == 8 && obs_dim_of(&c) == 28 && att_dim_of(&c) == 22 && c.sparse_reward != 0 && c.angle_representation == 0 &&
+          c.motor.noise_ratio != 0.0 && c.gyroscopic != 0) ? 1 : 0;
+}
+
 // Fold fw_config into the wave-uniform constant block (all derivations in double).
 template <typename T>
 bool build_params(const fw_config& c, uint64_t seed, int64_t env_offset, Params<T>& P, std::string& err) {
@@ -1823,6 +1854,7 @@ struct fw_env {
   int32_t g8_waves = 1;         // 8-lane mapping, waypoints task: waves per SIMD the step kernel is built for (1 | 2)
   int32_t capture_wave = 0;     // 8-lane mapping, camera tasks: fw_step workgroups carry a capture wave (fw_step_kernel_obj_g8h)
   int32_t aux_wave = 0;         // the axis-aligned row with motor noise, up to kAuxWaveMaxEnvs envs: a second wave per step workgroup draws the noise (fw_step_kernel_g8x)
+  int32_t step_shape = 0;       // the noise-wave row on the headline training config's shape (step_shape_of): that kernel with the shape compiled in (fw_step_kernel_g8xs)
   int32_t axis_aligned = 0;     // f64 wind-free waypoints on the 8-lane one-wave build: the tick's axis-aligned variant (axis_aligned_geometry)
   EnvKernel step, reset, collect;   // chosen once by fw_create from the fields above (select_kernels); collect.fn is null where fw_collect_step does not serve
   EnvKernel step_hl;                // fw_step_hl's kernel (hl_step_kernel_of); null where fw_step_hl does not serve
@@ -1996,7 +2028,7 @@ int upload_params(fw_env* h) {
 // A key names the fields of a handle that the choice depends on; kAny in a row matches every value.  The first row that matches
 // wins, so a special case stands above the general one.  A new kernel variant is one new row.
 constexpr int kAny = -1;
-struct KernelKey { int task, lanes, waves, windy, axis_aligned, capture_wave, aux_wave; };
+struct KernelKey { int task, lanes, waves, windy, axis_aligned, capture_wave, aux_wave, step_shape; };
 struct KernelRow { KernelKey key; EnvKernel step, reset, collect; };
 template <typename... A> const void* kfn(void (*kernel)(A...)) { return (const void*)kernel; }      // the host-side pointer hipLaunchKernel takes
 // The argument lists step_T / collect_step_T / reset_T build.  hipLaunchKernel takes them unchecked, so a kernel enters the table
@@ -2019,49 +2051,55 @@ template <typename T> EnvKernel axis_aligned_step_kernel() {
 template <typename T> EnvKernel aux_wave_step_kernel() {
   if constexpr (std::is_same<T, double>::value) return noise_wave<T>(fw_step_kernel_g8x<T>); else return {};
 }
+// ... and that one compiled for the headline training config's shape
+template <typename T> EnvKernel step_shape_step_kernel() {
+  if constexpr (std::is_same<T, double>::value) return noise_wave<T>(fw_step_kernel_g8xs<T>); else return {};
+}
 // (fw_collect_step: the four-action tasks on the 8-lane mapping -- collect_fill says so to the others; general tick, no capture wave)
 template <typename T> const KernelRow* env_kernels_of(const KernelKey& q) {
   constexpr int LL = FW_TASK_LOWLEVEL, WD = FW_TASK_WAYPOINTS_DIRECT, OBJ = FW_TASK_OBJLOCK, COMB = FW_TASK_WAYPOINT_OBJLOCK, WP = FW_TASK_WAYPOINTS;
   static const KernelRow rows[] = {
-    // task lanes waves windy axis  capture aux   fw_step                                                     fw_reset / fw_observe                                fw_collect_step
-    {{LL,   8, kAny, 1,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 8, true>),         no_objc<T>(fw_reset_kernel_ll<T, 8>),         {}},
-    {{LL,   8, kAny, 0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 8, false>),        no_objc<T>(fw_reset_kernel_ll<T, 8>),         {}},
-    {{LL,   1, kAny, 1,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 1, true>),         no_objc<T>(fw_reset_kernel_ll<T, 1>),         {}},
-    {{LL,   1, kAny, 0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 1, false>),        no_objc<T>(fw_reset_kernel_ll<T, 1>),         {}},
-    {{WD,   8, kAny, 1,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, true>),         reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
-    {{WD,   8, kAny, 0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, false>),        reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
-    {{WD,   1, kAny, 1,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, true>),         reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
-    {{WD,   1, kAny, 0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, false>),        reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
-    {{OBJ,  8, kAny, kAny, kAny, 1,    kAny}, two_wave<T>(fw_step_kernel_obj_g8h<T, OBJ>),      reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
-    {{OBJ,  8, kAny, kAny, kAny, 0,    kAny}, step_k<T>(fw_step_kernel_obj_g8<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
-    {{OBJ,  1, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 1, OBJ>),       {}},
-    {{COMB, 8, kAny, kAny, kAny, 1,    kAny}, two_wave<T>(fw_step_kernel_obj_g8h<T, COMB>),     reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
-    {{COMB, 8, kAny, kAny, kAny, 0,    kAny}, step_k<T>(fw_step_kernel_obj_g8<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
-    {{COMB, 1, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 1, COMB>),      {}},
-    {{WP,   8, 1,    0,    1,    kAny, 1},    aux_wave_step_kernel<T>(),                        reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
-    {{WP,   8, 1,    0,    1,    kAny, kAny}, axis_aligned_step_kernel<T>(),                    reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
-    {{WP,   8, 2,    1,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, true>),          reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, true>)},
-    {{WP,   8, 2,    0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, false>),         reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, false>)},
-    {{WP,   8, 1,    1,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, true>),            reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, true>)},
-    {{WP,   8, 1,    0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, false>),           reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
-    {{WP,   1, kAny, 1,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, true>),            reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
-    {{WP,   1, kAny, 0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, false>),           reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
+    // task lanes waves windy axis  capture aux   shape  fw_step                                                      fw_reset / fw_observe                                fw_collect_step
+    {{LL,   8, kAny, 1,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 8, true>),         no_objc<T>(fw_reset_kernel_ll<T, 8>),         {}},
+    {{LL,   8, kAny, 0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 8, false>),        no_objc<T>(fw_reset_kernel_ll<T, 8>),         {}},
+    {{LL,   1, kAny, 1,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 1, true>),         no_objc<T>(fw_reset_kernel_ll<T, 1>),         {}},
+    {{LL,   1, kAny, 0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 1, false>),        no_objc<T>(fw_reset_kernel_ll<T, 1>),         {}},
+    {{WD,   8, kAny, 1,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, true>),         reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
+    {{WD,   8, kAny, 0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, false>),        reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
+    {{WD,   1, kAny, 1,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, true>),         reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
+    {{WD,   1, kAny, 0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, false>),        reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
+    {{OBJ,  8, kAny, kAny, kAny, 1,    kAny, kAny}, two_wave<T>(fw_step_kernel_obj_g8h<T, OBJ>),      reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
+    {{OBJ,  8, kAny, kAny, kAny, 0,    kAny, kAny}, step_k<T>(fw_step_kernel_obj_g8<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
+    {{OBJ,  1, kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 1, OBJ>),       {}},
+    {{COMB, 8, kAny, kAny, kAny, 1,    kAny, kAny}, two_wave<T>(fw_step_kernel_obj_g8h<T, COMB>),     reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
+    {{COMB, 8, kAny, kAny, kAny, 0,    kAny, kAny}, step_k<T>(fw_step_kernel_obj_g8<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
+    {{COMB, 1, kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 1, COMB>),      {}},
+    {{WP,   8, 1,    0,    1,    kAny, 1,    1},    step_shape_step_kernel<T>(),                      reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   8, 1,    0,    1,    kAny, 1,    kAny}, aux_wave_step_kernel<T>(),                        reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   8, 1,    0,    1,    kAny, kAny, kAny}, axis_aligned_step_kernel<T>(),                    reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   8, 2,    1,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, true>),          reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, true>)},
+    {{WP,   8, 2,    0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, false>),         reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, false>)},
+    {{WP,   8, 1,    1,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, true>),            reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, true>)},
+    {{WP,   8, 1,    0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, false>),           reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   1, kAny, 1,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, true>),            reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
+    {{WP,   1, kAny, 0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, false>),           reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
   };
   auto fits = [](int row, int v) { return row == kAny || row == v; };
   for (const KernelRow& r : rows)
     if (const KernelKey& k = r.key; fits(k.task, q.task) && fits(k.lanes, q.lanes) && fits(k.waves, q.waves) && fits(k.windy, q.windy) &&
-                                    fits(k.axis_aligned, q.axis_aligned) && fits(k.capture_wave, q.capture_wave) && fits(k.aux_wave, q.aux_wave)) return &r;
+                                    fits(k.axis_aligned, q.axis_aligned) && fits(k.capture_wave, q.capture_wave) && fits(k.aux_wave, q.aux_wave) &&
+                                    fits(k.step_shape, q.step_shape)) return &r;
   return nullptr;
 }
 
 // The handle's kernels, from the fields fw_create has just fixed.  A combination without a row (or whose row holds no step or
 // reset kernel) is an error here, not a launch that silently does nothing.
 template <typename T> int select_kernels(fw_env* h) {
-  const KernelKey q = { h->cfg.task, h->lanes_per_env, h->g8_waves, h->cfg.wind_mode != FW_WIND_OFF ? 1 : 0, h->axis_aligned, h->capture_wave, h->aux_wave };
+  const KernelKey q = { h->cfg.task, h->lanes_per_env, h->g8_waves, h->cfg.wind_mode != FW_WIND_OFF ? 1 : 0, h->axis_aligned, h->capture_wave, h->aux_wave, h->step_shape };
   const KernelRow* r = env_kernels_of<T>(q);
   if (!r || !r->step.fn || !r->reset.fn) {
-    h->err = "no kernel is built for (task, dtype, lanes per env, waves per SIMD, wind, axis_aligned, capture_wave, aux_wave) =";
-    for (int x : { q.task, h->cfg.dtype, q.lanes, q.waves, q.windy, q.axis_aligned, q.capture_wave, q.aux_wave }) h->err += " " + std::to_string(x);
+    h->err = "no kernel is built for (task, dtype, lanes per env, waves per SIMD, wind, axis_aligned, capture_wave, aux_wave, step_shape) =";
+    for (int x : { q.task, h->cfg.dtype, q.lanes, q.waves, q.windy, q.axis_aligned, q.capture_wave, q.aux_wave, q.step_shape }) h->err += " " + std::to_string(x);
     return FW_EUNSUPPORTED;
   }
   h->step = r->step; h->reset = r->reset; h->collect = r->collect;
@@ -2358,6 +2396,10 @@ int32_t fw_create(const fw_config* cfg, int32_t num_envs, int32_t device, uint64
   const bool aux_row = h->axis_aligned && cfg->motor.noise_ratio != 0.0 && 120 / cfg->agent_hz <= 8;      // (Params: has_noise, step_ratio)
   h->aux_wave = (aux_row && num_envs <= kAuxWaveMaxEnvs) ? 1 : 0;
   if (const char* ev = getenv("FWSIM_AUX_WAVE")) { if (aux_row) h->aux_wave = atoi(ev) != 0 ? 1 : 0; }
+  // ... and the noise-wave kernel with the config's shape compiled in (fw_step_kernel_g8xs; bit-identical again), where the config
+  // has the one shape that is built.  FWSIM_STEP_SHAPE=0 turns it off; no value turns it on for another shape (wrong results).
+  h->step_shape = (h->aux_wave && step_shape_of(*cfg)) ? 1 : 0;
+  if (const char* ev = getenv("FWSIM_STEP_SHAPE")) { if (atoi(ev) == 0) h->step_shape = 0; }
   DeviceGuard g(device);
   rc = with_dtype(h, [&](auto t) { return create_T<decltype(t)>(h); });
   if (rc != FW_OK) {
@@ -3342,6 +3384,7 @@ int32_t fw_probe(fw_handle h, int32_t op, int32_t variant, const double* in, int
 int32_t fw_num_envs(fw_handle h) { return h ? h->n : FW_EINVAL; }
 int32_t fw_capture_wave(fw_handle h) { return h ? h->capture_wave : FW_EINVAL; }
 int32_t fw_aux_wave(fw_handle h) { return h ? h->aux_wave : FW_EINVAL; }
+int32_t fw_step_shape(fw_handle h) { return h ? h->step_shape : FW_EINVAL; }
 int32_t fw_axis_aligned(fw_handle h) { return h ? h->axis_aligned : FW_EINVAL; }
 int32_t fw_lanes_per_env(fw_handle h) { return h ? (h->lanes_per_env == 8 && h->g8_waves == 2 ? 16 : h->lanes_per_env) : FW_EINVAL; }
 

@@ -91,6 +91,45 @@ struct Params {
   int32_t ll_max_steps;                   // truncation step count
 };
 
+// The "shape" of a step kernel: the integer fields of Params that fix trip counts, row lengths and which branches exist.  Every
+// one of them is set by fw_create from the fw_config and never changes afterwards (fill_params is the only writer; fw_seed
+// re-uploads the same values), so a kernel may be compiled for one shape and chosen where the config has it (fw_env::step_shape).
+// A shape is a traits struct; code that has `SH` and `P` in scope asks FW_SH(field): the field of Params where the shape is not
+// fixed, the shape's constant where it is.  (Plain constants and a conditional, not accessor functions of P: a forced-inline
+// accessor -- even one that is handed the loaded field by value -- changes the order in which the optimiser sees the loads, and
+// with it the register allocation of kernels that have nothing to do with shapes.  With this form they compile to the very
+// code they had before, tools/kernel_resources.py.)
+struct ShapeOfParams {           // read Params at run time: every kernel but one.  The constants are never read.
+  static constexpr bool kFixed = false;
+  static constexpr int kTickUnroll = 1, kCtxUnroll = 1;          // `#pragma unroll` counts of the tick loop and the observation's waypoint loop (1 = rolled)
+  static constexpr int step_ratio = -1, ticks_per_aviary = -1, ctx = -1, num_targets = -1, obs_dim = -1, att_dim = -1, sparse = -1,
+                       angle_repr = -1, has_noise = -1, gyroscopic = -1, task = -1;
+};
+// The headline training config (config.py TRAIN_CONFIG waypoints): 30 Hz agent on the 120 Hz loop, 240 Hz physics, two waypoints
+// of eight in view, euler attitude (22 + 2 * 3 = 28 words per row), sparse reward, motor noise, gyroscopic term.  Host twin:
+// step_shape_of() in fwsim.hip -- a field added here is a condition added there.
+// Both loops stay rolled (CHANGELOG): the unrolled tick loop is faster but contracts the tick's FMAs differently from the rolled
+// body (results differ from the run-time-shape kernels), the unrolled waypoint loop gains nothing measurable.
+#ifndef FW_SHAPE_TICK_UNROLL
+#define FW_SHAPE_TICK_UNROLL 1
+#endif
+#ifndef FW_SHAPE_CTX_UNROLL
+#define FW_SHAPE_CTX_UNROLL 1
+#endif
+struct ShapeTrainWaypoints {
+  static constexpr bool kFixed = true;
+  static constexpr int kTickUnroll = FW_SHAPE_TICK_UNROLL, kCtxUnroll = FW_SHAPE_CTX_UNROLL;
+  static constexpr int step_ratio = 4, ticks_per_aviary = 2, ctx = 2, num_targets = 8, obs_dim = 28, att_dim = 22, sparse = 1,
+                       angle_repr = 0, has_noise = 1, gyroscopic = 1, task = FW_TASK_WAYPOINTS;
+};
+#define FW_SH(field) (SH::kFixed ? (int)SH::field : (int)P.field)
+// x*x + y*y + z*z as the step kernels of the run-time shape evaluate it in their sub-step loop: x*x rounded, then one FMA per
+// further square.  hipcc contracts `x*x + y*y + z*z` by the operand order the optimiser leaves the additions in, and that order
+// follows the loop structure around the expression: with the tick loop's trip count a constant the same source line came out as
+// fma(z, z, fma(x, x, y*y)), one ulp off in the stored waypoint distance (tests/test_step_shape_gpu.py caught it).  A fixed
+// shape therefore spells the contraction out; the run-time shapes keep the plain expression, and with it the code they had.
+__device__ __forceinline__ double sum_squares_fma(double x, double y, double z) { return __builtin_fma(z, z, __builtin_fma(y, y, x * x)); }
+
 template <typename T>
 struct DevState {
   T* r;          // [RF_COUNT][npad]
@@ -749,10 +788,11 @@ __device__ __forceinline__ void quat_integrate(const TickC<T>& C, Rigid<T>& S) {
 // G = 1: rolled loop over the 5 surfaces (constants by scalar loads at a wave-uniform index
 //        -- unrolling makes hipcc hoist ~100 constants into SGPRs and spill).
 // G = 8: `mine` holds this lane's surface constants in VGPRs, `wmask` zeroes lanes 5-7.
+// SH: the kernel's shape (ShapeOfParams above); the tick reads `gyroscopic` through it.
 // AX (G = 8, SC = SurfC<T>): axis-aligned geometry -- surface_wrench_ax (lanes 5-7: mine.hra = 0 instead of wmask), and the
 // inertia tensor is diagonal: I w and I^-1 rhs are three products each (the dropped terms are products with an exact 0, and
 // their consumers are products, so the contraction around them does not change).
-template <typename T, bool WIND, int G, bool AX = false, typename SC>
+template <typename T, bool WIND, int G, bool AX = false, typename SH = ShapeOfParams, typename SC>
 __device__ __forceinline__ bool physics_tick(const Params<T>& P, const TickC<T>& C, Rigid<T>& S, T R[9],
                                              const T cmd[FW_NUM_ACTUATORS], T noise_z, const T wind[3],
                                              SC& mine, T wmask, LaneAct<T>& LA) {
@@ -809,7 +849,7 @@ __device__ __forceinline__ bool physics_tick(const Params<T>& P, const TickC<T>&
   T Iw[3], rhs[3] = { Tq[0], Tq[1], Tq[2] }, al_b[3], al_w[3];
   if (AX) { Iw[0] = C.I[0] * w_b[0]; Iw[1] = C.I[4] * w_b[1]; Iw[2] = C.I[8] * w_b[2]; }
   else mv(C.I, w_b, Iw);
-  if (P.gyroscopic) {
+  if (FW_SH(gyroscopic)) {
     T g[3];
     cross(w_b, Iw, g);
     rhs[0] -= g[0]; rhs[1] -= g[1]; rhs[2] -= g[2];
@@ -897,7 +937,7 @@ __device__ __forceinline__ void quat_from_euler(const T e[3], T q[4]) {
 //   (fixedwing_base_env.py:288); away from the gimbal guard that round trip is
 //   the identity on the rotation, so q itself is used and the round trip is
 //   taken only on the (rare) guarded branch or when the quaternion is observed.
-template <typename T, bool LANES8 = false, typename W>
+template <typename T, bool LANES8 = false, typename SH = ShapeOfParams, typename W>
 __device__ __forceinline__ int write_obs_attitude(const Params<T>& P, const Rigid<T>& S, const T action[4], T R[9], W&& put) {
   rot_from_quat(S.q, R);
   T ang_vel[3], lin_vel[3], eul[3];
@@ -905,13 +945,13 @@ __device__ __forceinline__ int write_obs_attitude(const Params<T>& P, const Rigi
   mtv(R, S.v, lin_vel);
   bool lock = LANES8 ? euler_from_quat_lanes8(S.q, eul) : euler_from_quat(S.q, eul);
   T qrt[4] = { S.q[0], S.q[1], S.q[2], S.q[3] };
-  if (lock || P.angle_repr == 1) {
+  if (lock || FW_SH(angle_repr) == 1) {
     quat_from_euler(eul, qrt);
     rot_from_quat(qrt, R);
   }
   int o = 0;
   put(o++, ang_vel[0]); put(o++, ang_vel[1]); put(o++, ang_vel[2]);
-  if (P.angle_repr == 0) { put(o++, eul[0]); put(o++, eul[1]); put(o++, eul[2]); }
+  if (FW_SH(angle_repr) == 0) { put(o++, eul[0]); put(o++, eul[1]); put(o++, eul[2]); }
   else { put(o++, qrt[0]); put(o++, qrt[1]); put(o++, qrt[2]); put(o++, qrt[3]); }
   put(o++, lin_vel[0]); put(o++, lin_vel[1]); put(o++, lin_vel[2]);
   put(o++, S.p[0]); put(o++, S.p[1]); put(o++, S.p[2]);

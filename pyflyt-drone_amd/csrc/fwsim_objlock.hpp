@@ -1253,17 +1253,17 @@ __device__ __forceinline__ void obj_write_obs(const Params<T>& P, const ObjState
 // motor-noise normals (zero for warm-up lanes: their throttle is exactly 0).  OBJ adds the
 // duck / cylinder contacts per tick; the camera capture every physics_camera_ratio ticks
 // (envs/fixedwing_objlock_env.py:631-641) is the caller's next call: obj_capture_step, by the whole wave.
-template <typename T, bool WIND, int G, bool OBJ, bool AX = false, typename SC>
+template <typename T, bool WIND, int G, bool OBJ, bool AX = false, typename SH = ShapeOfParams, typename SC>
 __device__ __forceinline__ bool aviary_step(const Params<T>& P, const TickC<T>& C, const ObjC<T>& OC, const DevState<T>& D,
                                             int env, ObjState<T>& O, Rigid<T>& S, T R[9], const T cmd[FW_NUM_ACTUATORS],
                                             int32_t& tick, T z0, T z1, const T wb[3], const T wa[3], T gust[2],
                                             SC& mine, T wmask, LaneAct<T>& LA) {
   bool contact = false;
-#pragma unroll 1
-  for (int t = 0; t < P.ticks_per_aviary; ++t) {
+#pragma unroll SH::kTickUnroll
+  for (int t = 0; t < FW_SH(ticks_per_aviary); ++t) {
     T wind[3] = {(T)0, (T)0, (T)0};
     if (WIND) wind_from_phase<T>(P, wb, wa, gust, wind);
-    contact |= physics_tick<T, WIND, G, AX>(P, C, S, R, cmd, (t & 1) ? z1 : z0, wind, mine, wmask, LA);
+    contact |= physics_tick<T, WIND, G, AX, SH>(P, C, S, R, cmd, (t & 1) ? z1 : z0, wind, mine, wmask, LA);
     if (OBJ) contact |= obj_contacts<T, G>(P, C, OC, D, env, O, S, R);
     tick += 1;
     if (WIND) gust_advance<T>(P, gust);
