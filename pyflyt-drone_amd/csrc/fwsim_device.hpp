@@ -108,10 +108,12 @@ struct ShapeOfParams {           // read Params at run time: every kernel but on
 // The headline training config (config.py TRAIN_CONFIG waypoints): 30 Hz agent on the 120 Hz loop, 240 Hz physics, two waypoints
 // of eight in view, euler attitude (22 + 2 * 3 = 28 words per row), sparse reward, motor noise, gyroscopic term.  Host twin:
 // step_shape_of() in fwsim.hip -- a field added here is a condition added there.
-// Both loops stay rolled (CHANGELOG): the unrolled tick loop is faster but contracts the tick's FMAs differently from the rolled
-// body (results differ from the run-time-shape kernels), the unrolled waypoint loop gains nothing measurable.
+// The tick loop is unrolled (both ticks of an Aviary step in one body): measured faster (CHANGELOG), and bit-identical to the
+// rolled body of the run-time-shape kernels since the two places where the second copy was contracted differently are spelled
+// out (mtv_fma, rot_from_unit_quat_fma below).  -DFW_SHAPE_TICK_UNROLL=1 rebuilds the rolled body for an A/B.  The observation's
+// waypoint loop stays rolled: unrolled it gains nothing measurable.
 #ifndef FW_SHAPE_TICK_UNROLL
-#define FW_SHAPE_TICK_UNROLL 1
+#define FW_SHAPE_TICK_UNROLL 2
 #endif
 #ifndef FW_SHAPE_CTX_UNROLL
 #define FW_SHAPE_CTX_UNROLL 1
@@ -129,6 +131,15 @@ struct ShapeTrainWaypoints {
 // fma(z, z, fma(x, x, y*y)), one ulp off in the stored waypoint distance (tests/test_step_shape_gpu.py caught it).  A fixed
 // shape therefore spells the contraction out; the run-time shapes keep the plain expression, and with it the code they had.
 __device__ __forceinline__ double sum_squares_fma(double x, double y, double z) { return __builtin_fma(z, z, __builtin_fma(y, y, x * x)); }
+// The unrolled tick loop (kTickUnroll = 2) needs two more pins of this kind: in its second copy the transposed products in front
+// of the tick (R^T v, R^T w) and the rotation matrix behind it came out with the other product of each sum fused (the copy
+// shares a basic block with its neighbour, and which product of a sum gets fused depends on what else is in the block).  The
+// forms below are the ones the rolled loop of every step kernel has: the first product of R^T v rounded, the other two fused in
+// order; in R(q) the products with w and the second square rounded, the other one fused (rot_from_unit_quat_fma).
+__device__ __forceinline__ void mtv_fma(const double m[9], const double v[3], double o[3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) o[i] = __builtin_fma(m[i + 6], v[2], __builtin_fma(m[i + 3], v[1], m[i] * v[0]));
+}
 
 template <typename T>
 struct DevState {
@@ -701,6 +712,16 @@ __device__ __forceinline__ void rot_from_unit_quat(const T q[4], T m[9]) {
   m[3] = xy + wz;           m[4] = (T)1 - (xx + zz); m[5] = yz - wx;
   m[6] = xz - wy;           m[7] = yz + wx;           m[8] = (T)1 - (xx + yy);
 }
+// ... with the contraction of the rolled tick loop spelled out, for a fixed shape (see mtv_fma at sum_squares_fma)
+template <typename T>
+__device__ __forceinline__ void rot_from_unit_quat_fma(const T q[4], T m[9]) {
+  T x = q[0], y = q[1], z = q[2], w = q[3];
+  T xs = x + x, ys = y + y, zs = z + z;
+  T wx = w * xs, wy = w * ys, wz = w * zs, yy = y * ys, zz = z * zs;
+  m[0] = (T)1 - __builtin_fma(y, ys, zz); m[1] = __builtin_fma(x, ys, -wz);       m[2] = __builtin_fma(x, zs, wy);
+  m[3] = __builtin_fma(x, ys, wz);        m[4] = (T)1 - __builtin_fma(x, xs, zz); m[5] = __builtin_fma(y, zs, -wx);
+  m[6] = __builtin_fma(x, zs, -wy);       m[7] = __builtin_fma(y, zs, wx);        m[8] = (T)1 - __builtin_fma(x, xs, yy);
+}
 // bring an externally supplied quaternion (set_state) onto the unit sphere
 template <typename T>
 __device__ __forceinline__ void normalize_quat(T q[4]) {
@@ -806,8 +827,8 @@ __device__ __forceinline__ bool physics_tick(const Params<T>& P, const TickC<T>&
     tick_actuators<T>(C, S, cmd, noise_z);
   }
   T v_b[3], w_b[3], wind_b[3] = {(T)0, (T)0, (T)0};
-  mtv(R, S.v, v_b);
-  mtv(R, S.w, w_b);
+  if constexpr (SH::kFixed) { mtv_fma(R, S.v, v_b); mtv_fma(R, S.w, w_b); }
+  else { mtv(R, S.v, v_b); mtv(R, S.w, w_b); }
   if (WIND && P.wind_coupling == FW_WIND_COUPLE_AIRSPEED) mtv(R, wind, wind_b);
   T F[3] = {(T)0, (T)0, (T)0}, Tq[3] = {(T)0, (T)0, (T)0};
   if (G == 8) {
@@ -862,7 +883,7 @@ __device__ __forceinline__ bool physics_tick(const Params<T>& P, const TickC<T>&
 #pragma unroll
   for (int k = 0; k < 3; ++k) S.p[k] += S.v[k] * dt;
   quat_integrate<T>(C, S);
-  rot_from_unit_quat<T>(S.q, R);
+  if constexpr (SH::kFixed) rot_from_unit_quat_fma<T>(S.q, R); else rot_from_unit_quat<T>(S.q, R);
   // contacts: third row of R(q_new) dotted with the body-fixed points
   bool contact = false;
   if (G == 8) {                // lane `sub` tests point `sub`; OR over the group

@@ -13,8 +13,20 @@ wrench (v_mov_b32_dpp) -- and prints:
   * the split at the first DPP move of the loop: `surface` is what precedes it (actuator lag, body-frame velocities,
     surface_wrench: lane-parallel), `rigid` the rest (wrench sums, rigid-body update, contact test: replicated in all 8 lanes).
     The scheduler moves a few instructions across that line; the split is a guide, the totals are exact.
+  * `--substep`: the loop that encloses the tick loop (one iteration = one sub-step of the agent step: the ticks of an Aviary
+    step plus the task logic), counted along its common path -- every wave-uniform skip taken that does not skip the ticks, no
+    rare branch of the tick: `outer` (the path outside the tick loop), `tick` (the tick's common path) and `executed` = outer +
+    trips x tick, the instructions a wave issues per sub-step when nothing special happens (`--ticks N`: trips, default 2);
+    `all blocks` counts every block of the loop once, rare branches included (a rolled tick loop's body once, not per trip).
+    A kernel whose tick loop is unrolled has no inner loop: the path through the sub-step loop is then its own total and the
+    outer / tick split is not made.
 
-usage:  python tools/tick_isa_count.py <fwsim ...gfx950.s> [kernel-name substring ...]
+The `moves` class is register copying: v_accvgpr_read / write / mov, and v_mov_b32 / v_mov_b64 without DPP.
+
+A loop is taken for the tick loop only if it holds no memory instruction (the tick has none; the sub-step loop stores the step's
+outputs): with the tick loop unrolled the tick-loop report is left out instead of counting the sub-step loop in its place.
+
+usage:  python tools/tick_isa_count.py [--substep] [--ticks N] [--json] <fwsim ...gfx950.s> [kernel-name substring ...]
         (default substring: fw_step_kernel_g8; `--json` prints the tables as one JSON object)
 """
 import json
@@ -23,7 +35,7 @@ import subprocess
 import sys
 from collections import Counter, OrderedDict
 
-CLASSES = ("fma_f64", "mul_f64", "add_f64", "other_f64", "cndmask", "dpp", "other_valu", "salu", "s_nop", "s_waitcnt",
+CLASSES = ("fma_f64", "mul_f64", "add_f64", "other_f64", "cndmask", "dpp", "moves", "other_valu", "salu", "s_nop", "s_waitcnt",
            "branch", "memory")
 
 
@@ -39,6 +51,8 @@ def classify(op):
         return "cndmask"
     if op.endswith("_dpp") or op.startswith("v_mov_b32_dpp"):
         return "dpp"
+    if op.startswith("v_accvgpr_") or op in ("v_mov_b32", "v_mov_b64"):
+        return "moves"
     if op.startswith("v_") and "f64" in op:
         return "other_f64"
     if op.startswith(("global_", "buffer_", "ds_", "scratch_", "flat_", "s_load", "s_buffer_load")):
@@ -103,9 +117,8 @@ def blocks(fn):
     return out
 
 
-def tick_loop(bl):
-    """The loop (header label) that contains the most DPP moves; ties go to the deeper loop."""
-    # a block of a nested loop belongs to every enclosing loop: walk the header chain
+def loops_of(bl):
+    """{header: [blocks]}: a block of a nested loop belongs to every enclosing loop (walk the header chain)."""
     parent = {}
     for b in bl:
         lab = b[0].replace(".L", "")
@@ -126,14 +139,45 @@ def tick_loop(bl):
             continue
         for h in {b[2]} | ancestors(b[2]):
             loops.setdefault(h, []).append(b)
-    best = None
-    for h, bs in loops.items():
-        ndpp = sum(1 for b in bs for op, _ in b[1] if classify(op) == "dpp")
+    return loops
+
+
+def ndpp(bs):
+    return sum(1 for b in bs for op, _ in b[1] if classify(op) == "dpp")
+
+
+def has_memory(bs):
+    return any(classify(op) == "memory" for b in bs for op, _ in b[1])
+
+
+def dpp_loops(bl):
+    """[(dpp moves, depth, header, blocks)] of the loops that hold DPP moves, the one with most of them (ties: the deeper) first."""
+    out = []
+    for h, bs in loops_of(bl).items():
         depth = next((b[3] for b in bs if b[0].replace(".L", "") == h), 0)
-        key = (ndpp, depth)
-        if ndpp and (best is None or key > best[0]):
-            best = (key, h, bs)
-    return (best[1], best[2]) if best else (None, [])
+        if ndpp(bs):
+            out.append((ndpp(bs), depth, h, bs))
+    return sorted(out, key=lambda x: (-x[0], -x[1]))
+
+
+def tick_loop(bl):
+    """The loop (header label) that contains the most DPP moves; ties go to the deeper loop.  (None, []) where that loop holds
+    memory instructions: it is the sub-step loop then, with the tick loop unrolled into it."""
+    ls = dpp_loops(bl)
+    if not ls or has_memory(ls[0][3]):
+        return None, []
+    return ls[0][2], ls[0][3]
+
+
+def substep_loop(bl):
+    """The loop one iteration of which is a sub-step: the outermost loop that holds all the DPP moves of the tick loop (rolled),
+    or the loop with the most DPP moves itself where it holds memory instructions (tick loop unrolled)."""
+    ls = dpp_loops(bl)
+    if not ls:
+        return None, []
+    top = ls[0][0]
+    best = min((x for x in ls if x[0] == top), key=lambda x: x[1])
+    return best[2], best[3]
 
 
 def paths(bs, header):
@@ -173,6 +217,68 @@ def paths(bs, header):
     return walk(header, frozenset())
 
 
+def common_path(bs, header, longest=False):
+    """Block labels from the header to the back edge along the common path: the shortest path among those that run the most
+    DPP moves (the group sums of the tick: a path that skips the ticks is not the common one).  longest: the longest such path
+    instead, through the rare branches."""
+    labs = [b[0].replace(".L", "") for b in bs]
+    idx = {l: i for i, l in enumerate(labs)}
+    big = 1 + sum(len(b[1]) for b in bs)
+    cost = [(-len(b[1]) if longest else len(b[1])) - big * sum(1 for op, _ in b[1] if classify(op) == "dpp") for b in bs]
+    succ = {}
+    for i, b in enumerate(bs):
+        ops, s = b[1], []
+        last = ops[-1] if ops else ("", "")
+        for op, txt in ops[-2:]:
+            if op.startswith(("s_branch", "s_cbranch")):
+                s.append(txt.split()[-1].replace(".L", ""))
+        if not last[0].startswith("s_branch") and i + 1 < len(bs):
+            s.append(labs[i + 1])
+        succ[labs[i]] = s
+    memo = {}
+    def walk(l, stack):
+        if l in memo:
+            return memo[l]
+        best = None
+        stack = stack | {l}
+        for t in succ[l]:
+            if t not in idx:                            # a loop exit: not the way of a sub-step that is followed by another
+                continue
+            if t == header:
+                r = (0, [])
+            elif t in stack:
+                continue
+            else:
+                r = walk(t, stack)
+            if best is None or r[0] < best[0]:
+                best = r
+        best = best or (0, [])
+        memo[l] = (best[0] + cost[idx[l]], [l] + best[1])
+        return memo[l]
+    return walk(header, frozenset())[1]
+
+
+def substep_report(bl, trips):
+    sh, sbs = substep_loop(bl)
+    if not sbs:
+        return None
+    bmap = {b[0].replace(".L", ""): b for b in sbs}
+    path = common_path(sbs, sh)
+    th, tbs = tick_loop(bl)
+    tl = {b[0].replace(".L", "") for b in tbs}
+    outer = Counter(classify(op) for l in path if l not in tl for op, _ in bmap[l][1])
+    tick = Counter(classify(op) for l in path if l in tl for op, _ in bmap[l][1])
+    rolled = bool(tl) and th != sh
+    if not rolled:
+        tick = Counter()
+    ex = Counter({k: outer.get(k, 0) + (trips if rolled else 0) * tick.get(k, 0) for k in CLASSES})
+    every = Counter(classify(op) for b in sbs for op, _ in b[1])       # all blocks of the loop, each counted once
+    return OrderedDict(header=sh, blocks=len(sbs), path_blocks=len(path), tick_loop=th if rolled else None, trips=trips if rolled else 0,
+                       outer=OrderedDict((k, outer.get(k, 0)) for k in CLASSES), tick=OrderedDict((k, tick.get(k, 0)) for k in CLASSES),
+                       executed=OrderedDict((k, ex.get(k, 0)) for k in CLASSES), all=OrderedDict((k, every.get(k, 0)) for k in CLASSES),
+                       outer_total=sum(outer.values()), tick_total=sum(tick.values()), executed_total=sum(ex.values()))
+
+
 def count(bs):
     ops = [op for b in bs for op, _ in b[1]]
     c = Counter(classify(op) for op in ops)
@@ -180,15 +286,22 @@ def count(bs):
     return ops, c, first
 
 
-def report(path, subs):
+def report(path, subs, substep=False, trips=2):
     text = open(path).read()
     fns = [(n, f) for n, f in functions(text) if any(s in n or s in demangle([n])[n] for s in subs)]
     dm = demangle([n for n, _ in fns])
     res = OrderedDict()
     for name, fn in fns:
         bl = blocks(fn)
+        if substep:
+            r = substep_report(bl, trips)
+            if r:
+                res[dm[name]] = r
+            continue
         header, bs = tick_loop(bl)
         if not bs:
+            if dpp_loops(bl):
+                res[dm[name]] = None          # the tick loop is unrolled into the sub-step loop: see --substep
             continue
         ops, c, first = count(bs)
         lo, hi = paths(bs, header)
@@ -205,21 +318,35 @@ def report(path, subs):
 
 def main(argv):
     as_json = "--json" in argv
-    argv = [a for a in argv if a != "--json"]
+    substep = "--substep" in argv
+    trips = 2
+    if "--ticks" in argv:
+        i = argv.index("--ticks"); trips = int(argv[i + 1]); argv = argv[:i] + argv[i + 2:]
+    argv = [a for a in argv if a not in ("--json", "--substep")]
     if not argv:
         print(__doc__)
         return 2
-    res = report(argv[0], argv[1:] or ["fw_step_kernel_g8"])
+    res = report(argv[0], argv[1:] or ["fw_step_kernel_g8"], substep, trips)
     if as_json:
         print(json.dumps(res, indent=1))
         return 0
     w = max(len(k) for k in CLASSES)
     for name, r in res.items():
-        print(f"{name}\n  tick loop {r['header']} ({r['blocks']} blocks): all {r['all']}, min path {r['min_path']}, "
-              f"max path {r['max_path']}; surface {r['surface']} + rigid {r['rigid']}")
-        print(f"  {'class':<{w}} {'all':>6} {'surface':>8} {'rigid':>6}")
-        for k in CLASSES:
-            print(f"  {k:<{w}} {r['classes'][k]:>6} {r['surface_classes'][k]:>8} {r['rigid_classes'][k]:>6}")
+        if r is None:
+            print(f"{name}\n  tick loop: unrolled into the sub-step loop (no loop of its own; --substep counts the sub-step)")
+        elif substep:
+            how = (f"tick loop {r['tick_loop']} x {r['trips']}" if r["tick_loop"] else "tick loop unrolled")
+            print(f"{name}\n  sub-step loop {r['header']} ({r['blocks']} blocks, {r['path_blocks']} on the common path), {how}: "
+                  f"outer {r['outer_total']}, tick {r['tick_total']}, executed per sub-step {r['executed_total']}")
+            print(f"  {'class':<{w}} {'outer':>6} {'tick':>6} {'executed':>9} {'all blocks':>11}")
+            for k in CLASSES:
+                print(f"  {k:<{w}} {r['outer'][k]:>6} {r['tick'][k]:>6} {r['executed'][k]:>9} {r['all'][k]:>11}")
+        else:
+            print(f"{name}\n  tick loop {r['header']} ({r['blocks']} blocks): all {r['all']}, min path {r['min_path']}, "
+                  f"max path {r['max_path']}; surface {r['surface']} + rigid {r['rigid']}")
+            print(f"  {'class':<{w}} {'all':>6} {'surface':>8} {'rigid':>6}")
+            for k in CLASSES:
+                print(f"  {k:<{w}} {r['classes'][k]:>6} {r['surface_classes'][k]:>8} {r['rigid_classes'][k]:>6}")
     return 0
 
 

@@ -3,13 +3,14 @@
 Builds nothing itself: expects tools/_build/libfwsim_prof.so (bash tools/build_prof.sh: fwsim.hip with -DFW_PROFILE, ISA-checked);
 --phases expects libfwsim_prof_ph.so (bash tools/build_prof.sh phases) and splits the capture steps with 5+ envs due.
 usage: python tools/wave_profile.py <waypoints|waypoints_wind|objlock|combined> [steps]
+       (FWSIM_PROF_LIB=<path>: a profile build of another commit instead, for a before / after)
 """
 import ctypes as C, os, sys, numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import pyflyt_drone_amd as P
 from pyflyt_drone_amd import config as K, _lib
-_lib.LIB_PATH = os.path.join(ROOT, "tools", "_build", "libfwsim_prof.so")
+_lib.LIB_PATH = os.environ.get("FWSIM_PROF_LIB") or os.path.join(ROOT, "tools", "_build", "libfwsim_prof.so")     # FWSIM_PROF_LIB: the profile build of another commit (A/B)
 CFG = {"waypoints": K.train_waypoints_v3_config, "objlock": K.train_objlock_config, "combined": K.train_waypoint_objlock_config,
        "waypoints_wind": lambda: K.train_waypoints_v3_config(wind_config=K.TRAIN_OBJLOCK_WIND)}
 PHASES = "--phases" in sys.argv
