@@ -70,6 +70,13 @@ __global__ void fw_warm_kernel(Params<T>* Pm) {
   for (int k = 0; k < 9; ++k) Pm->warm_R[k] = Rw[k];
 }
 
+// Ki: the step image of a handle (fwsim_device.hpp: StepImage), behind its Params.  One wave; lanes 0-7 write a row each.
+template <typename T>
+__global__ void fw_step_image_kernel(Params<T>* Pm) {
+  if (threadIdx.x >= 8 || blockIdx.x != 0) return;
+  fill_step_image<T>(*Pm, const_cast<StepImage<T>*>(step_image_of<T>(Pm)), (int)threadIdx.x);
+}
+
 // Prefetch that stays where it is written.  What a resetting env copies in the epilogue is only USED inside the divergent reset
 // block, and LLVM sinks a plain load down to its only use: the round trip the prefetch was meant to hide then sits inside that
 // block (tools/wave_profile.py: ~2.3 k cycles in the waves that reset -- the slowest waves of nearly every launch -- whatever was
@@ -339,15 +346,20 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   // halves of every line are fetched by two different L2s (PMC: 2x the algorithmic read traffic).  Give each XCD a
   // contiguous range of env blocks instead.  (Speed only: nothing depends on where a block really lands.)
   const int bx = (int)blockIdx.x - (COLLECT ? CAp->n_act : 0);       // my index among the step (+ worker) workgroups
-  const int wg = bx % nblk;
+  // (a fixed shape: the grid of a kernel without act waves is nblk or 2 * nblk workgroups -- step_T -- so the remainder is a subtraction,
+  // not the 30-instruction division emulation both waves ran at entry)
+  const int wg = SH::kFixed ? (bx >= nblk ? bx - nblk : bx) : bx % nblk;
   const int blk = (G == 8 && (nblk & 7) == 0) ? (wg & 7) * (nblk >> 3) + (wg >> 3) : wg;
   const DevState<T> D = tile_view<T, EPW>(Dg, blk);  // this wave's tile: row stride EPW (a compile-time constant), global env ids
   if ((GENERAL || DEFER) && bx >= nblk) {
     if (AUX && threadIdx.x >= kWave) return;         // (a worker workgroup's second wave has nothing to do)
-    if (GENERAL) shadow_worker<T, G, TKIND>(Pp, OCp, D, blk); else scenario_worker<T, G>(Pp, D, blk);
+    DevState<T> Dw = D;
+    if constexpr (SH::kFixed) Dw.epoch = launch_index(Dg.lctr);     // a fixed shape numbers its launches in here (see `lctr_v` below): a worker reads its counter at once
+    if (GENERAL) shadow_worker<T, G, TKIND>(Pp, OCp, Dw, blk); else scenario_worker<T, G>(Pp, Dw, blk);
     FWP(if (D.prof && threadIdx.x == 0) {
-      long long* w = D.prof + ((size_t)(D.epoch % kProfSlots) * 2 * nblk + blockIdx.x) * kProfWords;
+      long long* w = D.prof + ((size_t)(Dw.epoch % kProfSlots) * 2 * nblk + blockIdx.x) * kProfWords;
       w[0] = FWP_NOW() - p_t0; })
+    if constexpr (SH::kFixed) launch_done(Dg.lctr, Dw.epoch);
     return;
   }
   const int lane = AUX ? (int)(threadIdx.x & (kWave - 1)) : (int)threadIdx.x;
@@ -402,11 +414,20 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   T ep_return = D.r[RF_EP_RETURN * n + envc];
   // tick constants + this lane's lifting surface (G = 8: resident in VGPRs for the whole launch)
   TickC<T> C; SurfC<T> mine_regs; T wmask;
-  load_tick_constants<T, G, DEFER && G == 8 && WPE == 1>(Pp, C, mine_regs, wmask);
+  // A fixed shape: this lane's row of the handle's step image and the clamp constants of quat_integrate (fwsim_device.hpp: StepImage),
+  // instead of 37 loads of mixed width from three places in Params and what was rebuilt behind them.
+  if constexpr (SH::kFixed) load_step_image<T>(Pp, C, mine_regs, wmask);
+  else load_tick_constants<T, G, DEFER && G == 8 && WPE == 1>(Pp, C, mine_regs, wmask);
+  // A fixed shape: the launch counter, by a vector load BEHIND the state and constant loads (they retire in order: nothing waits for it
+  // that would not wait anyway) instead of a scalar load in front of the worker / step split, which every scalar wait of the prologue
+  // paid for.  This wave first needs the launch index in the epilogue (`launch` below); it is pinned in front of the barrier so that
+  // the load is not sunk to its use.  Same word, same arithmetic as launch_index: the numbering is what it was.
+  uint32_t lctr_v = 0;
+  if constexpr (SH::kFixed) lctr_v = vload(Dg.lctr + blockIdx.x + opaque_zero());
   // (Tried for WPE = 2: this lane's surface constants in LDS, read field by field through a volatile reference -- 54 registers
   // fewer to hold, but the allocator spilled as much elsewhere and the ds_reads sit on the tick's critical path: 40.6 -> 50.9 us
   // at 16 384 envs.  surface_wrench / physics_tick keep the template parameter that made the experiment a four-line change.)
-  if (AX && sub >= FW_NUM_SURFACES) mine_regs.hra = (T)0;    // AX: lanes 5-7 evaluate a zero wrench, no mask (surface_wrench_ax)
+  if (AX && !SH::kFixed && sub >= FW_NUM_SURFACES) mine_regs.hra = (T)0;    // AX: lanes 5-7 evaluate a zero wrench, no mask (surface_wrench_ax; the step image holds the zero already)
   SurfC<T>& mine = mine_regs;
 
   normalize_quat<T>(S.q);
@@ -516,6 +537,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
     k_max_steps = P.max_steps; k_auto_reset = P.auto_reset; k_dome = P.dome; k_reach = P.reach;
     asm("" : "+s"(k_max_steps)); asm("" : "+s"(k_auto_reset)); asm("" : "+s"(k_dome)); asm("" : "+s"(k_reach));
   }
+  if constexpr (SH::kFixed) asm volatile("" : "+v"(lctr_v));       // the counter load stays in the prologue (see above)
   if constexpr (AUX) {                               // barrier 1: every lane of both waves, whatever its env does
     __syncthreads();
     nz0 = aux_nz[2 * lane]; nz1 = aux_nz[2 * lane + 1];
@@ -854,8 +876,12 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   // DEFER: the waypoint a worker block sampled ahead of time for my next episode, requested only by resetting envs and only
   // now -- its latency hides behind the observation pass below
   T tpre[3] = {(T)0, (T)0, (T)0};
+  // The launch index: D.epoch as the kernel set it at entry, or (a fixed shape) from the counter word fetched in the prologue: every lane
+  // loaded the same word, so any lane's copy serves.  The step wave gets here with all its lanes and on every path: it has no early return,
+  // and must not get one -- launch_done at the end of this function is what advances the workgroup's counter.
+  const uint32_t launch = SH::kFixed ? 1u + (uint32_t)__builtin_amdgcn_readfirstlane((int)lctr_v) : D.epoch;
   const bool pre = DEFER && resetting && D.shadow_on && (int)(sh_done & 0xFF) == 1 && (uint32_t)(sh_done >> 32) == (uint32_t)(episode + 1) &&
-                   (uint32_t)((sh_done >> 8) & 0xFFFFFFu) != (D.epoch & 0xFFFFFFu);
+                   (uint32_t)((sh_done >> 8) & 0xFFFFFFu) != (launch & 0xFFFFFFu);
   if (pre) {      // (every lane issues: rows >= num_targets of the shadow are zero and are not stored back)
 #pragma unroll
     for (int k = 0; k < 3; ++k) pf_issue(tpre[k], &D.rs[(size_t)(RF_TARGETS + 3 * sub + k) * n + env]);
@@ -906,7 +932,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   }
   const int ep_want = episode + 1 + ((GENERAL && resetting) ? 1 : 0);     // a reset taken below asks for the episode after next
   if ((GENERAL || DEFER) && D.shadow_on && active && leader && (uint32_t)(sh_req >> 32) != (uint32_t)ep_want)
-    D.sreq[env] = ((unsigned long long)(uint32_t)ep_want << 32) | (unsigned long long)D.epoch;   // ask for the next episode
+    D.sreq[env] = ((unsigned long long)(uint32_t)ep_want << 32) | (unsigned long long)launch;   // ask for the next episode
   T act_obs[4] = {(T)0, (T)0, (T)0, (T)0};
   if (LANE_T) {
     // every lane runs the pass (same issue cost as one lane), the leader stores; action and waypoints come by shuffle
@@ -1095,7 +1121,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
       p_r3 = max(p_r3, (long long)__shfl_xor((long long)p_r3, o, kWave));
     }
     if (lane == 0) {
-      long long* w = D.prof + ((size_t)(D.epoch % kProfSlots) * 2 * nblk + blockIdx.x) * kProfWords;
+      long long* w = D.prof + ((size_t)(launch % kProfSlots) * 2 * nblk + blockIdx.x) * kProfWords;
       const long long t3 = FWP_NOW();
       w[0] = t3 - p_t0; w[1] = p_t1 - p_t0; w[2] = p_reset; w[3] = p_avi; w[4] = p_task; w[5] = t3 - p_t2; w[6] = it | (nr << 8) | (nh << 16); w[7] = p_t0; w[8] = p_r1; w[9] = p_r2; w[10] = p_r3;
       w[11] = p_capmax | ((long long)p_ncapw << 48);
@@ -1103,6 +1129,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
       else if (HASOBJ) { w[8] = O.p_capm[0]; w[9] = O.p_capm[1]; w[10] = O.p_capm[2]; w[7] = O.p_capm[3];
         if (getenv_ph) { w[1] = O.p_ph[0]; w[3] = O.p_ph[1]; w[4] = O.p_ph[2]; w[5] = O.p_ph[3]; w[9] = O.p_ph[4]; w[6] = O.p_ph[5]; } }     // (the reset split is unused by these kernels)
     } })
+  if constexpr (SH::kFixed) launch_done(Dg.lctr, launch);         // (the kernel does not go through FW_STEP_RUN)
 }
 
 #ifndef FW_G1_WAVES
@@ -1123,7 +1150,10 @@ template <typename T>
 __global__ __launch_bounds__(2 * kWave) void fw_step_kernel_g8x(FW_STEP_ARGS) { FW_STEP_RUN(T, false, 8, FW_TASK_WAYPOINTS, 1, false, false, true, true); }
 // ... and that kernel compiled for the shape of the headline training config (step_body SH; fw_env::step_shape)
 template <typename T>
-__global__ __launch_bounds__(2 * kWave) void fw_step_kernel_g8xs(FW_STEP_ARGS) { FW_STEP_RUN(T, false, 8, FW_TASK_WAYPOINTS, 1, false, false, true, true, ShapeTrainWaypoints); }
+__global__ __launch_bounds__(2 * kWave) void fw_step_kernel_g8xs(FW_STEP_ARGS) {
+  // (not FW_STEP_RUN: step_body reads and advances the launch counter itself where the shape is fixed, off the path to the state loads)
+  step_body<T, false, 8, FW_TASK_WAYPOINTS, 1, false, false, true, true, ShapeTrainWaypoints>(FW_STEP_PASS);
+}
 // ... and the same mapping capped at 256 registers: two waves per SIMD (8 192 < N <= 65 536 envs)
 template <typename T, bool GENERAL>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2, 2)))
@@ -2010,7 +2040,7 @@ template <typename T>
 int upload_params(fw_env* h) {
   Params<T> P;
   if (!build_params<T>(h->cfg, h->seed, h->env_offset, P, h->err)) return FW_EINVAL;
-  if (!h->params_dev) HIP_TRY(h, hipMalloc(&h->params_dev, sizeof(Params<T>)));
+  if (!h->params_dev) HIP_TRY(h, hipMalloc(&h->params_dev, step_image_offset<T>() + sizeof(StepImage<T>)));     // Params, then the step image
   HIP_TRY(h, hipMemcpy(h->params_dev, &P, sizeof P, hipMemcpyHostToDevice));
   ObjC<T> OC;
   build_objc<T>(h->cfg, OC);
@@ -2018,6 +2048,14 @@ int upload_params(fw_env* h) {
   HIP_TRY(h, hipMemcpy(h->objc_dev, &OC, sizeof OC, hipMemcpyHostToDevice));
   if (P.warm_valid) {
     hipLaunchKernelGGL(fw_warm_kernel<T>, dim3(1), dim3(kWave), 0, 0, (Params<T>*)h->params_dev);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipDeviceSynchronize());
+  }
+  // The step image follows Params: it is refilled wherever Params is written, and this function is the only place (fw_create and
+  // fw_seed; fw_set_state, fw_reset and the command paths write state rows, never Params).  Read by the fixed-shape step kernel alone,
+  // which exists in f64 only.
+  if constexpr (std::is_same<T, double>::value) {
+    hipLaunchKernelGGL(fw_step_image_kernel<T>, dim3(1), dim3(kWave), 0, 0, (Params<T>*)h->params_dev);
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipDeviceSynchronize());
   }

@@ -668,7 +668,53 @@ struct TickC {
   T wind_force_coef;
   T cpt[3];                  // G = 8: this lane's collision point
   T cvalid;                  // 1 if this lane's collision point exists
+  T k_clamp, ch_clamp;       // a fixed shape: quat_integrate's clamp constants (StepImage below); nobody else writes or reads them
 };
+
+// ------------------------------------------------------------------------
+// A fixed shape: what the prologue of every launch would derive from Params alone, computed ONCE per handle on the device
+// (fw_step_image_kernel in fwsim.hip, launched wherever Params is uploaded: fw_create and fw_seed -- upload_params is the only
+// host path that writes Params; fw_set_state and the command paths write state rows alone).  The block sits directly behind the
+// handle's Params in the same allocation (step_image_of), so no kernel's argument list changes.
+//   * clamp constants of quat_integrate: ang = lim / dt, sin(ang dt / 2) / ang and cos(ang dt / 2), by the very functions and
+//     operands of the tick (M<T>::div_, M<T>::sincos_), hence the very bits -- host libm would not give them.  Left in the tick,
+//     the compiler hoists them out of the rare branch into the prologue of every launch: two reciprocals with their Newton
+//     steps, two corrected divisions and the whole Cody-Waite sincos, 126 instructions of the step wave.
+//   * row `sub`: everything lane `sub` of an env's group keeps in registers across the launch, in the order it is loaded --
+//     surface min(sub, 4) with hra = 0 from sub = 5 on (surface_wrench_ax), the TickC fields the axis-aligned tick reads (the
+//     diagonals of I / Iinv alone), collision point `sub` and whether it exists.  Nothing to rebuild behind the loads.
+//     The rows are stored interleaved, two words at a time: words 2j, 2j + 1 of row `sub` sit at lane_words[j][sub], so the 16-byte
+//     load j of a wave's 64 lanes (8 groups reading the same 8 rows) touches ONE 128-byte line.
+//     (Tried: the rows stored one after the other, [8][K], each lane reading consecutive 16 bytes from its row's base.  Every load
+//     of the wave then touches 8 lines 368 bytes apart: + 0.65 us per step against the gathering from Params it replaced, the slowest
+//     wave's prologue 4.9 k -> 5.9 k cycles, with 126 instructions FEWER in front of the barrier.  Interleaved: - 0.1 us.)
+//     (Tried: the mixer and the four run-time numbers of the task logic in the image as well, as wave-uniform vector loads handed to
+//     the scalar file: + 0.13 us.  They stay scalar loads of Params.  The clamp constants alone, without the rows: no gain measured,
+//     the arithmetic ran behind the state loads' latency; they are here because the rows' load brings them for two more words.)
+// ------------------------------------------------------------------------
+template <typename T>
+struct LaneImage {
+  SurfC<T> s;
+  T motor_dt_tau, noise_ratio;
+  T mF[3], mT[3];
+  T inv_mass, gravity, dt, hdt;
+  T Id[3], Iinvd[3];         // diagonals
+  T cpt[3];
+  T cvalid;
+};
+template <typename T>
+struct StepImage {
+  T ang_clamp, k_clamp, ch_clamp;
+  T pad_[13];                // (the rows start on a 128-byte line)
+  static constexpr int kLaneWords = (int)(sizeof(LaneImage<T>) / sizeof(T));
+  T lane_words[kLaneWords / 2][8][2];
+};
+static_assert(StepImage<double>::kLaneWords % 2 == 0 && offsetof(StepImage<double>, lane_words) % 128 == 0, "a 16-byte load of the rows touches one 128-byte line");
+// the image behind a handle's Params, on a 128-byte line of its own (hipMalloc aligns the block)
+template <typename T> __host__ __device__ inline size_t step_image_offset() { return (sizeof(Params<T>) + 127) & ~(size_t)127; }
+template <typename T> __device__ __forceinline__ const StepImage<T>* step_image_of(const Params<T>* Pp) {
+  return reinterpret_cast<const StepImage<T>*>(reinterpret_cast<const unsigned char*>(Pp) + step_image_offset<T>());
+}
 
 __device__ __forceinline__ int opaque_zero() {
   int z;
@@ -770,7 +816,9 @@ __device__ __forceinline__ void tick_actuators(const TickC<T>& C, Rigid<T>& S, c
 // sin(th)/th and cos(th), th = |w| dt / 2 <= pi/8, are even polynomials in th^2, so no
 // sqrt / sincos / division sits on the critical path; the angular-motion clamp
 // (|w| dt > pi/4, i.e. > 188 rad/s) takes the literal formula on a rare branch.
-template <typename T>
+// PRE (a fixed shape): the clamp's constants come from the handle's step image (C.k_clamp, C.ch_clamp) instead of being
+// derived here; the branch selects them under the same condition.
+template <typename T, bool PRE = false>
 __device__ __forceinline__ void quat_integrate(const TickC<T>& C, Rigid<T>& S) {
   const T dt = C.dt, hdt = C.hdt;
   T w2 = S.w[0] * S.w[0] + S.w[1] * S.w[1] + S.w[2] * S.w[2];
@@ -785,10 +833,13 @@ __device__ __forceinline__ void quat_integrate(const TickC<T>& C, Rigid<T>& S) {
   T k = sinc * hdt;                              // sin(th)/|w|
   const T lim = (T)(0.25 * kPi);
   if (w2 * dt * dt > lim * lim) {                // ANGULAR_MOTION_THRESHOLD clamp (rare)
-    T ang = M<T>::div_(lim, dt);
-    T sh;
-    M<T>::sincos_((T)0.5 * ang * dt, &sh, &ch);
-    k = M<T>::div_(sh, ang);
+    if constexpr (PRE) { ch = C.ch_clamp; k = C.k_clamp; }
+    else {
+      T ang = M<T>::div_(lim, dt);
+      T sh;
+      M<T>::sincos_((T)0.5 * ang * dt, &sh, &ch);
+      k = M<T>::div_(sh, ang);
+    }
   }
   T ax = S.w[0] * k, ay = S.w[1] * k, az = S.w[2] * k;
   T qx = S.q[0], qy = S.q[1], qz = S.q[2], qw = S.q[3];
@@ -804,6 +855,56 @@ __device__ __forceinline__ void quat_integrate(const TickC<T>& C, Rigid<T>& S) {
   S.q[0] = nx * inv; S.q[1] = ny * inv; S.q[2] = nz * inv; S.q[3] = nw * inv;
 }
 
+// The step image of a handle (StepImage above), written by lanes 0-7 of one wave: lane `sub` writes row `sub`, lane 0 the clamp
+// constants -- the statements of quat_integrate's clamp branch on the operands it has there (dt as load_tick_constants hands it on).
+template <typename T>
+__device__ __forceinline__ void fill_step_image(const Params<T>& P, StepImage<T>* img, int sub) {
+  if (sub == 0) {
+    const T dt = P.dt;
+    const T lim = (T)(0.25 * kPi);
+    T ang = M<T>::div_(lim, dt);
+    T sh, ch;
+    M<T>::sincos_((T)0.5 * ang * dt, &sh, &ch);
+    img->ang_clamp = ang; img->k_clamp = M<T>::div_(sh, ang); img->ch_clamp = ch;
+  }
+  LaneImage<T> L;
+  L.s = P.s[min(sub, FW_NUM_SURFACES - 1)];
+  if (sub >= FW_NUM_SURFACES) L.s.hra = (T)0;
+  L.motor_dt_tau = P.motor_dt_tau; L.noise_ratio = P.noise_ratio;
+  for (int k = 0; k < 3; ++k) {
+    L.mF[k] = P.m_force[k]; L.mT[k] = P.m_wrench_t[k];
+    L.Id[k] = P.I[4 * k]; L.Iinvd[k] = P.Iinv[4 * k];
+    L.cpt[k] = P.coll[sub][k];
+  }
+  L.inv_mass = P.inv_mass; L.gravity = P.gravity; L.dt = P.dt; L.hdt = (T)0.5 * P.dt;
+  L.cvalid = (sub < P.n_coll) ? (T)1 : (T)0;
+  T w[StepImage<T>::kLaneWords];
+  __builtin_memcpy(w, &L, sizeof L);
+  for (int j = 0; j < StepImage<T>::kLaneWords; ++j) img->lane_words[j / 2][sub][j % 2] = w[j];
+}
+// load_tick_constants of a fixed shape (8 lanes per env, axis-aligned tick): this lane's row of the image through a per-lane
+// address, i.e. vector loads of 16 bytes each from one base, 128 bytes apart.  The off-diagonal words of I / Iinv, dt_tau[] (the lane's own is in
+// `mine`) and wind_force_coef are not read by that tick and stay unset.
+template <typename T>
+__device__ __forceinline__ void load_step_image(const Params<T>* Pp, TickC<T>& C, SurfC<T>& mine, T& wmask) {
+  const int sub = (int)(threadIdx.x & 7);
+  const StepImage<T>* img = step_image_of<T>(Pp) + opaque_zero();
+  typedef T pair_t __attribute__((ext_vector_type(2)));
+  const pair_t* row = reinterpret_cast<const pair_t*>(&img->lane_words[0][sub][0]);
+  T w[StepImage<T>::kLaneWords];
+#pragma unroll
+  for (int j = 0; j < StepImage<T>::kLaneWords / 2; ++j) { const pair_t x = row[8 * j]; w[2 * j] = x.x; w[2 * j + 1] = x.y; }
+  LaneImage<T> L;
+  __builtin_memcpy(&L, w, sizeof L);
+  mine = L.s;
+  C.motor_dt_tau = L.motor_dt_tau; C.noise_ratio = L.noise_ratio;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { C.mF[k] = L.mF[k]; C.mT[k] = L.mT[k]; C.I[4 * k] = L.Id[k]; C.Iinv[4 * k] = L.Iinvd[k]; C.cpt[k] = L.cpt[k]; }
+  C.inv_mass = L.inv_mass; C.gravity = L.gravity; C.dt = L.dt; C.hdt = L.hdt;
+  C.cvalid = L.cvalid;
+  C.k_clamp = img->k_clamp; C.ch_clamp = img->ch_clamp;
+  wmask = (sub < FW_NUM_SURFACES) ? (T)1 : (T)0;
+}
 // Full tick.  R = R(S.q) on entry and on exit (carried across ticks: it is needed for the
 // contact test of this tick and the body-frame velocities of the next one).
 // G = 1: rolled loop over the 5 surfaces (constants by scalar loads at a wave-uniform index
@@ -882,7 +983,7 @@ __device__ __forceinline__ bool physics_tick(const Params<T>& P, const TickC<T>&
   for (int k = 0; k < 3; ++k) { S.v[k] += acc[k] * dt; S.w[k] += al_w[k] * dt; }
 #pragma unroll
   for (int k = 0; k < 3; ++k) S.p[k] += S.v[k] * dt;
-  quat_integrate<T>(C, S);
+  quat_integrate<T, SH::kFixed>(C, S);
   if constexpr (SH::kFixed) rot_from_unit_quat_fma<T>(S.q, R); else rot_from_unit_quat<T>(S.q, R);
   // contacts: third row of R(q_new) dotted with the body-fixed points
   bool contact = false;

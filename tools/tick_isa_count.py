@@ -26,7 +26,13 @@ The `moves` class is register copying: v_accvgpr_read / write / mov, and v_mov_b
 A loop is taken for the tick loop only if it holds no memory instruction (the tick has none; the sub-step loop stores the step's
 outputs): with the tick loop unrolled the tick-loop report is left out instead of counting the sub-step loop in its place.
 
-usage:  python tools/tick_isa_count.py [--substep] [--ticks N] [--json] <fwsim ...gfx950.s> [kernel-name substring ...]
+  * `--prologue`: kernel entry to the s_barrier in front of the sub-step loop, for the step wave and for the second wave of a
+    two-wave step kernel (the wave that issues more vector loads on its way is the step wave): instructions by opcode class along
+    the shortest path (every skip of a rare branch taken), the longest path's total, and how many s_waitcnt on lgkmcnt / vmcnt
+    stand in front of the path's first vector load -- the serial round trips a launch pays before its state is even requested.
+    (A one-wave kernel meets its only barrier at the very end: the report then spans the kernel and says nothing about a prologue.)
+
+usage:  python tools/tick_isa_count.py [--substep | --prologue] [--ticks N] [--json] <fwsim ...gfx950.s> [kernel-name substring ...]
         (default substring: fw_step_kernel_g8; `--json` prints the tables as one JSON object)
 """
 import json
@@ -279,6 +285,95 @@ def substep_report(bl, trips):
                        outer_total=sum(outer.values()), tick_total=sum(tick.values()), executed_total=sum(ex.values()))
 
 
+def is_vector_load(op):
+    """A load through the vector memory path (what brings the state and the launch constants in): a class, not one opcode."""
+    return classify(op) == "memory" and op.startswith(("global_load", "buffer_load", "flat_load", "scratch_load"))
+
+
+def successors(bl):
+    """{label: [successor labels]} of a function's blocks in layout order (branch targets of the last two instructions, and the
+    fall-through unless the block ends in an unconditional branch or the program's end)."""
+    labs = [b[0].replace(".L", "") for b in bl]
+    succ = {}
+    for i, b in enumerate(bl):
+        ops, s = b[1], []
+        last = ops[-1] if ops else ("", "")
+        for op, txt in ops[-2:]:
+            if op.startswith(("s_branch", "s_cbranch")):
+                s.append(txt.split()[-1].replace(".L", ""))
+        if not last[0].startswith(("s_branch", "s_endpgm", "s_setpc")) and i + 1 < len(bl):
+            s.append(labs[i + 1])
+        succ[labs[i]] = s
+    return labs, succ
+
+
+def prologue_report(bl):
+    """Kernel entry -> s_barrier, for every barrier of the function that can be reached without passing another one: a two-wave
+    step kernel has two, the second wave's (it draws the noise, meets the barrier and ends) and the step wave's in front of the
+    sub-step loop; the step wave is the one that issues more vector loads on its way (the state).  Counted along the shortest
+    path (every wave-uniform skip of a rare branch taken: the common launch) by opcode class, with the longest path's total
+    beside it, and the number of s_waitcnt on lgkmcnt / vmcnt in front of the first vector load of the path."""
+    if not bl:
+        return None
+    labs, succ = successors(bl)
+    idx = {l: i for i, l in enumerate(labs)}
+
+    def upto_barrier(b):
+        ops = b[1]
+        k = next((j for j, (op, _) in enumerate(ops) if op == "s_barrier"), None)
+        return (ops, False) if k is None else (ops[:k + 1], True)
+
+    memo = {}
+
+    def walk(l, stack):
+        """{barrier block: (min count, min path, max count)} reachable from l without crossing another barrier"""
+        if l in memo:
+            return memo[l]
+        ops, hit = upto_barrier(bl[idx[l]])
+        if hit:
+            memo[l] = {l: (len(ops), [l], len(ops))}
+            return memo[l]
+        out = {}
+        stack = stack | {l}
+        for t in succ[l]:
+            if t not in idx or t in stack:
+                continue
+            for tgt, (lo, path, hi) in walk(t, stack).items():
+                cand = (lo + len(ops), [l] + path, hi + len(ops))
+                if tgt not in out:
+                    out[tgt] = cand
+                else:
+                    cur = out[tgt]
+                    best = cand if cand[0] < cur[0] else cur
+                    out[tgt] = (best[0], best[1], max(cur[2], cand[2]))
+        memo[l] = out
+        return out
+
+    sys.setrecursionlimit(max(sys.getrecursionlimit(), 4 * len(bl) + 100))
+    found = walk(labs[0], frozenset())
+    waves = []
+    for tgt, (lo, path, hi) in found.items():
+        ops = [op for l in path for op, _ in upto_barrier(bl[idx[l]])[0]]
+        txt = [t for l in path for _, t in upto_barrier(bl[idx[l]])[0]]
+        c = Counter(classify(op) for op in ops)
+        first = next((k for k, op in enumerate(ops) if is_vector_load(op)), len(ops))
+        waits = [t for op, t in zip(ops[:first], txt[:first]) if op == "s_waitcnt"]
+        waves.append(OrderedDict(
+            barrier_block=tgt, path_blocks=len(path), total=lo, max_path=hi,
+            vector_loads=sum(1 for op in ops if is_vector_load(op)),
+            classes=OrderedDict((k, c.get(k, 0)) for k in CLASSES),
+            before_first_vector_load=first,
+            waits_lgkmcnt_before_first_vector_load=sum(1 for t in waits if "lgkmcnt" in t),
+            waits_vmcnt_before_first_vector_load=sum(1 for t in waits if "vmcnt" in t)))
+    if not waves:
+        return None
+    waves.sort(key=lambda w: -w["vector_loads"])
+    out = OrderedDict(step_wave=waves[0])
+    if len(waves) > 1:
+        out["second_wave"] = waves[1]
+    return out
+
+
 def count(bs):
     ops = [op for b in bs for op, _ in b[1]]
     c = Counter(classify(op) for op in ops)
@@ -286,13 +381,18 @@ def count(bs):
     return ops, c, first
 
 
-def report(path, subs, substep=False, trips=2):
+def report(path, subs, substep=False, trips=2, prologue=False):
     text = open(path).read()
     fns = [(n, f) for n, f in functions(text) if any(s in n or s in demangle([n])[n] for s in subs)]
     dm = demangle([n for n, _ in fns])
     res = OrderedDict()
     for name, fn in fns:
         bl = blocks(fn)
+        if prologue:
+            r = prologue_report(bl)
+            if r:
+                res[dm[name]] = r
+            continue
         if substep:
             r = substep_report(bl, trips)
             if r:
@@ -319,20 +419,31 @@ def report(path, subs, substep=False, trips=2):
 def main(argv):
     as_json = "--json" in argv
     substep = "--substep" in argv
+    prologue = "--prologue" in argv
     trips = 2
     if "--ticks" in argv:
         i = argv.index("--ticks"); trips = int(argv[i + 1]); argv = argv[:i] + argv[i + 2:]
-    argv = [a for a in argv if a not in ("--json", "--substep")]
+    argv = [a for a in argv if a not in ("--json", "--substep", "--prologue")]
     if not argv:
         print(__doc__)
         return 2
-    res = report(argv[0], argv[1:] or ["fw_step_kernel_g8"], substep, trips)
+    res = report(argv[0], argv[1:] or ["fw_step_kernel_g8"], substep, trips, prologue)
     if as_json:
         print(json.dumps(res, indent=1))
         return 0
     w = max(len(k) for k in CLASSES)
     for name, r in res.items():
-        if r is None:
+        if prologue:
+            print(name)
+            for wave, q in r.items():
+                print(f"  {wave.replace('_', ' ')}: entry -> s_barrier in {q['barrier_block']} ({q['path_blocks']} blocks on the shortest path): "
+                      f"{q['total']} instructions (longest path {q['max_path']}), {q['vector_loads']} vector loads; in front of the first one: "
+                      f"{q['before_first_vector_load']} instructions, {q['waits_lgkmcnt_before_first_vector_load']} s_waitcnt on lgkmcnt, "
+                      f"{q['waits_vmcnt_before_first_vector_load']} on vmcnt")
+            print(f"  {'class':<{w}} " + " ".join(f"{wave:>12}" for wave in r))
+            for k in CLASSES:
+                print(f"  {k:<{w}} " + " ".join(f"{q['classes'][k]:>12}" for q in r.values()))
+        elif r is None:
             print(f"{name}\n  tick loop: unrolled into the sub-step loop (no loop of its own; --substep counts the sub-step)")
         elif substep:
             how = (f"tick loop {r['tick_loop']} x {r['trips']}" if r["tick_loop"] else "tick loop unrolled")
