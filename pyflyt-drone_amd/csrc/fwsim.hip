@@ -544,6 +544,78 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   }
 
   FWP(const long long p_t1 = FWP_NOW();)
+  if constexpr (SH::kFixed) {
+    // A fixed shape: the agent step is a counted loop.  This kernel has no in-loop reset, no warm-up phase and no camera, and its
+    // step_ratio is a constant, so the phase machine below reduces to one per-lane bit: `stepping`, cleared where that machine sets
+    // step_over.  Noise shuffle, Aviary step and task logic of a sub-step are those of the general loop, in its order.  The
+    // end-of-step latch -- which that loop tests for at the head of every iteration -- runs once, behind the loop, for every active
+    // lane: a lane that has finished reads nothing of what the latch writes (step_count is compared with max_steps by stepping
+    // lanes only, and they have not latched).  A wave whose envs are all done -- at entry or early -- leaves at the ballot.
+    // The loop stays rolled: unrolled twice it measured the same, unrolled four times slower (CHANGELOG).
+    bool stepping = active && !done_at_entry;
+#pragma unroll 1
+    for (it = 0; it < SH::step_ratio; ++it) {
+      FWP(const long long p_b = FWP_NOW();)
+      if (__ballot(stepping) == 0ull) break;         // wave-uniform exit
+      // noise of this iteration's Aviary step (all stepping envs of the wave are at sub-step `it`)
+      const int src = (lane & ~(G - 1)) | (it & (G - 1));
+      const T z0 = __shfl(nz0, src, kWave), z1 = __shfl(nz1, src, kWave);
+      bool contact = false;
+      if (stepping) contact = aviary_step<T, false, G, false, AX, SH>(P, C, OC, D, env, O, S, R, cmd, tick, z0, z1, wb, wa, gust, mine, wmask, LA);    // :339
+      FWP(const long long p_c = FWP_NOW(); p_avi += p_c - p_b;)
+      if (stepping) {
+        // compute_state(): WaypointHandler.distance_to_targets side effects
+        const int nleft = SH::num_targets - num_reached;
+        const T old_dist = new_dist;
+        if (nleft > 0) {
+          T dx = tcur[0] - S.p[0], dy = tcur[1] - S.p[1], dz = tcur[2] - S.p[2];
+          new_dist = M<T>::sqrt_(sum_squares_fma(dx, dy, dz));
+        }
+        tgt_obs = num_reached;
+        // compute_base_term_trunc_reward(): :296-312
+        if (step_count > k_max_steps) flags |= FL_TRUNC;
+        if (contact) { rew = (T)-100; flags |= FL_COLLISION | FL_TERM; }
+        if (sum_squares_fma(S.p[0], S.p[1], S.p[2]) > k_dome * k_dome) { rew = (T)-100; flags |= FL_OOB | FL_TERM; }
+        // waypoint reward (upstream FixedwingWaypointsEnv)
+        if (nleft > 0) {
+          if (!SH::sparse) {
+            T progress = (old_dist != (T)0) ? (old_dist - new_dist) : (T)0;
+            rew += M<T>::fmax_((T)3 * progress, (T)0);
+            rew += M<T>::rcp_(new_dist);
+          }
+          if (new_dist < k_reach) {
+            rew = (T)100;
+            num_reached += 1;
+            if (num_reached == SH::num_targets) flags |= FL_TRUNC | FL_COMPLETE;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) tcur[k] = __shfl(tmine[k], gbase | (num_reached & (G - 1)), kWave);   // advance_targets(): the next waypoint's lane hands it over
+          }
+        }
+        if (flags & (FL_TERM | FL_TRUNC)) stepping = false;     // :334-337 (the last sub-step ends with the loop)
+        FWP(p_task += FWP_NOW() - p_c;)
+      }
+    }
+    // ---- end of env.step(): :346, outputs, SB3 worker auto-reset ---- once, for every env of the wave: in front of the epilogue's
+    // loads as the latch always was, with the outputs leaving for memory here (see STASH)
+    FWP(const long long p_a = FWP_NOW();)
+    if (active) {
+      step_count += 1;
+      ep_return += rew;
+      if (leader) {
+        reward[env] = rew;
+        terminated[env] = (uint8_t)((flags & FL_TERM) ? 1 : 0);
+        truncated[env] = (uint8_t)((flags & FL_TRUNC) ? 1 : 0);
+        if (info) {
+          int4* ip = reinterpret_cast<int4*>(info + (size_t)env * FW_INFO_DIM);
+          ip[0] = make_int4(num_reached, (flags & FL_COLLISION) ? 1 : 0, (flags & FL_OOB) ? 1 : 0, (flags & FL_COMPLETE) ? 1 : 0);
+          ip[1] = make_int4(out_strike, 0, step_count, 0);
+        }
+      }
+      resetting = (flags & (FL_TERM | FL_TRUNC)) && k_auto_reset;
+      FWP(if (resetting) p_nreset += 1;)
+    }
+    FWP(p_reset += FWP_NOW() - p_a;)
+  } else {
 #pragma unroll 1
   for (;;) {
     FWP(const long long p_a = FWP_NOW();)
@@ -868,6 +940,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
     }
     }
     it += 1;
+  }
   }
   FWP(const long long p_t2 = FWP_NOW();)
   // G = 8: waypoints sampled by sibling lanes during an in-launch reset are read back below

@@ -21,7 +21,12 @@ wrench (v_mov_b32_dpp) -- and prints:
     A kernel whose tick loop is unrolled has no inner loop: the path through the sub-step loop is then its own total and the
     outer / tick split is not made.
 
-The `moves` class is register copying: v_accvgpr_read / write / mov, and v_mov_b32 / v_mov_b64 without DPP.
+The `moves` class is register copying: v_accvgpr_read / write / mov, and v_mov_b32 / v_mov_b64 without DPP.  `--substep` splits
+it by kind (move_kind): `agpr` = v_accvgpr_* (the allocator parking values in the accumulation registers), `copy` = a v_mov or
+s_mov from a register (phi copies at joins and loop heads), `literal` = a v_mov or s_mov of a constant (coefficients rebuilt in
+place).  The s_mov of either kind belong to the `salu` class of the table above and are listed here as well, since they are
+the scalar half of the same copying.  The per-block table lists every block of the sub-step loop in layout order, the blocks
+of the common path marked `*`, with its instructions by f64 arithmetic, DPP, v_cndmask, the three kinds of move and the rest.
 
 A loop is taken for the tick loop only if it holds no memory instruction (the tick has none; the sub-step loop stores the step's
 outputs): with the tick loop unrolled the tick-loop report is left out instead of counting the sub-step loop in its place.
@@ -74,6 +79,33 @@ def classify(op):
     if op.startswith("s_"):
         return "salu"
     return "other_valu"
+
+
+MOVE_KINDS = ("agpr", "copy", "literal")
+
+
+def move_kind(op, txt):
+    """agpr / copy / literal for an instruction that only moves a value (see the module text); None for everything else."""
+    op = re.sub(r"_e(32|64)$", "", op)
+    if op.startswith("v_accvgpr_"):
+        return "agpr"
+    if op not in ("v_mov_b32", "v_mov_b64", "s_mov_b32", "s_mov_b64"):
+        return None
+    parts = txt.split(None, 1)
+    toks = [t.strip() for t in parts[1].split(",")] if len(parts) > 1 else []
+    src = toks[1].split()[0] if len(toks) > 1 and toks[1] else ""
+    return "copy" if re.fullmatch(r"[vsa]\d+|[vsa]\[\d+:\d+\]|vcc(_lo|_hi)?|exec(_lo|_hi)?|m0", src) else "literal"
+
+
+def block_row(b):
+    """One row of the per-block table: instructions of a block by what they are there for."""
+    c = Counter(classify(op) for op, _ in b[1])
+    k = Counter(move_kind(op, txt) for op, txt in b[1])
+    f64 = c["fma_f64"] + c["mul_f64"] + c["add_f64"] + c["other_f64"]
+    row = OrderedDict(block=b[0].replace(".L", ""), total=len(b[1]), f64=f64, dpp=c["dpp"], cndmask=c["cndmask"],
+                      agpr=k["agpr"], copy=k["copy"], literal=k["literal"])
+    row["other"] = row["total"] - f64 - c["dpp"] - c["cndmask"] - k["agpr"] - k["copy"] - k["literal"]
+    return row
 
 
 def demangle(names):
@@ -279,7 +311,20 @@ def substep_report(bl, trips):
         tick = Counter()
     ex = Counter({k: outer.get(k, 0) + (trips if rolled else 0) * tick.get(k, 0) for k in CLASSES})
     every = Counter(classify(op) for b in sbs for op, _ in b[1])       # all blocks of the loop, each counted once
-    return OrderedDict(header=sh, blocks=len(sbs), path_blocks=len(path), tick_loop=th if rolled else None, trips=trips if rolled else 0,
+    on_path = set(path)
+    kinds = OrderedDict()
+    for k in MOVE_KINDS:
+        k_outer = sum(1 for l in path if l not in tl for op, txt in bmap[l][1] if move_kind(op, txt) == k)
+        k_tick = sum(1 for l in path if l in tl for op, txt in bmap[l][1] if move_kind(op, txt) == k) if rolled else 0
+        kinds[k] = OrderedDict(outer=k_outer, tick=k_tick, executed=k_outer + (trips if rolled else 0) * k_tick,
+                               all=sum(1 for b in sbs for op, txt in b[1] if move_kind(op, txt) == k))
+    per_block = []
+    for b in sbs:
+        row = block_row(b)
+        row["on_path"] = row["block"] in on_path
+        row["block"] = row["block"].rstrip(":")
+        per_block.append(row)
+    return OrderedDict(move_kinds=kinds, per_block=per_block, header=sh, blocks=len(sbs), path_blocks=len(path), tick_loop=th if rolled else None, trips=trips if rolled else 0,
                        outer=OrderedDict((k, outer.get(k, 0)) for k in CLASSES), tick=OrderedDict((k, tick.get(k, 0)) for k in CLASSES),
                        executed=OrderedDict((k, ex.get(k, 0)) for k in CLASSES), all=OrderedDict((k, every.get(k, 0)) for k in CLASSES),
                        outer_total=sum(outer.values()), tick_total=sum(tick.values()), executed_total=sum(ex.values()))
@@ -452,6 +497,14 @@ def main(argv):
             print(f"  {'class':<{w}} {'outer':>6} {'tick':>6} {'executed':>9} {'all blocks':>11}")
             for k in CLASSES:
                 print(f"  {k:<{w}} {r['outer'][k]:>6} {r['tick'][k]:>6} {r['executed'][k]:>9} {r['all'][k]:>11}")
+            print("  moves by kind (v_accvgpr_* | v_mov / s_mov from a register | v_mov / s_mov of a constant):")
+            for k, q in r["move_kinds"].items():
+                print(f"  {k:<{w}} {q['outer']:>6} {q['tick']:>6} {q['executed']:>9} {q['all']:>11}")
+            print("  per block (layout order; * = on the common path):")
+            print(f"  {'block':<12} {'total':>6} {'f64':>5} {'dpp':>5} {'cndmask':>8} {'agpr':>5} {'copy':>5} {'literal':>8} {'other':>6}")
+            for q in r["per_block"]:
+                print(f"  {q['block'] + ('*' if q['on_path'] else ''):<12} {q['total']:>6} {q['f64']:>5} {q['dpp']:>5} {q['cndmask']:>8} "
+                      f"{q['agpr']:>5} {q['copy']:>5} {q['literal']:>8} {q['other']:>6}")
         else:
             print(f"{name}\n  tick loop {r['header']} ({r['blocks']} blocks): all {r['all']}, min path {r['min_path']}, "
                   f"max path {r['max_path']}; surface {r['surface']} + rigid {r['rigid']}")
