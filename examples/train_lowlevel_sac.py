@@ -1,15 +1,21 @@
 """Device-resident counterpart of the reference's examples/lowlevel.py: the low-level controller trained with SAC instead of PPO.
 
 Same hyper-parameters (SB3 ``SAC("MlpPolicy")``: net_arch [256, 256], buffer 200 000, batch 256, gamma 0.99, tau 0.02, lr 3e-4, one
-gradient step per env step, automatic entropy coefficient, no VecNormalize, 100 000 steps) on the low-level env this project has
-(``FW_TASK_LOWLEVEL``: 21 observations, six actuator commands); the script's own reward / termination / reset variant of the env is
-not built.  A vec-step -- act, env step, store, ``gradient_steps`` x (sample, update) -- is one captured graph
-(pyflyt_drone_amd/sac.py); ``--no-fused_update`` runs the gradient steps in torch on the same act / store / sample / noise kernels.
+gradient step per env step, automatic entropy coefficient, no VecNormalize, 100 000 steps).  A vec-step -- act, env step, store,
+``gradient_steps`` x (sample, update) -- is one captured graph (pyflyt_drone_amd/sac.py); ``--no-fused_update`` runs the gradient
+steps in torch on the same act / store / sample / noise kernels.
+
+``--env tracking`` (the default) trains on the low-level env of train/train_lowlevel_cmd.py (``FixedwingLowLevelVecEnv``);
+``--env demo`` trains and evaluates on the env the reference script itself defines (``FixedwingLowLevelDemoVecEnv``, DESIGN.md
+section 2d: 120 m / 25 m/s start, its reward and episode ends, its constructor defaults) -- the like-for-like run of the script.
+In ``demo`` mode every evaluation line also carries the heading MAE and RMSE in degrees, the unit the script reports.
 
     python examples/train_lowlevel_sac.py --out runs/lowlevel_sac
+    python examples/train_lowlevel_sac.py --env demo --out runs/lowlevel_sac_demo
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -26,6 +32,8 @@ TRAIN_CONFIG = dict(total_timesteps=100_000, learning_rate=3e-4, buffer_size=200
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--env", choices=("tracking", "demo"), default="tracking",
+                    help="tracking: the env of train/train_lowlevel_cmd.py; demo: the env examples/lowlevel.py defines for this run")
     ap.add_argument("--total_timesteps", type=int, default=TRAIN_CONFIG["total_timesteps"])
     ap.add_argument("--num_envs", type=int, default=16)
     ap.add_argument("--gradient_steps", type=int, default=-1, help="per vec-step; -1: one per env (update-to-data 1, as the reference)")
@@ -33,15 +41,20 @@ def main():
                     help="fw_sac_update (default) or the torch gradient step")
     ap.add_argument("--use_graphs", action=argparse.BooleanOptionalAction, default=True)
     ap.add_argument("--eval_freq", type=int, default=TRAIN_CONFIG["eval_freq"], help="env steps between evaluations")
-    ap.add_argument("--eval_max_steps", type=int, default=1800, help="time limit of an evaluation episode (agent steps)")
+    ap.add_argument("--eval_max_steps", type=int, default=1800, help="time limit of an evaluation episode (agent steps; --env tracking only: demo evaluates on the script's own 60 s clock)")
     ap.add_argument("--out", type=str, default="runs/lowlevel_sac")
     a = ap.parse_args()
     c = TRAIN_CONFIG
     os.makedirs(a.out, exist_ok=True)
-    env = P.FixedwingLowLevelVecEnv(num_envs=a.num_envs, seed=c["seed"])
     from pyflyt_drone_amd import config as K
-    eval_env = R.VecNormalizeDevice(P.FixedwingVecEnv(K.lowlevel_config(max_episode_steps=a.eval_max_steps), 16, seed=c["seed"],
-                                                      global_env_offset=a.num_envs),
+    demo = a.env == "demo"
+    if demo:
+        env = P.FixedwingLowLevelDemoVecEnv(num_envs=a.num_envs, seed=c["seed"])
+        eval_cfg = K.lowlevel_demo_config()
+    else:
+        env = P.FixedwingLowLevelVecEnv(num_envs=a.num_envs, seed=c["seed"])
+        eval_cfg = K.lowlevel_config(max_episode_steps=a.eval_max_steps)
+    eval_env = R.VecNormalizeDevice(P.FixedwingVecEnv(eval_cfg, 16, seed=c["seed"], global_env_offset=a.num_envs),
                                     training=False, norm_obs=False, norm_reward=False)
     model = S.SAC(env, S.SACConfig(learning_rate=c["learning_rate"], buffer_size=c["buffer_size"], batch_size=c["batch_size"],
                                    gamma=c["gamma"], tau=c["tau"], gradient_steps=a.gradient_steps,
@@ -55,11 +68,13 @@ def main():
         state["train_s"] += time.perf_counter() - state["mark"]
         r = evaluate.evaluate_policy(sac.policy, eval_env, c["n_eval_episodes"], deterministic=True)
         logs = sac.read_logs()
+        trk = r.tracking_scalars()
+        deg = {f"eval/heading_{k}_deg": round(math.degrees(trk[f"eval/heading_{k}"]), 4) for k in ("mae", "rmse")} if demo else {}
         line = {"timesteps": sac.num_timesteps, "n_updates": sac.n_updates,
                 "env_steps_per_s": round(sac.num_timesteps / max(state["train_s"], 1e-9), 1),
                 "eval_ep_rew_mean": round(float(sum(r.episode_rewards) / len(r.episode_rewards)), 3),
                 "eval_ep_len_mean": round(float(sum(r.episode_lengths) / len(r.episode_lengths)), 1),
-                **{k: round(float(v), 5) for k, v in r.tracking_scalars().items()},
+                **{k: round(float(v), 5) for k, v in trk.items()}, **deg,
                 **{k: round(float(logs[k]), 5) for k in S.SCALARS}}
         print(json.dumps(line), flush=True)
         state["mark"] = time.perf_counter()
@@ -70,7 +85,7 @@ def main():
             state["next_eval"] += a.eval_freq
         return True
 
-    print(json.dumps({"config": {**{k: v for k, v in c.items()}, "num_envs": a.num_envs, "gradient_steps": model.G,
+    print(json.dumps({"config": {**{k: v for k, v in c.items()}, **({"env": a.env} if demo else {}), "num_envs": a.num_envs, "gradient_steps": model.G,
                                  "fused_update": a.fused_update, "use_graphs": a.use_graphs}}), flush=True)
     evaluate_now(model)                      # the untrained actor: the line later evaluations are read against
     try:

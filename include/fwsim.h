@@ -79,6 +79,14 @@ enum {
                                  * base env of train/train_highlevel_cmd.py's HighLevelCmdEnv */
 };
 
+/* fw_config.lowlevel_variant (FW_TASK_LOWLEVEL only; DESIGN.md section 2d "SAC script's variant").  Both variants share the 21
+ * observation columns, the six actions and the FW_SL_* state tail; they differ in start, reward, episode ends and in which
+ * action obs[12:18] shows. */
+enum {
+  FW_LL_VARIANT_TRACKING = 0,   /* envs/fixedwing_envs/fixedwing_lowlevel_env.py (train/train_lowlevel_cmd.py) */
+  FW_LL_VARIANT_SAC_DEMO = 1    /* the FixedwingLowLevelEnv examples/lowlevel.py defines for its SAC run */
+};
+
 /* fw_config.dtype */
 enum { FW_F64 = 0, FW_F32 = 1 };
 
@@ -155,7 +163,12 @@ typedef struct fw_config {
                                   * (Round 5; one of the former reserved words, which callers zero: same layout, same ABI version.) */
   int32_t lowlevel_max_episode_steps; /* FW_TASK_LOWLEVEL: truncation at this many agent steps (2000, fixedwing_lowlevel_env.py:137).
                                   * (A former reserved word, which callers zero: same layout, same ABI version.) */
-  int32_t reserved_i[6];
+  int32_t lowlevel_variant;     /* FW_TASK_LOWLEVEL: FW_LL_VARIANT_* -- which of the reference's two low-level envs.  0 (what every caller
+                                  * before it sends) is fixedwing_lowlevel_env.py; 1 is the env examples/lowlevel.py defines for its SAC run.
+                                  * (This word and the next: former reserved words, which callers zero: same layout, same ABI version.) */
+  int32_t lowlevel_fixed_heading; /* FW_LL_VARIANT_SAC_DEMO: 1 = target_heading_random=False (examples/lowlevel.py:109): psi_ref = 0.
+                                  * Must be 0 or 1 there; the first variant neither reads nor checks it. */
+  int32_t reserved_i[4];
 
   /* ---- env / task scalars ---- */
   double flight_dome_size;
@@ -214,7 +227,9 @@ typedef struct fw_config {
   /* ---- low-level task (envs/fixedwing_envs/fixedwing_lowlevel_env.py:32-33, 86-91); former reserved words, zero elsewhere ---- */
   double lowlevel_speed_range[2];   /* V_ref ~ U(lo, hi), (10, 20) */
   double lowlevel_height_range[2];  /* h_ref ~ U(lo, hi), (5, 20) */
-  double reserved_d[4];
+  double lowlevel_min_speed;        /* FW_LL_VARIANT_SAC_DEMO: the stall-penalty threshold min_speed_mps, 8.0 (examples/lowlevel.py:41, 183);
+                                     * finite and >= 0 there; the first variant neither reads nor checks it.  (A former reserved word, zero elsewhere.) */
+  double reserved_d[3];
 } fw_config;
 
 /* ---- canonical per-env state record (doubles; used by fw_get_state/fw_set_state) ---- */
@@ -264,7 +279,8 @@ enum {
 /* low-level tail (offsets from FW_S_TASK): the episode's target and the action its observation shows.  The episode's step
  * count is FW_S_STEP_COUNT, as for every task.  FW_TASK_WAYPOINTS_DIRECT uses the same two slots: FW_SL_TARGET holds the last
  * conditioned command of fw_command_hl, FW_SL_PREV_ACTION the six actuator commands its observation shows (obs[12:18] / [13:19]);
- * FW_S_ACTION stays zero for it. */
+ * FW_S_ACTION stays zero for it.  With lowlevel_variant = FW_LL_VARIANT_SAC_DEMO, FW_SL_PREV_ACTION is the last action taken, clipped to
+ * [-1, 1]: the row of the step that took it shows the one before (examples/lowlevel.py:127-133), fw_observe and the next step's row show it. */
 enum {
   FW_SL_TARGET = 0,        /* 3: psi_ref, h_ref, V_ref            fixedwing_lowlevel_env.py:86-91 */
   FW_SL_PREV_ACTION = 3,   /* 6: the last action (obs[12:18])     :99 */

@@ -6,14 +6,14 @@ BASELINE.json: the fixed-wing flight-dynamics step + reward + observation of
 SB3 ``VecEnv`` surface the reference's training scripts consume.
 """
 from . import config
-from .config import (FwConfig, highlevel_config, lowlevel_config, train_waypoints_v3_config, waypoints_config, waypoints_direct_config)
+from .config import (FwConfig, highlevel_config, lowlevel_config, lowlevel_demo_config, train_waypoints_v3_config, waypoints_config, waypoints_direct_config)
 from .spaces import Box
-from .vec_env import (FixedwingLowLevelVecEnv, FixedwingObjLockVecEnv, FixedwingVecEnv, FixedwingWaypointObjLockVecEnv,
+from .vec_env import (FixedwingLowLevelDemoVecEnv, FixedwingLowLevelVecEnv, FixedwingObjLockVecEnv, FixedwingVecEnv, FixedwingWaypointObjLockVecEnv,
                       FixedwingWaypointsDirectVecEnv, FixedwingWaypointsVecEnv)
 from . import rollout
 from . import checkpoint, evaluate, flight, highlevel, monitor
 from .highlevel import HighLevelCmdVecEnv
 
 __all__ = ["config", "FwConfig", "Box", "FixedwingVecEnv", "FixedwingWaypointsVecEnv", "FixedwingObjLockVecEnv", "FixedwingWaypointObjLockVecEnv",
-           "FixedwingLowLevelVecEnv", "FixedwingWaypointsDirectVecEnv", "HighLevelCmdVecEnv", "waypoints_config",
-           "train_waypoints_v3_config", "lowlevel_config", "waypoints_direct_config", "highlevel_config"]
+           "FixedwingLowLevelVecEnv", "FixedwingLowLevelDemoVecEnv", "FixedwingWaypointsDirectVecEnv", "HighLevelCmdVecEnv", "waypoints_config",
+           "train_waypoints_v3_config", "lowlevel_config", "lowlevel_demo_config", "waypoints_direct_config", "highlevel_config"]

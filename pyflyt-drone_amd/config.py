@@ -32,6 +32,7 @@ FW_INFO_DIM = 8
 FW_OK, FW_EINVAL, FW_EHIP, FW_ENOMEM, FW_EVERSION, FW_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
 FW_TASK_WAYPOINTS, FW_TASK_OBJLOCK, FW_TASK_WAYPOINT_OBJLOCK, FW_TASK_LOWLEVEL, FW_TASK_WAYPOINTS_DIRECT = 0, 1, 2, 3, 5      # (4 is not a task)
 FW_F64, FW_F32 = 0, 1
+FW_LL_VARIANT_TRACKING, FW_LL_VARIANT_SAC_DEMO = 0, 1      # fw_config.lowlevel_variant (FW_TASK_LOWLEVEL)
 FW_WIND_OFF, FW_WIND_CONSTANT, FW_WIND_GUST_SINE = 0, 1, 2
 FW_WIND_COUPLE_NONE, FW_WIND_COUPLE_FORCE, FW_WIND_COUPLE_AIRSPEED = 0, 1, 2
 
@@ -83,7 +84,8 @@ class FwConfig(C.Structure):
         ("duck_camera_capture_interval_steps", C.c_int32), ("duck_lock_hold_steps", C.c_int32),
         ("duck_lock_decay_steps", C.c_int32), ("duck_switch_min_consecutive_seen", C.c_int32),
         ("camera_resolution", C.c_int32), ("duck_vision_no_deltas", C.c_int32),
-        ("lowlevel_max_episode_steps", C.c_int32), ("reserved_i", C.c_int32 * 6),
+        ("lowlevel_max_episode_steps", C.c_int32), ("lowlevel_variant", C.c_int32), ("lowlevel_fixed_heading", C.c_int32),
+        ("reserved_i", C.c_int32 * 4),
         # env / task scalars
         ("flight_dome_size", C.c_double), ("max_duration_seconds", C.c_double),
         ("goal_reach_distance", C.c_double), ("waypoint_min_height", C.c_double),
@@ -114,7 +116,7 @@ class FwConfig(C.Structure):
         ("camera_fov_deg", C.c_double), ("camera_near", C.c_double), ("camera_far", C.c_double),
         # low-level task
         ("lowlevel_speed_range", C.c_double * 2), ("lowlevel_height_range", C.c_double * 2),
-        ("reserved_d", C.c_double * 4),
+        ("lowlevel_min_speed", C.c_double), ("reserved_d", C.c_double * 3),
     ]
 
     def copy(self) -> "FwConfig":
@@ -659,6 +661,59 @@ def lowlevel_config_from_reference_kwargs(*, render_mode=None, wind_config: Opti
     if render_mode is not None:
         raise ValueError(f"Invalid render mode {render_mode}, rendering is not part of the device env.")
     return lowlevel_config(dtype=dtype, wind_config=wind_config, motor_noise=motor_noise, auto_reset=auto_reset)
+
+
+def lowlevel_demo_episode_steps(max_duration_seconds: float, agent_hz: int) -> int:
+    """The step at which the SAC script's clock truncates an episode (examples/lowlevel.py:66, 125, 206): the first k for which
+    the float64 running sum of k terms ``1.0 / float(agent_hz)`` is ``>= max_duration_seconds``.  The loop, not a product: 1801 for
+    (60, 30), because after 1800 additions the sum is still below 60.0."""
+    if not float(agent_hz) > 0.0:
+        raise ValueError(f"agent_hz must be positive, got {agent_hz}")
+    dt, limit = 1.0 / float(agent_hz), float(max_duration_seconds)
+    if not (dt > 0.0 and math.isfinite(dt) and math.isfinite(limit)):
+        raise ValueError(f"agent_hz must be positive and max_duration_seconds finite, got {agent_hz}, {max_duration_seconds}")
+    if limit / dt > 1.0e7:      # (the sum has to be walked: ten million steps, 23 hours of flight, take about a second here)
+        raise ValueError(f"max_duration_seconds {max_duration_seconds} at agent_hz {agent_hz} is more than 10 000 000 steps")
+    elapsed, k = 0.0, 0
+    while True:
+        k += 1
+        elapsed += dt
+        if elapsed >= limit:
+            return k
+
+
+def lowlevel_demo_config(*, flight_dome_size: float = 800.0, max_duration_seconds: float = 60.0, agent_hz: int = 30,
+                         render_mode=None, start_height_m: float = 120.0, start_speed_mps: float = 25.0,
+                         min_speed_mps: float = 8.0, target_speed_range=(20.0, 35.0), target_height_range=(100.0, 200.0),
+                         target_heading_random: bool = True, dtype: str = "float64", motor_noise: bool = True,
+                         auto_reset: bool = True, wind_config: Optional[Mapping[str, Any]] = None) -> FwConfig:
+    """The ``FixedwingLowLevelEnv`` that examples/lowlevel.py defines for its SAC run (:33-98), keyword for keyword:
+    ``FW_TASK_LOWLEVEL`` with ``lowlevel_variant = FW_LL_VARIANT_SAC_DEMO``.  Start at [0, 0, start_height_m] with zero
+    orientation and world velocity [start_speed_mps, 0, 0], no warm-up; one Aviary step per agent step whatever ``agent_hz``
+    says (:123), so ``cfg.agent_hz`` stays 120 and the script's ``agent_hz`` is only its clock, folded into
+    ``lowlevel_max_episode_steps`` (:func:`lowlevel_demo_episode_steps`).  The reward weights, the 35 / 20 degree attitude
+    limits, the 1 m / 5 m/s termination and the 1.2 x dome truncation are the script's literals, compiled in."""
+    if render_mode is not None:
+        raise ValueError(f"Invalid render mode {render_mode}, rendering is not part of the device env.")
+    if not (math.isfinite(float(min_speed_mps)) and float(min_speed_mps) >= 0.0):
+        raise ValueError(f"min_speed_mps must be finite and >= 0, got {min_speed_mps}")
+    steps = lowlevel_demo_episode_steps(max_duration_seconds, agent_hz)
+    c = base_config(task=FW_TASK_LOWLEVEL, dtype=dtype, angle_representation="euler", agent_hz=120,
+                    flight_dome_size=float(flight_dome_size), max_duration_seconds=float(max_duration_seconds),
+                    start_pos=(0.0, 0.0, float(start_height_m)), wind_config=wind_config, motor_noise=motor_noise,
+                    auto_reset=auto_reset)
+    c.warmup_aviary_steps = 0
+    _set_vec(c.start_vel, (float(start_speed_mps), 0.0, 0.0))
+    c.num_targets, c.context_length = 0, 0
+    lo, hi = (float(v) for v in target_speed_range)
+    c.lowlevel_speed_range[0], c.lowlevel_speed_range[1] = lo, hi
+    lo, hi = (float(v) for v in target_height_range)
+    c.lowlevel_height_range[0], c.lowlevel_height_range[1] = lo, hi
+    c.lowlevel_max_episode_steps = steps
+    c.lowlevel_variant = FW_LL_VARIANT_SAC_DEMO
+    c.lowlevel_fixed_heading = 0 if bool(target_heading_random) else 1
+    c.lowlevel_min_speed = float(min_speed_mps)
+    return c
 
 
 def obs_dim(c: FwConfig) -> int:

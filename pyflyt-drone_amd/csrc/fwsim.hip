@@ -1718,6 +1718,8 @@ __global__ __launch_bounds__(kWave) void fw_reset_kernel_ll(const Params<T>* __r
   }
 }
 
+// the low-level task's second variant: the env of the reference's SAC script (fw_step_kernel_lld / fw_reset_kernel_lld)
+#include "fwsim_lowlevel_demo.hpp"
 // the low-level task's command input and trace (fw_command_ll / fw_trace_ll): the target goes to ll_target_slot above
 #include "fwsim_command.hpp"
 #include "fwsim_flight.hpp"
@@ -1784,6 +1786,13 @@ int validate(const fw_config* c, std::string& msg) {
     }
     if (c->num_targets != 0) { snprintf(buf, sizeof buf, "the low-level task has no waypoints: num_targets must be 0, got %d", c->num_targets); return fail(FW_EINVAL); }
     if (c->lowlevel_max_episode_steps <= 0) { snprintf(buf, sizeof buf, "lowlevel_max_episode_steps must be positive, got %d", c->lowlevel_max_episode_steps); return fail(FW_EINVAL); }
+    if (c->lowlevel_variant != FW_LL_VARIANT_TRACKING && c->lowlevel_variant != FW_LL_VARIANT_SAC_DEMO) {
+      snprintf(buf, sizeof buf, "lowlevel_variant must be 0 (fixedwing_lowlevel_env.py) or 1 (the SAC script's env), got %d", c->lowlevel_variant);
+      return fail(FW_EINVAL);
+    }
+    // the next two words belong to the SAC script's variant alone: the first variant ignores them, as it did while they were reserved
+    if (c->lowlevel_variant == FW_LL_VARIANT_SAC_DEMO && c->lowlevel_fixed_heading != 0 && c->lowlevel_fixed_heading != 1) { snprintf(buf, sizeof buf, "lowlevel_fixed_heading must be 0 or 1, got %d", c->lowlevel_fixed_heading); return fail(FW_EINVAL); }
+    if (c->lowlevel_variant == FW_LL_VARIANT_SAC_DEMO && !(std::isfinite(c->lowlevel_min_speed) && c->lowlevel_min_speed >= 0.0)) { snprintf(buf, sizeof buf, "lowlevel_min_speed must be finite and >= 0, got %g", c->lowlevel_min_speed); return fail(FW_EINVAL); }
     if (c->physics_hz != 240 || c->control_hz != 120 || c->agent_hz != 120) {
       snprintf(buf, sizeof buf, "the low-level task steps one Aviary step per agent step: physics_hz 240, control_hz 120, agent_hz 120 (got %d, %d, %d)",
                c->physics_hz, c->control_hz, c->agent_hz);
@@ -2113,8 +2122,10 @@ template <typename T>
 int upload_params(fw_env* h) {
   Params<T> P;
   if (!build_params<T>(h->cfg, h->seed, h->env_offset, P, h->err)) return FW_EINVAL;
-  if (!h->params_dev) HIP_TRY(h, hipMalloc(&h->params_dev, step_image_offset<T>() + sizeof(StepImage<T>)));     // Params, then the step image
+  if (!h->params_dev) HIP_TRY(h, hipMalloc(&h->params_dev, lld_consts_offset<T>() + sizeof(LldC<T>)));     // Params, then the step image, then the low-level variant's constants
   HIP_TRY(h, hipMemcpy(h->params_dev, &P, sizeof P, hipMemcpyHostToDevice));
+  const LldC<T> LC = { (T)h->cfg.lowlevel_min_speed, h->cfg.lowlevel_fixed_heading };
+  HIP_TRY(h, hipMemcpy((unsigned char*)h->params_dev + lld_consts_offset<T>(), &LC, sizeof LC, hipMemcpyHostToDevice));
   ObjC<T> OC;
   build_objc<T>(h->cfg, OC);
   if (!h->objc_dev) HIP_TRY(h, hipMalloc(&h->objc_dev, sizeof(ObjC<T>)));
@@ -2139,7 +2150,7 @@ int upload_params(fw_env* h) {
 // A key names the fields of a handle that the choice depends on; kAny in a row matches every value.  The first row that matches
 // wins, so a special case stands above the general one.  A new kernel variant is one new row.
 constexpr int kAny = -1;
-struct KernelKey { int task, lanes, waves, windy, axis_aligned, capture_wave, aux_wave, step_shape; };
+struct KernelKey { int task, lanes, waves, windy, axis_aligned, capture_wave, aux_wave, step_shape, variant; };   // variant: fw_config.lowlevel_variant
 struct KernelRow { KernelKey key; EnvKernel step, reset, collect; };
 template <typename... A> const void* kfn(void (*kernel)(A...)) { return (const void*)kernel; }      // the host-side pointer hipLaunchKernel takes
 // The argument lists step_T / collect_step_T / reset_T build.  hipLaunchKernel takes them unchecked, so a kernel enters the table
@@ -2170,47 +2181,52 @@ template <typename T> EnvKernel step_shape_step_kernel() {
 template <typename T> const KernelRow* env_kernels_of(const KernelKey& q) {
   constexpr int LL = FW_TASK_LOWLEVEL, WD = FW_TASK_WAYPOINTS_DIRECT, OBJ = FW_TASK_OBJLOCK, COMB = FW_TASK_WAYPOINT_OBJLOCK, WP = FW_TASK_WAYPOINTS;
   static const KernelRow rows[] = {
-    // task lanes waves windy axis  capture aux   shape  fw_step                                                      fw_reset / fw_observe                                fw_collect_step
-    {{LL,   8, kAny, 1,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 8, true>),         no_objc<T>(fw_reset_kernel_ll<T, 8>),         {}},
-    {{LL,   8, kAny, 0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 8, false>),        no_objc<T>(fw_reset_kernel_ll<T, 8>),         {}},
-    {{LL,   1, kAny, 1,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 1, true>),         no_objc<T>(fw_reset_kernel_ll<T, 1>),         {}},
-    {{LL,   1, kAny, 0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_ll<T, 1, false>),        no_objc<T>(fw_reset_kernel_ll<T, 1>),         {}},
-    {{WD,   8, kAny, 1,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, true>),         reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
-    {{WD,   8, kAny, 0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, false>),        reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
-    {{WD,   1, kAny, 1,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, true>),         reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
-    {{WD,   1, kAny, 0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, false>),        reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
-    {{OBJ,  8, kAny, kAny, kAny, 1,    kAny, kAny}, two_wave<T>(fw_step_kernel_obj_g8h<T, OBJ>),      reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
-    {{OBJ,  8, kAny, kAny, kAny, 0,    kAny, kAny}, step_k<T>(fw_step_kernel_obj_g8<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
-    {{OBJ,  1, kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 1, OBJ>),       {}},
-    {{COMB, 8, kAny, kAny, kAny, 1,    kAny, kAny}, two_wave<T>(fw_step_kernel_obj_g8h<T, COMB>),     reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
-    {{COMB, 8, kAny, kAny, kAny, 0,    kAny, kAny}, step_k<T>(fw_step_kernel_obj_g8<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
-    {{COMB, 1, kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 1, COMB>),      {}},
-    {{WP,   8, 1,    0,    1,    kAny, 1,    1},    step_shape_step_kernel<T>(),                      reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
-    {{WP,   8, 1,    0,    1,    kAny, 1,    kAny}, aux_wave_step_kernel<T>(),                        reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
-    {{WP,   8, 1,    0,    1,    kAny, kAny, kAny}, axis_aligned_step_kernel<T>(),                    reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
-    {{WP,   8, 2,    1,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, true>),          reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, true>)},
-    {{WP,   8, 2,    0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, false>),         reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, false>)},
-    {{WP,   8, 1,    1,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, true>),            reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, true>)},
-    {{WP,   8, 1,    0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, false>),           reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
-    {{WP,   1, kAny, 1,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, true>),            reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
-    {{WP,   1, kAny, 0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, false>),           reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
+    // task lanes waves windy axis  capture aux   shape variant  fw_step                                                      fw_reset / fw_observe                                fw_collect_step
+    {{LL,   8, kAny, 1,    kAny, kAny, kAny, kAny, 1   }, step_k<T>(fw_step_kernel_lld<T, 8, true>),        no_objc<T>(fw_reset_kernel_lld<T, 8>),        {}},
+    {{LL,   8, kAny, 0,    kAny, kAny, kAny, kAny, 1   }, step_k<T>(fw_step_kernel_lld<T, 8, false>),       no_objc<T>(fw_reset_kernel_lld<T, 8>),        {}},
+    {{LL,   1, kAny, 1,    kAny, kAny, kAny, kAny, 1   }, step_k<T>(fw_step_kernel_lld<T, 1, true>),        no_objc<T>(fw_reset_kernel_lld<T, 1>),        {}},
+    {{LL,   1, kAny, 0,    kAny, kAny, kAny, kAny, 1   }, step_k<T>(fw_step_kernel_lld<T, 1, false>),       no_objc<T>(fw_reset_kernel_lld<T, 1>),        {}},
+    {{LL,   8, kAny, 1,    kAny, kAny, kAny, kAny, 0   }, step_k<T>(fw_step_kernel_ll<T, 8, true>),         no_objc<T>(fw_reset_kernel_ll<T, 8>),         {}},
+    {{LL,   8, kAny, 0,    kAny, kAny, kAny, kAny, 0   }, step_k<T>(fw_step_kernel_ll<T, 8, false>),        no_objc<T>(fw_reset_kernel_ll<T, 8>),         {}},
+    {{LL,   1, kAny, 1,    kAny, kAny, kAny, kAny, 0   }, step_k<T>(fw_step_kernel_ll<T, 1, true>),         no_objc<T>(fw_reset_kernel_ll<T, 1>),         {}},
+    {{LL,   1, kAny, 0,    kAny, kAny, kAny, kAny, 0   }, step_k<T>(fw_step_kernel_ll<T, 1, false>),        no_objc<T>(fw_reset_kernel_ll<T, 1>),         {}},
+    {{WD,   8, kAny, 1,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, true>),         reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
+    {{WD,   8, kAny, 0,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, false>),        reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
+    {{WD,   1, kAny, 1,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, true>),         reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
+    {{WD,   1, kAny, 0,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, false>),        reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
+    {{OBJ,  8, kAny, kAny, kAny, 1,    kAny, kAny, kAny}, two_wave<T>(fw_step_kernel_obj_g8h<T, OBJ>),      reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
+    {{OBJ,  8, kAny, kAny, kAny, 0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g8<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
+    {{OBJ,  1, kAny, kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 1, OBJ>),       {}},
+    {{COMB, 8, kAny, kAny, kAny, 1,    kAny, kAny, kAny}, two_wave<T>(fw_step_kernel_obj_g8h<T, COMB>),     reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
+    {{COMB, 8, kAny, kAny, kAny, 0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g8<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
+    {{COMB, 1, kAny, kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 1, COMB>),      {}},
+    {{WP,   8, 1,    0,    1,    kAny, 1,    1,    kAny}, step_shape_step_kernel<T>(),                      reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   8, 1,    0,    1,    kAny, 1,    kAny, kAny}, aux_wave_step_kernel<T>(),                        reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   8, 1,    0,    1,    kAny, kAny, kAny, kAny}, axis_aligned_step_kernel<T>(),                    reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   8, 2,    1,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, true>),          reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, true>)},
+    {{WP,   8, 2,    0,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, false>),         reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, false>)},
+    {{WP,   8, 1,    1,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, true>),            reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, true>)},
+    {{WP,   8, 1,    0,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, false>),           reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   1, kAny, 1,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, true>),            reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
+    {{WP,   1, kAny, 0,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, false>),           reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
   };
   auto fits = [](int row, int v) { return row == kAny || row == v; };
   for (const KernelRow& r : rows)
     if (const KernelKey& k = r.key; fits(k.task, q.task) && fits(k.lanes, q.lanes) && fits(k.waves, q.waves) && fits(k.windy, q.windy) &&
                                     fits(k.axis_aligned, q.axis_aligned) && fits(k.capture_wave, q.capture_wave) && fits(k.aux_wave, q.aux_wave) &&
-                                    fits(k.step_shape, q.step_shape)) return &r;
+                                    fits(k.step_shape, q.step_shape) && fits(k.variant, q.variant)) return &r;
   return nullptr;
 }
 
 // The handle's kernels, from the fields fw_create has just fixed.  A combination without a row (or whose row holds no step or
 // reset kernel) is an error here, not a launch that silently does nothing.
 template <typename T> int select_kernels(fw_env* h) {
-  const KernelKey q = { h->cfg.task, h->lanes_per_env, h->g8_waves, h->cfg.wind_mode != FW_WIND_OFF ? 1 : 0, h->axis_aligned, h->capture_wave, h->aux_wave, h->step_shape };
+  const KernelKey q = { h->cfg.task, h->lanes_per_env, h->g8_waves, h->cfg.wind_mode != FW_WIND_OFF ? 1 : 0, h->axis_aligned, h->capture_wave, h->aux_wave, h->step_shape,
+                        h->cfg.task == FW_TASK_LOWLEVEL ? h->cfg.lowlevel_variant : 0 };
   const KernelRow* r = env_kernels_of<T>(q);
   if (!r || !r->step.fn || !r->reset.fn) {
-    h->err = "no kernel is built for (task, dtype, lanes per env, waves per SIMD, wind, axis_aligned, capture_wave, aux_wave, step_shape) =";
-    for (int x : { q.task, h->cfg.dtype, q.lanes, q.waves, q.windy, q.axis_aligned, q.capture_wave, q.aux_wave, q.step_shape }) h->err += " " + std::to_string(x);
+    h->err = "no kernel is built for (task, dtype, lanes per env, waves per SIMD, wind, axis_aligned, capture_wave, aux_wave, step_shape, lowlevel_variant) =";
+    for (int x : { q.task, h->cfg.dtype, q.lanes, q.waves, q.windy, q.axis_aligned, q.capture_wave, q.aux_wave, q.step_shape, q.variant }) h->err += " " + std::to_string(x);
     return FW_EUNSUPPORTED;
   }
   h->step = r->step; h->reset = r->reset; h->collect = r->collect;

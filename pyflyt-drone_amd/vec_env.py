@@ -487,3 +487,23 @@ class FixedwingLowLevelVecEnv(FixedwingVecEnv):
         obs = super().reset()
         self.reset_infos = [{"target": obs[i, 18:21].astype(np.float64)} for i in range(self.num_envs)]      # (:94)
         return obs
+
+
+class FixedwingLowLevelDemoVecEnv(FixedwingLowLevelVecEnv):
+    """The ``FixedwingLowLevelEnv`` that examples/lowlevel.py defines for its SAC run, vectorised: the script's constructor keywords
+    and defaults (``config.lowlevel_demo_config``), six actuator commands in [-1, 1] (clipped by the env, :121), the same 21
+    observation columns as :class:`FixedwingLowLevelVecEnv` -- except that ``obs[:, 12:18]`` is the previous step's clipped action
+    (:133, 153) -- and ``infos[i]["target"]`` on reset and step."""
+
+    def __init__(self, num_envs: int, *, flight_dome_size: float = 800.0, max_duration_seconds: float = 60.0, agent_hz: int = 30,
+                 render_mode=None, start_height_m: float = 120.0, start_speed_mps: float = 25.0, min_speed_mps: float = 8.0,
+                 target_speed_range=(20.0, 35.0), target_height_range=(100.0, 200.0), target_heading_random: bool = True,
+                 dtype: str = "float64", motor_noise: bool = True, device=None, seed: int = 0, global_env_offset: int = 0,
+                 wind_config: Optional[dict] = None):
+        cfg = K.lowlevel_demo_config(flight_dome_size=flight_dome_size, max_duration_seconds=max_duration_seconds,
+                                     agent_hz=agent_hz, render_mode=render_mode, start_height_m=start_height_m,
+                                     start_speed_mps=start_speed_mps, min_speed_mps=min_speed_mps,
+                                     target_speed_range=target_speed_range, target_height_range=target_height_range,
+                                     target_heading_random=target_heading_random, dtype=dtype, motor_noise=motor_noise,
+                                     wind_config=wind_config)
+        FixedwingVecEnv.__init__(self, cfg, num_envs, device=device, seed=seed, global_env_offset=global_env_offset)
