@@ -8,16 +8,19 @@
 // (attitude 12 / 13, last actuator command 6, aux 6, 3 context_length target deltas), so that in Euler mode columns 0:18 are
 // columns 0:18 of the low-level task's observation (ll_write_obs).
 //
-// Kernels of their own rather than instantiations of step_body / fw_reset_kernel: the four-action kernels stay exactly as they
-// were.  What the other kernels are built from is shared: the inlined Aviary step, begin_reset / end_reset and the scenario
-// sampler, the attitude block of the observation.  Auto-resets run in the kernel (sampler, and the warm-up when wind acts on the
+// One step frame (fw_step_kernel_wd) and one reset kernel (fw_reset_kernel_wd), beside step_body / fw_reset_kernel of the
+// four-action tasks.  The step frame serves fw_step and fw_step_hl alike: where the six commands come from is its template
+// parameter SRC (WdSource below); the phase machine, the end-of-step block with the auto-reset, the motor noise and the Aviary
+// step, the waypoint reward / termination block, the warm-up branch and the epilogue are written once.  What the other kernels
+// are built from is shared: the inlined Aviary step, begin_reset / end_reset and the scenario sampler, the attitude block of the
+// observation.  Auto-resets run in the kernel (sampler, and the warm-up when wind acts on the
 // dynamics; wind-free the cached warm state is copied): FW_CTR_FALLBACKS.  The shadow / scenario hand-off of step_body is not
 // wired to this task.
 //
 // The six-wide last command lives in the task tail (FW_SL_PREV_ACTION, through ll_load_tail / ll_store_tail); FW_SL_TARGET holds
 // the last conditioned command of fw_command_hl.  RF_ACTION is not touched.
 //
-// Included by fwsim.hip behind the low-level task's kernels.
+// Included by fwsim.hip behind the low-level task's kernels and the controller (fwsim_hl_step.hpp).
 #pragma once
 
 // the flattened waypoint observation with a six-wide action block: the shared attitude writer's columns, with its four action
@@ -52,14 +55,27 @@ template <typename T> __device__ __forceinline__ void wd_default_command(const P
   tgt[2] = M<T>::sqrt_(P.start_vel[0] * P.start_vel[0] + P.start_vel[1] * P.start_vel[1] + P.start_vel[2] * P.start_vel[2]);
 }
 
+// Where the six actuator commands of an agent step come from -- the template parameter SRC of fw_step_kernel_wd, which also decides
+// the type of the kernel's fourth parameter:
+//   WD_HELD  fw_step: `const T* actions` [N, 6], read once in front of the loop and held for every Aviary step of the agent step;
+//   WD_CTL   fw_step_hl: fwsim_ctl::CtlArgs, the frozen low-level controller (fwsim_hl_step.hpp), evaluated in front of every stepping
+//            Aviary step on the command in force -- the env's FW_SL_TARGET tail, which fw_command_hl / fw_collect_act_hl wrote.  Its
+//            statistics and (G = 8) weights are staged in LDS behind the observation tile; the output in force when the step ends goes
+//            to CtlArgs::low_action.  Warm-up steps keep the all-zero setpoint and run no controller; an env that is done at entry
+//            runs nothing.
+enum WdSource { WD_HELD = 0, WD_CTL = 1 };
+template <typename T, int SRC> struct WdSourceArg { typedef const T* __restrict__ type; };
+template <typename T> struct WdSourceArg<T, WD_CTL> { typedef fwsim_ctl::CtlArgs type; };
+
 // K1 (waypoints, direct actuator commands): one agent step.  G lanes per env as in step_body (G = 8: lane j evaluates lifting
-// surface j and samples waypoint j of a reset); WIND = the config has wind.  One tick site: the step's Aviary steps and the warm-up
-// of an in-kernel reset share the loop, as in step_body.  Outputs are latched in registers and stored once at the end.
-template <typename T, int G, bool WIND>
+// surface j and samples waypoint j of a reset); WIND = the config has wind; SRC as above.  One tick site: the step's Aviary steps and
+// the warm-up of an in-kernel reset share the loop, as in step_body.  Outputs are latched in registers and stored once at the end.
+template <typename T, int G, bool WIND, int SRC>
 __global__ __launch_bounds__(kWave) void fw_step_kernel_wd(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp, DevState<T> Dg,
-                                                           const T* __restrict__ actions, T* __restrict__ obs, T* __restrict__ reward,
+                                                           typename WdSourceArg<T, SRC>::type input, T* __restrict__ obs, T* __restrict__ reward,
                                                            uint8_t* __restrict__ terminated, uint8_t* __restrict__ truncated,
                                                            T* __restrict__ terminal_obs, int32_t* __restrict__ info) {
+  constexpr bool CTL = SRC == WD_CTL;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   T* tile = reinterpret_cast<T*>(smem_raw);
   const Params<T>& P = *Pp;
@@ -74,6 +90,29 @@ __global__ __launch_bounds__(kWave) void fw_step_kernel_wd(const Params<T>* __re
   const size_t n = D.npad;
   const int Dobs = P.obs_dim, ld = Dobs + 1;
 
+  // ---- WD_CTL: the controller's LDS behind the tile: statistics, (G = 8) the policy net, one activation row per env ----
+  double *cstd = nullptr, *cmean = nullptr;
+  float *wlds = nullptr, *rowp = nullptr;
+  if constexpr (CTL) {
+    using namespace fwsim_ctl;
+    cstd = reinterpret_cast<double*>(smem_raw + Dg.stash_off);
+    cmean = cstd + kStatDoubles / 2;
+    wlds = reinterpret_cast<float*>(cstd + kStatDoubles);
+    rowp = wlds + (G == 8 ? kNetFloatsPad : 0) + row * kRowLd;
+    ctl_load_stats(input.mean, input.var, input.eps, cstd, cmean);
+    if (G == 8) {
+      int i0 = 0;
+      if ((reinterpret_cast<uintptr_t>(input.params) & 15) == 0) {       // (an allocation of its own is; a view into a larger buffer may not be)
+        const float4* __restrict__ src = reinterpret_cast<const float4*>(input.params);
+        float4* dst = reinterpret_cast<float4*>(wlds);
+        for (int i = lane; i < kNetFloats / 4; i += kWave) dst[i] = src[i];
+        i0 = kNetFloats & ~3;
+      }
+      for (int i = i0 + lane; i < kNetFloats; i += kWave) wlds[i] = input.params[i];
+    }
+    __syncthreads();                                 // (uniform: before anything diverges)
+  }
+
   int32_t step_count = D.i[IF_STEP * n + envc];
   int32_t tick = D.i[IF_TICK * n + envc];
   int32_t episode = D.i[IF_EPISODE * n + envc];
@@ -83,7 +122,7 @@ __global__ __launch_bounds__(kWave) void fw_step_kernel_wd(const Params<T>* __re
   load_rigid<T>(D, envc, S);
   T new_dist = D.r[RF_NEW_DIST * n + envc];
   T ep_return = D.r[RF_EP_RETURN * n + envc];
-  T hl_cmd[3], act[6];                               // the tail: fw_command_hl's last command, the actuator commands the observation shows
+  T hl_cmd[3], act[6];                               // the tail: fw_command_hl's last command, the actuator commands last issued (the observation shows them)
   ll_load_tail<T>(D, envc, hl_cmd, act);
   T wb[3] = {(T)0, (T)0, (T)0}, wa[3] = {(T)0, (T)0, (T)0}, wphase = (T)0;
   if (WIND) {
@@ -103,15 +142,22 @@ __global__ __launch_bounds__(kWave) void fw_step_kernel_wd(const Params<T>* __re
   const bool done_at_entry = (flags & (FL_TERM | FL_TRUNC)) != 0;
   int tgt_obs = (flags >> FL_TGT_SHIFT) & 15;        // target index the last compute_state() saw
   flags &= FL_MASK;
-  if (!done_at_entry) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) act[k] = actions[(size_t)envc * 6 + k];
-  }
   // mode -1: the surfaces take a[0..4] as given, the throttle command is 0.5 a[5] + 0.5 (as FW_TASK_LOWLEVEL)
-  const T cmd[FW_NUM_ACTUATORS] = { act[0], act[1], act[2], act[3], act[4], act[5] * (T)0.5 + (T)0.5 };
+  T cmd[FW_NUM_ACTUATORS], cmd_mine = (T)0;          // (WD_HELD only: the step's commands, and this lane's surface's)
+  if constexpr (!CTL) {
+    if (!done_at_entry) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) act[k] = input[(size_t)envc * 6 + k];
+    }
+#pragma unroll
+    for (int k = 0; k < FW_NUM_SURFACES; ++k) cmd[k] = act[k];
+    cmd[FW_NUM_SURFACES] = act[5] * (T)0.5 + (T)0.5;
+  }
   LaneAct<T> LA; LA.a = (T)0; LA.cmd = (T)0;
-  T cmd_mine = (T)0;
-  if (G == 8) { lane_act_scatter<T>(S, LA); cmd_mine = lane_pick5<T>(cmd[0], cmd[1], cmd[2], cmd[3], cmd[4]); LA.cmd = cmd_mine; }
+  if (G == 8) {
+    lane_act_scatter<T>(S, LA);
+    if constexpr (!CTL) { cmd_mine = lane_pick5<T>(cmd[0], cmd[1], cmd[2], cmd[3], cmd[4]); LA.cmd = cmd_mine; }
+  }
 
   // current and next waypoint stay in registers
   T tcur[3], tnext[3];
@@ -141,6 +187,13 @@ __global__ __launch_bounds__(kWave) void fw_step_kernel_wd(const Params<T>* __re
       ep_return += rew;
       phase = PH_DONE;
       o_rew = rew; o_flags = flags; o_reached = num_reached; o_steps = step_count;
+      if constexpr (CTL) {
+        if (input.low_action && leader) {               // the controller's output in force when the step ended (a reset below zeroes act)
+          T* la = reinterpret_cast<T*>(input.low_action) + (size_t)env * 6;
+#pragma unroll
+          for (int k = 0; k < 6; ++k) la[k] = act[k];
+        }
+      }
       if ((flags & (FL_TERM | FL_TRUNC)) && P.auto_reset) {
         if (G == 8) lane_act_gather<T>(S, LA);        // the terminal observation shows all six actuators
         if (terminal_obs && leader) {
@@ -170,13 +223,41 @@ __global__ __launch_bounds__(kWave) void fw_step_kernel_wd(const Params<T>* __re
     const bool stepped = phase != PH_DONE;
     const bool stepping = phase == PH_STEP;
     if (stepped) {
+      if constexpr (CTL) {
+        if (stepping) {
+          // ---- the controller, at the rate it was trained at: (attitude block, last actuator commands, command) -> six commands ----
+          using namespace fwsim_ctl;
+          T xa[12];
+          ctl_attitude_row<T>(S, xa);
+          if (leader) {
+#pragma unroll
+            for (int d = 0; d < 12; ++d) rowp[d] = ctl_normalise((double)xa[d], cmean[d], cstd[d], input.clip);
+#pragma unroll
+            for (int d = 0; d < 6; ++d) rowp[12 + d] = ctl_normalise((double)act[d], cmean[12 + d], cstd[12 + d], input.clip);
+#pragma unroll
+            for (int d = 0; d < 3; ++d) rowp[18 + d] = ctl_normalise((double)hl_cmd[d], cmean[18 + d], cstd[18 + d], input.clip);
+          }
+          float a[kA];
+          if constexpr (G == 8) ctl_forward<G>(wlds, rowp, sub, a);
+          else ctl_forward<G>((ctl_const_ptr)input.params, rowp, sub, a);
+#pragma unroll
+          for (int k = 0; k < 6; ++k) act[k] = (T)a[k];
+        }
+      }
       // motor noise of this Aviary step; the warm-up runs under a zero setpoint without noise
       T z0 = (T)0, z1 = (T)0;
       if (P.has_noise && stepping) rng_normal2<T>(P, genv, (uint32_t)episode, (uint32_t)(tick / P.ticks_per_aviary), z0, z1);
       T c_eff[FW_NUM_ACTUATORS];
+      if constexpr (CTL) {
 #pragma unroll
-      for (int c = 0; c < FW_NUM_ACTUATORS; ++c) c_eff[c] = stepping ? cmd[c] : (T)0;
-      LA.cmd = stepping ? cmd_mine : (T)0;
+        for (int c = 0; c < FW_NUM_SURFACES; ++c) c_eff[c] = stepping ? act[c] : (T)0;
+        c_eff[FW_NUM_SURFACES] = stepping ? act[5] * (T)0.5 + (T)0.5 : (T)0;
+        if (G == 8) LA.cmd = lane_pick5<T>(c_eff[0], c_eff[1], c_eff[2], c_eff[3], c_eff[4]);
+      } else {
+#pragma unroll
+        for (int c = 0; c < FW_NUM_ACTUATORS; ++c) c_eff[c] = stepping ? cmd[c] : (T)0;
+        LA.cmd = stepping ? cmd_mine : (T)0;
+      }
       const bool contact = aviary_step<T, WIND, G, false>(P, C, *OCp, D, envc, O, S, R, c_eff, tick, z0, z1, wb, wa, gust, mine, wmask, LA);
       if (stepping) {
         // compute_state(): WaypointHandler.distance_to_targets side effects

@@ -58,3 +58,38 @@ def test_a_changed_kernel_a_removed_one_and_a_new_one_with_scratch_each_fail():
     for bad in (NEW[:3] + (16, 0), NEW[:3] + (0, 2)):
         lines, rc = T.report(_asm([A, B]), _asm([A, B, bad]))
         assert rc == 1 and lines[lines.index("_Z1cPf") + 1].endswith("SCRATCH / VGPR SPILL") and "1 new (1 of them" in lines[-1]
+
+
+def test_a_name_map_compares_a_renamed_kernel_with_its_predecessor(tmp_path, capsys):
+    """The optional third argument, lines of `new_mangled_name old_mangled_name`: a renamed kernel with the same body is identical, one
+    with a changed instruction is DIFFERENT (exit status 1) -- neither is NEW plus REMOVED -- and a pair that names a kernel its build
+    does not have is an error."""
+    T = _tool()
+    renamed = "_Z1bILi1EEvPf"                            # _Z1bPf with one more template parameter
+    paths = {}
+    for name, text in (("parent.s", _asm([A, B])),
+                       ("same.s", _asm([(renamed,) + B[1:], (A[0], ["v_add_f32 v0, v0, v1", "s_cbranch_scc1 .LBB1_1"]) + A[2:]])),
+                       ("changed.s", _asm([A, (renamed, ["v_mul_f32 v0, v0, v2"]) + B[2:]])),
+                       ("names.txt", f"{renamed} {B[0]}\n"),
+                       ("absent_new.txt", f"_Z1zPf {B[0]}\n"), ("absent_old.txt", f"{renamed} _Z1zPf\n")):
+        (tmp_path / name).write_text(text)
+        paths[name] = str(tmp_path / name)
+    run = lambda this, *names: T.main(["kernel_resources.py", paths["parent.s"], paths[this]] + [paths[n] for n in names])
+
+    assert run("same.s", "names.txt") == 0
+    lines = capsys.readouterr().out.splitlines()
+    assert lines[-1] == "# 2 existing kernels identical, 0 different, 0 new (0 of them with scratch or spilled vector registers), 0 removed"
+    assert lines[lines.index(B[0]) + 1] == "    20 | 30 | 4 | 0 | 2 | 3 | 0 | 512 | unchanged | identical" and renamed not in lines
+
+    assert run("changed.s", "names.txt") == 1
+    lines = capsys.readouterr().out.splitlines()
+    assert lines[lines.index(B[0]) + 1].endswith("| unchanged | DIFFERENT") and lines[-1].startswith("# 1 existing kernels identical, 1 different, 0 new") and lines[-1].endswith(", 0 removed")
+
+    assert run("same.s") == 1                            # without the map: NEW plus REMOVED
+    out = capsys.readouterr().out
+    assert "1 new" in out and "1 removed" in out
+
+    for names in ("absent_new.txt", "absent_old.txt"):
+        assert run("same.s", names) == 2
+        cap = capsys.readouterr()
+        assert cap.out == "" and "name map" in cap.err and "_Z1zPf" in cap.err

@@ -1,5 +1,5 @@
 """The low-level task's second variant on the GPU: the FixedwingLowLevelEnv that the reference's examples/lowlevel.py defines for its SAC
-run (fw_step_kernel_lld / fw_reset_kernel_lld, `lowlevel_variant = 1`).  Line numbers are examples/lowlevel.py's.
+run (fw_step_kernel_ll / fw_reset_kernel_ll with V = 1, `lowlevel_variant = 1`).  Line numbers are examples/lowlevel.py's.
 
 As for the first variant (tests/test_lowlevel_gpu.py) the CPU oracle has no such task, so the kernels are checked in two ways:
 * physics: the oracle's mode-0 path behind a routing mixer sees the actuator commands the kernel gets; rigid state and actuators

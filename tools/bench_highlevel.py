@@ -22,7 +22,7 @@ Legs (one JSON line per leg, size and launch mode):
              --updates updates after a warm-up update, fused beside torch.
   hz         the controller rate (HighLevelCmdVecEnv(controller_hz=...)), every rate of --controller_hz in the same session, f64,
              graph-replayed: the vec-step (30: fw_command_hl -> fw_collect_act_a -> fw_step; 120: fw_command_hl -> fw_step_hl), the
-             step launch alone (fw_step with low_action as it stands / fw_step_hl) and the fused collected vec-step of rollout.PPO
+             step launch alone (fw_step with low_action as it stands / fw_step_hl: fw_step_kernel_wd with SRC = WD_HELD / WD_CTL) and the fused collected vec-step of rollout.PPO
              (fw_collect_act_hl -> step_low -> fw_collect_stats).  Each line carries its ratio to the 30 Hz line of the same session.
 Modes: "graph" replays a captured hipGraph of 64 vec-steps, "eager" launches them one by one.  A timed region is --steps vec-steps
 between two device synchronisations; --repeats regions, the median is reported with the spread.  Under `rocprofv3 --kernel-trace
@@ -327,7 +327,7 @@ def main():
                         resets=env.get_counters()["resets"], rejected=int(env.rejected.item()))
                 r = graph_us(env.step_low)
                 r["us_per_call"] = r.pop("us_per_vec_step")
-                emit_hz("step_launch_alone", hz, r, kernel="fw_step_kernel_wdc" if env.controller_in_step else "fw_step_kernel_wd")
+                emit_hz("step_launch_alone", hz, r, kernel="fw_step_kernel_wd<WD_CTL>" if env.controller_in_step else "fw_step_kernel_wd<WD_HELD>")
                 env.close()
             for hz in a.controller_hz:
                 ppo = hl_ppo(n, True, a.n_steps, controller_hz=hz)

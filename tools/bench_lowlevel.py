@@ -1,4 +1,4 @@
-"""Step time of the low-level task's kernels (fw_step_kernel_ll; --variant 1: fw_step_kernel_lld, the SAC script's env), which
+"""Step time of the low-level task's kernels (fw_step_kernel_ll<T, G, WIND, V>; --variant 1: V = 1, the SAC script's env), which
 bench.py does not cover.
 
     python tools/bench_lowlevel.py [--envs 4096] [--steps 2000] [--warmup 200] [--lanes 1|8] [--dtype float64|float32] [--variant 0|1]

@@ -1,12 +1,17 @@
 """Per-kernel resources of two builds of csrc/fwsim.hip, side by side: registers, scratch, occupancy, spills, LDS, and whether a
 kernel's device code is the same in both.
 
-    python tools/kernel_resources.py PARENT.s THIS.s > profiles/rNN_<what>_resources.txt
+    python tools/kernel_resources.py PARENT.s THIS.s [NAMES.txt] > profiles/rNN_<what>_resources.txt
 
 PARENT.s / THIS.s: the gfx950 device assembly of the two builds (`hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared
 -save-temps`, the file `*-hip-amdgcn-amd-amdhsa-gfx950.s`).  The comparison is the one of `tools/check_isa.py --same-device-code`
 (its `functions()`); this tool only adds the table of figures, read from the code-object metadata and the "Kernel info" comment of
-each kernel.  Exits non-zero when an existing kernel differs or is gone, or a new one uses scratch or spills vector registers."""
+each kernel.  Exits non-zero when an existing kernel differs or is gone, or a new one uses scratch or spills vector registers.
+
+NAMES.txt (optional): lines of `new_mangled_name old_mangled_name`, for a change that renames kernels (a template that gains a
+parameter, two kernels that become one).  THIS.s is read with every new name replaced by its old one, so a renamed kernel is compared
+with its predecessor instead of being listed as NEW plus REMOVED.  A pair whose new name is not a function of THIS.s, or whose old name
+is not one of PARENT.s, is an error (exit status 2)."""
 import os
 import re
 import sys
@@ -65,7 +70,37 @@ def report(parent_text, this_text):
     return lines, (1 if diff or bad_new or gone else 0)
 
 
-if __name__ == "__main__":
-    table, rc = report(open(sys.argv[1]).read(), open(sys.argv[2]).read())
+def rename(parent_text, this_text, pairs):
+    """this_text with the new mangled name of every (new, old) pair replaced by the old one; ValueError for a pair that names a
+    kernel its build does not have, or an old name that this build still uses."""
+    old_names, new_names = set(functions(parent_text)), set(functions(this_text))
+    for new, old in pairs:
+        if new not in new_names:
+            raise ValueError(f"name map: {new} is not a function of THIS.s")
+        if old not in old_names:
+            raise ValueError(f"name map: {old} is not a function of PARENT.s")
+        if old in new_names:
+            raise ValueError(f"name map: {old} is still a function of THIS.s")
+    to_old = dict(pairs)
+    return re.sub(r"\b_Z\w+", lambda m: to_old.get(m.group(0), m.group(0)), this_text)
+
+
+def main(argv):
+    parent, this = open(argv[1]).read(), open(argv[2]).read()
+    pairs = []
+    if len(argv) > 3:
+        pairs = [tuple(l.split()) for l in open(argv[3]).read().splitlines() if l.strip() and not l.startswith("#")]
+        try:
+            this = rename(parent, this, pairs)
+        except ValueError as e:
+            print(e, file=sys.stderr)
+            return 2
+    table, rc = report(parent, this)
+    if pairs:
+        table.insert(4, f"# {len(pairs)} kernels of this build are listed under their predecessors' names ({os.path.basename(argv[3])}: new name -> old name)")
     print("\n".join(table))
-    sys.exit(rc)
+    return rc
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))
