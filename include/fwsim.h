@@ -875,6 +875,11 @@ int32_t fw_aux_wave(fw_handle h);
  * integers are constants of the kernel instead of loads; environment variable FWSIM_STEP_SHAPE=0 at fw_create turns it off, no value
  * turns it on for another config), else 0.  Diagnostic; results are bit-identical to the noise-wave kernel. */
 int32_t fw_step_shape(fw_handle h);
+/* 1 when this handle's fw_step runs the fixed-shape kernel whose second wave stays to the end of the launch (behind the noise draw it
+ * pre-samples the next episodes' waypoints for its own tile -- the grid has no worker workgroups -- and then writes the observation
+ * rows, the terminal observations among them, while the step wave stores state and counters; up to 4096 envs; environment variable
+ * FWSIM_OBS_WAVE=0|1 at fw_create overrides where fw_step_shape is 1; default on), else 0.  Diagnostic; results are bit-identical. */
+int32_t fw_obs_wave(fw_handle h);
 /* TEST HOOK, not used by the product: evaluates ONE device building block (a __device__ function of csrc/fwsim_device.hpp, called,
  * not copied) on n rows.  `in` [n, in_cols] and `out` [n, out_cols] are DEVICE buffers of doubles; the constants (Params / TickC /
  * SurfC as fw_create folded them) and the dtype are the handle's: a row is converted to the handle's dtype inside the kernel and

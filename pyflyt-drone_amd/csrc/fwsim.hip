@@ -229,10 +229,11 @@ __device__ __forceinline__ void shadow_worker(const Params<T>* __restrict__ Pp, 
 // Wind-free waypoints: the reset itself is cached (warm state, its observation), what remains per env is sampling the next
 // episode's waypoints (3 Philox blocks + 2 sincos per waypoint).  The same hand-off as above lets a worker block do that
 // ahead of time into the shadow's waypoint rows; the reset then only copies 3 words per lane (requested at launch start).
-template <typename T, int G>
+// (WAVE1: the caller is the second wave of a step workgroup working that workgroup's own tile, fw_step_kernel_g8xo; every other caller is wave 0)
+template <typename T, int G, bool WAVE1 = false>
 __device__ __forceinline__ void scenario_worker(const Params<T>* __restrict__ Pp, DevState<T> D, int blk) {
   constexpr int EPW = kWave / G;
-  const int lane = threadIdx.x, sub = (G == 1) ? 0 : (lane & (G - 1)), row = lane / G;
+  const int lane = WAVE1 ? threadIdx.x & (kWave - 1) : threadIdx.x, sub = (G == 1) ? 0 : (lane & (G - 1)), row = lane / G;
   const int env = blk * EPW + row;
   const bool active = env < D.n;
   const int envc = active ? env : D.n - 1;
@@ -287,6 +288,8 @@ constexpr bool getenv_ph = false;
 #define FWP(...)
 #endif
 
+constexpr int kObsHandWords = 20;   // fw_step_kernel_g8xo: words per env of the LDS block the step wave hands the observation wave (step_body OBSW)
+
 // Per-lane phase of the fused step state machine.
 enum Phase : int { PH_STEP = 0, PH_WARM = 1, PH_DONE = 2 };
 
@@ -319,8 +322,15 @@ enum Phase : int { PH_STEP = 0, PH_WARM = 1, PH_DONE = 2 };
 // variants become constants, and the four numbers of the task logic that stay run-time values (max_steps, auto_reset, dome, reach) are
 // loaded once in front of the sub-step loop.  Integers only: the floating-point results are those of the run-time shape, bit for
 // bit (sum_squares_fma pins the two sums of squares whose FMA contraction would otherwise follow the shape of the loop around them).
+// OBSW = the second wave stays to the end of the launch (fw_step_kernel_g8xo; a fixed shape with AUX only).  Behind barrier 1 it is the
+// scenario worker of its own tile -- the grid has no worker half, which could not start before whole step workgroups had left -- and
+// then the observation writer: the step wave leaves what the pass reads (rigid state, actuators, target index, a mode word per env:
+// 0 no reset, 1 reset whose first row the worker left, 2 reset by the in-kernel fallback) in LDS behind the normals, the waves meet at
+// a SECOND __syncthreads() behind the end-of-step latch, and the second wave runs the pass, the terminal-observation copy and the
+// flush while the step wave stores state, counters and -- mode 2 only -- the new episode's row, straight to memory (the flush skips
+// those rows: no word of `obs` has two writers).  Both waves execute both barriers unconditionally; nothing else synchronises them.
 template <typename T, bool GENERAL, int G, int TKIND, int WPE = 1, bool COLLECT = false, bool HELP = false, bool AX = false, bool AUX = false,
-          typename SH = ShapeOfParams>
+          typename SH = ShapeOfParams, int OBSM = 0>
 __device__ __forceinline__
 void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp, DevState<T> Dg,
                const T* __restrict__ actions, T* __restrict__ obs, T* __restrict__ reward,
@@ -339,6 +349,10 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   // sampling inside the step loop, and the waves that contain a reset finish with the others.
   constexpr bool DEFER = !GENERAL && TKIND == FW_TASK_WAYPOINTS;
   static_assert(!SH::kFixed || (std::is_same<T, double>::value && DEFER && G == 8 && !COLLECT && !HELP), "a fixed shape is threaded through the wind-free 8-lane waypoints path only");
+  // OBSM: 0 = no such wave; 2 = fw_step_kernel_g8xo as described above; 1 = its first half alone, for measuring part by part (-DFW_OBSW_MODE=1:
+  // the grid without worker workgroups and the second wave as scenario worker, which then returns; the step wave keeps the whole epilogue)
+  constexpr bool OBSG = OBSM != 0, OBSW = OBSM == 2;
+  static_assert(!OBSG || (SH::kFixed && AUX), "the observation wave is the noise wave of a fixed shape");
   const int nblk = (Dg.npad + EPW - 1) / EPW;        // step blocks; blocks beyond are shadow workers
   FWP(const long long p_t0 = FWP_NOW(); long long p_reset = 0, p_avi = 0, p_task = 0, p_r1 = 0, p_r2 = 0, p_r3 = 0; int p_nreset = 0, p_nhit = 0;)
   // XCD-aware block -> env-block map (G = 8): a wave touches 64 B of every SoA row, i.e. half a 128-B L2 line, and
@@ -351,8 +365,8 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   const int wg = SH::kFixed ? (bx >= nblk ? bx - nblk : bx) : bx % nblk;
   const int blk = (G == 8 && (nblk & 7) == 0) ? (wg & 7) * (nblk >> 3) + (wg >> 3) : wg;
   const DevState<T> D = tile_view<T, EPW>(Dg, blk);  // this wave's tile: row stride EPW (a compile-time constant), global env ids
-  if ((GENERAL || DEFER) && bx >= nblk) {
-    if (AUX && threadIdx.x >= kWave) return;         // (a worker workgroup's second wave has nothing to do)
+  if (!OBSG && (GENERAL || DEFER) && bx >= nblk) {    // (OBSG: the grid is the step workgroups alone)
+    if (AUX && threadIdx.x >= kWave) return;        // (a worker workgroup's second wave has nothing to do)
     DevState<T> Dw = D;
     if constexpr (SH::kFixed) Dw.epoch = launch_index(Dg.lctr);     // a fixed shape numbers its launches in here (see `lctr_v` below): a worker reads its counter at once
     if (GENERAL) shadow_worker<T, G, TKIND>(Pp, OCp, Dw, blk); else scenario_worker<T, G>(Pp, Dw, blk);
@@ -377,6 +391,9 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   // AUX, second wave: the normals of my lane's Aviary step -- the very call the step wave of the one-wave kernel makes below (same
   // lane map, same arguments, zeros where that wave draws nothing) -- left in LDS for the step wave; then the barrier, and done.
   T* aux_nz = AUX ? reinterpret_cast<T*>(smem_raw + Dg.mbox_off) : nullptr;     // [kWave][2], behind tile and stash (step_lds_bytes_h)
+  // OBSW: the hand-off block behind the normals, kObsHandWords words per env: p, q, v, w (0-12), the five surface actuators (13-17, each
+  // from the lane that owns it), the motor (18), and two integers in word 19: the target index of the last compute_state, the mode
+  T* obs_hand = OBSW ? aux_nz + 2 * kWave : nullptr;
   if constexpr (AUX) {
     if (threadIdx.x >= kWave) {
       const int32_t a_tick = D.i[IF_TICK * n + envc], a_episode = D.i[IF_EPISODE * n + envc], a_flags = D.i[IF_FLAGS * n + envc];
@@ -385,6 +402,99 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
         rng_normal2<T>(P, (uint32_t)(P.env_offset + envc), (uint32_t)a_episode, (uint32_t)(a_tick / FW_SH(ticks_per_aviary)) + (uint32_t)sub, a_z0, a_z1);
       aux_nz[2 * lane] = a_z0; aux_nz[2 * lane + 1] = a_z1;
       __syncthreads();                               // barrier 1 (the step wave's is in front of its sub-step loop)
+      if constexpr (OBSG) {
+        // ---- the scenario worker of this tile: requests of earlier launches only (the step wave writes this launch's `sreq` behind
+        // barrier 2), and nothing it writes is read in this launch (the `launch` field of `sdone`, tested by the step wave) ----
+        FWP(const long long o_t1 = FWP_NOW();)
+        // (the env count through a scalar register of its own: read as a part of the kernel-argument tuple it keeps all eight of that tuple's
+        // registers live across the worker, and the allocator, short of scalar registers there, reserves a stack slot that it then never uses)
+        int o_n = D.n;
+        asm volatile("" : "+s"(o_n));
+        const uint32_t o_launch = launch_index(Dg.lctr);     // the workgroup's counter: the step wave advances it at the very end, behind barrier 2
+        if (D.shadow_on) {
+          DevState<T> Dw = D;
+          Dw.epoch = o_launch; Dw.n = o_n;
+          scenario_worker<T, G, true>(Pp, Dw, blk);
+        }
+        FWP(const long long o_t2 = FWP_NOW();)
+        if constexpr (!OBSW) {                       // (the measuring build with the first half alone: done; the counter word was read ~25 k cycles before the step wave stores it)
+          FWP(if (D.prof && lane == 0) { long long* w = D.prof + ((size_t)(o_launch % kProfSlots) * 2 * nblk + nblk + blockIdx.x) * kProfWords; w[0] = o_t2 - o_t1; w[1] = o_t1 - p_t0; w[6] = o_t2 - p_t0; w[7] = p_t0; })
+          return;
+        } else {
+        // ---- what the observation pass needs and the launch does not change, on the step wave's lane map; unconditional, so that
+        // no load waits behind barrier 2 (this wave has the whole sub-step loop to spare) ----
+        const int o_gbase = lane & ~(G - 1);
+        T o_tmine[3] = {(T)0, (T)0, (T)0};
+        if (sub < SH::num_targets) {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) o_tmine[k] = D.r[(size_t)(RF_TARGETS + 3 * sub + k) * n + envc];
+        }
+        const T o_keep = actions[(size_t)envc * 4 + (sub & 3)];
+        T o_act[4], o_stale[4], o_dow[4] = {(T)0, (T)0, (T)0, (T)0};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { o_act[k] = __shfl(o_keep, o_gbase | k, kWave); o_stale[k] = D.r[(size_t)(RF_ACTION + k) * n + envc]; }
+        if (a_flags & (FL_TERM | FL_TRUNC)) {        // done at entry (bare-Gymnasium view): the stored action
+#pragma unroll
+          for (int k = 0; k < 4; ++k) o_act[k] = o_stale[k];
+        }
+        static_assert(!OBSW || SH::obs_dim <= 4 * G, "the env's eight lanes hold the worker's first row in four words each");
+        static_assert(!OBSW || SH::att_dim <= 32, "the step wave's fallback row takes its cached attitude block from the env's lanes (kWO * G words): no tile write is left behind barrier 2");
+        if (D.shadow_on) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { const int k = sub + j * G; if (k < Dobs) o_dow[j] = Dg.sobs[(size_t)envc * Dobs + k]; }
+        }
+        FWP(const long long o_t3 = FWP_NOW();)
+        __syncthreads();                             // barrier 2 (the step wave's is behind its end-of-step latch)
+        FWP(const long long o_t4 = FWP_NOW();)
+        const T* hr = obs_hand + row * kObsHandWords;
+        Rigid<T> So;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { So.p[k] = hr[k]; So.v[k] = hr[7 + k]; So.w[k] = hr[10 + k]; }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) So.q[k] = hr[3 + k];
+#pragma unroll
+        for (int k = 0; k < FW_NUM_ACTUATORS; ++k) So.act[k] = hr[13 + k];
+        const int o_tgt = reinterpret_cast<const int*>(hr + 19)[0], o_mode = reinterpret_cast<const int*>(hr + 19)[1];
+        // the pass of the one-wave epilogue, call for call
+        T Ro[9];
+        int o = write_obs_attitude<T, true, SH>(P, So, o_act, Ro, [&](int k, T v) { if (leader) tile[row * ld + k] = v; });
+#pragma unroll SH::kCtxUnroll
+        for (int i = 0; i < SH::ctx; ++i) {
+          const int t = o_tgt + i;
+          T tw[3], d[3], b[3] = {(T)0, (T)0, (T)0};
+#pragma unroll
+          for (int k = 0; k < 3; ++k) tw[k] = __shfl(o_tmine[k], o_gbase | (t & (G - 1)), kWave);
+          if (t < SH::num_targets) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) d[k] = tw[k] - So.p[k];
+            mtv(Ro, d, b);
+          }
+          if (leader) { tile[row * ld + o] = b[0]; tile[row * ld + o + 1] = b[1]; tile[row * ld + o + 2] = b[2]; }
+          o += 3;
+        }
+        if (o_mode != 0) {                           // group-uniform: the row just written is the terminal observation
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          if (terminal_obs) {
+            T* trow = terminal_obs + (size_t)env * Dobs;
+            for (int k = sub; k < Dobs; k += G) trow[k] = tile[row * ld + k];
+          }
+          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+          if (o_mode == 1) {                         // ... and the new episode's row is the one the worker left
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { const int k = sub + j * G; if (k < Dobs) tile[row * ld + k] = o_dow[j]; }
+          }
+        }
+        FWP(const long long o_t5 = FWP_NOW();)
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+        // flush_obs_tile on this wave's lanes, without the rows the step wave stores itself (mode 2)
+        flush_obs_tile_rows<T>(tile, ld, obs, env0, EPW, o_n, Dobs, lane,
+                               [&](int r) { return reinterpret_cast<const int*>(obs_hand + r * kObsHandWords + 19)[1] != 2; });
+        FWP(if (D.prof && lane == 0) {               // this wave's slot: the one a worker workgroup of the two-half grid has
+          long long* w = D.prof + ((size_t)(o_launch % kProfSlots) * 2 * nblk + nblk + blockIdx.x) * kProfWords;
+          const long long o_t6 = FWP_NOW();
+          w[0] = o_t2 - o_t1; w[1] = o_t1 - p_t0; w[2] = o_t3 - o_t2; w[3] = o_t4 - o_t3; w[4] = o_t5 - o_t4; w[5] = o_t6 - o_t5; w[6] = o_t6 - p_t0; w[7] = p_t0; })
+        }
+      }
       return;
     }
   }
@@ -432,7 +542,11 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
 
   normalize_quat<T>(S.q);
   T R[9];
-  rot_from_unit_quat<T>(S.q, R);
+  // A fixed shape spells the contraction out.  In fw_step_kernel_g8xo, without the worker branch in front, the plain form came out with the
+  // other product of each sum fused (one ulp in v once in a few hundred env-steps, tests/test_obs_wave_gpu.py); the spelled-out form is what
+  // the compiler makes of the plain one in the prologues of the other step kernels (read from their assembly, not from their source), and
+  // fw_step_kernel_g8xs compiles to the code it had with either, so the twins share the one that does not depend on the compiler's choice.
+  if constexpr (OBSG || SH::kFixed) rot_from_unit_quat_fma<T>(S.q, R); else rot_from_unit_quat<T>(S.q, R);
   ObjState<T> O;
   const ObjC<T>& OC = *OCp;
   if (HASOBJ) { obj_load<T, OBJ>(D, envc, O); obj_update_near_mask<T, G>(P, OC, D, envc, O, S); }
@@ -945,7 +1059,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   FWP(const long long p_t2 = FWP_NOW();)
   // G = 8: waypoints sampled by sibling lanes during an in-launch reset are read back below
   if (G > 1 && !DEFER) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  if (G == 8) lane_act_gather<T>(S, LA);             // S.act[0..4] current again for the observation and the state store
+  if (G == 8 && !OBSW) lane_act_gather<T>(S, LA);    // S.act[0..4] current again for the observation and the state store (OBSW: through the hand-off block below)
   // DEFER: the waypoint a worker block sampled ahead of time for my next episode, requested only by resetting envs and only
   // now -- its latency hides behind the observation pass below
   T tpre[3] = {(T)0, (T)0, (T)0};
@@ -955,6 +1069,26 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   const uint32_t launch = SH::kFixed ? 1u + (uint32_t)__builtin_amdgcn_readfirstlane((int)lctr_v) : D.epoch;
   const bool pre = DEFER && resetting && D.shadow_on && (int)(sh_done & 0xFF) == 1 && (uint32_t)(sh_done >> 32) == (uint32_t)(episode + 1) &&
                    (uint32_t)((sh_done >> 8) & 0xFFFFFFu) != (launch & 0xFFFFFFu);
+  if constexpr (OBSW) {
+    // What the observation pass reads, for the second wave; then barrier 2 -- every lane of both waves, whatever its env does.  From
+    // here on the tile, the terminal observation and the `obs` rows of modes 0 and 1 belong to that wave.
+    T* hr = obs_hand + row * kObsHandWords;
+    if (leader) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { hr[k] = S.p[k]; hr[7 + k] = S.v[k]; hr[10 + k] = S.w[k]; }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) hr[3 + k] = S.q[k];
+      hr[13 + FW_NUM_SURFACES] = S.act[FW_NUM_SURFACES];
+      reinterpret_cast<int*>(hr + 19)[0] = tgt_obs;
+      reinterpret_cast<int*>(hr + 19)[1] = resetting ? (pre ? 1 : 2) : 0;
+    }
+    if (sub < FW_NUM_SURFACES) hr[13 + sub] = LA.a;
+    FWP(p_r1 = FWP_NOW();)
+    __syncthreads();
+    FWP(p_r1 = FWP_NOW() - p_r1;)                    // the wait at barrier 2
+#pragma unroll
+    for (int k = 0; k < FW_NUM_SURFACES; ++k) S.act[k] = hr[13 + k];       // lane_act_gather, for the state store
+  }
   if (pre) {      // (every lane issues: rows >= num_targets of the shadow are zero and are not stored back)
 #pragma unroll
     for (int k = 0; k < 3; ++k) pf_issue(tpre[k], &D.rs[(size_t)(RF_TARGETS + 3 * sub + k) * n + env]);
@@ -963,7 +1097,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   constexpr bool WO = DEFER && G == 8;               // (one lane per env: the block is copied straight from memory below)
   constexpr int kWO = WO ? 32 / G : 1;
   T wo[kWO];
-  if (WO && resetting) {
+  if (WO && resetting && !(OBSW && pre)) {           // (OBSW: the step wave builds the new row on the fallback path alone)
 #pragma unroll
     for (int j = 0; j < kWO; ++j) { const int k = sub + j * G; wo[j] = (k < FW_SH(att_dim)) ? vload(&Pp->warm_obs[k]) : (T)0; }
   }
@@ -973,7 +1107,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
   T dow[kDOW], dnd = (T)0;
   if (WO && pre && Dobs <= kDOW * G) {
 #pragma unroll
-    for (int j = 0; j < kDOW; ++j) { const int k = sub + j * G; dow[j] = (T)0; if (k < Dobs) pf_issue(dow[j], &Dg.sobs[(size_t)env * Dobs + k]); }
+    for (int j = 0; j < kDOW; ++j) { const int k = sub + j * G; dow[j] = (T)0; if (!OBSW && k < Dobs) pf_issue(dow[j], &Dg.sobs[(size_t)env * Dobs + k]); }     // (OBSW: the second wave has the row)
     pf_issue(dnd, &D.rs[(size_t)RF_NEW_DIST * n + env]);
   }
 
@@ -1015,6 +1149,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
 #pragma unroll
       for (int k = 0; k < 4; ++k) act_obs[k] = D.r[(size_t)(RF_ACTION + k) * n + envc];
     }
+    if constexpr (!OBSW) {                           // (OBSW: the second wave runs the pass; act_obs is kept for the state store)
     T Ro[9];
     int o = write_obs_attitude<T, true, SH>(P, S, act_obs, Ro, [&](int k, T v) { if (leader) tile[row * ld + k] = v; });
 #pragma unroll SH::kCtxUnroll
@@ -1031,6 +1166,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
       if (leader) { tile[row * ld + o] = b[0]; tile[row * ld + o + 1] = b[1]; tile[row * ld + o + 2] = b[2]; }
       o += 3;
     }
+    }
   } else if (active && leader) {
     load_action<T, COLLECT>(D, actions, env, act_src, act_obs);
     if (OBJ) obj_write_obs<T>(P, O, S, act_obs, [&](int k, T v) { tile[row * ld + k] = v; });
@@ -1042,17 +1178,21 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
     // the hand-issued prefetches: ONE wait, here -- behind the observation pass and AHEAD of the terminal-observation stores below
     // (vmcnt counts stores too: a wait placed after them pays their acknowledgement, ~2 k cycles) -- tied to every value
     pf_wait(tpre[0], tpre[1], tpre[2], dnd);
-    if (WO) pf_tie(dow[0], dow[1], dow[2], dow[3]);
+    if (WO && !OBSW) pf_tie(dow[0], dow[1], dow[2], dow[3]);
   }
   if (DEFER && resetting) {                          // group-uniform: all G lanes of the env take part
-    // the row just written is the terminal observation: move it out before the new episode's row replaces it
+    // the row just written is the terminal observation: move it out before the new episode's row replaces it (OBSW: the second wave does)
+    if constexpr (!OBSW) {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     if (terminal_obs) {
       T* trow = terminal_obs + (size_t)env * Dobs;
       for (int k = sub; k < Dobs; k += G) trow[k] = tile[row * ld + k];
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    FWP(const long long p_e1 = FWP_NOW(); p_r1 = p_e1 - p_e0;)      // obs pass end -> terminal observation copied out
+    }
+    FWP(const long long p_e1 = FWP_NOW(); if (!OBSW) p_r1 = p_e1 - p_e0;)      // obs pass end -> terminal observation copied out (OBSW: p_r1 is the wait at barrier 2)
+    // the new episode's row goes into the tile -- or (OBSW, where only the fallback path gets here with a row to build) straight to memory
+    T* const orow = OBSW ? obs + (size_t)env * Dobs : nullptr;
     episode += 1;
     if (leader) { stat_add(D.stats, FW_CTR_RESETS); stat_add(D.stats, pre ? FW_CTR_SCENARIO_HITS : FW_CTR_FALLBACKS); }
     Scenario<T> sc;
@@ -1070,7 +1210,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
     const int nt = min(FW_SH(ctx), FW_SH(num_targets));
     T t0[3] = {(T)0, (T)0, (T)0};
     const bool copied = WO && pre && Dobs <= kDOW * G;    // the worker left the whole first observation row: nothing to compute
-    if (copied) {
+    if (copied && !OBSW) {
 #pragma unroll
       for (int j = 0; j < kDOW; ++j) { const int k = sub + j * G; if (k < Dobs) tile[row * ld + k] = dow[j]; }
     }
@@ -1091,12 +1231,13 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
         mtv(P.warm_R, d, b);
         if (i == 0) { t0[0] = tw[0]; t0[1] = tw[1]; t0[2] = tw[2]; }
       }
-      if (leader) { tile[row * ld + FW_SH(att_dim) + 3 * i] = b[0]; tile[row * ld + FW_SH(att_dim) + 3 * i + 1] = b[1]; tile[row * ld + FW_SH(att_dim) + 3 * i + 2] = b[2]; }
+      if (OBSW) { if (leader) { orow[SH::att_dim + 3 * i] = b[0]; orow[SH::att_dim + 3 * i + 1] = b[1]; orow[SH::att_dim + 3 * i + 2] = b[2]; } }
+      else if (leader) { tile[row * ld + FW_SH(att_dim) + 3 * i] = b[0]; tile[row * ld + FW_SH(att_dim) + 3 * i + 1] = b[1]; tile[row * ld + FW_SH(att_dim) + 3 * i + 2] = b[2]; }
     }
     FWP(const long long p_e2 = FWP_NOW(); p_r2 = p_e2 - p_e1;)      // new waypoints stored, their deltas in the tile
     if (WO && !copied) {
 #pragma unroll
-      for (int j = 0; j < kWO; ++j) { const int k = sub + j * G; if (k < FW_SH(att_dim)) tile[row * ld + k] = wo[j]; }   // the env's lanes share the cached attitude block
+      for (int j = 0; j < kWO; ++j) { const int k = sub + j * G; if (k < FW_SH(att_dim)) { if (OBSW) orow[k] = wo[j]; else tile[row * ld + k] = wo[j]; } }   // the env's lanes share the cached attitude block
     }
     if (!copied) for (int k = sub + (WO ? kWO * G : 0); k < FW_SH(att_dim); k += G) tile[row * ld + k] = Pp->warm_obs[k];
 #pragma unroll
@@ -1178,11 +1319,12 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
       ip[1] = make_int4(o_st, OBJ ? o_st : 0, o_sc, 0);
     }
   }
-  if (HELP || AUX) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }   // (the capture / second wave takes no part: no s_barrier)
+  if (OBSW) {}                                       // (the second wave flushes the tile it wrote)
+  else if (HELP || AUX) { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); }   // (the capture / second wave takes no part: no s_barrier)
   else __syncthreads();
   // (COLLECT: the partial sums first -- the fold waves at the end of the launch are waiting for them, nobody for the observation rows)
   if (COLLECT) collect_stats_tail<T>(*CAp, D.epoch, tile, ld, min(EPW, D.n - env0), wg, nblk, active && leader, latch[4 * row], latch[4 * row + 1] != 0.0, env, c_ret);
-  flush_obs_tile<T>(tile, ld, obs, env0, EPW, D.n, Dobs);
+  if (!OBSW) flush_obs_tile<T>(tile, ld, obs, env0, EPW, D.n, Dobs);
   if (COLLECT && active && leader) collect_clear_actions<T>(const_cast<T*>(actions) + (size_t)env * 4);      // "not there yet" for the next launch
   FWP(long long p_capmax = HASOBJ ? O.p_cap : 0; const int p_ncapw = HASOBJ ? __popcll(__ballot(leader && O.p_ncap > 0)) : 0;)
   FWP(if (D.prof) {
@@ -1226,6 +1368,14 @@ template <typename T>
 __global__ __launch_bounds__(2 * kWave) void fw_step_kernel_g8xs(FW_STEP_ARGS) {
   // (not FW_STEP_RUN: step_body reads and advances the launch counter itself where the shape is fixed, off the path to the state loads)
   step_body<T, false, 8, FW_TASK_WAYPOINTS, 1, false, false, true, true, ShapeTrainWaypoints>(FW_STEP_PASS);
+}
+#ifndef FW_OBSW_MODE
+#define FW_OBSW_MODE 2   // 1: a measuring build with the grid change and the worker alone (step_body OBSM; profiles/r24_obs_wave_ab.txt)
+#endif
+// ... and that one with the second wave kept to the end: scenario worker of its tile, then the observation rows (step_body OBSW; fw_env::obs_wave)
+template <typename T>
+__global__ __launch_bounds__(2 * kWave) void fw_step_kernel_g8xo(FW_STEP_ARGS) {
+  step_body<T, false, 8, FW_TASK_WAYPOINTS, 1, false, false, true, true, ShapeTrainWaypoints, FW_OBSW_MODE>(FW_STEP_PASS);
 }
 // ... and the same mapping capped at 256 registers: two waves per SIMD (8 192 < N <= 65 536 envs)
 template <typename T, bool GENERAL>
@@ -1490,6 +1640,7 @@ void fw_reset_kernel(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict
 // ======================================================================
 namespace {
 
+constexpr bool kObsWaveDefault = true;    // the observation-wave row (fw_step_kernel_g8xo) is on wherever it exists: measured at 4096 and 2048 envs, profiles/r24_obs_wave_ab.txt
 constexpr int kAuxWaveMaxEnvs = 4096;  // noise wave beside every step wave (fw_step_kernel_g8x): 512 two-wave workgroups, one wave per SIMD on 1024 SIMDs
 constexpr int kG8MaxEnvs = 16384;   // measured crossover on MI355X: 8 lanes/env wins up to 2^14 envs (51 vs 70 us), loses at 2^15 (93 vs 76 us)
 thread_local std::string g_err;
@@ -1718,6 +1869,7 @@ struct fw_env {
   int32_t capture_wave = 0;     // 8-lane mapping, camera tasks: fw_step workgroups carry a capture wave (fw_step_kernel_obj_g8h)
   int32_t aux_wave = 0;         // the axis-aligned row with motor noise, up to kAuxWaveMaxEnvs envs: a second wave per step workgroup draws the noise (fw_step_kernel_g8x)
   int32_t step_shape = 0;       // the noise-wave row on the headline training config's shape (step_shape_of): that kernel with the shape compiled in (fw_step_kernel_g8xs)
+  int32_t obs_wave = 0;         // the fixed-shape row with its second wave kept to the end of the launch: scenario worker of its tile, then the observation rows (fw_step_kernel_g8xo)
   int32_t axis_aligned = 0;     // f64 wind-free waypoints on the 8-lane one-wave build: the tick's axis-aligned variant (axis_aligned_geometry)
   EnvKernel step, reset, collect;   // chosen once by fw_create from the fields above (select_kernels); collect.fn is null where fw_collect_step does not serve
   EnvKernel step_hl;                // fw_step_hl's kernel (hl_step_kernel_of); null where fw_step_hl does not serve
@@ -1834,7 +1986,11 @@ template <typename T> size_t tile_bytes(const fw_env* h) {
 // dynamic LDS of a step launch: the tile (or the camera's map) + the output stash of the envs of a wave
 template <typename T> size_t step_lds_bytes(const fw_env* h) { return ((tile_bytes<T>(h) + 15) & ~(size_t)15) + sizeof(double) * 4 * (size_t)(kWave / h->lanes_per_env); }
 // ... of a step launch whose workgroups carry a second wave: + the capture mailbox, or the noise wave's [kWave][2] normals in its place (DevState::mbox_off)
-template <typename T> size_t step_lds_bytes_h(const fw_env* h) { return ((step_lds_bytes<T>(h) + 15) & ~(size_t)15) + std::max(mbox_bytes(sizeof(T)), sizeof(T) * 2 * (size_t)kWave); }
+// ... and behind the normals, where the second wave writes the observation rows, the step wave's hand-off block ([envs per wave][kObsHandWords], step_body OBSW)
+template <typename T> size_t step_lds_bytes_h(const fw_env* h) {
+  const size_t hand = h->obs_wave ? sizeof(T) * (size_t)kObsHandWords * (size_t)(kWave / h->lanes_per_env) : 0;
+  return ((step_lds_bytes<T>(h) + 15) & ~(size_t)15) + std::max(mbox_bytes(sizeof(T)), sizeof(T) * 2 * (size_t)kWave + hand);
+}
 inline dim3 grid_of(const fw_env* h) { return dim3((unsigned)(h->npad / (kWave / h->lanes_per_env))); }
 
 // ObjLock task constants (analytic camera axes, shaping coefficients of envs/fixedwing_objlock_env.py:54-80)
@@ -1901,7 +2057,7 @@ int upload_params(fw_env* h) {
 // A key names the fields of a handle that the choice depends on; kAny in a row matches every value.  The first row that matches
 // wins, so a special case stands above the general one.  A new kernel variant is one new row.
 constexpr int kAny = -1;
-struct KernelKey { int task, lanes, waves, windy, axis_aligned, capture_wave, aux_wave, step_shape, variant; };   // variant: fw_config.lowlevel_variant
+struct KernelKey { int task, lanes, waves, windy, axis_aligned, capture_wave, aux_wave, step_shape, obs_wave, variant; };   // variant: fw_config.lowlevel_variant
 struct KernelRow { KernelKey key; EnvKernel step, reset, collect; };
 template <typename... A> const void* kfn(void (*kernel)(A...)) { return (const void*)kernel; }      // the host-side pointer hipLaunchKernel takes
 // The argument lists step_T / collect_step_T / reset_T build.  hipLaunchKernel takes them unchecked, so a kernel enters the table
@@ -1928,56 +2084,61 @@ template <typename T> EnvKernel aux_wave_step_kernel() {
 template <typename T> EnvKernel step_shape_step_kernel() {
   if constexpr (std::is_same<T, double>::value) return noise_wave<T>(fw_step_kernel_g8xs<T>); else return {};
 }
+// ... and that one with the second wave as scenario worker and observation writer: the grid has no worker half (the two-wave launch shape of the capture wave)
+template <typename T> EnvKernel obs_wave_step_kernel() {
+  if constexpr (std::is_same<T, double>::value) return two_wave<T>(fw_step_kernel_g8xo<T>); else return {};
+}
 // (fw_collect_step: the four-action tasks on the 8-lane mapping -- collect_fill says so to the others; general tick, no capture wave)
 template <typename T> const KernelRow* env_kernels_of(const KernelKey& q) {
   constexpr int LL = FW_TASK_LOWLEVEL, WD = FW_TASK_WAYPOINTS_DIRECT, OBJ = FW_TASK_OBJLOCK, COMB = FW_TASK_WAYPOINT_OBJLOCK, WP = FW_TASK_WAYPOINTS;
   static const KernelRow rows[] = {
-    // task lanes waves windy axis  capture aux   shape variant  fw_step                                                      fw_reset / fw_observe                                fw_collect_step
-    {{LL,   8, kAny, 1,    kAny, kAny, kAny, kAny, 1   }, step_k<T>(fw_step_kernel_ll<T, 8, true, 1>),       no_objc<T>(fw_reset_kernel_ll<T, 8, 1>),      {}},
-    {{LL,   8, kAny, 0,    kAny, kAny, kAny, kAny, 1   }, step_k<T>(fw_step_kernel_ll<T, 8, false, 1>),      no_objc<T>(fw_reset_kernel_ll<T, 8, 1>),      {}},
-    {{LL,   1, kAny, 1,    kAny, kAny, kAny, kAny, 1   }, step_k<T>(fw_step_kernel_ll<T, 1, true, 1>),       no_objc<T>(fw_reset_kernel_ll<T, 1, 1>),      {}},
-    {{LL,   1, kAny, 0,    kAny, kAny, kAny, kAny, 1   }, step_k<T>(fw_step_kernel_ll<T, 1, false, 1>),      no_objc<T>(fw_reset_kernel_ll<T, 1, 1>),      {}},
-    {{LL,   8, kAny, 1,    kAny, kAny, kAny, kAny, 0   }, step_k<T>(fw_step_kernel_ll<T, 8, true, 0>),       no_objc<T>(fw_reset_kernel_ll<T, 8, 0>),      {}},
-    {{LL,   8, kAny, 0,    kAny, kAny, kAny, kAny, 0   }, step_k<T>(fw_step_kernel_ll<T, 8, false, 0>),      no_objc<T>(fw_reset_kernel_ll<T, 8, 0>),      {}},
-    {{LL,   1, kAny, 1,    kAny, kAny, kAny, kAny, 0   }, step_k<T>(fw_step_kernel_ll<T, 1, true, 0>),       no_objc<T>(fw_reset_kernel_ll<T, 1, 0>),      {}},
-    {{LL,   1, kAny, 0,    kAny, kAny, kAny, kAny, 0   }, step_k<T>(fw_step_kernel_ll<T, 1, false, 0>),      no_objc<T>(fw_reset_kernel_ll<T, 1, 0>),      {}},
-    {{WD,   8, kAny, 1,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, true, WD_HELD>),  reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
-    {{WD,   8, kAny, 0,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, false, WD_HELD>), reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
-    {{WD,   1, kAny, 1,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, true, WD_HELD>),  reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
-    {{WD,   1, kAny, 0,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, false, WD_HELD>), reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
-    {{OBJ,  8, kAny, kAny, kAny, 1,    kAny, kAny, kAny}, two_wave<T>(fw_step_kernel_obj_g8h<T, OBJ>),      reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
-    {{OBJ,  8, kAny, kAny, kAny, 0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g8<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
-    {{OBJ,  1, kAny, kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 1, OBJ>),       {}},
-    {{COMB, 8, kAny, kAny, kAny, 1,    kAny, kAny, kAny}, two_wave<T>(fw_step_kernel_obj_g8h<T, COMB>),     reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
-    {{COMB, 8, kAny, kAny, kAny, 0,    kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g8<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
-    {{COMB, 1, kAny, kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 1, COMB>),      {}},
-    {{WP,   8, 1,    0,    1,    kAny, 1,    1,    kAny}, step_shape_step_kernel<T>(),                      reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
-    {{WP,   8, 1,    0,    1,    kAny, 1,    kAny, kAny}, aux_wave_step_kernel<T>(),                        reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
-    {{WP,   8, 1,    0,    1,    kAny, kAny, kAny, kAny}, axis_aligned_step_kernel<T>(),                    reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
-    {{WP,   8, 2,    1,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, true>),          reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, true>)},
-    {{WP,   8, 2,    0,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, false>),         reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, false>)},
-    {{WP,   8, 1,    1,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, true>),            reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, true>)},
-    {{WP,   8, 1,    0,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, false>),           reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
-    {{WP,   1, kAny, 1,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, true>),            reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
-    {{WP,   1, kAny, 0,    kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, false>),           reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
+    // task lanes waves windy axis  capture aux   shape obsw  variant  fw_step                                                      fw_reset / fw_observe                                fw_collect_step
+    {{LL,   8, kAny, 1,    kAny, kAny, kAny, kAny, kAny, 1   }, step_k<T>(fw_step_kernel_ll<T, 8, true, 1>),       no_objc<T>(fw_reset_kernel_ll<T, 8, 1>),      {}},
+    {{LL,   8, kAny, 0,    kAny, kAny, kAny, kAny, kAny, 1   }, step_k<T>(fw_step_kernel_ll<T, 8, false, 1>),      no_objc<T>(fw_reset_kernel_ll<T, 8, 1>),      {}},
+    {{LL,   1, kAny, 1,    kAny, kAny, kAny, kAny, kAny, 1   }, step_k<T>(fw_step_kernel_ll<T, 1, true, 1>),       no_objc<T>(fw_reset_kernel_ll<T, 1, 1>),      {}},
+    {{LL,   1, kAny, 0,    kAny, kAny, kAny, kAny, kAny, 1   }, step_k<T>(fw_step_kernel_ll<T, 1, false, 1>),      no_objc<T>(fw_reset_kernel_ll<T, 1, 1>),      {}},
+    {{LL,   8, kAny, 1,    kAny, kAny, kAny, kAny, kAny, 0   }, step_k<T>(fw_step_kernel_ll<T, 8, true, 0>),       no_objc<T>(fw_reset_kernel_ll<T, 8, 0>),      {}},
+    {{LL,   8, kAny, 0,    kAny, kAny, kAny, kAny, kAny, 0   }, step_k<T>(fw_step_kernel_ll<T, 8, false, 0>),      no_objc<T>(fw_reset_kernel_ll<T, 8, 0>),      {}},
+    {{LL,   1, kAny, 1,    kAny, kAny, kAny, kAny, kAny, 0   }, step_k<T>(fw_step_kernel_ll<T, 1, true, 0>),       no_objc<T>(fw_reset_kernel_ll<T, 1, 0>),      {}},
+    {{LL,   1, kAny, 0,    kAny, kAny, kAny, kAny, kAny, 0   }, step_k<T>(fw_step_kernel_ll<T, 1, false, 0>),      no_objc<T>(fw_reset_kernel_ll<T, 1, 0>),      {}},
+    {{WD,   8, kAny, 1,    kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, true, WD_HELD>),  reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
+    {{WD,   8, kAny, 0,    kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 8, false, WD_HELD>), reset_k<T>(fw_reset_kernel_wd<T, 8>),         {}},
+    {{WD,   1, kAny, 1,    kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, true, WD_HELD>),  reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
+    {{WD,   1, kAny, 0,    kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_wd<T, 1, false, WD_HELD>), reset_k<T>(fw_reset_kernel_wd<T, 1>),         {}},
+    {{OBJ,  8, kAny, kAny, kAny, 1,    kAny, kAny, kAny, kAny}, two_wave<T>(fw_step_kernel_obj_g8h<T, OBJ>),      reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
+    {{OBJ,  8, kAny, kAny, kAny, 0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g8<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 8, OBJ>),       collect_k<T>(fw_collect_kernel_obj_g8<T, OBJ>)},
+    {{OBJ,  1, kAny, kAny, kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, OBJ>),         reset_k<T>(fw_reset_kernel<T, 1, OBJ>),       {}},
+    {{COMB, 8, kAny, kAny, kAny, 1,    kAny, kAny, kAny, kAny}, two_wave<T>(fw_step_kernel_obj_g8h<T, COMB>),     reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
+    {{COMB, 8, kAny, kAny, kAny, 0,    kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g8<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 8, COMB>),      collect_k<T>(fw_collect_kernel_obj_g8<T, COMB>)},
+    {{COMB, 1, kAny, kAny, kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_obj_g1<T, COMB>),        reset_k<T>(fw_reset_kernel<T, 1, COMB>),      {}},
+    {{WP,   8, 1,    0,    1,    kAny, 1,    1,    1,    kAny}, obs_wave_step_kernel<T>(),                        reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   8, 1,    0,    1,    kAny, 1,    1,    kAny, kAny}, step_shape_step_kernel<T>(),                      reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   8, 1,    0,    1,    kAny, 1,    kAny, kAny, kAny}, aux_wave_step_kernel<T>(),                        reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   8, 1,    0,    1,    kAny, kAny, kAny, kAny, kAny}, axis_aligned_step_kernel<T>(),                    reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   8, 2,    1,    kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, true>),          reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, true>)},
+    {{WP,   8, 2,    0,    kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8w2<T, false>),         reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8w2<T, false>)},
+    {{WP,   8, 1,    1,    kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, true>),            reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, true>)},
+    {{WP,   8, 1,    0,    kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g8<T, false>),           reset_k<T>(fw_reset_kernel<T, 8, WP>),        collect_k<T>(fw_collect_kernel_g8<T, false>)},
+    {{WP,   1, kAny, 1,    kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, true>),            reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
+    {{WP,   1, kAny, 0,    kAny, kAny, kAny, kAny, kAny, kAny}, step_k<T>(fw_step_kernel_g1<T, false>),           reset_k<T>(fw_reset_kernel<T, 1, WP>),        {}},
   };
   auto fits = [](int row, int v) { return row == kAny || row == v; };
   for (const KernelRow& r : rows)
     if (const KernelKey& k = r.key; fits(k.task, q.task) && fits(k.lanes, q.lanes) && fits(k.waves, q.waves) && fits(k.windy, q.windy) &&
                                     fits(k.axis_aligned, q.axis_aligned) && fits(k.capture_wave, q.capture_wave) && fits(k.aux_wave, q.aux_wave) &&
-                                    fits(k.step_shape, q.step_shape) && fits(k.variant, q.variant)) return &r;
+                                    fits(k.step_shape, q.step_shape) && fits(k.obs_wave, q.obs_wave) && fits(k.variant, q.variant)) return &r;
   return nullptr;
 }
 
 // The handle's kernels, from the fields fw_create has just fixed.  A combination without a row (or whose row holds no step or
 // reset kernel) is an error here, not a launch that silently does nothing.
 template <typename T> int select_kernels(fw_env* h) {
-  const KernelKey q = { h->cfg.task, h->lanes_per_env, h->g8_waves, h->cfg.wind_mode != FW_WIND_OFF ? 1 : 0, h->axis_aligned, h->capture_wave, h->aux_wave, h->step_shape,
+  const KernelKey q = { h->cfg.task, h->lanes_per_env, h->g8_waves, h->cfg.wind_mode != FW_WIND_OFF ? 1 : 0, h->axis_aligned, h->capture_wave, h->aux_wave, h->step_shape, h->obs_wave,
                         h->cfg.task == FW_TASK_LOWLEVEL ? h->cfg.lowlevel_variant : 0 };
   const KernelRow* r = env_kernels_of<T>(q);
   if (!r || !r->step.fn || !r->reset.fn) {
-    h->err = "no kernel is built for (task, dtype, lanes per env, waves per SIMD, wind, axis_aligned, capture_wave, aux_wave, step_shape, lowlevel_variant) =";
-    for (int x : { q.task, h->cfg.dtype, q.lanes, q.waves, q.windy, q.axis_aligned, q.capture_wave, q.aux_wave, q.step_shape, q.variant }) h->err += " " + std::to_string(x);
+    h->err = "no kernel is built for (task, dtype, lanes per env, waves per SIMD, wind, axis_aligned, capture_wave, aux_wave, step_shape, obs_wave, lowlevel_variant) =";
+    for (int x : { q.task, h->cfg.dtype, q.lanes, q.waves, q.windy, q.axis_aligned, q.capture_wave, q.aux_wave, q.step_shape, q.obs_wave, q.variant }) h->err += " " + std::to_string(x);
     return FW_EUNSUPPORTED;
   }
   h->step = r->step; h->reset = r->reset; h->collect = r->collect;
@@ -2278,6 +2439,12 @@ int32_t fw_create(const fw_config* cfg, int32_t num_envs, int32_t device, uint64
   // has the one shape that is built.  FWSIM_STEP_SHAPE=0 turns it off; no value turns it on for another shape (wrong results).
   h->step_shape = (h->aux_wave && step_shape_of(*cfg)) ? 1 : 0;
   if (const char* ev = getenv("FWSIM_STEP_SHAPE")) { if (atoi(ev) == 0) h->step_shape = 0; }
+  // ... and the fixed-shape kernel with its second wave kept to the end of the launch (fw_step_kernel_g8xo; bit-identical again): that
+  // wave is the scenario worker of its tile and writes the observation rows.  FWSIM_OBS_WAVE=0|1 overrides where the row exists.
+  // Never above kAuxWaveMaxEnvs envs, whatever FWSIM_AUX_WAVE says: both waves of a workgroup last the whole launch.
+  const bool obs_row = h->step_shape && num_envs <= kAuxWaveMaxEnvs;
+  h->obs_wave = (obs_row && kObsWaveDefault) ? 1 : 0;
+  if (const char* ev = getenv("FWSIM_OBS_WAVE")) { if (obs_row) h->obs_wave = atoi(ev) != 0 ? 1 : 0; }
   DeviceGuard g(device);
   rc = with_dtype(h, [&](auto t) { return create_T<decltype(t)>(h); });
   if (rc != FW_OK) {
@@ -3263,6 +3430,7 @@ int32_t fw_num_envs(fw_handle h) { return h ? h->n : FW_EINVAL; }
 int32_t fw_capture_wave(fw_handle h) { return h ? h->capture_wave : FW_EINVAL; }
 int32_t fw_aux_wave(fw_handle h) { return h ? h->aux_wave : FW_EINVAL; }
 int32_t fw_step_shape(fw_handle h) { return h ? h->step_shape : FW_EINVAL; }
+int32_t fw_obs_wave(fw_handle h) { return h ? h->obs_wave : FW_EINVAL; }
 int32_t fw_axis_aligned(fw_handle h) { return h ? h->axis_aligned : FW_EINVAL; }
 int32_t fw_lanes_per_env(fw_handle h) { return h ? (h->lanes_per_env == 8 && h->g8_waves == 2 ? 16 : h->lanes_per_env) : FW_EINVAL; }
 

@@ -1280,16 +1280,21 @@ __device__ __forceinline__ T end_reset(const Params<T>& P, const DevState<T>& D,
 // ------------------------------------------------------------------------
 // LDS-staged, coalesced store of a [rows x D] observation tile
 // ------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ void flush_obs_tile(const T* tile, int ld, T* obs, int blk_env0, int rows_max, int n, int D) {
+// (`lane`: the index of the storing lane within its wave; `keep(row)`: rows it refuses are left to another writer -- fw_step_kernel_g8xo)
+template <typename T, typename K>
+__device__ __forceinline__ void flush_obs_tile_rows(const T* tile, int ld, T* obs, int blk_env0, int rows_max, int n, int D, int lane, K&& keep) {
   // tile[row*ld + k]; global rows [blk_env0, blk_env0+rows) are one contiguous span of rows*D elements
   const int rows = min(rows_max, n - blk_env0);
   const int total = rows * D;
   T* dst = obs + (size_t)blk_env0 * D;
-  for (int e = threadIdx.x; e < total; e += kWave) {
+  for (int e = lane; e < total; e += kWave) {
     int row = e / D, col = e - row * D;
-    dst[e] = tile[row * ld + col];
+    if (keep(row)) dst[e] = tile[row * ld + col];
   }
+}
+template <typename T>
+__device__ __forceinline__ void flush_obs_tile(const T* tile, int ld, T* obs, int blk_env0, int rows_max, int n, int D) {
+  flush_obs_tile_rows<T>(tile, ld, obs, blk_env0, rows_max, n, D, (int)threadIdx.x, [](int) { return true; });
 }
 
 }  // namespace fwsim

@@ -205,6 +205,8 @@ class FixedwingVecEnv(FusedVecEnv):
         self.lanes_per_env = int(_lib.lib().fw_lanes_per_env(h))    # which lane mapping fw_create picked (diagnostic)
         self.g8_waves = 2 if self.lanes_per_env == 16 else 1
         self.capture_wave = bool(_lib.lib().fw_capture_wave(h))      # camera tasks: step workgroups with a capture wave (FWSIM_CAPTURE_WAVE=1)
+        # headline kernel with its second wave kept to the end: scenario worker, then the observation rows (FWSIM_OBS_WAVE=0|1)
+        self.obs_wave = bool(_lib.lib().fw_obs_wave(h)) if hasattr(_lib.lib(), "fw_obs_wave") else False
         if self.lanes_per_env == 16:                                # (16 = the 8-lane mapping built for two waves per SIMD)
             self.lanes_per_env = 8
         n, d = self.num_envs, self.obs_dim

@@ -44,7 +44,10 @@ print(f"{which} N={N}: {nblk} step waves/launch, last 256 of {steps} launches; c
 print("  mean over all waves : " + "  ".join(f"{n} {st[:, :, k].mean():8.0f}" for k, n in enumerate(names)))
 print("  slowest wave/launch : " + "  ".join(f"{n} {S[:, k].mean():8.0f}" for k, n in enumerate(names)))
 it = st[:, :, 6] & 0xFF; nr = (st[:, :, 6] >> 8) & 0xFF; nh = (st[:, :, 6] >> 16) & 0xFF
-if not cap_words:      # (the camera kernels use these words for their capture steps, below)
+OBSW = bool(getattr(e, "obs_wave", False))          # fw_step_kernel_g8xo: word 8 of a step wave is its wait at barrier 2, the terminal observation is wave 1's
+if OBSW:
+    print(f"  slowest wave behind barrier 2 (waves with a reset): waypoints and, on the fallback, the new row {S[:, 9].mean():.0f}  warm state / first distance {S[:, 10].mean():.0f}")
+elif not cap_words:      # (the camera kernels use these words for their capture steps, below)
     print(f"  slowest wave reset split: terminal obs {S[:, 8].mean():.0f}  swap-in / begin_reset {S[:, 9].mean():.0f}  first compute_state {S[:, 10].mean():.0f}")
 print(f"  loop iterations: mean {it.mean():.2f}  slowest-wave mean {(S[:, 6] & 0xFF).mean():.2f}  max {it.max()}")
 print(f"  env resets/launch {nr.sum(axis=1).mean():.1f}  of which swapped-in shadows {nh.sum(axis=1).mean():.1f}")
@@ -60,5 +63,40 @@ if cap.any():
         if ne.sum():
             print(f"    capture steps with {nm}: {ne.mean():.2f} per wave-step, {cyc.sum() / max(1, ne.sum()):.0f} cycles each (all waves); "
                   f"slowest wave: {ns.mean():.2f} per step, {cs.sum() / max(1, ns.sum()):.0f} cycles each")
-if wk.any():
+# Start stamps (word 7 of a step wave's slot).  Workgroup b is dealt to XCD b % 8.  Whether the counters of different workgroups can be
+# compared is not assumed: both spreads are printed.  Measured on an MI355X (profiles/r24_obs_wave_profile_*.txt): 2e8 cycles within
+# the group b % 8 and 1.9e12 over the launch, against launches of 3e4 cycles -- the counters are NOT common to an XCD, let alone to
+# the chip, so stamps compare only between the two waves of one workgroup (one CU), and nothing below orders workgroups by stamp.
+if not cap_words:
+    t0 = st[:, :, 7]
+    spread = np.array([[np.ptp(t0[l, x::8]) for x in range(8)] for l in range(256)]) if nblk >= 16 else np.zeros((256, 1))
+    print(f"  start stamps within an XCD (max - min over its {nblk // 8} step waves): mean {spread.mean():.0f}  worst XCD of a launch {spread.max(axis=1).mean():.0f}  max {spread.max()}")
+    print(f"  start stamps over the whole launch (max - min over {nblk} step waves): mean {np.ptp(t0, axis=1).mean():.0f}  max {np.ptp(t0, axis=1).max()}")
+if OBSW:
+    # The second wave of workgroup b stamps slot nblk + b: noise draw up to barrier 1, worker, pre-loads, the wait at barrier 2, pass
+    # (with the terminal-observation copy), flush.  The two waves of a workgroup sit on one CU: their stamps compare.
+    W = buf[:, nblk:, :]
+    wnames = [("noise+barrier 1", 1), ("worker", 0), ("pre-loads", 2), ("wait at barrier 2", 3), ("pass", 4), ("flush", 5), ("total", 6)]
+    end_step, end_obs = st[:, :, 7] + st[:, :, 0], W[:, :, 7] + W[:, :, 6]
+    later = np.maximum(end_step, end_obs)                           # the later of a workgroup's two ends, as a stamp
+    wg_len = later - np.minimum(st[:, :, 7], W[:, :, 7])            # ... and from the workgroup's first stamp
+    comparable = np.ptp(st[:, :, 7], axis=1).max() < 100 * wg_len.max()        # one clock for the whole launch? (see the spreads above)
+    last = (later if comparable else wg_len).argmax(axis=1)          # the workgroup that finishes last -- or, without a common clock, the longest one
+    lastname = "finishing last" if comparable else "that lasts longest"
+    ar = np.arange(256)
+    Wl, Sl = W[ar, last], st[ar, last]
+    print("  observation wave, mean over all   : " + "  ".join(f"{n} {W[:, :, k].mean():7.0f}" for n, k in wnames))
+    print(f"  ... of the workgroup {lastname}: " + "  ".join(f"{n} {Wl[:, k].mean():7.0f}" for n, k in wnames))
+    print(f"  step wave: wait at barrier 2 mean {st[:, :, 8].mean():.0f} (last workgroup {Sl[:, 8].mean():.0f})  tail behind it mean {(st[:, :, 5] - st[:, :, 8]).mean():.0f} (last workgroup {(Sl[:, 5] - Sl[:, 8]).mean():.0f})")
+    print(f"  workgroup length (first stamp to the later end): mean {wg_len.mean():.0f}  longest of a launch {wg_len.max(axis=1).mean():.0f}")
+    print(f"  the observation wave ends after the step wave in {100.0 * (end_obs > end_step).mean():.1f}% of the workgroups, by {(end_obs - end_step)[end_obs > end_step].mean() if (end_obs > end_step).any() else 0:.0f} cycles; "
+          f"in the workgroup {lastname} in {100.0 * (end_obs[ar, last] > end_step[ar, last]).mean():.1f}% of the launches")
+    K = int(os.environ.get("PROF_LAUNCHES", 8))
+    print(f"  per launch (the last {K}; the workgroup {lastname}): step wave total / wait b2 / tail | obs wave worker / wait b2 / pass / flush / total | later end - workgroup's first stamp, which wave")
+    order = [(steps - k) % 256 for k in range(K - 1, -1, -1)]        # slots are launch % 256 and launches count from 1: the newest K
+    for l in order:
+        b = last[l]
+        print(f"    wg {b:4d}: {st[l, b, 0]:6d} / {st[l, b, 8]:5d} / {st[l, b, 5] - st[l, b, 8]:5d} | {W[l, b, 0]:5d} / {W[l, b, 3]:6d} / {W[l, b, 4]:5d} / {W[l, b, 5]:5d} / {W[l, b, 6]:6d} | "
+              f"{wg_len[l, b]:6d} {'obs' if end_obs[l, b] > end_step[l, b] else 'step'}")
+elif wk.any():
     print(f"  shadow worker waves: busy {100.0 * (wk > 2000).mean():.1f}%  mean busy cycles {wk[wk > 2000].mean() if (wk > 2000).any() else 0:.0f}  max {wk.max()}")
