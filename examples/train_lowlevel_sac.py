@@ -42,6 +42,12 @@ def main():
     ap.add_argument("--use_graphs", action=argparse.BooleanOptionalAction, default=True)
     ap.add_argument("--eval_freq", type=int, default=TRAIN_CONFIG["eval_freq"], help="env steps between evaluations")
     ap.add_argument("--eval_max_steps", type=int, default=1800, help="time limit of an evaluation episode (agent steps; --env tracking only: demo evaluates on the script's own 60 s clock)")
+    ap.add_argument("--episode_stats", action="store_true",
+                    help="SB3's rollout/* figures (ep_rew_mean, ep_len_mean, success_rate over the last 100 training episodes, and the "
+                         "rollout/interval/* means over all episodes since the last line) in every evaluation line")
+    ap.add_argument("--episode_fold", choices=("one", "wide", "auto"), default="one",
+                    help="the device form of the episode fold behind --episode_stats: one workgroup, one workgroup per span of envs "
+                         "(large env counts), or chosen by the env count")
     ap.add_argument("--out", type=str, default="runs/lowlevel_sac")
     a = ap.parse_args()
     c = TRAIN_CONFIG
@@ -59,7 +65,8 @@ def main():
     model = S.SAC(env, S.SACConfig(learning_rate=c["learning_rate"], buffer_size=c["buffer_size"], batch_size=c["batch_size"],
                                    gamma=c["gamma"], tau=c["tau"], gradient_steps=a.gradient_steps,
                                    target_update_interval=c["target_update_interval"], learning_starts=c["learning_starts"],
-                                   net_arch=c["net_arch"], seed=c["seed"], use_graphs=a.use_graphs, fused_update=a.fused_update))
+                                   net_arch=c["net_arch"], seed=c["seed"], use_graphs=a.use_graphs, fused_update=a.fused_update,
+                                   episode_stats=a.episode_stats, episode_fold=a.episode_fold))
     t0 = time.perf_counter()
     state = {"next_eval": a.eval_freq, "train_s": 0.0, "mark": t0}
 
@@ -75,7 +82,8 @@ def main():
                 "eval_ep_rew_mean": round(float(sum(r.episode_rewards) / len(r.episode_rewards)), 3),
                 "eval_ep_len_mean": round(float(sum(r.episode_lengths) / len(r.episode_lengths)), 1),
                 **{k: round(float(v), 5) for k, v in trk.items()}, **deg,
-                **{k: round(float(logs[k]), 5) for k in S.SCALARS}}
+                **{k: round(float(logs[k]), 5) for k in S.SCALARS},
+                **{k: (round(v, 5) if math.isfinite(v) else None) for k, v in sac.rollout_stats.items()}}
         print(json.dumps(line), flush=True)
         state["mark"] = time.perf_counter()
 

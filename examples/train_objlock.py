@@ -40,6 +40,9 @@ def main():
     ap.add_argument("--episode_stats", action="store_true",
                     help="SB3's rollout/* figures (ep_rew_mean, ep_len_mean, success_rate over the last 100 episodes, and the "
                          "rollout/interval/* means over all episodes since the last line) in every printed update line")
+    ap.add_argument("--episode_fold", choices=("one", "wide", "auto"), default="one",
+                    help="the device form of the episode fold behind --episode_stats: one workgroup, one workgroup per span of envs "
+                         "(large env counts), or chosen by the env count")
     ap.add_argument("--diagnostics", action="store_true",
                     help="SB3's train/* figures (approx_kl, clip_fraction, explained_variance, ...) in every printed update line")
     a = ap.parse_args()
@@ -57,7 +60,7 @@ def main():
     if vecnorm:
         checkpoint.load_vecnormalize(vecnorm, env, training=True, norm_reward=True)
     n_steps = R.n_steps_for(cfg["samples_per_update"], a.num_envs, world)      # holds the samples per update: n_steps ~ 1 / (envs x world)
-    model = R.PPO(env, R.PPOConfig(diagnostics=a.diagnostics, episode_stats=a.episode_stats, n_steps=n_steps, batch_size=cfg["batch_size"], n_epochs=cfg["n_epochs"], learning_rate=cfg["learning_rate"],
+    model = R.PPO(env, R.PPOConfig(diagnostics=a.diagnostics, episode_stats=a.episode_stats, episode_fold=a.episode_fold, n_steps=n_steps, batch_size=cfg["batch_size"], n_epochs=cfg["n_epochs"], learning_rate=cfg["learning_rate"],
                                    gamma=cfg["gamma"], gae_lambda=cfg["gae_lambda"], clip_range=cfg["clip_range"], ent_coef=cfg["ent_coef"],
                                    vf_coef=cfg["vf_coef"], max_grad_norm=cfg["max_grad_norm"], seed=cfg["seed"]))
     if a.pretrained_model:

@@ -429,6 +429,20 @@ int32_t fw_eval_track(const void* reward, int32_t reward_is_f64, const uint8_t* 
 int64_t fw_episode_state_bytes(int32_t N, int32_t W);
 int32_t fw_episode_fold(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
                         int32_t info_dim, void* state, int32_t N, int32_t W, void* hip_stream);
+/* The same fold over many workgroups, for env counts at which one workgroup walking all N envs costs more than the step itself
+ * (DESIGN.md section 4b "Episode statistics").  Same semantics, same state block (layout and fw_episode_state_bytes above): the two
+ * forms may be mixed on one block from one vec-step to the next.  Every word of the block comes out the same bits as from
+ * fw_episode_fold except the two double totals [10] and [11], whose summation order differs (fixed too: the same bits in every run).
+ * fw_episode_fold_span() is the number of envs a workgroup owns, a build constant (a multiple of 64); B = ceil(N / span) workgroups.
+ * The workspace is the caller's: fw_episode_fold_workspace_bytes(N) bytes of device memory (FW_EINVAL for N <= 0), no
+ * initialisation needed -- every call writes every word it later reads.  Three launches on the caller's stream (count the dones per
+ * workgroup; fold, each workgroup ranking its dones behind those of the workgroups below it; one workgroup adds the partial sums to
+ * the header), kernel boundaries the only synchronisation between workgroups: no atomics, no in-grid waits, no host reads, fixed
+ * addresses, graph-capturable.  No upper limit on N other than int32.  FW_EINVAL as for fw_episode_fold, and for a NULL workspace. */
+int32_t fw_episode_fold_span(void);
+int64_t fw_episode_fold_workspace_bytes(int32_t N);
+int32_t fw_episode_fold_wide(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
+                             int32_t info_dim, void* state, void* workspace, int32_t N, int32_t W, void* hip_stream);
 /* fw_eval_track for FW_TASK_LOWLEVEL, plus its tracking figures.  Everything fw_eval_track does, and from the
  * post-step observation row o of env i -- terminal_obs[i] where terminated | truncated, else obs[i]; [N, 21], obs_is_f64 the env
  * dtype -- with e_psi = wrap(o[18] - o[5]) (to [-pi, pi)), e_h = o[19] - o[11], e_V = o[20] - |o[6:9]|, w = |o[0:3]| it adds

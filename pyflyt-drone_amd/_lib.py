@@ -27,6 +27,7 @@ EXPORTS = (
     "fw_collect_act_hl", "fw_sizeof_collect_hl_args", "fw_eval_track_hl", "fw_trace_hl",
     "fw_ppo_diag_floats", "fw_ppo_update_diag",
     "fw_episode_state_bytes", "fw_episode_fold",
+    "fw_episode_fold_span", "fw_episode_fold_workspace_bytes", "fw_episode_fold_wide",
     "fw_trace_rows", "fw_eval_track_wp",
     "fw_step_hl", "fw_sizeof_step_hl_args", "fw_controller_forward",
     "fw_probe",
@@ -124,6 +125,11 @@ def lib() -> C.CDLL:
             L.fw_episode_state_bytes.restype = i64; L.fw_episode_state_bytes.argtypes = [i32, i32]
             L.fw_episode_fold.restype = i32
             L.fw_episode_fold.argtypes = [vp, i32, vp, vp, vp, i32, vp, i32, i32, vp]
+        if hasattr(L, "fw_episode_fold_wide"):  # the multi-workgroup form (an A/B library of an older commit predates it; build() insists on it)
+            L.fw_episode_fold_span.restype = i32; L.fw_episode_fold_span.argtypes = []
+            L.fw_episode_fold_workspace_bytes.restype = i64; L.fw_episode_fold_workspace_bytes.argtypes = [i32]
+            L.fw_episode_fold_wide.restype = i32
+            L.fw_episode_fold_wide.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp]
         L.fw_eval_track_ll.restype = i32
         L.fw_eval_track_ll.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp]
         L.fw_eval_track_hl.restype = i32

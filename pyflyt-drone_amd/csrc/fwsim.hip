@@ -2666,6 +2666,35 @@ int32_t fw_episode_fold(const void* reward, int32_t reward_is_f64, const uint8_t
   return FW_OK;
 }
 
+int32_t fw_episode_fold_span(void) { return kEpSpan; }
+
+static inline int64_t ep_wide_blocks(int32_t N) { return ((int64_t)N + kEpSpan - 1) / kEpSpan; }
+
+int64_t fw_episode_fold_workspace_bytes(int32_t N) {
+  if (N <= 0) { g_err = "fw_episode_fold_workspace_bytes: N must be positive, got N=" + std::to_string(N); return FW_EINVAL; }
+  const int64_t B = ep_wide_blocks(N);
+  return 8 * (1 + (int64_t)kEpParts * B + (B + 1) / 2);
+}
+
+int32_t fw_episode_fold_wide(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
+                             int32_t info_dim, void* state, void* workspace, int32_t N, int32_t W, void* hip_stream) {
+  if (!reward || !terminated || !truncated || !state) { g_err = "fw_episode_fold_wide: reward, terminated, truncated and state must be non-NULL"; return FW_EINVAL; }
+  if (!workspace) { g_err = "fw_episode_fold_wide: workspace must be non-NULL (fw_episode_fold_workspace_bytes(N) bytes of device memory)"; return FW_EINVAL; }
+  if (N <= 0 || W <= 0) { g_err = "fw_episode_fold_wide: N and W must be positive, got N=" + std::to_string(N) + ", W=" + std::to_string(W); return FW_EINVAL; }
+  if (info && info_dim <= 0) { g_err = "fw_episode_fold_wide: info given with info_dim=" + std::to_string(info_dim); return FW_EINVAL; }
+  EpisodeWideArgs X;
+  X.F.reward = reward; X.F.reward_is_f64 = reward_is_f64; X.F.terminated = terminated; X.F.truncated = truncated; X.F.info = info;
+  X.F.info_dim = info_dim; X.F.state = reinterpret_cast<int64_t*>(state); X.F.N = N; X.F.W = W;
+  X.ws = reinterpret_cast<int64_t*>(workspace); X.B = (int32_t)ep_wide_blocks(N);
+  DeviceGuard g(device_of(reward));
+  hipStream_t s = (hipStream_t)hip_stream;
+  hipLaunchKernelGGL(fw_episode_count_kernel, dim3(X.B), dim3(kEpSpan), 0, s, X);
+  hipLaunchKernelGGL(fw_episode_fold_wide_kernel, dim3(X.B), dim3(kEpSpan), 0, s, X);
+  hipLaunchKernelGGL(fw_episode_finish_kernel, dim3(1), dim3(kEpFinishThreads), 0, s, X);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+
 int32_t fw_eval_track_ll(const void* reward, int32_t reward_is_f64, const uint8_t* terminated, const uint8_t* truncated, const int32_t* info,
                          int32_t info_dim, const void* obs, const void* terminal_obs, int32_t obs_is_f64, int32_t obs_dim,
                          const int64_t* targets, int64_t* counts, double* cur_rew, int64_t* cur_len, int64_t* step_ctr, double* cur_track,

@@ -291,6 +291,185 @@ __global__ __launch_bounds__(kEpThreads) void fw_episode_fold_kernel(EpisodeFold
   }
 }
 
+// The same fold over many workgroups (fw_episode_fold_wide): the same state block, three launches on one stream, workgroup b owning
+// envs [b * kEpSpan, min(N, (b + 1) * kEpSpan)), one env per thread.  Kernel boundaries are the only synchronisation between
+// workgroups: no atomics, no in-grid waits, and a kernel that reads a header word does not write it (the idiom of fw_replay_store /
+// fw_sac_update) -- only the one-workgroup finish moves the header.  The caller-owned workspace, in 8-byte words, B = ceil(N / kEpSpan):
+//   [0]            D, the step's dones (written by workgroup 0 of the fold, read by the finish)
+//   [1, 1 + 10 B)  part[c][b]: workgroup b's sums -- c = 0 length, 1 truncated, 2..7 the info sums (int64), 8 return, 9 squared return (double)
+//   then B int32   count[b]: workgroup b's dones (written by the count kernel, read by every workgroup of the fold)
+// Every word is written by the call that reads it.  The ring order comes out of a scan: a done's rank is the sum of the counts of the
+// workgroups below its own, the dones of the waves below its own (LDS) and of the lanes below its own (ballot); the ranks kept by one
+// step are consecutive and at most W, so no two workgroups write one slot.
+#ifndef FW_EP_SPAN
+#define FW_EP_SPAN 256
+#endif
+constexpr int kEpSpan = FW_EP_SPAN;         // envs (= threads) per workgroup of the wide form
+constexpr int kEpSpanWaves = kEpSpan / 64;
+constexpr int kEpParts = 4 + kEpInfoSums;   // words of part[] per workgroup
+constexpr int kEpFinishThreads = 1024;
+static_assert(kEpSpan % 64 == 0 && kEpSpan >= 64 && kEpSpan <= 1024, "the wide fold runs one env per thread, whole waves");
+struct EpisodeWideArgs {
+  EpisodeFoldArgs F;
+  int64_t* ws;
+  int32_t B;
+};
+__device__ __forceinline__ int32_t* ep_ws_count(int64_t* ws, int B) { return reinterpret_cast<int32_t*>(ws + 1 + (size_t)kEpParts * B); }
+
+__global__ __launch_bounds__(kEpSpan) void fw_episode_count_kernel(EpisodeWideArgs X) {
+  __shared__ int s_cnt[kEpSpanWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long i = (long long)blockIdx.x * kEpSpan + tid;
+  const bool done = i < X.F.N && (X.F.terminated[i] | X.F.truncated[i]) != 0;
+  const unsigned long long ballot = __ballot(done);
+  if (lane == 0) s_cnt[wave] = __popcll(ballot);
+  __syncthreads();
+  if (tid == 0) {
+    int c = 0;
+#pragma unroll
+    for (int w = 0; w < kEpSpanWaves; ++w) c += s_cnt[w];
+    ep_ws_count(X.ws, X.B)[blockIdx.x] = c;
+  }
+}
+
+__global__ __launch_bounds__(kEpSpan) void fw_episode_fold_wide_kernel(EpisodeWideArgs X) {
+  __shared__ long long s_cnt[kEpSpanWaves][3];         // dones of the workgroups below this one, of all of them, of this wave
+  __shared__ long long s_int[kEpSpanWaves][2 + kEpInfoSums];
+  __shared__ double s_dbl[kEpSpanWaves][2];
+  const EpisodeFoldArgs& A = X.F;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x, B = X.B;
+  const int N = A.N, W = A.W;
+  const long long* hdr = reinterpret_cast<const long long*>(A.state);          // read only: the finish kernel writes the header
+  long long* ring = reinterpret_cast<long long*>(A.state) + EP_HEADER_WORDS;
+  double* ring_ret = reinterpret_cast<double*>(ring);
+  long long* ring_len = ring + (size_t)W;
+  long long* ring_step = ring_len + W;
+  long long* ring_env = ring_step + W;
+  long long* ring_trunc = ring_env + W;
+  int32_t* ring_info = reinterpret_cast<int32_t*>(ring_trunc + W);
+  double* cur_ret = reinterpret_cast<double*>(ring_trunc + W + (size_t)W * (kEpInfo / 2));
+  long long* cur_len = reinterpret_cast<long long*>(cur_ret) + N;
+  const long long pushed0 = hdr[EP_EPISODES], step = hdr[EP_STEPS] + 1;
+
+  // the scan over workgroups: every workgroup reduces the count array itself (integers: any order)
+  const int32_t* count = ep_ws_count(X.ws, B);
+  long long below = 0, all = 0;
+  for (int k = tid; k < B; k += kEpSpan) { const long long c = count[k]; all += c; below += k < b ? c : 0; }
+  below = ep_wave_sum(below); all = ep_wave_sum(all);
+
+  const long long i = (long long)b * kEpSpan + tid;
+  bool done = false, trunc = false;
+  double cr = 0.0;
+  long long cl = 0;
+  if (i < N) {
+    const double r = A.reward_is_f64 ? reinterpret_cast<const double*>(A.reward)[i] : (double)reinterpret_cast<const float*>(A.reward)[i];
+    cr = cur_ret[i] + r;
+    cl = cur_len[i] + 1;
+    trunc = A.truncated[i] != 0;
+    done = trunc || A.terminated[i] != 0;
+    cur_ret[i] = done ? 0.0 : cr;
+    cur_len[i] = done ? 0 : cl;
+  }
+  const unsigned long long ballot = __ballot(done);
+  if (lane == 0) { s_cnt[wave][0] = below; s_cnt[wave][1] = all; s_cnt[wave][2] = __popcll(ballot); }
+  __syncthreads();
+  long long base = 0, D = 0;
+#pragma unroll
+  for (int w = 0; w < kEpSpanWaves; ++w) { base += s_cnt[w][0] + (w < wave ? s_cnt[w][2] : 0); D += s_cnt[w][1]; }
+  const long long first_kept = D - W;          // ranks below it would be pushed out of the ring by this very step
+
+  long long n_trunc = 0, sum_len = 0, sum_info[kEpInfoSums] = {0, 0, 0, 0, 0, 0};
+  double sum_ret = 0.0, sum_ret2 = 0.0;
+  const int ncol = A.info ? (A.info_dim < kEpInfo ? A.info_dim : kEpInfo) : 0;
+  if (done) {
+    const long long rank = base + __popcll(ballot & ((1ull << lane) - 1ull));
+    int32_t row[kEpInfo];
+#pragma unroll
+    for (int k = 0; k < kEpInfo; ++k) row[k] = k < ncol ? A.info[(size_t)i * A.info_dim + k] : 0;
+    sum_ret = cr; sum_ret2 = cr * cr; sum_len = cl; n_trunc = trunc;
+#pragma unroll
+    for (int k = 0; k < kEpInfoSums; ++k) sum_info[k] = row[k];
+    if (rank >= first_kept) {
+      const size_t s = (size_t)((pushed0 + rank) % W);
+      ring_ret[s] = cr; ring_len[s] = cl; ring_step[s] = step; ring_env[s] = i; ring_trunc[s] = trunc;
+#pragma unroll
+      for (int k = 0; k < kEpInfo; ++k) ring_info[s * kEpInfo + k] = row[k];
+    }
+  }
+
+  // the workgroup's sums: lane tree, then the waves in order -- a fixed order for the doubles
+  sum_ret = ep_wave_sum(sum_ret); sum_ret2 = ep_wave_sum(sum_ret2);
+  sum_len = ep_wave_sum(sum_len); n_trunc = ep_wave_sum(n_trunc);
+#pragma unroll
+  for (int k = 0; k < kEpInfoSums; ++k) sum_info[k] = ep_wave_sum(sum_info[k]);
+  if (lane == 0) {
+    s_dbl[wave][0] = sum_ret; s_dbl[wave][1] = sum_ret2;
+    s_int[wave][0] = sum_len; s_int[wave][1] = n_trunc;
+#pragma unroll
+    for (int k = 0; k < kEpInfoSums; ++k) s_int[wave][2 + k] = sum_info[k];
+  }
+  __syncthreads();
+  long long* part = reinterpret_cast<long long*>(X.ws) + 1;
+  if (tid < 2 + kEpInfoSums) {
+    long long v = 0;
+#pragma unroll
+    for (int w = 0; w < kEpSpanWaves; ++w) v += s_int[w][tid];
+    part[(size_t)tid * B + b] = v;
+  } else if (tid < kEpParts) {
+    double v = 0.0;
+#pragma unroll
+    for (int w = 0; w < kEpSpanWaves; ++w) v += s_dbl[w][tid - (2 + kEpInfoSums)];
+    reinterpret_cast<double*>(part)[(size_t)tid * B + b] = v;
+  } else if (tid == kEpParts && b == 0) {
+    X.ws[0] = D;
+  }
+}
+
+// One workgroup: the workgroups' sums in ascending workgroup order per thread (thread t takes b = t, t + 1024, ...), lane tree, waves
+// in order -- a fixed tree for the two doubles, the same bits in every run -- then the header.
+__global__ __launch_bounds__(kEpFinishThreads) void fw_episode_finish_kernel(EpisodeWideArgs X) {
+  constexpr int kWaves = kEpFinishThreads / 64;
+  __shared__ long long s_int[kWaves][2 + kEpInfoSums];
+  __shared__ double s_dbl[kWaves][2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, B = X.B;
+  long long* hdr = reinterpret_cast<long long*>(X.F.state);
+  const long long* part = reinterpret_cast<const long long*>(X.ws) + 1;
+  const double* partd = reinterpret_cast<const double*>(part);
+  long long vi[2 + kEpInfoSums] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double vd[2] = {0.0, 0.0};
+  for (int k = tid; k < B; k += kEpFinishThreads) {
+#pragma unroll
+    for (int c = 0; c < 2 + kEpInfoSums; ++c) vi[c] += part[(size_t)c * B + k];
+    vd[0] += partd[(size_t)(2 + kEpInfoSums) * B + k]; vd[1] += partd[(size_t)(3 + kEpInfoSums) * B + k];
+  }
+#pragma unroll
+  for (int c = 0; c < 2 + kEpInfoSums; ++c) vi[c] = ep_wave_sum(vi[c]);
+  vd[0] = ep_wave_sum(vd[0]); vd[1] = ep_wave_sum(vd[1]);
+  if (lane == 0) {
+#pragma unroll
+    for (int c = 0; c < 2 + kEpInfoSums; ++c) s_int[wave][c] = vi[c];
+    s_dbl[wave][0] = vd[0]; s_dbl[wave][1] = vd[1];
+  }
+  __syncthreads();
+  if (tid < 2 + kEpInfoSums) {
+    long long v = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) v += s_int[w][tid];
+    const int at = tid == 0 ? EP_SUM_LEN : tid == 1 ? EP_TRUNCATED : EP_SUM_INFO + (tid - 2);
+    hdr[at] += v;
+  } else if (tid < kEpParts) {
+    const int c = tid - (2 + kEpInfoSums);
+    double v = 0.0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) v += s_dbl[w][c];
+    double* tot = reinterpret_cast<double*>(hdr) + (c == 0 ? EP_SUM_RET : EP_SUM_RET2);
+    tot[0] += v;
+  } else if (tid == kEpParts) {
+    hdr[EP_EPISODES] += X.ws[0];
+    hdr[EP_STEPS] += 1;
+  }
+}
+
 // K4a: per-column batch moments of obs[N,D] (two-pass-free: shifted sums in double), one
 // workgroup per column chunk; K4b merges them into the running statistics (Chan et al.) and
 // K4c normalises.  N*D is small (4096 x 28), so the three launches are latency-trivial and

@@ -6,7 +6,9 @@ SB3 gets these from ``Monitor`` (a per-env running return and length, an ``info[
 (``venv.rewards`` / ``terminated`` / ``truncated`` / ``info`` hold the step until the next launch overwrites them): per-env
 accumulators, a ring of the last W finished episodes in SB3's order, and running totals since creation, all in one caller-owned
 state block on the device (layout: include/fwsim.h).  No step, collector or update kernel knows about it; ``PPOConfig.episode_stats``
-puts the launch behind every vec-step of every collector, inside the captured rollout graph.
+puts the launch behind every vec-step of every collector, inside the captured rollout graph.  One workgroup walks all envs in that
+launch; for large env counts ``fold="wide"`` runs the same fold over one workgroup per span of envs instead (``fw_episode_fold_wide``,
+three launches, the same block).
 
 With thousands of envs a 100-episode window is a sliver of one vec-step (every env meets the time limit in the same step), so
 ``scalars()`` also reports the means over ALL episodes finished since the previous call under ``rollout/interval/*`` -- the figures to
@@ -33,6 +35,21 @@ _TOTALS = ("episodes", "steps", "truncated", "sum_len") + tuple("sum_" + k for k
 _WINDOW = ("n", "ret", "len", "truncated") + INFO_SUMS
 
 
+FOLD_FORMS = ("one", "wide", "auto")        # fw_episode_fold (one workgroup), fw_episode_fold_wide (one per span of envs), or by env count
+# fold="auto": the wide form from this env count on -- the smallest measured env count from which it is not slower than the
+# one-workgroup form (profiles/r25_episode_fold_wide.jsonl, "what": "wide")
+WIDE_FROM_ENVS = 4096
+
+
+def resolve_fold(fold: str, num_envs: int) -> str:
+    """``"one"`` or ``"wide"`` for a ``fold`` option; ``ValueError`` for anything but :data:`FOLD_FORMS`."""
+    if fold not in FOLD_FORMS:
+        raise ValueError(f"fold must be one of {FOLD_FORMS}, got {fold!r}")
+    if fold == "auto":
+        return "wide" if int(num_envs) >= WIDE_FROM_ENVS else "one"
+    return fold
+
+
 def state_words(num_envs: int, window: int) -> int:
     """Words of the documented layout (what ``fw_episode_state_bytes`` must at least return, in bytes / 8)."""
     return HEADER_WORDS + RING_WORDS * int(window) + 2 * int(num_envs)
@@ -51,12 +68,17 @@ class EpisodeMonitor:
 
     ``fold(rewards, terminated, truncated, info)`` books one vec-step: the kernel on device tensors, a plain torch statement of the
     same semantics on CPU tensors (the reference the kernel is tested against).  The truncated flag of an episode is the env's
-    ``truncated`` output of its last step."""
+    ``truncated`` output of its last step.
 
-    def __init__(self, num_envs: int, window: int = 100, device="cpu"):
+    ``fold``: the device form -- ``"one"`` (``fw_episode_fold``: one workgroup walks all envs), ``"wide"`` (``fw_episode_fold_wide``:
+    one workgroup per ``fw_episode_fold_span()`` envs, three launches, for large env counts) or ``"auto"`` (``"wide"`` from
+    :data:`WIDE_FROM_ENVS` envs on).  Both work on the same block; only the two double totals may differ in their last bits."""
+
+    def __init__(self, num_envs: int, window: int = 100, device="cpu", fold: str = "one"):
         self.num_envs, self.window_size = int(num_envs), int(window)
         if self.num_envs <= 0 or self.window_size <= 0:
             raise ValueError(f"EpisodeMonitor needs num_envs > 0 and window > 0, got {num_envs} and {window}")
+        self.fold_form = resolve_fold(fold, self.num_envs)      # "one" or "wide"; not part of a checkpoint (the block is form-agnostic)
         self.device = torch.device(device)
         words = state_words(self.num_envs, self.window_size)
         if self.device.type == "cuda":
@@ -65,6 +87,12 @@ class EpisodeMonitor:
                 _lib.check(nbytes)
             words = max(words, (nbytes + 7) // 8)
         self.state = torch.zeros(words, dtype=torch.int64, device=self.device)       # zeroed once; the kernel owns it from here on
+        self.workspace = None              # fw_episode_fold_wide's scratch: allocated once (a captured graph holds its address)
+        if self.device.type == "cuda" and self.fold_form == "wide":
+            nbytes = int(_lib.lib().fw_episode_fold_workspace_bytes(self.num_envs))
+            if nbytes < 0:
+                _lib.check(nbytes)
+            self.workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=self.device)
         self._saved = None                 # snapshot(): a device copy of the block
         self._last = None                  # the totals at the previous scalars() call (the base of rollout/interval/*)
 
@@ -103,6 +131,11 @@ class EpisodeMonitor:
             raise ValueError("fold() takes contiguous tensors")
         if stream is None:
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if self.workspace is not None:
+            _lib.check(_lib.lib().fw_episode_fold_wide(_ptr(rewards), int(rewards.dtype == torch.float64), _ptr(terminated),
+                                                       _ptr(truncated), _ptr(info), int(info.shape[1]) if info is not None else 0,
+                                                       _ptr(self.state), _ptr(self.workspace), N, self.window_size, stream))
+            return
         _lib.check(_lib.lib().fw_episode_fold(_ptr(rewards), int(rewards.dtype == torch.float64), _ptr(terminated), _ptr(truncated),
                                               _ptr(info), int(info.shape[1]) if info is not None else 0, _ptr(self.state), N,
                                               self.window_size, stream))
@@ -243,9 +276,9 @@ class VecMonitorDevice:
     """Pass-through wrapper of a device env for callers that run their own loop: folds after every ``step`` / ``step_tensor``
     (SB3's ``VecMonitor``).  Everything else is the wrapped env's; ``.monitor`` is the :class:`EpisodeMonitor`."""
 
-    def __init__(self, venv, window: int = 100):
+    def __init__(self, venv, window: int = 100, fold: str = "one"):
         self.venv = venv
-        self.monitor = EpisodeMonitor(venv.num_envs, window, venv.device)
+        self.monitor = EpisodeMonitor(venv.num_envs, window, venv.device, fold)
 
     def _fold(self) -> None:
         v = self.venv

@@ -577,8 +577,14 @@ class PPOConfig:
                                            # success_rate over the last stats_window_size episodes, and the means over all episodes of the
                                            # interval); one more launch per vec-step (fw_episode_fold, monitor.EpisodeMonitor); off: nothing changes
     stats_window_size: int = 100           #        SB3's stats_window_size: episodes in the window
+    episode_fold: str = "one"              #        the fold's device form: "one" (fw_episode_fold, one workgroup), "wide" (fw_episode_fold_wide, one
+                                           #        workgroup per span of envs, three launches: large env counts), "auto" (by monitor.WIDE_FROM_ENVS)
     dist_update: str = "replicated"        # multi-process job: "replicated" = all-gather the rollout shards, every rank runs the same
                                            # minibatch sequence (no per-minibatch collective); "allreduce" = local minibatches + gradient all-reduce
+
+    def __post_init__(self):
+        if self.episode_fold not in ("one", "wide", "auto"):
+            raise ValueError(f"episode_fold must be 'one', 'wide' or 'auto', got {self.episode_fold!r}")
 
 
 class _PpoHyper(C.Structure):
@@ -946,12 +952,14 @@ class PPO:
         self._stats = {}                   # PPO.rollout_stats of the last rollout, once read
         self._stats_host = self._stats_event = None      # the monitor's header + ring in pinned memory, and the event behind the copy
         self._stats_pending, self._stats_figures = False, None
+        from .monitor import resolve_fold
+        resolve_fold(getattr(cfg, "episode_fold", "one"), env.num_envs)          # (ValueError for an unknown form, flag on or off)
         if getattr(cfg, "episode_stats", False):
             from .monitor import EpisodeMonitor
             missing = [k for k in ("rewards", "terminated", "truncated") if not hasattr(getattr(env, "venv", None), k)]
             if missing:
                 raise ValueError("PPOConfig.episode_stats reads the env's output buffers after every step: the env has no " + ", ".join(missing))
-            self.episode_monitor = EpisodeMonitor(env.num_envs, int(cfg.stats_window_size), self.device)
+            self.episode_monitor = EpisodeMonitor(env.num_envs, int(cfg.stats_window_size), self.device, getattr(cfg, "episode_fold", "one"))
         self._diag_buf = self._diag_i = None      # torch path: [rows, 5] float32 device buffer and the device-side minibatch counter
         self._g_update_diag = False               # ... and whether the captured update graph books its rows
 

@@ -61,8 +61,16 @@ class SACConfig:
     seed: int = 0
     use_graphs: bool = True
     fused_update: bool = True
+    episode_stats: bool = False          # SB3's rollout/* figures: SAC.rollout_stats (monitor.EpisodeMonitor folded behind every env step,
+                                         # one more launch per vec-step, inside the captured graphs); off: nothing changes
+    stats_window_size: int = 100         #     SB3's stats_window_size: episodes in the window
+    episode_fold: str = "one"            #     the fold's device form: "one", "wide" or "auto" (monitor.EpisodeMonitor)
 
     def __post_init__(self):
+        if self.episode_fold not in ("one", "wide", "auto"):
+            raise ValueError(f"episode_fold must be 'one', 'wide' or 'auto', got {self.episode_fold!r}")
+        if int(self.stats_window_size) <= 0:
+            raise ValueError("stats_window_size must be positive")
         self.net_arch = tuple(int(h) for h in self.net_arch)
         if len(self.net_arch) != 2 or self.net_arch[0] != self.net_arch[1] or self.net_arch[0] <= 0:
             raise ValueError(f"net_arch must be two equal positive widths, got {self.net_arch}")
@@ -446,6 +454,21 @@ class SAC:
         self._started = False
         self._graphs = {}
         self.logs: Dict[str, float] = {}
+        # SACConfig.episode_stats: the device-side episode monitor, folded once per vec-step behind the env step
+        self.episode_monitor = None
+        if cfg.episode_stats:
+            from .monitor import EpisodeMonitor
+            missing = [k for k in ("rewards", "terminated", "truncated") if not hasattr(env, k)]
+            if missing:
+                raise ValueError("SACConfig.episode_stats reads the env's output buffers after every step: the env has no " + ", ".join(missing))
+            self.episode_monitor = EpisodeMonitor(self.N, int(cfg.stats_window_size), self.device, cfg.episode_fold)
+
+    @property
+    def rollout_stats(self) -> Dict[str, float]:
+        """``EpisodeMonitor.scalars()`` (SACConfig.episode_stats; ``{}`` with the flag off): SB3's ``rollout/ep_rew_mean`` /
+        ``ep_len_mean`` / ``success_rate`` over the window, ``rollout/episodes`` and the ``rollout/interval/*`` means over the episodes
+        finished since the figures were last read.  One small host read when somebody looks, like ``read_logs()``."""
+        return {} if self.episode_monitor is None else self.episode_monitor.scalars()
 
     @property
     def policy(self) -> SacPolicy:
@@ -499,6 +522,9 @@ class SAC:
     def _vec_step_body(self, warm: bool, with_train: bool) -> None:
         self.act(ACT_WARMUP if warm else ACT_STOCHASTIC)
         self.env.step_tensor(self.act_env)
+        if self.episode_monitor is not None:       # (same stream: the env's output buffers hold the step until the next launch)
+            e = self.env
+            self.episode_monitor.fold(e.rewards, e.terminated, e.truncated, getattr(e, "info", None))
         self._store()
         if with_train:
             for _ in range(self.G):
@@ -581,9 +607,12 @@ class SAC:
     # ------------------------------------------------------------------ checkpoints
     def state_dict(self, include_buffer: bool = False):
         self.sync_policy()
-        return {"policy": self._policy.state_dict(), "n_updates": self._policy.n_updates,
-                "optimizers": {k: (o.state_dict() if o is not None else None) for k, o in self.optimizers.items()},
-                "buffer": self.buffer.state_dict(include_buffer), "num_timesteps": self.num_timesteps, "config": asdict(self.cfg)}
+        sd = {"policy": self._policy.state_dict(), "n_updates": self._policy.n_updates,
+              "optimizers": {k: (o.state_dict() if o is not None else None) for k, o in self.optimizers.items()},
+              "buffer": self.buffer.state_dict(include_buffer), "num_timesteps": self.num_timesteps, "config": asdict(self.cfg)}
+        if self.episode_monitor is not None:
+            sd["episode_stats"] = self.episode_monitor.state_dict()
+        return sd
 
     def load_state_dict(self, sd) -> None:
         self.fused.ahead = 0
@@ -595,3 +624,5 @@ class SAC:
         self.buffer.load_state_dict(sd["buffer"])
         self.num_timesteps = int(sd["num_timesteps"])
         self.fused._sig = None
+        if self.episode_monitor is not None and sd.get("episode_stats") is not None:
+            self.episode_monitor.load_state_dict(sd["episode_stats"])

@@ -4,9 +4,13 @@ flag off.
   fold     device time of one fw_episode_fold at 16, 4096, 24 576 and 65 536 envs (window 100): 64 folds over seeded step outputs
            (a tenth of the envs done per step, every env done once) captured in one hipGraph; a region = --replays replays between
            two device synchronisations, timed with events; median of --regions regions
-  collect  a collected vec-step with and without the flag: the one-launch and the three-launch collector (waypoints, 4096 envs) and
-           the high-level collector (16 envs).  Both arms live in one process and alternate; a region = --rollouts replays of the
-           captured rollout graph between two synchronisations; median of --regions regions per arm
+  wide     fw_episode_fold against fw_episode_fold_wide (EpisodeMonitor(fold="one" / "wide")) on the same seeded step outputs at 16,
+           4096, 24 576, 65 536 and 2^20 envs: the two forms alternate region by region in one process; median of --regions regions
+           and the min / max of each arm.  The span is the loaded library's: run once per candidate build (FWSIM_LIB)
+  collect  a collected vec-step without the flag, with it, and with it on the multi-workgroup fold (episode_fold="wide"): the
+           one-launch and the three-launch collector (waypoints, 4096 envs; --collect_65536: the three-launch one at 65 536 too) and
+           the high-level collector (16 envs, no wide arm).  The arms live in one process and alternate; a region = --rollouts
+           replays of the captured rollout graph between two synchronisations; median of --regions regions per arm
   e2e      env-steps/s of examples/train_fixedwing_waypoints.py with and without --episode_stats over --total_timesteps steps each
            (child processes, one at a time, the arms in turn --e2e_repeats times), and a closing line with the medians
   parent   the flag-off headline step through tools/bench_lib.py with this build's library, the parent commit's (--parent_lib) and a
@@ -14,6 +18,8 @@ flag off.
 
     python tools/bench_episode_stats.py --what fold --out profiles/r14_episode_stats_bench.jsonl
     python tools/bench_episode_stats.py --what collect --out profiles/r14_episode_stats_bench.jsonl
+    python tools/bench_episode_stats.py --what wide --out profiles/r25_episode_fold_wide.jsonl
+    python tools/bench_episode_stats.py --what collect --collect_65536 --out profiles/r25_episode_fold_wide.jsonl
     python tools/bench_episode_stats.py --what e2e --out profiles/r14_episode_stats_bench.jsonl
     python tools/bench_episode_stats.py --what parent --parent_lib /path/to/parent/libfwsim_hip.so --out profiles/r14_episode_stats_bench.jsonl
 """
@@ -31,6 +37,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 FOLD_ENVS = (16, 4096, 24576, 65536)
+WIDE_ENVS = FOLD_ENVS + (1 << 20,)
 
 
 def median(xs):
@@ -84,7 +91,64 @@ def bench_fold(a, dev):
     return rows
 
 
-def _collector(kind, stats):
+def _span():
+    from pyflyt_drone_amd import _lib
+    return int(_lib.lib().fw_episode_fold_span())
+
+
+def bench_wide(a, dev):
+    """Both forms of the fold on the same seeded step outputs, alternating region by region in one process; one row per env count.
+    The span is the loaded library's (FWSIM_LIB: one run per candidate span)."""
+    import torch
+    from pyflyt_drone_amd import monitor as M
+    span = _span()
+    rows = []
+    for N in WIDE_ENVS:
+        T = 64 if N <= 65536 else 16                         # (2^20 envs: 16 steps of outputs are 0.8 GB as it is)
+        g = torch.Generator(device="cuda"); g.manual_seed(N)
+        rew = torch.randn((T, N), device="cuda", generator=g, dtype=torch.float64)
+        done = torch.rand((T, N), device="cuda", generator=g) < 0.1
+        done[T // 2] = True                                  # every env meets a time limit together once per graph
+        trunc = (done & (torch.rand((T, N), device="cuda", generator=g) < 0.5)).to(torch.uint8)
+        term = (done & (trunc == 0)).to(torch.uint8)
+        info = torch.randint(0, 2, (T, N, 8), device="cuda", generator=g, dtype=torch.int32)
+        del done
+        arms, graphs = {k: M.EpisodeMonitor(N, a.window, "cuda", fold=k) for k in ("one", "wide")}, {}
+        for k, m in arms.items():
+            for t in range(T):                               # warm-up: the code object is loaded, the ring is full
+                m.fold(rew[t], term[t], trunc[t], info[t])
+            torch.cuda.synchronize()
+            graphs[k] = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graphs[k]):
+                for t in range(T):
+                    m.fold(rew[t], term[t], trunc[t], info[t])
+            graphs[k].replay(); torch.cuda.synchronize()
+        replays = a.replays if N <= 65536 else 1
+        times = {k: [] for k in arms}
+        for _ in range(a.regions):                           # the arms alternate region by region
+            for k in arms:
+                def work(gr=graphs[k]):
+                    for _ in range(replays):
+                        gr.replay()
+                times[k] += regions(work, 1, replays * T)
+        med = {k: median(v) for k, v in times.items()}
+        spread = {k: max(v) - min(v) for k, v in times.items()}
+        same = arms["one"].totals()["episodes"] == arms["wide"].totals()["episodes"]
+        rows.append({"what": "wide", "envs": N, "span": span, "workgroups": -(-N // span), "window": a.window,
+                     "folds_per_region": replays * T, "regions_per_arm": a.regions,
+                     "one_us_per_fold_median": round(med["one"], 3), "wide_us_per_fold_median": round(med["wide"], 3),
+                     "one_min_max_us": [round(min(times["one"]), 3), round(max(times["one"]), 3)],
+                     "wide_min_max_us": [round(min(times["wide"]), 3), round(max(times["wide"]), 3)],
+                     "one_over_wide": round(med["one"] / med["wide"], 3),
+                     "wide_faster_by_more_than_both_spreads": bool(med["one"] - med["wide"] > spread["one"] + spread["wide"]),
+                     "wide_not_slower": bool(med["wide"] <= med["one"]),
+                     "episodes_folded_equal": bool(same), "device": dev})
+        del rew, trunc, term, info, arms, graphs
+        torch.cuda.empty_cache()
+    return rows
+
+
+def _collector(kind, stats, fold="one", envs=4096):
     import numpy as np
     import torch
     import pyflyt_drone_amd as P
@@ -98,16 +162,18 @@ def _collector(kind, stats):
         env = R.VecNormalizeDevice(HighLevelCmdVecEnv(16, pol, (mean, var), seed=13), gamma=0.995)
         return R.PPO(env, R.PPOConfig(n_steps=16, batch_size=64, n_epochs=1, gamma=0.995, seed=13, fused_three_actions=True,
                                       episode_stats=stats))
-    env = R.VecNormalizeDevice(P.FixedwingWaypointsVecEnv(4096, angle_representation="euler", seed=11))
+    env = R.VecNormalizeDevice(P.FixedwingWaypointsVecEnv(envs, angle_representation="euler", seed=11))
     return R.PPO(env, R.PPOConfig(n_steps=16, batch_size=128, n_epochs=1, seed=11, one_launch_collect=(kind == "one_launch"),
-                                  episode_stats=stats))
+                                  episode_stats=stats, episode_fold=fold))
 
 
 def bench_collect(a, dev):
     import torch
     rows = []
-    for kind in ("one_launch", "three_launch", "highlevel"):
-        arms = {"off": _collector(kind, False), "on": _collector(kind, True)}
+    for kind, envs in (("one_launch", 4096), ("three_launch", 4096), ("highlevel", 16)) + ((("three_launch", 65536),) if a.collect_65536 else ()):
+        arms = {"off": _collector(kind, False, envs=envs), "on": _collector(kind, True, envs=envs)}
+        if kind != "highlevel":
+            arms["wide"] = _collector(kind, True, "wide", envs=envs)
         for p in arms.values():
             for _ in range(3):                               # eager, capture, replay
                 p.collect_rollouts()
@@ -130,6 +196,12 @@ def bench_collect(a, dev):
                      "off_min_max_us": [round(min(times["off"]), 3), round(max(times["off"]), 3)],
                      "on_min_max_us": [round(min(times["on"]), 3), round(max(times["on"]), 3)],
                      "episodes_seen": stats.get("rollout/episodes"), "device": dev})
+        if "wide" in arms:                                   # the third arm: the flag on, the multi-workgroup fold
+            rows[-1].update({"wide_us_per_vec_step": round(med["wide"], 3), "wide_minus_off_us": round(med["wide"] - med["off"], 3),
+                             "wide_over_off": round(med["wide"] / med["off"], 4),
+                             "wide_min_max_us": [round(min(times["wide"]), 3), round(max(times["wide"]), 3)],
+                             "span": _span(),
+                             "episodes_seen_wide": arms["wide"].rollout_stats.get("rollout/episodes")})
         for p in arms.values():
             p.env.venv.close()
     return rows
@@ -193,7 +265,8 @@ def bench_parent(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", choices=("fold", "collect", "e2e", "parent"), default="fold")
+    ap.add_argument("--what", choices=("fold", "wide", "collect", "e2e", "parent"), default="fold")
+    ap.add_argument("--collect_65536", action="store_true", help="collect: the three-launch collector at 65 536 envs as well")
     ap.add_argument("--regions", type=int, default=30)
     ap.add_argument("--replays", type=int, default=4, help="fold: graph replays (64 folds each) per region")
     ap.add_argument("--rollouts", type=int, default=8, help="collect: rollout-graph replays (16 vec-steps each) per region")
@@ -209,7 +282,7 @@ def main():
     else:
         import torch
         dev = torch.cuda.get_device_name(0)
-        rows = bench_fold(a, dev) if a.what == "fold" else bench_collect(a, dev)
+        rows = {"fold": bench_fold, "wide": bench_wide, "collect": bench_collect}[a.what](a, dev)
     for r in rows:
         print(json.dumps(r), flush=True)
     if a.out:
