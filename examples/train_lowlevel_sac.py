@@ -12,6 +12,11 @@ In ``demo`` mode every evaluation line also carries the heading MAE and RMSE in 
 
     python examples/train_lowlevel_sac.py --out runs/lowlevel_sac
     python examples/train_lowlevel_sac.py --env demo --out runs/lowlevel_sac_demo
+
+At thousands of envs the reference's update-to-data ratio of 1 is thousands of small gradient steps per vec-step; the large-env recipe
+is one gradient step per vec-step on a batch as large as the env count (the wide form of ``fw_sac_update``, batches up to 8192):
+
+    python examples/train_lowlevel_sac.py --num_envs 4096 --batch_size 4096 --gradient_steps 1 --total_timesteps 2000000
 """
 import argparse
 import json
@@ -37,6 +42,9 @@ def main():
     ap.add_argument("--total_timesteps", type=int, default=TRAIN_CONFIG["total_timesteps"])
     ap.add_argument("--num_envs", type=int, default=16)
     ap.add_argument("--gradient_steps", type=int, default=-1, help="per vec-step; -1: one per env (update-to-data 1, as the reference)")
+    ap.add_argument("--batch_size", type=int, default=TRAIN_CONFIG["batch_size"],
+                    help="rows per gradient step: a multiple of 16 up to 512, or a multiple of 64 up to 8192; the large-env recipe is "
+                         "--num_envs 4096 --batch_size 4096 --gradient_steps 1")
     ap.add_argument("--fused_update", action=argparse.BooleanOptionalAction, default=True,
                     help="fw_sac_update (default) or the torch gradient step")
     ap.add_argument("--use_graphs", action=argparse.BooleanOptionalAction, default=True)
@@ -62,7 +70,7 @@ def main():
         eval_cfg = K.lowlevel_config(max_episode_steps=a.eval_max_steps)
     eval_env = R.VecNormalizeDevice(P.FixedwingVecEnv(eval_cfg, 16, seed=c["seed"], global_env_offset=a.num_envs),
                                     training=False, norm_obs=False, norm_reward=False)
-    model = S.SAC(env, S.SACConfig(learning_rate=c["learning_rate"], buffer_size=c["buffer_size"], batch_size=c["batch_size"],
+    model = S.SAC(env, S.SACConfig(learning_rate=c["learning_rate"], buffer_size=c["buffer_size"], batch_size=a.batch_size,
                                    gamma=c["gamma"], tau=c["tau"], gradient_steps=a.gradient_steps,
                                    target_update_interval=c["target_update_interval"], learning_starts=c["learning_starts"],
                                    net_arch=c["net_arch"], seed=c["seed"], use_graphs=a.use_graphs, fused_update=a.fused_update,
@@ -93,7 +101,7 @@ def main():
             state["next_eval"] += a.eval_freq
         return True
 
-    print(json.dumps({"config": {**{k: v for k, v in c.items()}, **({"env": a.env} if demo else {}), "num_envs": a.num_envs, "gradient_steps": model.G,
+    print(json.dumps({"config": {**{k: v for k, v in c.items()}, "batch_size": a.batch_size, "total_timesteps": a.total_timesteps, "eval_freq": a.eval_freq, **({"env": a.env} if demo else {}), "num_envs": a.num_envs, "gradient_steps": model.G,
                                  "fused_update": a.fused_update, "use_graphs": a.use_graphs}}), flush=True)
     evaluate_now(model)                      # the untrained actor: the line later evaluations are read against
     try:

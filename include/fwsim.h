@@ -930,7 +930,8 @@ int32_t fw_probe(fw_handle h, int32_t op, int32_t variant, const double* in, int
 /* ---- Soft actor-critic for the low-level task (csrc/fwsim_sac.hpp; SB3 `SAC("MlpPolicy")`, one gradient step of `SAC.train()`) ----
  * ReLU MLPs in fp32: the actor obs_dim -> hidden -> hidden -> 2 act_dim (mean | log_std, clamped to [-20, 2]), two critics and their two
  * targets (obs_dim + act_dim) -> hidden -> hidden -> 1.  Built for obs_dim <= 64, act_dim <= 8, hidden 64 or 256 and batches that are
- * multiples of 16 in [16, 512]: anything else FW_EUNSUPPORTED; NULL pointers and non-positive sizes FW_EINVAL.  No handle: every
+ * multiples of 16 in [16, 512] or multiples of 64 in (512, 8192] (the wide form of the gradient step, below): anything else
+ * FW_EUNSUPPORTED; NULL pointers and non-positive sizes FW_EINVAL.  No handle: every
  * buffer is a device buffer of the caller, everything is stream-ordered, nothing allocates, synchronises or reads device state on the
  * host, so all five entry points can be captured into a graph.
  *
@@ -961,15 +962,20 @@ int32_t fw_replay_store(float* ring, int64_t capacity, int64_t* counters, const 
                         const void* next_obs, const void* terminal_obs, const uint8_t* terminated, const uint8_t* truncated, int32_t env_is_f64,
                         int32_t N, int32_t obs_dim, int32_t act_dim, void* hip_stream);
 /* `batch` uniform row indices in [0, counters[1]) from Philox keyed by (seed, counters[3]); gathers the rows into out [batch, row_floats]
- * and writes the indices to idx_out (optional). */
+ * and writes the indices to idx_out (optional).  Any positive batch: the batch rule above is fw_sac_update's and its workspace's. */
 int32_t fw_replay_sample(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
                          float* out, int32_t* idx_out, void* hip_stream);
-/* eps and eps' [2][batch][act_dim] of gradient step counters[3]: the values fw_sac_update draws inside. */
+/* eps and eps' [2][batch][act_dim] of gradient step counters[3]: the values fw_sac_update draws inside.  A row's noise does not
+ * depend on the batch size.  Any positive batch, as fw_replay_sample. */
 int32_t fw_sac_noise(uint64_t seed, const int64_t* counters, int32_t batch, int32_t act_dim, float* out, void* hip_stream);
 /* One gradient step on the image from batch_rows [batch, 2 obs_dim + act_dim + 2]: a fixed sequence of 24 launches, kernel boundaries
  * the only synchronisation between workgroups, every weight gradient summed over the batch by one workgroup in a fixed order (two runs
  * give the same bits).  out (optional) [5]: critic loss, actor loss, ent-coef loss, alpha (before the step), mean logp.  Increments
- * tail[0] and counters[3]. */
+ * tail[0] and counters[3].
+ * batch > 512 takes the wide form, 29 launches: the stages that sum over the batch run one workgroup per 256 rows and a one-lane fold
+ * adds their partial sums in ascending order; a weight gradient is split into chunks of 512 batch rows (one workgroup per tile and
+ * chunk) and a second launch adds the chunks in ascending order and applies Adam.  The split depends on batch alone: two runs still
+ * give the same bits.  fw_sac_update_workspace_bytes grows by the partial sums for these sizes only. */
 int32_t fw_sac_update(float* image, const float* batch_rows, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch, const fw_sac_hyper* hyper,
                       int64_t* counters, float* out, void* workspace, int64_t workspace_bytes, void* hip_stream);
 const char* fw_last_error(fw_handle h); /* h may be NULL: last create/validate error */

@@ -3485,9 +3485,10 @@ static int32_t sac_check_shape(const char* who, int32_t d, int32_t A, int32_t H)
 }
 static int32_t sac_check_batch(const char* who, int32_t B) {
   if (B <= 0) { g_err = std::string(who) + ": the batch size must be positive"; return FW_EINVAL; }
-  if (!sac_batch_ok(B)) { g_err = std::string(who) + ": built for batch sizes that are multiples of 16 in [16, 512], got " + std::to_string(B); return FW_EUNSUPPORTED; }
+  if (!sac_batch_ok(B)) { g_err = std::string(who) + ": built for batch sizes that are multiples of 16 in [16, 512] or multiples of 64 in (512, 8192], got " + std::to_string(B); return FW_EUNSUPPORTED; }
   return FW_OK;
 }
+static int64_t sac_ws_floats(int32_t d, int32_t A, int32_t H, int32_t B) { return (int64_t)sac_ws_wide(d, A, H, B).total; }
 int32_t fw_sizeof_sac_hyper(void) { return (int32_t)sizeof(fw_sac_hyper); }
 int32_t fw_sac_param_count(int32_t obs_dim, int32_t act_dim, int32_t hidden) {
   const int32_t rc = sac_check_shape("fw_sac_param_count", obs_dim, act_dim, hidden);
@@ -3496,7 +3497,7 @@ int32_t fw_sac_param_count(int32_t obs_dim, int32_t act_dim, int32_t hidden) {
 int64_t fw_sac_update_workspace_bytes(int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch) {
   int32_t rc = sac_check_shape("fw_sac_update_workspace_bytes", obs_dim, act_dim, hidden);
   if (rc == FW_OK) rc = sac_check_batch("fw_sac_update_workspace_bytes", batch);
-  return rc != FW_OK ? rc : (int64_t)sac_ws(obs_dim, act_dim, hidden, batch).total * (int64_t)sizeof(float);
+  return rc != FW_OK ? rc : sac_ws_floats(obs_dim, act_dim, hidden, batch) * (int64_t)sizeof(float);
 }
 int32_t fw_sac_act(const float* image, const void* obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t mode,
                    uint64_t seed, int64_t env_offset, const int64_t* counters, float* act_f32, void* act_env, float* obs_stage, float* logp,
@@ -3559,7 +3560,7 @@ int32_t fw_sac_update(float* image, const float* batch_rows, int32_t obs_dim, in
   int32_t rc = sac_check_shape("fw_sac_update", obs_dim, act_dim, hidden);
   if (rc == FW_OK) rc = sac_check_batch("fw_sac_update", batch);
   if (rc != FW_OK) return rc;
-  if (workspace_bytes < (int64_t)sac_ws(obs_dim, act_dim, hidden, batch).total * (int64_t)sizeof(float)) { g_err = "fw_sac_update: the workspace is smaller than fw_sac_update_workspace_bytes asks for"; return FW_EINVAL; }
+  if (workspace_bytes < sac_ws_floats(obs_dim, act_dim, hidden, batch) * (int64_t)sizeof(float)) { g_err = "fw_sac_update: the workspace is smaller than fw_sac_update_workspace_bytes asks for"; return FW_EINVAL; }
   static_assert(sizeof(fw_sac_hyper) == sizeof(SacHyper), "fw_sac_hyper and SacHyper must agree");
   DeviceGuard g(device_of(image));
   SacStepArgs S{};

@@ -17,6 +17,12 @@
 // (forward, G W^T) all precede the one that updates them, so every gradient comes from the pre-step weights (the actor loss reads the
 // critics AFTER their step, as SB3 does).
 //
+// Batches of 16 to 512 rows (multiples of 16) take that sequence.  Larger ones, up to 8192 rows in multiples of 64, take the WIDE form
+// of the same stages, 29 launches: the three stages that sum over the batch run one workgroup per 256 rows, each storing its sum to a
+// workspace slot that a one-lane fold launch adds in ascending order; a weight gradient is cut into chunks of 512 batch rows, one
+// workgroup per (tile, chunk) storing raw partial sums, and a second launch adds the chunks of each element in ascending order and
+// applies Adam.  The number of chunks depends on B alone, so two runs still give the same bits.
+//
 // Device counters (int64[4], caller-owned): [0] ring cursor (rows), [1] rows filled, [2] vec-steps stored, [3] gradient steps.  The
 // kernels that read a counter never write it in the same launch: fw_replay_store and fw_sac_update advance them from one lane of a
 // closing launch, with plain vector stores.
@@ -30,6 +36,10 @@
 namespace fwsim {
 
 constexpr int kSacMaxD = 64, kSacMaxA = 8, kSacMaxB = 512;
+// the wide form of the gradient step (B > kSacMaxB): element-wise stages of kSacStageRows rows per workgroup, weight gradients split
+// over the batch in chunks of kSacSplitRows rows
+constexpr int kSacMaxBWide = 8192, kSacWideMultiple = 64, kSacStageRows = 256, kSacSplitRows = 512;
+constexpr int kSacWideSlots = 2 * kSacMaxBWide / kSacStageRows;          // partial sums of one stage (the head stage has 2B rows)
 constexpr uint32_t kSacTagAct = 0x5AC0A000u, kSacTagWarm = 0x5AC0B000u, kSacTagSample = 0x5AC0C000u, kSacTagNoise = 0x5AC0D000u;
 constexpr float kSacLogStdMin = -20.0f, kSacLogStdMax = 2.0f, kSacHalfLog2Pi = 0.9189385332046727f, kSacTanhEps = 1e-6f;
 
@@ -40,26 +50,28 @@ struct SacHyper {          // mirrors fw_sac_hyper (include/fwsim.h)
 };
 
 struct SacNet { int W1, b1, W2, b2, W3, b3, n; };
-__host__ __device__ inline SacNet sac_net(int in, int H, int out) {
-  SacNet s;
+__host__ __device__ constexpr SacNet sac_net(int in, int H, int out) {
+  SacNet s{};
   s.W1 = 0; s.b1 = in * H; s.W2 = s.b1 + H; s.b2 = s.W2 + H * H; s.W3 = s.b2 + H; s.b3 = s.W3 + H * out; s.n = s.b3 + out;
   return s;
 }
 struct SacLayout { int actor, q1, q2, lec, t1, t2, P, T, m, v, tail, total; };
-__host__ __device__ inline SacLayout sac_layout(int d, int A, int H) {
+__host__ __device__ constexpr SacLayout sac_layout(int d, int A, int H) {
   const int na = sac_net(d, H, 2 * A).n, nc = sac_net(d + A, H, 1).n;
-  SacLayout L;
+  SacLayout L{};
   L.actor = 0; L.q1 = na; L.q2 = na + nc; L.lec = na + 2 * nc; L.t1 = L.lec + 1; L.t2 = L.t1 + nc; L.P = L.t2 + nc;
   L.T = L.lec + 1; L.m = L.P; L.v = L.P + L.T; L.tail = L.P + 2 * L.T; L.total = L.tail + 4;
   return L;
 }
 inline bool sac_shape_ok(int d, int A, int H) { return d >= 1 && d <= kSacMaxD && A >= 1 && A <= kSacMaxA && (H == 64 || H == 256); }
-inline bool sac_batch_ok(int B) { return B >= 16 && B <= kSacMaxB && B % 16 == 0; }
+inline bool sac_batch_wide(int B) { return B > kSacMaxB && B <= kSacMaxBWide && B % kSacWideMultiple == 0; }
+inline bool sac_batch_ok(int B) { return (B >= 16 && B <= kSacMaxB && B % 16 == 0) || sac_batch_wide(B); }
+__host__ __device__ constexpr int sac_splits(int B) { return (B + kSacSplitRows - 1) / kSacSplitRows; }
 
 // workspace of fw_sac_update (floats)
 struct SacWs { int noise, h1a, h2a, outa, logp, xpi, xnext, ch1, ch2, q, g3, G2, G1, dx, gout, scal, total; };
-__host__ __device__ inline SacWs sac_ws(int d, int A, int H, int B) {
-  SacWs w; int o = 0;
+__host__ __device__ constexpr SacWs sac_ws(int d, int A, int H, int B) {
+  SacWs w{}; int o = 0;
   auto take = [&](int n) { const int at = o; o += (n + 3) & ~3; return at; };
   w.noise = take(2 * B * A); w.h1a = take(2 * B * H); w.h2a = take(2 * B * H); w.outa = take(2 * B * 2 * A); w.logp = take(2 * B);
   w.xpi = take(B * (d + A)); w.xnext = take(B * (d + A)); w.ch1 = take(4 * B * H); w.ch2 = take(4 * B * H); w.q = take(4 * B);
@@ -67,6 +79,21 @@ __host__ __device__ inline SacWs sac_ws(int d, int A, int H, int B) {
   w.scal = take(16); w.total = o;
   return w;
 }
+// what the wide form (B > kSacMaxB) adds behind it: the stages' partial sums (slots: head | target | actor-q, kSacWideSlots each) and
+// the weight gradients' partial sums (part[split][T], indexed like the trained part of the image); up to kSacMaxB nothing is added
+struct SacWsWide { int slots, part, total; };
+__host__ __device__ constexpr SacWsWide sac_ws_wide(int d, int A, int H, int B) {
+  SacWsWide w{};
+  w.slots = w.part = w.total = sac_ws(d, A, H, B).total;
+  if (B > kSacMaxB) {
+    w.part = w.slots + 3 * kSacWideSlots;
+    w.total = w.part + ((sac_splits(B) * sac_layout(d, A, H).T + 3) & ~3);
+  }
+  return w;
+}
+// The kernels index the workspace with int.  The layout grows with every argument, so the largest shape decides; constant evaluation
+// rejects a signed overflow, so this line compiles only while every offset of that shape fits.
+static_assert(sac_ws_wide(kSacMaxD, kSacMaxA, 256, kSacMaxBWide).total > 0, "fw_sac_update's workspace offsets must stay inside int");
 // scal: the step's scalars, written by the head / target / actor kernels and read by later launches
 enum { SAC_S_ALPHA = 0, SAC_S_STEP_SIZE = 1, SAC_S_INV_BC2 = 2, SAC_S_POLYAK = 3, SAC_S_MEAN_LOGP = 4, SAC_S_ENT_LOSS = 5,
        SAC_S_CRITIC_LOSS = 6, SAC_S_ACTOR_LOSS = 7 };
@@ -260,6 +287,8 @@ __device__ __forceinline__ void sac_adam(float* p, float* m1, float* m2, float g
 }
 
 constexpr int kSgKc = 32, kSgLda = kSgKc + 1, kSgLdb = 64 + 1;
+// (fw_sac_wgrad_split_kernel below carries a copy of this kernel's staging and MFMA loop with other K bounds: a change to one belongs in
+// the other.  A shared inlined loop was tried; it changes this kernel's register allocation, so the existing path would have moved.)
 __global__ __launch_bounds__(256) void fw_sac_gemm_kernel(SacGemmArgs G) {
   __shared__ float As[64 * kSgLda], Bs[kSgKc * kSgLdb];
   const SacGemmJob& J = G.job[blockIdx.z];
@@ -318,6 +347,78 @@ __global__ __launch_bounds__(256) void fw_sac_gemm_kernel(SacGemmArgs G) {
     }
   }
   if (do_col && n0 + t < J.N) sac_adam(J.pb + n0 + t, J.mb1 + n0 + t, J.mb2 + n0 + t, colsum, ss, ib, G.beta1, G.beta2, G.eps);
+}
+
+// ---- the wide form's weight gradients: X^T G split over the batch, then one fold with Adam ----
+// One workgroup per (64 x 64 weight tile, chunk of kSacSplitRows batch rows): fw_sac_gemm_kernel's staging and MFMA loop over the rows
+// of its chunk alone, the raw accumulators (and the bias column sums of the chunk) stored to part[split][element], element = the
+// offset of the weight in the image.  Every element of a family's range is written by exactly one workgroup per split.
+// The loop is fw_sac_gemm_kernel's, line for line, with [kb, ke) for [0, K): keep the two in step.
+struct SacSplitArgs { SacGemmJob job[kSacMaxJobs]; const float* image; float* part; int T, nsplit; };
+__global__ __launch_bounds__(256) void fw_sac_wgrad_split_kernel(SacSplitArgs G) {
+  __shared__ float As[64 * kSgLda], Bs[kSgKc * kSgLdb];
+  const int split = blockIdx.z % G.nsplit;
+  const SacGemmJob& J = G.job[blockIdx.z / G.nsplit];
+  const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
+  if (m0 >= J.M || n0 >= J.N) return;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, i = lane & 15, g = lane >> 4;
+  const int left = (J.N - n0 + 15) >> 4, ntile = left < 4 ? left : 4;
+  const int kb = split * kSacSplitRows, ke = kb + kSacSplitRows < J.K ? kb + kSacSplitRows : J.K;
+  f32x4 acc[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const bool do_col = J.pb != nullptr && m0 == 0 && t < 64;
+  float colsum = 0.f;
+  for (int k0 = kb; k0 < ke; k0 += kSgKc) {
+    for (int idx = t; idx < 64 * kSgKc; idx += 256) {
+      int m, k;
+      if (J.sak == 1) { k = idx % kSgKc; m = idx / kSgKc; } else { m = idx & 63; k = idx >> 6; }
+      const int gm = m0 + m, gk = k0 + k;
+      As[m * kSgLda + k] = (gm < J.M && gk < ke) ? J.A[(size_t)gm * J.sam + (size_t)gk * J.sak] : 0.f;
+    }
+    for (int idx = t; idx < 64 * kSgKc; idx += 256) {
+      int k, n;
+      if (J.sbn == 1) { n = idx & 63; k = idx >> 6; } else { k = idx % kSgKc; n = idx / kSgKc; }
+      const int gk = k0 + k, gn = n0 + n;
+      Bs[k * kSgLdb + n] = (gk < ke && gn < J.N) ? J.B[(size_t)gk * J.sbk + (size_t)gn * J.sbn] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < kSgKc / 4; ++s) {
+      const int k = 4 * s + g;
+      const float a = As[(16 * w + i) * kSgLda + k];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < ntile) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Bs[k * kSgLdb + 16 * j + i], acc[j], 0, 0, 0);
+    }
+    if (do_col)
+      for (int k = 0; k < kSgKc; ++k) colsum += Bs[k * kSgLdb + t];
+    __syncthreads();
+  }
+  float* out = G.part + (size_t)split * G.T;
+  const size_t woff = (size_t)(J.C - G.image);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (j >= ntile) continue;
+    const int n = n0 + 16 * j + i;
+    if (n >= J.N) continue;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int m = m0 + 16 * w + 4 * g + v;
+      if (m < J.M) out[woff + (size_t)m * J.ldc + n] = acc[j][v];
+    }
+  }
+  if (do_col && n0 + t < J.N) out[(size_t)(J.pb - G.image) + n0 + t] = colsum;
+}
+// image[e0, e1): the gradient is the sum of the splits in ascending order; Adam as in fw_sac_gemm_kernel's epilogue (a parameter and
+// its moments sit at the same offset of their blocks)
+struct SacAdamFoldArgs { float* image; const float* part; const float* scal; int e0, e1, T, nsplit, m, v; float beta1, beta2, eps; };
+__global__ __launch_bounds__(256) void fw_sac_adam_fold_kernel(SacAdamFoldArgs F) {
+  const int e = F.e0 + blockIdx.x * 256 + threadIdx.x;
+  if (e >= F.e1) return;
+  float g = F.part[e];
+  for (int s = 1; s < F.nsplit; ++s) g += F.part[(size_t)s * F.T + e];
+  sac_adam(F.image + e, F.image + F.m + e, F.image + F.v + e, g, F.scal[SAC_S_STEP_SIZE], F.scal[SAC_S_INV_BC2], F.beta1, F.beta2, F.eps);
 }
 
 // ---- the element-wise stages: one workgroup each, sums over the batch in a fixed order ----
@@ -409,6 +510,74 @@ __global__ __launch_bounds__(256) void fw_sac_actor_q_kernel(SacStepArgs S) {
   const float sum = sac_block_sum(part, red);
   if (t == 0) S.ws[W.scal + SAC_S_ACTOR_LOSS] = sum * invB;
 }
+// The wide form of the three (B > kSacMaxB; the kernels above stay as they are, so their device code does not move): workgroup k
+// takes rows [k kSacStageRows, (k + 1) kSacStageRows), one per thread, with the arithmetic of the loops above, and stores its sum
+// (thread order) to slot k of its stage; the fold launch behind it adds the slots in ascending order on one lane and does what thread
+// 0 does above.
+enum { SAC_STAGE_HEAD = 0, SAC_STAGE_TARGET = 1, SAC_STAGE_ACTOR_Q = 2 };
+template <int STAGE>
+__global__ __launch_bounds__(256) void fw_sac_stage_wide_kernel(SacStepArgs S) {
+  static_assert(kSacStageRows == 256, "one row per thread");
+  __shared__ float red[256];
+  const int d = S.d, A = S.A, B = S.B, Kc = d + A, R = 2 * d + A + 2, r = blockIdx.x * kSacStageRows + threadIdx.x;
+  const SacWs W = sac_ws(d, A, S.H, B);
+  const float alpha = STAGE == SAC_STAGE_HEAD ? 0.f : S.ws[W.scal + SAC_S_ALPHA], invB = 1.0f / (float)B;
+  const float* q = S.ws + W.q;
+  float part = 0.f;
+  if (STAGE == SAC_STAGE_HEAD && r < 2 * B) {
+    const int which = r >= B, b = which ? r - B : r;
+    const float* o = S.ws + W.outa + (size_t)r * 2 * A;
+    float* x = S.ws + (which ? W.xnext : W.xpi) + (size_t)b * Kc;
+    const float* src = S.batch + (size_t)b * R + (which ? Kc + 1 : 0);
+    for (int k = 0; k < d; ++k) x[k] = src[k];
+    const float lp = sac_squash(o, o + A, S.ws + W.noise + ((size_t)which * B + b) * A, A, false, x + d);
+    S.ws[W.logp + r] = lp;
+    if (!which) part = lp;
+  }
+  if (STAGE == SAC_STAGE_TARGET && r < B) {
+    const float* row = S.batch + (size_t)r * R;
+    const float y = row[d + A] + (1.0f - row[R - 1]) * S.hp.gamma * (fminf(q[2 * B + r], q[3 * B + r]) - alpha * S.ws[W.logp + B + r]);
+    const float e1 = q[r] - y, e2 = q[B + r] - y;
+    S.ws[W.g3 + r] = e1 * invB; S.ws[W.g3 + B + r] = e2 * invB;
+    part = e1 * e1 + e2 * e2;
+  }
+  if (STAGE == SAC_STAGE_ACTOR_Q && r < B) {
+    const bool first = q[r] <= q[B + r];
+    S.ws[W.g3 + r] = first ? -invB : 0.f; S.ws[W.g3 + B + r] = first ? 0.f : -invB;
+    part = alpha * S.ws[W.logp + r] - (first ? q[r] : q[B + r]);
+  }
+  const float sum = sac_block_sum(part, red);
+  if (threadIdx.x == 0) S.ws[sac_ws_wide(d, A, S.H, B).slots + STAGE * kSacWideSlots + blockIdx.x] = sum;
+}
+__global__ __launch_bounds__(64) void fw_sac_stage_fold_kernel(SacStepArgs S, int stage, int nslots) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const SacWs W = sac_ws(S.d, S.A, S.H, S.B);
+  const SacLayout L = sac_layout(S.d, S.A, S.H);
+  const float* slot = S.ws + sac_ws_wide(S.d, S.A, S.H, S.B).slots + stage * kSacWideSlots;
+  float* sc = S.ws + W.scal;
+  const float invB = 1.0f / (float)S.B;
+  float sum = 0.f;
+  for (int k = 0; k < nslots; ++k) sum += slot[k];
+  if (stage == SAC_STAGE_TARGET) { sc[SAC_S_CRITIC_LOSS] = 0.5f * sum * invB; return; }
+  if (stage == SAC_STAGE_ACTOR_Q) { sc[SAC_S_ACTOR_LOSS] = sum * invB; return; }
+  const float mean_logp = sum / (float)S.B;
+  const int step = ((const int32_t*)(S.image + L.tail))[0] + 1;
+  const double bc1 = 1.0 - pow((double)S.hp.beta1, (double)step), bc2 = 1.0 - pow((double)S.hp.beta2, (double)step);
+  const float step_size = (float)((double)S.hp.lr / bc1), inv_bc2 = (float)(1.0 / sqrt(bc2));
+  sc[SAC_S_STEP_SIZE] = step_size; sc[SAC_S_INV_BC2] = inv_bc2;
+  const int tui = S.hp.target_update_interval < 1 ? 1 : S.hp.target_update_interval;
+  sc[SAC_S_POLYAK] = (step % tui) == 0 ? 1.f : 0.f;
+  sc[SAC_S_MEAN_LOGP] = mean_logp;
+  if (S.hp.auto_ent) {
+    float* lec = S.image + L.lec;
+    sc[SAC_S_ALPHA] = expf(*lec);
+    sc[SAC_S_ENT_LOSS] = -(*lec * (mean_logp + S.hp.target_entropy));
+    sac_adam(lec, S.image + L.m + L.lec, S.image + L.v + L.lec, -(mean_logp + S.hp.target_entropy), step_size, inv_bc2,
+             S.hp.beta1, S.hp.beta2, S.hp.eps);
+  } else {
+    sc[SAC_S_ALPHA] = S.hp.ent_coef; sc[SAC_S_ENT_LOSS] = 0.f;
+  }
+}
 // dL/d(mean, raw log_std) of the actor loss from dL/da (the critics' input gradient) and the log-probability
 __global__ __launch_bounds__(256) void fw_sac_actor_grad_kernel(SacStepArgs S) {
   const int d = S.d, A = S.A, B = S.B, Kc = d + A, e = blockIdx.x * 256 + threadIdx.x;
@@ -463,8 +632,28 @@ inline SacGemmJob sac_job(const float* A, int sam, int sak, const float* Bm, int
   j.A = A; j.sam = sam; j.sak = sak; j.B = Bm; j.sbk = sbk; j.sbn = sbn; j.C = C; j.ldc = ldc; j.M = M; j.N = N; j.K = K;
   return j;
 }
+// the wide form's weight gradients of the image range [e0, e1): the split grid, then the fold with Adam
+inline void sac_launch_wgrad_wide(hipStream_t st, const SacStepArgs& S, const SacGemmJob* jobs, int n, int e0, int e1) {
+  const SacLayout L = sac_layout(S.d, S.A, S.H);
+  const SacWs W = sac_ws(S.d, S.A, S.H, S.B);
+  const SacWsWide V = sac_ws_wide(S.d, S.A, S.H, S.B);
+  SacSplitArgs G;
+  int maxM = 0, maxN = 0;
+  for (int k = 0; k < kSacMaxJobs; ++k) {
+    G.job[k] = jobs[k < n ? k : 0];
+    if (k < n) { maxM = jobs[k].M > maxM ? jobs[k].M : maxM; maxN = jobs[k].N > maxN ? jobs[k].N : maxN; }
+  }
+  G.image = S.image; G.part = S.ws + V.part; G.T = L.T; G.nsplit = sac_splits(S.B);
+  hipLaunchKernelGGL(fw_sac_wgrad_split_kernel, dim3((maxN + 63) / 64, (maxM + 63) / 64, n * G.nsplit), dim3(256), 0, st, G);
+  const SacAdamFoldArgs F{S.image, S.ws + V.part, S.ws + W.scal, e0, e1, L.T, G.nsplit, L.m, L.v, S.hp.beta1, S.hp.beta2, S.hp.eps};
+  hipLaunchKernelGGL(fw_sac_adam_fold_kernel, dim3((e1 - e0 + 255) / 256), dim3(256), 0, st, F);
+}
+// One gradient step.  Up to kSacMaxB rows: 24 launches.  The wide form: 29 -- each of the three batch-sum stages is a grid and a fold
+// (+3), each of the two weight-gradient launches a split grid and a fold with Adam (+2); everything else is the same launch on a
+// grid that grows with B.
 inline void sac_update_launch(hipStream_t st, const SacStepArgs& S) {
   const int d = S.d, A = S.A, H = S.H, B = S.B, Kc = d + A, O = 2 * A, R = 2 * d + A + 2;
+  const bool wide = B > kSacMaxB;
   const SacLayout L = sac_layout(d, A, H);
   const SacWs W = sac_ws(d, A, H, B);
   const SacNet na = sac_net(d, H, O), nc = sac_net(Kc, H, 1);
@@ -490,6 +679,16 @@ inline void sac_update_launch(hipStream_t st, const SacStepArgs& S) {
     j.pb = P + net + b; j.mb1 = P + L.m + net + b; j.mb2 = P + L.v + net + b;
     return j;
   };
+  auto stage = [&](void (*one)(SacStepArgs), void (*many)(SacStepArgs), int which, int rows) {      // a batch-sum stage
+    if (!wide) { hipLaunchKernelGGL(one, dim3(1), dim3(256), 0, st, S); return; }
+    const int n = (rows + kSacStageRows - 1) / kSacStageRows;
+    hipLaunchKernelGGL(many, dim3(n), dim3(256), 0, st, S);
+    hipLaunchKernelGGL(fw_sac_stage_fold_kernel, dim3(1), dim3(64), 0, st, S, which, n);
+  };
+  auto step_weights = [&](const SacGemmJob* jobs, int n, int e0, int e1) {      // the weight gradients of image[e0, e1) with Adam
+    if (wide) sac_launch_wgrad_wide(st, S, jobs, n, e0, e1);
+    else sac_launch_gemm(st, S, SAC_EPI_ADAM, jobs, n);
+  };
   // 0: the step's noise
   hipLaunchKernelGGL(fw_sac_noise_kernel, dim3((2 * B * ((A + 3) / 4) + 255) / 256), dim3(256), 0, st, S.hp.seed, (const int64_t*)S.ctr, B, A, ws + W.noise);
   // 1-4: the actor on [s; s']
@@ -500,7 +699,7 @@ inline void sac_update_launch(hipStream_t st, const SacStepArgs& S) {
   sac_launch_gemm(st, S, SAC_EPI_RELU, jb, 1);
   jb[0] = fwd(L.actor, na, 3, ws + W.h2a, H, H, ws + W.outa, 2 * B);
   sac_launch_gemm(st, S, SAC_EPI_LINEAR, jb, 1);
-  hipLaunchKernelGGL(fw_sac_head_kernel, dim3(1), dim3(256), 0, st, S);
+  stage(fw_sac_head_kernel, fw_sac_stage_wide_kernel<SAC_STAGE_HEAD>, SAC_STAGE_HEAD, 2 * B);
   // 5-8: Q1, Q2 on (s, a) and the targets on (s', a') in one grid per layer
   auto critic_forward = [&](int count, const float* x01, int ld01, const float* x23) {
     for (int k = 0; k < count; ++k) jb[k] = fwd(crit[k], nc, 1, k < 2 ? x01 : x23, k < 2 ? ld01 : Kc, Kc, ws + W.ch1 + (size_t)k * B * H, B);
@@ -518,7 +717,7 @@ inline void sac_update_launch(hipStream_t st, const SacStepArgs& S) {
     sac_launch_gemm(st, S, SAC_EPI_MASK, jb, 2);
   };
   critic_forward(4, bt, R, ws + W.xnext);
-  hipLaunchKernelGGL(fw_sac_target_kernel, dim3(1), dim3(256), 0, st, S);
+  stage(fw_sac_target_kernel, fw_sac_stage_wide_kernel<SAC_STAGE_TARGET>, SAC_STAGE_TARGET, B);
   // 9-11: the critics' backward pass, then all six weight gradients with Adam in one grid
   critic_backward();
   for (int k = 0; k < 2; ++k) {
@@ -526,10 +725,10 @@ inline void sac_update_launch(hipStream_t st, const SacStepArgs& S) {
     jb[3 * k + 1] = grad(crit[k], nc.W2, nc.b2, ws + W.ch1 + (size_t)k * B * H, H, H, ws + W.G2 + (size_t)k * B * H, H, B);
     jb[3 * k + 2] = grad(crit[k], nc.W1, nc.b1, bt, R, Kc, ws + W.G1 + (size_t)k * B * H, H, B);
   }
-  sac_launch_gemm(st, S, SAC_EPI_ADAM, jb, 6);
+  step_weights(jb, 6, L.q1, L.lec);
   // 12-19: the stepped critics on (s, a_pi), their gradient with respect to the action
   critic_forward(2, ws + W.xpi, Kc, nullptr);
-  hipLaunchKernelGGL(fw_sac_actor_q_kernel, dim3(1), dim3(256), 0, st, S);
+  stage(fw_sac_actor_q_kernel, fw_sac_stage_wide_kernel<SAC_STAGE_ACTOR_Q>, SAC_STAGE_ACTOR_Q, B);
   critic_backward();
   for (int k = 0; k < 2; ++k) jb[k] = sac_job(ws + W.G1 + (size_t)k * B * H, H, 1, P + crit[k] + nc.W1, 1, H, ws + W.dx + (size_t)k * B * Kc, Kc, B, Kc, H);
   sac_launch_gemm(st, S, SAC_EPI_LINEAR, jb, 2);
@@ -542,7 +741,7 @@ inline void sac_update_launch(hipStream_t st, const SacStepArgs& S) {
   jb[0] = grad(L.actor, na.W3, na.b3, ws + W.h2a, H, H, ws + W.gout, O, B);
   jb[1] = grad(L.actor, na.W2, na.b2, ws + W.h1a, H, H, ws + W.G2, H, B);
   jb[2] = grad(L.actor, na.W1, na.b1, bt, R, d, ws + W.G1, H, B);
-  sac_launch_gemm(st, S, SAC_EPI_ADAM, jb, 3);
+  step_weights(jb, 3, L.actor, L.q1);
   // 23: Polyak, outputs, counters
   hipLaunchKernelGGL(fw_sac_finish_kernel, dim3((2 * nc.n + 255) / 256), dim3(256), 0, st, S);
 }

@@ -34,6 +34,7 @@ from . import _lib
 
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
 MAX_OBS_DIM, MAX_ACT_DIM, HIDDEN_WIDTHS, MAX_BATCH = 64, 8, (64, 256), 512
+MAX_BATCH_WIDE, WIDE_BATCH_MULTIPLE = 8192, 64                  # above MAX_BATCH: the wide form of the gradient step
 CTR_CURSOR, CTR_SIZE, CTR_STEPS, CTR_GRAD = 0, 1, 2, 3          # the device counters (int64[4])
 
 
@@ -98,9 +99,11 @@ class SACConfig:
 
 
 def fits(obs_dim: int, act_dim: int, hidden: int, batch_size: int) -> bool:
-    """What the kernels are built for (include/fwsim.h): anything else is ``FW_EUNSUPPORTED``."""
-    return (1 <= obs_dim <= MAX_OBS_DIM and 1 <= act_dim <= MAX_ACT_DIM and hidden in HIDDEN_WIDTHS
-            and 16 <= batch_size <= MAX_BATCH and batch_size % 16 == 0)
+    """What the kernels are built for (include/fwsim.h): anything else is ``FW_EUNSUPPORTED``.  Batches: multiples of 16 in
+    [16, ``MAX_BATCH``], or multiples of ``WIDE_BATCH_MULTIPLE`` in (``MAX_BATCH``, ``MAX_BATCH_WIDE``] (the wide form)."""
+    batch_ok = ((16 <= batch_size <= MAX_BATCH and batch_size % 16 == 0)
+                or (MAX_BATCH < batch_size <= MAX_BATCH_WIDE and batch_size % WIDE_BATCH_MULTIPLE == 0))
+    return 1 <= obs_dim <= MAX_OBS_DIM and 1 <= act_dim <= MAX_ACT_DIM and hidden in HIDDEN_WIDTHS and batch_ok
 
 
 def ring_capacity(buffer_size: int, num_envs: int) -> int:
@@ -439,7 +442,10 @@ class SAC:
         self.G = cfg.resolved_gradient_steps(self.N)
         if not fits(self.d, self.A, cfg.hidden, cfg.batch_size):
             raise ValueError(f"the SAC kernels take obs_dim <= {MAX_OBS_DIM}, act_dim <= {MAX_ACT_DIM}, hidden in {HIDDEN_WIDTHS} and batch "
-                             f"sizes that are multiples of 16 up to {MAX_BATCH}; got ({self.d}, {self.A}, {cfg.hidden}, {cfg.batch_size})")
+                             f"sizes that are multiples of 16 in [16, {MAX_BATCH}] or multiples of {WIDE_BATCH_MULTIPLE} in "
+                             f"({MAX_BATCH}, {MAX_BATCH_WIDE}]; got ({self.d}, {self.A}, {cfg.hidden}, {cfg.batch_size})")
+        if cfg.buffer_size < self.N:
+            raise ValueError(f"buffer_size {cfg.buffer_size} cannot hold one vec-step of {self.N} envs")
         self.buffer = ReplayBufferDevice(cfg.buffer_size, self.N, self.d, self.A, self.device)
         self.fused = FusedSacUpdate(self._policy, self.optimizers, cfg)
         kw = dict(dtype=torch.float32, device=self.device)

@@ -3,11 +3,15 @@
   * act / store / sample microseconds at 16 and 4096 envs;
   * one gradient step at (d 21, A 6, B 256) and H 256 / 64: fw_sac_update (as launched, and replayed from a captured graph), the torch
     step eager and the torch step replayed from a captured graph (capturable Adam) -- the baseline is this project's own torch path;
-  * end-to-end env-steps/s of sac.SAC at 16 envs with gradient_steps 1 and -1.
+  * the same four at H 256 for every batch size of --batches (default 256 ... 8192: up to 512 rows the 24-launch form, above it the
+    wide form), with microseconds per step and per sample;
+  * end-to-end env-steps/s of sac.SAC at 16 envs with gradient_steps 1 and -1, and at 4096 envs with one 4096-row gradient step per
+    vec-step on both env variants (the large-env recipe of examples/train_lowlevel_sac.py).
 
-Timing: device events around `iters` back-to-back calls after `warmup` calls, median of `repeats` such blocks.
+Timing: device events around `iters` back-to-back calls after `warmup` calls, median of `repeats` such blocks.  --runs N repeats the
+chosen sections N times (a "run" field tells them apart): the spread between runs is the run-to-run noise of a figure.
 
-    python tools/bench_sac.py [--quick]
+    python tools/bench_sac.py [--quick] [--sections pieces,update,batches,end_to_end,end_to_end_large] [--batches 256,4096] [--runs 3]
 """
 import argparse
 import json
@@ -48,8 +52,15 @@ def graphed(fn):
     return g.replay
 
 
+RUN = {}
+
+
 def emit(**kw):
-    print(json.dumps(kw), flush=True)
+    print(json.dumps({**kw, **RUN}), flush=True)
+
+
+def per_sample(t, B):
+    return {**t, "us_per_sample": round(t["us"] / B, 5)}
 
 
 def filled_learner(H, B, fused, capturable=False, d=21, A=6, rows=4096):
@@ -72,8 +83,8 @@ def bench_update(H, B, it):
     fused = S.FusedSacUpdate(pol, opts, cfg); fused.pack()
     batch = buf.sample(cfg.seed, torch.zeros((B, buf.row), device="cuda"))
     step = lambda: fused.run(batch, buf.counters)
-    emit(what="gradient_step", path="fused", **shape, **timed_us(step, *it))
-    emit(what="gradient_step", path="fused_graph", **shape, **timed_us(graphed(step), *it))
+    emit(what="gradient_step", path="fused", **shape, **per_sample(timed_us(step, *it), B))
+    emit(what="gradient_step", path="fused_graph", **shape, **per_sample(timed_us(graphed(step), *it), B))
     for name, cap in (("torch_eager", False), ("torch_graph", True)):
         cfg, pol, opts, buf = filled_learner(H, B, False, capturable=cap)
         batch = buf.sample(cfg.seed, torch.zeros((B, buf.row), device="cuda"))
@@ -88,7 +99,7 @@ def bench_update(H, B, it):
                 continue
         else:
             run = step
-        emit(what="gradient_step", path=name, **shape, **timed_us(run, *it))
+        emit(what="gradient_step", path=name, **shape, **per_sample(timed_us(run, *it), B))
 
 
 def bench_pieces(n, it):
@@ -118,21 +129,62 @@ def bench_end_to_end(gradient_steps, fused, graphs, vec_steps):
     env.close()
 
 
+def bench_end_to_end_large(variant, envs, batch, vec_steps):
+    """The large-env recipe: one `batch`-row gradient step per vec-step of `envs` envs, fused, one captured graph per vec-step."""
+    make = P.FixedwingLowLevelDemoVecEnv if variant == "demo" else P.FixedwingLowLevelVecEnv
+    env = make(num_envs=envs, seed=0)
+    sac = S.SAC(env, S.SACConfig(seed=0, batch_size=batch, gradient_steps=1, learning_starts=envs))
+    sac.learn(envs * 8)                      # the warm-up step, the first trained steps, the captures
+    torch.cuda.synchronize()
+    t0, n0 = time.perf_counter(), sac.num_timesteps
+    sac.learn(envs * vec_steps)
+    dt = time.perf_counter() - t0
+    emit(what="end_to_end", env=variant, envs=envs, batch=batch, gradient_steps=sac.G, fused_update=True, use_graphs=True, vec_steps=vec_steps,
+         env_steps_per_s=round((sac.num_timesteps - n0) / dt, 1), us_per_vec_step=round(dt * 1e6 / vec_steps, 1))
+    env.close()
+
+
+SECTIONS = ("pieces", "update", "batches", "end_to_end", "end_to_end_large")
+BATCHES = (256, 512, 576, 1024, 2048, 4096, 8192)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="a tenth of the iterations")
+    ap.add_argument("--sections", type=str, default=",".join(SECTIONS), help="comma-separated, of " + ", ".join(SECTIONS))
+    ap.add_argument("--batches", type=str, default=",".join(str(b) for b in BATCHES),
+                    help="batch sizes of the `batches` section (H 256, d 21, A 6): one gradient step fused, torch eager and torch graph-captured")
+    ap.add_argument("--runs", type=int, default=1, help="repeat the chosen sections this many times")
     a = ap.parse_args()
+    sections = [s for s in a.sections.split(",") if s]
+    unknown = [s for s in sections if s not in SECTIONS]
+    if unknown:
+        ap.error(f"unknown sections {unknown}")
     it = (20, 5, 3) if a.quick else (200, 20, 5)            # iters, warmup, repeats
+    if os.environ.get("FWSIM_LIB"):          # an A/B build of the library (pyflyt_drone_amd/_lib.py): every line says so
+        RUN["lib"] = os.path.basename(os.environ["FWSIM_LIB"])
     emit(what="device", name=torch.cuda.get_device_name(0), torch=torch.__version__)
-    for n in (16, 4096):
-        bench_pieces(n, it)
-    for H in (256, 64):
-        bench_update(H, 256, it)
     vs = 50 if a.quick else 500
-    for gs in (1, -1):
-        bench_end_to_end(gs, True, True, vs)
-        bench_end_to_end(gs, True, False, vs)
-        bench_end_to_end(gs, False, True, max(vs // 5, 10))
+    for run in range(a.runs):
+        if a.runs > 1:
+            RUN["run"] = run
+        if "pieces" in sections:
+            for n in (16, 4096):
+                bench_pieces(n, it)
+        if "update" in sections:
+            for H in (256, 64):
+                bench_update(H, 256, it)
+        if "batches" in sections:
+            for B in (int(b) for b in a.batches.split(",")):
+                bench_update(256, B, it)
+        if "end_to_end" in sections:
+            for gs in (1, -1):
+                bench_end_to_end(gs, True, True, vs)
+                bench_end_to_end(gs, True, False, vs)
+                bench_end_to_end(gs, False, True, max(vs // 5, 10))
+        if "end_to_end_large" in sections:
+            for variant in ("tracking", "demo"):
+                bench_end_to_end_large(variant, 4096, 4096, max(vs // 2, 20))
 
 
 if __name__ == "__main__":
