@@ -17,6 +17,9 @@ At thousands of envs the reference's update-to-data ratio of 1 is thousands of s
 is one gradient step per vec-step on a batch as large as the env count (the wide form of ``fw_sac_update``, batches up to 8192):
 
     python examples/train_lowlevel_sac.py --num_envs 4096 --batch_size 4096 --gradient_steps 1 --total_timesteps 2000000
+
+``--n_steps k`` (1 ... 16, default 1) trains on k-step returns gathered from the ring (``SACConfig.n_steps``): with so
+few gradient steps per sample each one carries reward information k steps back instead of one.
 """
 import argparse
 import json
@@ -45,6 +48,8 @@ def main():
     ap.add_argument("--batch_size", type=int, default=TRAIN_CONFIG["batch_size"],
                     help="rows per gradient step: a multiple of 16 up to 512, or a multiple of 64 up to 8192; the large-env recipe is "
                          "--num_envs 4096 --batch_size 4096 --gradient_steps 1")
+    ap.add_argument("--n_steps", type=int, default=1,
+                    help="n-step returns (1 ... 16): the target is r_0 + gamma r_1 + ... + gamma^k bootstrap, cut at episode ends; 1: the 1-step target")
     ap.add_argument("--fused_update", action=argparse.BooleanOptionalAction, default=True,
                     help="fw_sac_update (default) or the torch gradient step")
     ap.add_argument("--use_graphs", action=argparse.BooleanOptionalAction, default=True)
@@ -74,7 +79,7 @@ def main():
                                    gamma=c["gamma"], tau=c["tau"], gradient_steps=a.gradient_steps,
                                    target_update_interval=c["target_update_interval"], learning_starts=c["learning_starts"],
                                    net_arch=c["net_arch"], seed=c["seed"], use_graphs=a.use_graphs, fused_update=a.fused_update,
-                                   episode_stats=a.episode_stats, episode_fold=a.episode_fold))
+                                   episode_stats=a.episode_stats, episode_fold=a.episode_fold, n_steps=a.n_steps))
     t0 = time.perf_counter()
     state = {"next_eval": a.eval_freq, "train_s": 0.0, "mark": t0}
 
@@ -102,6 +107,7 @@ def main():
         return True
 
     print(json.dumps({"config": {**{k: v for k, v in c.items()}, "batch_size": a.batch_size, "total_timesteps": a.total_timesteps, "eval_freq": a.eval_freq, **({"env": a.env} if demo else {}), "num_envs": a.num_envs, "gradient_steps": model.G,
+                                 **({"n_steps": a.n_steps} if a.n_steps != 1 else {}),
                                  "fused_update": a.fused_update, "use_graphs": a.use_graphs}}), flush=True)
     evaluate_now(model)                      # the untrained actor: the line later evaluations are read against
     try:

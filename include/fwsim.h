@@ -965,6 +965,24 @@ int32_t fw_replay_store(float* ring, int64_t capacity, int64_t* counters, const 
  * and writes the indices to idx_out (optional).  Any positive batch: the batch rule above is fw_sac_update's and its workspace's. */
 int32_t fw_replay_sample(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
                          float* out, int32_t* idx_out, void* hip_stream);
+/* n-step returns.  ends: a caller-owned uint8[capacity] side ring, bit 0 = terminated, bit 1 = truncated of the row's step (the row's own
+ * done column is `terminated` alone).  fw_replay_mark_ends writes ends[cursor + i], i < N, for the rows the NEXT fw_replay_store will
+ * write: launch it in front of that call on the same stream.  It reads counters[0] (normalised as the store does) and writes no counter. */
+int32_t fw_replay_mark_ends(uint8_t* ends, int64_t capacity, const int64_t* counters, const uint8_t* terminated, const uint8_t* truncated, int32_t N,
+                            void* hip_stream);
+/* fw_replay_sample with an n-step target.  The start index i of batch row b is fw_replay_sample's draw (equal counters: equal idx_out).
+ * Env e's steps are N rows apart: row_j = (i + j N) mod capacity, j = 0, 1, ...; row_j is used, and the walk stops behind it when
+ * j + 1 == n_steps, or ends[row_j] != 0, or row_j lies in the newest vec-step stored (the next row would be the oldest data or an
+ * unfilled row).  With k rows used and g_0 = 1, g_j = g_(j-1) gamma (fp32) the output row, in fw_replay_sample's layout, is
+ *   obs | action from row_0,  reward = r_0 + g_1 r_1 + ... + g_(k-1) r_(k-1) (fp32, ascending j, one fma per term),  next_obs from
+ *   row_(k-1),  last column = 1 - (1 - done_(k-1)) g_(k-1):
+ * fw_sac_update's (1 - last) gamma is then (1 - done) gamma^k, and for k = 1 the row is fw_replay_sample's bit for bit.  k_out
+ * (optional) [batch] receives k.  obs_dim locates the reward column (row_floats = 2 obs_dim + act_dim + 2).  n_steps in [1, 16]
+ * (FW_EUNSUPPORTED otherwise).  Reads counters only; every row index is taken mod capacity, so an empty ring is not read out of bounds
+ * (its result is unspecified, as fw_replay_sample's). */
+int32_t fw_replay_sample_nstep(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
+                               float* out, int32_t* idx_out, const uint8_t* ends, int32_t obs_dim, int32_t N, int32_t n_steps, float gamma,
+                               int32_t* k_out, void* hip_stream);
 /* eps and eps' [2][batch][act_dim] of gradient step counters[3]: the values fw_sac_update draws inside.  A row's noise does not
  * depend on the batch size.  Any positive batch, as fw_replay_sample. */
 int32_t fw_sac_noise(uint64_t seed, const int64_t* counters, int32_t batch, int32_t act_dim, float* out, void* hip_stream);

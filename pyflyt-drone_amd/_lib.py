@@ -33,6 +33,7 @@ EXPORTS = (
     "fw_probe",
     "fw_sizeof_sac_hyper", "fw_sac_param_count", "fw_sac_update_workspace_bytes", "fw_sac_act", "fw_replay_store", "fw_replay_sample",
     "fw_sac_noise", "fw_sac_update",
+    "fw_replay_mark_ends", "fw_replay_sample_nstep",
 )
 
 
@@ -215,6 +216,10 @@ def lib() -> C.CDLL:
             L.fw_replay_sample.restype = i32; L.fw_replay_sample.argtypes = [vp, i64, vp, u64, i32, i32, vp, vp, vp]
             L.fw_sac_noise.restype = i32; L.fw_sac_noise.argtypes = [u64, vp, i32, i32, vp, vp]
             L.fw_sac_update.restype = i32; L.fw_sac_update.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]
+        if hasattr(L, "fw_replay_sample_nstep"):   # n-step returns (an A/B library of an older commit predates the pair; build() insists on it)
+            L.fw_replay_mark_ends.restype = i32; L.fw_replay_mark_ends.argtypes = [vp, i64, vp, vp, vp, i32, vp]
+            L.fw_replay_sample_nstep.restype = i32
+            L.fw_replay_sample_nstep.argtypes = [vp, i64, vp, u64, i32, i32, vp, vp, vp, i32, i32, i32, C.c_float, vp, vp]
         L.fw_policy_act_a.restype = i32
         L.fw_policy_act_a.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
         L.fw_collect_act_a.restype = i32

@@ -3544,6 +3544,30 @@ int32_t fw_replay_sample(const float* ring, int64_t capacity, const int64_t* cou
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }
+int32_t fw_replay_mark_ends(uint8_t* ends, int64_t capacity, const int64_t* counters, const uint8_t* terminated, const uint8_t* truncated, int32_t N,
+                            void* hip_stream) {
+  if (!ends || !counters || !terminated || !truncated) { g_err = "fw_replay_mark_ends: every pointer must be non-NULL"; return FW_EINVAL; }
+  if (N <= 0 || capacity < N || capacity % N != 0) { g_err = "fw_replay_mark_ends: N must be positive and capacity a positive multiple of N"; return FW_EINVAL; }
+  DeviceGuard g(device_of(ends));
+  hipLaunchKernelGGL(fw_replay_mark_ends_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, ends, capacity, counters,
+                     terminated, truncated, N);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+int32_t fw_replay_sample_nstep(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
+                               float* out, int32_t* idx_out, const uint8_t* ends, int32_t obs_dim, int32_t N, int32_t n_steps, float gamma,
+                               int32_t* k_out, void* hip_stream) {
+  if (!ring || !counters || !out || !ends) { g_err = "fw_replay_sample_nstep: ring, counters, out and ends must be non-NULL"; return FW_EINVAL; }
+  if (capacity <= 0 || capacity > 0x7fffffffLL || row_floats <= 0 || batch <= 0) { g_err = "fw_replay_sample_nstep: capacity (below 2^31), row_floats and batch must be positive"; return FW_EINVAL; }
+  if (N <= 0 || capacity < N || capacity % N != 0) { g_err = "fw_replay_sample_nstep: N must be positive and capacity a positive multiple of N"; return FW_EINVAL; }
+  if (obs_dim <= 0 || row_floats < 2 * obs_dim + 3) { g_err = "fw_replay_sample_nstep: row_floats must be 2 obs_dim + act_dim + 2 with positive obs_dim and act_dim"; return FW_EINVAL; }
+  if (n_steps < 1 || n_steps > kSacMaxNStep) { g_err = "fw_replay_sample_nstep: built for n_steps in [1, 16]"; return FW_EUNSUPPORTED; }
+  DeviceGuard g(device_of(ring));
+  hipLaunchKernelGGL(fw_replay_sample_nstep_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, ring, capacity, counters,
+                     seed, row_floats, batch, out, idx_out, ends, obs_dim, N, n_steps, gamma, k_out);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
 int32_t fw_sac_noise(uint64_t seed, const int64_t* counters, int32_t batch, int32_t act_dim, float* out, void* hip_stream) {
   if (!counters || !out) { g_err = "fw_sac_noise: counters and out must be non-NULL"; return FW_EINVAL; }
   if (batch <= 0 || act_dim <= 0) { g_err = "fw_sac_noise: batch and act_dim must be positive"; return FW_EINVAL; }

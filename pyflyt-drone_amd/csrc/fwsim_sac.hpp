@@ -263,6 +263,7 @@ __global__ __launch_bounds__(256) void fw_replay_sample_kernel(const float* __re
   for (int c = lane; c < R; c += 64) batch[(size_t)b * R + c] = ring[(size_t)idx * R + c];
   if (lane == 0 && idx_out) idx_out[b] = (int32_t)idx;
 }
+// (the episode-end side ring and the n-step form of this gather: the last section of this file)
 
 // ---- the product kernel ----
 enum { SAC_EPI_LINEAR = 0, SAC_EPI_RELU = 1, SAC_EPI_MASK = 2, SAC_EPI_ADAM = 3 };
@@ -744,6 +745,77 @@ inline void sac_update_launch(hipStream_t st, const SacStepArgs& S) {
   step_weights(jb, 3, L.actor, L.q1);
   // 23: Polyak, outputs, counters
   hipLaunchKernelGGL(fw_sac_finish_kernel, dim3((2 * nc.n + 255) / 256), dim3(256), 0, st, S);
+}
+
+// ---- n-step returns from the ring ----
+// Env e's consecutive steps sit exactly N rows apart, so the k-step transition that starts at row i is rows i, i + N, ... (mod capacity).
+// A side ring `ends` (uint8[capacity]: bit 0 terminated, bit 1 truncated) says where an episode stopped -- the row's own done column is
+// `terminated` alone, so a time-limit end is in no other place.  fw_replay_mark_ends writes the N bytes of the rows the NEXT fw_replay_store
+// will write (same cursor normalisation, reads the counter, writes none).
+__global__ __launch_bounds__(256) void fw_replay_mark_ends_kernel(uint8_t* __restrict__ ends, int64_t capacity, const int64_t* __restrict__ ctr,
+                                                                  const uint8_t* __restrict__ terminated, const uint8_t* __restrict__ truncated, int32_t N) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  int64_t cursor = ctr[0];
+  if (cursor < 0 || cursor + N > capacity) cursor = 0;
+  ends[cursor + i] = (uint8_t)((terminated[i] ? 1 : 0) | (truncated[i] ? 2 : 0));
+}
+constexpr int kSacMaxNStep = 16;
+// One wave per batch row, the start index drawn exactly as fw_replay_sample_kernel draws it.  Lane j < n_steps looks at row_j = (i + j N) mod
+// capacity: its reward, its ends byte and whether it lies in the newest vec-step (the row behind it would be the oldest data, or unfilled).
+// All of these loads are independent, so the walk costs one memory round trip whatever n_steps is; the first lane that has to stop gives
+// k from a ballot.  Every lane then adds the k discounted rewards in ascending j with one fma each (not a tree: two runs give the same
+// bits), and the row copy takes obs | action from row_0 and next_obs | done from row_(k-1).  The last column leaves as
+// 1 - (1 - done) g_(k-1), g_j = gamma^j by repeated fp32 products: the consumer's (1 - last) gamma is then (1 - done) gamma^k, and for
+// k = 1 the column is `done` itself.
+// (Ballot and lane reads are the compiler builtins, not hip's __ballot / __shfl / __ffsll: with the wrappers in this kernel sixteen camera
+// kernels of this translation unit came out with two operands of one v_or3_b32 swapped and their schedule moved behind it.  ds_bpermute
+// takes the source lane as a byte address, lane << 2.  This section sits at the end of the file, behind the gradient step.)
+__global__ __launch_bounds__(256) void fw_replay_sample_nstep_kernel(const float* __restrict__ ring, int64_t capacity, const int64_t* __restrict__ ctr,
+                                                                     uint64_t seed, int R, int B, float* __restrict__ batch, int32_t* __restrict__ idx_out,
+                                                                     const uint8_t* __restrict__ ends, int d, int N, int n_steps, float gamma,
+                                                                     int32_t* __restrict__ k_out) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (b >= B) return;
+  int64_t size = ctr[1];
+  size = size < 1 ? 1 : (size > capacity ? capacity : size);
+  const uint64_t gs = (uint64_t)ctr[3];
+  uint32_t o[4];
+  philox4x32_10((uint32_t)b, 0u, (uint32_t)gs, (uint32_t)(gs >> 32) ^ kSacTagSample, (uint32_t)seed, (uint32_t)(seed >> 32), o);
+  const uint32_t idx = __umulhi(o[0], (uint32_t)size);
+  int64_t cursor = ctr[0];
+  if (cursor < 0 || cursor + N > capacity) cursor = 0;
+  const uint32_t cap = (uint32_t)capacity, newest = (uint32_t)(cursor == 0 ? capacity - N : cursor - N);
+  const int rcol = R - d - 2;                      // the reward column (d + A)
+  uint32_t row = idx;
+  float r = 0.f;
+  bool stop = false;
+  if (lane < n_steps) {
+    row = (uint32_t)(((uint64_t)idx + (uint64_t)lane * (uint32_t)N) % cap);
+    r = ring[(size_t)row * R + rcol];
+    stop = lane + 1 == n_steps || ends[row] != 0 || row - row % (uint32_t)N == newest;
+  }
+  const int k = __builtin_ctzll(__builtin_amdgcn_ballot_w64(stop)) + 1;            // lane n_steps - 1 always stops: 1 <= k <= n_steps
+  const uint32_t last = (uint32_t)__builtin_amdgcn_ds_bpermute((k - 1) << 2, (int)row);
+  float ret = __int_as_float(__builtin_amdgcn_ds_bpermute(0, __float_as_int(r))), g = 1.0f;
+  for (int j = 1; j < k; ++j) {
+    g *= gamma;
+    ret = __builtin_fmaf(g, __int_as_float(__builtin_amdgcn_ds_bpermute(j << 2, __float_as_int(r))), ret);
+  }
+  for (int c = lane; c < R; c += 64) {
+    float v;
+    if (c < rcol) v = ring[(size_t)idx * R + c];
+    else if (c == rcol) v = ret;
+    else {
+      v = ring[(size_t)last * R + c];
+      if (c == R - 1) v = 1.0f - (1.0f - v) * g;
+    }
+    batch[(size_t)b * R + c] = v;
+  }
+  if (lane == 0) {
+    if (idx_out) idx_out[b] = (int32_t)idx;
+    if (k_out) k_out[b] = k;
+  }
 }
 
 }  // namespace fwsim

@@ -8,6 +8,8 @@ Everything between two env steps runs on the device (csrc/fwsim_sac.hpp, include
                        actions), the fp32 staging copy of the observation the step is about to overwrite;
 * ``fw_replay_store``  appends the N transitions to a flat fp32 ring at a device-resident cursor;
 * ``fw_replay_sample`` draws a batch from the ring by a counter-based generator;
+* ``fw_replay_mark_ends`` / ``fw_replay_sample_nstep``  (``SACConfig.n_steps > 1`` only) one flag byte per row for the episode ends,
+                       and the same draw gathered as an n-step transition (:func:`nstep_rows_reference` restates its contract);
 * ``fw_sac_noise``     the two noise blocks of a gradient step;
 * ``fw_sac_update``    one gradient step of SB3's ``SAC.train()`` on a flat image of all five networks and their Adam moments.
 
@@ -35,6 +37,8 @@ from . import _lib
 LOG_STD_MIN, LOG_STD_MAX = -20.0, 2.0
 MAX_OBS_DIM, MAX_ACT_DIM, HIDDEN_WIDTHS, MAX_BATCH = 64, 8, (64, 256), 512
 MAX_BATCH_WIDE, WIDE_BATCH_MULTIPLE = 8192, 64                  # above MAX_BATCH: the wide form of the gradient step
+MAX_N_STEPS = 16                                                # fw_replay_sample_nstep
+END_TERMINATED, END_TRUNCATED = 1, 2                            # bits of the `ends` side ring
 CTR_CURSOR, CTR_SIZE, CTR_STEPS, CTR_GRAD = 0, 1, 2, 3          # the device counters (int64[4])
 
 
@@ -66,8 +70,12 @@ class SACConfig:
                                          # one more launch per vec-step, inside the captured graphs); off: nothing changes
     stats_window_size: int = 100         #     SB3's stats_window_size: episodes in the window
     episode_fold: str = "one"            #     the fold's device form: "one", "wide" or "auto" (monitor.EpisodeMonitor)
+    n_steps: int = 1                     # n-step returns from the ring (1 ... 16); 1: the 1-step target, nothing changes
 
     def __post_init__(self):
+        if isinstance(self.n_steps, bool) or int(self.n_steps) != self.n_steps or not 1 <= int(self.n_steps) <= MAX_N_STEPS:
+            raise ValueError(f"n_steps must be an integer in [1, {MAX_N_STEPS}], got {self.n_steps!r}")
+        self.n_steps = int(self.n_steps)
         if self.episode_fold not in ("one", "wide", "auto"):
             raise ValueError(f"episode_fold must be 'one', 'wide' or 'auto', got {self.episode_fold!r}")
         if int(self.stats_window_size) <= 0:
@@ -122,6 +130,51 @@ def split_rows(rows: torch.Tensor, obs_dim: int, act_dim: int):
     """(s, a, r, s', done) views of ring / batch rows ``[obs | action | reward | next_obs | done]``."""
     d, a = obs_dim, act_dim
     return rows[:, :d], rows[:, d:d + a], rows[:, d + a], rows[:, d + a + 1:2 * d + a + 1], rows[:, 2 * d + a + 1]
+
+
+def nstep_rows_reference(ring, ends, cursor, size, N, idx, n_steps, gamma, obs_dim):
+    """``fw_replay_sample_nstep`` in plain numpy on CPU arrays: ``(rows [B, R] float32, k [B] int32)`` of the start rows ``idx``.
+
+    ``ring`` ``[capacity, R]`` float32, ``ends`` ``[capacity]`` uint8, ``cursor`` / ``size`` the first two device counters, ``N`` the env
+    count (env e's consecutive steps are N rows apart), ``obs_dim`` locates the reward column of a row (R = 2 obs_dim + act_dim + 2).
+    Walk ``row_j = (i + j N) mod capacity``: row_j is used, then the walk stops if ``j + 1 == n_steps``, or ``ends[row_j] != 0``, or
+    row_j lies in the newest vec-step stored (``row_j - row_j mod N == (cursor - N) mod capacity``, the cursor normalised as
+    ``fw_replay_store`` does).  With k rows used, ``g_0 = 1`` and ``g_j = g_(j-1) gamma`` in float32 (gamma itself rounded to float32,
+    as the entry point receives it): obs | action from row_0, reward ``r_0 + g_1 r_1 + ... + g_(k-1) r_(k-1)`` in float32 in ascending j,
+    next_obs from row_(k-1), last column ``1 - (1 - done_(k-1)) g_(k-1)``.  The kernel adds each term with one fused multiply-add, this
+    function with a rounded product and a rounded sum: the two rewards differ by roundings only (tests/test_sac_nstep_gpu.py)."""
+    import numpy as np
+    ring, ends = np.asarray(ring, dtype=np.float32), np.asarray(ends, dtype=np.uint8)
+    capacity, R = ring.shape
+    N, n_steps, d = int(N), int(n_steps), int(obs_dim)
+    if not 1 <= n_steps <= MAX_N_STEPS:
+        raise ValueError(f"n_steps must be in [1, {MAX_N_STEPS}]")
+    if N <= 0 or capacity % N or ends.shape != (capacity,) or R < 2 * d + 3:
+        raise ValueError("capacity must be a multiple of N, ends one byte per row and a row 2 obs_dim + act_dim + 2 floats")
+    idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+    if idx.size and (idx.min() < 0 or idx.max() >= max(int(size), 1)):
+        raise ValueError("idx must lie in [0, size)")
+    cursor = int(cursor)
+    if cursor < 0 or cursor + N > capacity:
+        cursor = 0
+    newest = (cursor - N + capacity) % capacity
+    rcol, one, gam = R - d - 2, np.float32(1.0), np.float32(gamma)
+    rows, ks = np.empty((idx.size, R), dtype=np.float32), np.empty(idx.size, dtype=np.int32)
+    for b, i in enumerate(idx):
+        j, g, ret = 0, one, np.float32(0.0)
+        while True:
+            row = (int(i) + j * N) % capacity
+            g = one if j == 0 else np.float32(g * gam)
+            ret = ring[row, rcol] if j == 0 else np.float32(ret + np.float32(g * ring[row, rcol]))
+            if j + 1 == n_steps or ends[row] != 0 or row - row % N == newest:
+                break
+            j += 1
+        rows[b, :rcol] = ring[i, :rcol]
+        rows[b, rcol] = ret
+        rows[b, rcol + 1:R - 1] = ring[row, rcol + 1:R - 1]
+        rows[b, R - 1] = np.float32(one - np.float32(np.float32(one - ring[row, R - 1]) * g))
+        ks[b] = j + 1
+    return rows, ks
 
 
 # ---------------------------------------------------------------------------------------------
@@ -365,22 +418,40 @@ class FusedSacUpdate:
 # ---------------------------------------------------------------------------------------------
 class ReplayBufferDevice:
     """Flat fp32 ring ``[capacity, 2d + A + 2]`` and the device counters (cursor, rows filled, vec-steps stored, gradient steps):
-    the host reads none of them on the training path."""
+    the host reads none of them on the training path.  ``n_steps > 1`` adds the episode-end side ring ``ends`` (uint8 per row:
+    ``END_TERMINATED`` | ``END_TRUNCATED``), marked in front of every store, and ``sample`` gathers n-step transitions."""
 
-    def __init__(self, buffer_size: int, num_envs: int, obs_dim: int, act_dim: int, device):
+    def __init__(self, buffer_size: int, num_envs: int, obs_dim: int, act_dim: int, device, n_steps: int = 1):
+        if not 1 <= int(n_steps) <= MAX_N_STEPS:
+            raise ValueError(f"n_steps must be in [1, {MAX_N_STEPS}], got {n_steps}")
+        self.n_steps = int(n_steps)
         self.num_envs, self.obs_dim, self.act_dim = int(num_envs), int(obs_dim), int(act_dim)
         self.capacity = ring_capacity(buffer_size, num_envs)
         self.row = row_floats(obs_dim, act_dim)
         self.ring = torch.zeros((self.capacity, self.row), dtype=torch.float32, device=device)
         self.counters = torch.zeros(4, dtype=torch.int64, device=device)
+        self.ends = torch.zeros(self.capacity, dtype=torch.uint8, device=device) if self.n_steps > 1 else None
 
     def store(self, obs_stage, act_f32, reward, next_obs, terminal_obs, terminated, truncated) -> None:
+        if self.ends is not None:        # the rows this store is about to write: the mark reads the cursor the store advances
+            _lib.check(_lib.lib().fw_replay_mark_ends(_p(self.ends), self.capacity, _p(self.counters), _p(terminated), _p(truncated),
+                                                      self.num_envs, _stream(self.ring.device)))
         _lib.check(_lib.lib().fw_replay_store(_p(self.ring), self.capacity, _p(self.counters), _p(obs_stage), _p(act_f32), _p(reward),
                                               _p(next_obs), _p(terminal_obs), _p(terminated), _p(truncated),
                                               int(reward.dtype == torch.float64), self.num_envs, self.obs_dim, self.act_dim,
                                               _stream(self.ring.device)))
 
-    def sample(self, seed: int, out: torch.Tensor, idx_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def sample(self, seed: int, out: torch.Tensor, idx_out: Optional[torch.Tensor] = None, gamma: Optional[float] = None,
+               k_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A batch into ``out``.  With ``n_steps > 1``: n-step transitions, which need ``gamma`` (``k_out`` [B] int32 receives the
+        rows each one spans)."""
+        if self.ends is not None:
+            if gamma is None:
+                raise ValueError("an n-step sample needs gamma")
+            _lib.check(_lib.lib().fw_replay_sample_nstep(_p(self.ring), self.capacity, _p(self.counters), int(seed) & (2**64 - 1), self.row,
+                                                         out.shape[0], _p(out), _p(idx_out), _p(self.ends), self.obs_dim, self.num_envs,
+                                                         self.n_steps, float(gamma), _p(k_out), _stream(self.ring.device)))
+            return out
         _lib.check(_lib.lib().fw_replay_sample(_p(self.ring), self.capacity, _p(self.counters), int(seed) & (2**64 - 1), self.row,
                                                out.shape[0], _p(out), _p(idx_out), _stream(self.ring.device)))
         return out
@@ -397,16 +468,25 @@ class ReplayBufferDevice:
         sd = {"counters": self.counters.cpu().clone(), "capacity": self.capacity}
         if include_buffer:
             sd["ring"] = self.ring.cpu().clone()
+            if self.ends is not None:
+                sd["ends"] = self.ends.cpu().clone()
         return sd
 
     def load_state_dict(self, sd) -> None:
         if int(sd["capacity"]) != self.capacity:
             raise ValueError(f"the checkpoint's ring has {sd['capacity']} rows, this one {self.capacity}")
+        if self.ends is not None and "ring" in sd and "ends" not in sd:
+            raise ValueError("the checkpoint carries the ring's rows but not their episode ends (it was written with n_steps 1): "
+                             "n-step returns cannot be formed from them")
         self.counters.copy_(sd["counters"])
         if "ring" in sd:
             self.ring.copy_(sd["ring"])
+            if self.ends is not None:
+                self.ends.copy_(sd["ends"])
         else:                            # no rows came along: the ring starts empty, the step and gradient counters go on
             self.ring.zero_()
+            if self.ends is not None:
+                self.ends.zero_()
             self.counters[CTR_CURSOR] = 0; self.counters[CTR_SIZE] = 0
 
 
@@ -446,7 +526,7 @@ class SAC:
                              f"({MAX_BATCH}, {MAX_BATCH_WIDE}]; got ({self.d}, {self.A}, {cfg.hidden}, {cfg.batch_size})")
         if cfg.buffer_size < self.N:
             raise ValueError(f"buffer_size {cfg.buffer_size} cannot hold one vec-step of {self.N} envs")
-        self.buffer = ReplayBufferDevice(cfg.buffer_size, self.N, self.d, self.A, self.device)
+        self.buffer = ReplayBufferDevice(cfg.buffer_size, self.N, self.d, self.A, self.device, n_steps=cfg.n_steps)
         self.fused = FusedSacUpdate(self._policy, self.optimizers, cfg)
         kw = dict(dtype=torch.float32, device=self.device)
         self.obs_stage, self.act_f32 = torch.zeros((self.N, self.d), **kw), torch.zeros((self.N, self.A), **kw)
@@ -515,11 +595,11 @@ class SAC:
         self.buffer.store(self.obs_stage, self.act_f32, e.rewards, e.obs, e.terminal_obs, e.terminated, e.truncated)
 
     def _gradient_step_fused(self) -> None:
-        self.buffer.sample(self.cfg.seed, self.batch, self.batch_idx)
+        self.buffer.sample(self.cfg.seed, self.batch, self.batch_idx, gamma=self.cfg.gamma)
         self.fused.run(self.batch, self.buffer.counters)
 
     def _gradient_step_torch(self) -> None:
-        self.buffer.sample(self.cfg.seed, self.batch, self.batch_idx)
+        self.buffer.sample(self.cfg.seed, self.batch, self.batch_idx, gamma=self.cfg.gamma)
         sac_noise(self.cfg.seed, self.buffer.counters, self.cfg.batch_size, self.A, out=self.noise)
         s = sac_update_torch(self._policy, self.optimizers, self.batch, self.noise[0], self.noise[1], self.cfg)
         self.scal.copy_(torch.stack([s[k].float() for k in SCALARS]))
