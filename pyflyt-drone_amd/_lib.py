@@ -10,6 +10,8 @@ import ctypes as C
 import os
 import subprocess
 
+import torch
+
 from . import config as K
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -251,6 +253,33 @@ def check(rc: int, handle=None) -> None:
     if rc == K.FW_ENOMEM:
         raise MemoryError(msg)
     raise RuntimeError(msg)
+
+
+def devptr(t):
+    """the device address of tensor ``t`` as a ``void*`` argument; None (an argument left out) stays None"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream(device):
+    """torch's current stream on ``device`` as a ``void* hip_stream`` argument"""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+# fw_collect_act_a's previous-step block when there is nothing to finalise: prev_reward, prev_terminated, prev_truncated,
+# prev_terminal_obs, ret_var, norm_reward, clip_reward, eps_reward, gamma, rew_out, start_out
+NOTHING_TO_FINALISE = (None, None, None, None, None, 0, 0.0, 0.0, 0.0, None, None)
+
+
+def collect_act_a(params, obs, n: int, obs_dim: int, act_dim: int, obs_mean, obs_var, clip_obs: float, eps_obs: float, *, nets: int,
+                  deterministic: int, stream, rng=None, env_offset: int = 0, obs_copy=None, act_raw=None, act_env=None, logp=None,
+                  value=None, prev=NOTHING_TO_FINALISE) -> None:
+    """``fw_collect_act_a`` by keyword.  Tensors in (None: an output left out); ``obs`` / ``act_env`` say their own dtype.  ``prev``:
+    the eleven arguments of the previous-step block as the C call takes them (pointers, not tensors).  The defaults are the
+    policy-only call of a frozen policy: no rollout rows, no value, nothing of a previous step to finalise."""
+    check(lib().fw_collect_act_a(devptr(params), devptr(obs), int(obs.dtype == torch.float64), n, obs_dim, act_dim, devptr(obs_mean),
+                                 devptr(obs_var), float(clip_obs), float(eps_obs), nets, deterministic, devptr(rng), int(env_offset),
+                                 devptr(obs_copy), devptr(act_raw), devptr(act_env),
+                                 int(act_env is not None and act_env.dtype == torch.float64), devptr(logp), devptr(value), *prev, stream))
 
 
 def validate(cfg: K.FwConfig) -> None:

@@ -101,75 +101,33 @@ def fly(policy, env, schedule: torch.Tensor, use_fused: Optional[bool] = None, g
     ``env``, a ``VecNormalizeDevice(training=False)`` around a low-level task env.  ``env.reset()`` first; then per vec-step k:
     ``fw_command_ll`` (row k of the schedule, conditioned) -> act -> ``fw_step`` -> ``fw_trace_ll`` (row k of the trace).  The act
     is the torch forward (``use_fused`` None / False, as ``evaluate`` does for six actions) or ``fw_collect_act_a``
-    (``use_fused=True``, the launch of ``ReplayedEvaluation._fused6_step``).  With ``graph_steps > 0`` the body is captured as a
+    (``use_fused=True``, the launch of ``evalstep.ActAStep``).  With ``graph_steps > 0`` the body is captured as a
     hipGraph of that many vec-steps and replayed (the schedule row and the trace row are picked on the device); the steps that do
     not fill a whole graph run eagerly after it.  ``graph_steps <= 0`` runs every step eagerly; both give the same trace bit for
     bit.  T may not exceed the episode length: inside a run only a termination ends an episode."""
     if not torch.is_tensor(schedule):
         schedule = torch.as_tensor(schedule, dtype=torch.float64)
     T = _check_fly_args(env, schedule)
-    from .evaluate import ReplayedEvaluation
+    from . import evalstep
     venv, n, dev = env.venv, env.num_envs, env.device
-    fused = bool(use_fused)
-    if fused and not ReplayedEvaluation._fused6_applies(policy, env):
-        raise ValueError("use_fused=True needs the six-action MlpPolicy and an evaluation normaliser (training=False) on the GPU")
+    kind = evalstep.select(policy, env, use_fused, ("act_a",),
+                           "use_fused=True needs the six-action MlpPolicy and an evaluation normaliser (training=False) on the GPU")
+    step = evalstep.make(kind, policy, env)
     sched = schedule.to(device=dev, dtype=torch.float64).contiguous()
-    L = _lib.lib()
+    L, p = _lib.lib(), _lib.devptr
     step_idx = torch.zeros((), dtype=torch.int64, device=dev)
     trace = torch.zeros((T, n, len(TRACE_COLS)), dtype=torch.float64, device=dev)
     is_f64 = int(venv.obs.dtype == torch.float64)
-    if fused:
-        from .rollout import FusedPpoUpdate
-        f = FusedPpoUpdate(policy, None, env.obs_dim)
-        f.load_params_from_torch()
-        flat = f.flat
-        act_env = torch.zeros((n, 6), dtype=venv.torch_dtype, device=dev)
-        act_raw = torch.zeros((n, 6), dtype=torch.float32, device=dev)
-        logp = torch.zeros(n, dtype=torch.float32, device=dev)
-
-    def p(t):
-        return None if t is None else t.data_ptr()
-
-    def act():
-        st = torch.cuda.current_stream(dev).cuda_stream
-        if fused:
-            _lib.check(L.fw_collect_act_a(p(flat), p(venv.obs), is_f64, n, env.obs_dim, 6, p(env.obs_rms.mean), p(env.obs_rms.var),
-                                          float(env.clip_obs), float(env.epsilon), 1, 1, None, int(getattr(venv, "global_env_offset", 0)),
-                                          None, p(act_raw), p(act_env), int(act_env.dtype == torch.float64), p(logp), None,
-                                          None, None, None, None, None, 0, 0.0, 0.0, 0.0, None, None, st))
-            return act_env
-        obs_n = env._process_obs(venv.obs, update=False)
-        with torch.no_grad():
-            actions, _, _ = policy(obs_n, deterministic=True)
-        return actions.clamp(-1.0, 1.0).to(venv.torch_dtype)
 
     def body():
         venv.command_tensor(sched, T, step_idx)
-        venv.step_tensor(act())
+        step()
         _lib.check(L.fw_trace_ll(p(venv.obs), p(venv.terminal_obs), p(venv.terminated), p(venv.truncated), is_f64, n, p(trace), T,
-                                 p(step_idx), torch.cuda.current_stream(dev).cuda_stream))
+                                 p(step_idx), _lib.stream(dev)))
 
-    side = torch.cuda.Stream(device=dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(side):
-        env.reset()
-        start = trace_rows(venv.obs)
-        reps = T // graph_steps if graph_steps and graph_steps > 0 else 0
-        if reps:
-            act()                            # one act outside the capture warms its libraries / kernel attributes up (no env state)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side):
-                for _ in range(graph_steps):
-                    body()
-            for _ in range(reps):
-                graph.replay()
-        for _ in range(T - reps * (graph_steps if reps else 0)):
-            body()
-    torch.cuda.current_stream(dev).wait_stream(side)
-    tr = trace.cpu().numpy()
-    done = tr[:, :, 7] != FLAG_RUNNING
-    ended_at = np.where(done.any(axis=0), done.argmax(axis=0), -1).astype(np.int64)
-    return CommandTrace(trace=tr, start=start.cpu().numpy(), schedule=schedule.detach().cpu().numpy(), dt=AGENT_DT, ended_at=ended_at)
+    # (step.prepare: one act outside the capture warms its libraries / kernel attributes up, the fused act's too; no env state)
+    tr, start, ended_at = evalstep.replay_flight(env, trace, graph_steps, body, step.prepare, lambda: trace_rows(venv.obs), 7)
+    return CommandTrace(trace=tr, start=start, schedule=schedule.detach().cpu().numpy(), dt=AGENT_DT, ended_at=ended_at)
 
 
 def _segments(c: np.ndarray):

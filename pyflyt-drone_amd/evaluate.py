@@ -38,7 +38,9 @@ from typing import Callable, Dict, List, Optional
 import numpy as np
 import torch
 
+from . import _lib, evalstep
 from . import config as K
+from ._lib import devptr as _p, stream as _stream
 from .rollout import clip_actions, policy_inputs
 
 
@@ -100,9 +102,7 @@ def _track_terms_hl(o: torch.Tensor, c: torch.Tensor, p: torch.Tensor, first: to
 def _hl_bounds(venv):
     """(alt_high, speed_high) of a HighLevelCmdVecEnv's action Box when the command figures apply to ``venv`` (its 30-value
     observation), else None"""
-    if not (hasattr(venv, "command") and hasattr(venv, "step_low") and hasattr(venv, "rejected") and hasattr(venv, "terminal_obs")):
-        return None
-    if int(venv.obs.shape[1]) != 30:
+    if not evalstep.is_highlevel(venv):
         return None
     from .highlevel import AIRSPEED_HIGH
     return float(venv.cfg.flight_dome_size), float(AIRSPEED_HIGH)
@@ -275,6 +275,11 @@ class EvalResult:
         return out
 
 
+def _targets(n_eval_episodes: int, n: int) -> np.ndarray:
+    """episodes wanted of each of ``n`` envs: SB3's ``(n_eval_episodes + i) // n_envs``"""
+    return np.array([(n_eval_episodes + i) // n for i in range(n)], dtype=np.int64)
+
+
 @torch.no_grad()
 def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool = True,
                     callback: Optional[Callable[[dict], None]] = None, max_vec_steps: Optional[int] = None,
@@ -313,7 +318,7 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
     venv = env.venv
     n = env.num_envs
     path_layout = _path_layout(venv) if path_figures else None
-    targets = np.array([(n_eval_episodes + i) // n for i in range(n)], dtype=np.int64)
+    targets = _targets(n_eval_episodes, n)
     if use_graph is None:
         use_graph = (deterministic and generator is None and torch.device(env.device).type == "cuda" and hasattr(venv, "step_tensor")
                      and not getattr(policy, "uses_image", False))        # (a CNN front end keeps MIOpen out of captures)
@@ -371,20 +376,7 @@ def evaluate_policy(policy, env, n_eval_episodes: int = 10, deterministic: bool 
                         res.add_command(hl_h[i])
                     if path_h is not None:
                         res.add_path(path_h[i], _path_complete(info_h[i] if info_h is not None else None))
-                    info = {"episode": {"r": float(rew_h[i]), "l": int(len_h[i])}}
-                    if info_h is not None:
-                        info["num_targets_reached"] = int(info_h[i, K.INFO_NUM_TARGETS_REACHED])
-                        info["collision"] = bool(info_h[i, K.INFO_COLLISION])
-                        info["out_of_bounds"] = bool(info_h[i, K.INFO_OUT_OF_BOUNDS])
-                        info["env_complete"] = bool(info_h[i, K.INFO_ENV_COMPLETE])
-                        res.num_targets_reached.append(info["num_targets_reached"])
-                        if is_objlock:
-                            info["duck_strike"] = bool(info_h[i, K.INFO_DUCK_STRIKE])
-                            info["is_success"] = bool(info_h[i, K.INFO_IS_SUCCESS])
-                            res.duck_strike.append(info["duck_strike"])
-                        else:
-                            info["is_success"] = info["env_complete"]
-                        res.is_success.append(info["is_success"])
+                    info = _episode_info(res, float(rew_h[i]), int(len_h[i]), info_h[i] if info_h is not None else None, is_objlock)
                     if callback is not None:
                         callback(info)
             m = torch.as_tensor(d, device=env.device)
@@ -421,14 +413,14 @@ def _episode_info(res: "EvalResult", rew: float, length: int, info_row, is_objlo
     return info
 
 
-_REPLAY_STEPS = 8
+REPLAY_STEPS = 8
 
 
 class ReplayedEvaluation:
     """evaluate_policy with the loop body captured: policy forward, env step, normalisation and the per-episode bookkeeping
     (reward / length accumulators, the slot of the episode that just ended, its info row) are device ops on fixed buffers.
 
-    ``run()`` drives it from the host (one look at the episode counters per replay of ``_REPLAY_STEPS`` steps).
+    ``run()`` drives it from the host (one look at the episode counters per replay of ``REPLAY_STEPS`` steps).
     ``launch()`` enqueues the WHOLE evaluation on a side stream -- as many replays as the longest possible episodes need,
     ``episodes per env x (max_steps + 2)`` vec-steps -- and returns at once: the evaluation (a few envs) then runs beside the
     training that continues on the main stream (the PPO update keeps eight of the 256 CUs busy); ``ready()`` / ``result()``
@@ -439,26 +431,23 @@ class ReplayedEvaluation:
     statistics) -> ``fw_step`` -> ``fw_eval_track_ll``, in sequence.
 
     The high-level command task's bookkeeping is one ``fw_eval_track_hl`` launch per vec-step, which also sums its command figures.
-    ``use_fused=True`` with its three-action MlpPolicy (``fused3``): a vec-step is ``fw_collect_act_hl`` (commander and controller,
-    policy nets only, deterministic, frozen statistics) -> ``fw_step`` (``step_low``) -> ``fw_eval_track_hl``, in sequence.
+    ``use_fused=True`` with its three-action MlpPolicy (``step.kind == "act_hl"``): a vec-step is ``fw_collect_act_hl`` (commander and
+    controller, policy nets only, deterministic, frozen statistics) -> ``fw_step`` (``step_low``) -> ``fw_eval_track_hl``, in sequence.
 
     ``path_figures=True`` (the waypoint, ObjLock, combined and direct-command waypoints tasks): the bookkeeping of a vec-step is one
     ``fw_eval_track_wp`` launch -- in place of the framework ops behind the torch forward, and of ``fw_eval_track`` behind
-    ``fw_collect_step`` -- which also carries the twelve path sums of ``flight.PATH_SUMS``.  Off, nothing is launched that was not."""
+    ``fw_collect_step`` -- which also carries the twelve path sums of ``flight.PATH_SUMS``.  Off, nothing is launched that was not.
+
+    ``step`` is the act and the env step (an :mod:`evalstep` object; ``step.kind`` names it, ``fused`` says it is not the torch forward)."""
 
     def __init__(self, policy, env, targets: np.ndarray, callback=None, use_fused: Optional[bool] = None, path_figures: bool = False):
         self.policy, self.env, self.callback = policy, env, callback
         venv, n, dev = env.venv, env.num_envs, env.device
         self.path_layout = _path_layout(venv) if path_figures else None
-        self.fused = self._fused_applies(policy, env) if use_fused is None else bool(use_fused)
-        # the six-action policy of the low-level task: only on request (the default keeps its torch forward)
-        self.fused6 = self.fused and not self._fused_applies(policy, env) and self._fused6_applies(policy, env)
-        # the three-action policy of the high-level command task: only on request, likewise
-        self.fused3 = self.fused and not self._fused_applies(policy, env) and not self.fused6 and self._fused3_applies(policy, env)
-        if self.fused and not (self._fused_applies(policy, env) or self.fused6 or self.fused3):
-            raise ValueError("use_fused=True needs the MlpPolicy, a device env on the 8-lane mapping (any mapping for the low-level task's "
-                             "six actions and for the high-level command task's three actions on its 30-value observation) and an "
-                             "evaluation normaliser (training=False)")
+        # fw_collect_step by default where it applies; the six- and three-action policies get their fused act only on request
+        kind = evalstep.select(policy, env, use_fused, evalstep.FUSED_KINDS, default="collect_step", refusal=(
+            "use_fused=True needs the MlpPolicy, a device env on the 8-lane mapping (any mapping for the low-level task's six actions and "
+            "for the high-level command task's three actions on its 30-value observation) and an evaluation normaliser (training=False)"))
         self.venv, self.n, self.dev, self.targets = venv, n, dev, targets
         self.E = E = max(int(targets.max()), 1)
         self.has_info = hasattr(venv, "info")
@@ -486,108 +475,26 @@ class ReplayedEvaluation:
         if self.path_layout is not None:
             from . import flight
             self.cur_path = flight.path_init(n, dev)
-            self.carry = torch.zeros((n, flight.CARRY_DIM), dtype=torch.float64, device=dev)      # seeded behind the reset (_begin)
+            self.carry = torch.zeros((n, flight.CARRY_DIM), dtype=torch.float64, device=dev)      # seeded behind the reset (begin)
             self.fin_path = torch.zeros((n, E, len(flight.PATH_SUMS)), dtype=torch.float64, device=dev)
         self.obs = None
         self.side = torch.cuda.Stream(device=dev)
         self.done_event = None
         self.steps = 0
-        if self.fused:
-            self._fused_setup()
+        # a vec-step is the act and the env step (self.step, chosen above) and then the episode bookkeeping of the task
+        self.step = evalstep.make(kind, policy, env, through_wrapper=True)
+        # (kept as the plain function: a bound method stored on the object would make it a reference cycle, and its graph and
+        # buffers would then be freed by the cycle collector at a moment of its choosing, inside somebody's capture for one)
+        cls = type(self)
+        self._books = (cls._track_step if self.track else cls._track_hl_step if self.hl is not None
+                       else cls._track_wp_step if self.path_layout is not None
+                       else cls._track_plain_step if kind == "collect_step" else cls._track_torch)
 
-    # ---- a vec-step as ONE fw_collect_step launch (deterministic, statistics frozen) ----
-    @staticmethod
-    def _fused_applies(policy, env) -> bool:
-        from . import _lib
-        from .rollout import FusedPpoUpdate
-        venv = env.venv
-        if not (hasattr(venv, "_h") and hasattr(venv, "step_tensor") and torch.device(env.device).type == "cuda"):
-            return False
-        if env.training or not env.norm_obs or not FusedPpoUpdate.fits(policy, env.obs_dim, torch.device(env.device)):
-            return False
-        if env.obs_dim > 62:                   # fw_collect_step's act waves take up to 62 features (fits() allows the update's 64): torch replay path
-            return False
-        return int(_lib.lib().fw_lanes_per_env(venv._h)) in (8, 16)
-
-    @staticmethod
-    def _fused6_applies(policy, env) -> bool:
-        """the low-level task's six-action MlpPolicy through fw_collect_act_a (either lane mapping)"""
-        from .rollout import FusedPpoUpdate
-        venv = env.venv
-        if not (hasattr(venv, "_h") and hasattr(venv, "step_tensor") and torch.device(env.device).type == "cuda"):
-            return False
-        if env.training or not env.norm_obs or getattr(getattr(venv, "cfg", None), "task", None) != K.FW_TASK_LOWLEVEL:
-            return False
-        return FusedPpoUpdate.fits(policy, env.obs_dim, torch.device(env.device), act_dims=(6,))
-
-    @staticmethod
-    def _fused3_applies(policy, env) -> bool:
-        """the high-level command task's three-action MlpPolicy through fw_collect_act_hl (either lane mapping)"""
-        from .rollout import FusedPpoUpdate
-        venv = env.venv
-        if not (hasattr(venv, "collect_act_hl") and _hl_bounds(venv) is not None and torch.device(env.device).type == "cuda"):
-            return False
-        if env.training or not env.norm_obs or env.obs_dim != 30:
-            return False
-        return FusedPpoUpdate.fits(policy, 30, torch.device(env.device), act_dims=(3,))
-
-    def _fused_setup(self) -> None:
-        from . import _lib
-        from .rollout import FusedPpoUpdate
-        env, venv, dev, n = self.env, self.venv, self.dev, self.n
-        L = _lib.lib()
-        f = FusedPpoUpdate(self.policy, None, env.obs_dim)
-        f.load_params_from_torch()
-        self._flat = f.flat                                         # the kernel's parameter image of the policy being evaluated
-        if self.fused6:                                             # fw_collect_act_a's outputs: clipped actions for fw_step, the rest unread
-            self._act_env = torch.zeros((n, 6), dtype=venv.torch_dtype, device=dev)
-            self._act_raw = torch.zeros((n, 6), dtype=torch.float32, device=dev)
-            self._logp = torch.zeros(n, dtype=torch.float32, device=dev)
-            return
-        if self.fused3:                                             # fw_collect_act_hl's rollout rows: unread (the env owns command / low_action)
-            self._act_raw = torch.zeros((n, 3), dtype=torch.float32, device=dev)
-            self._logp = torch.zeros(n, dtype=torch.float32, device=dev)
-            return
-        self._act_env = torch.full((n, 4), float("nan"), dtype=venv.torch_dtype, device=dev)      # NaN = "not there yet" (fw_collect_step)
-        self._act_raw = torch.zeros((n, 4), dtype=torch.float32, device=dev)                     # rollout-buffer rows the launch fills: not looked at
-        self._logp, self._val = torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev)
-        self._rng = torch.zeros(2, dtype=torch.int64, device=dev)
-        nb = int(L.fw_collect_step_workspace_bytes(venv._h))
-        self._ws = torch.empty((nb + 7) // 8, dtype=torch.float64, device=dev)
-        self._ws_ready = False
-
-    def _fused6_step(self) -> None:
-        """a vec-step of the six-action policy: fw_collect_act_a (policy net only, deterministic, frozen statistics, nothing of the
-        previous step to finalise) -> fw_step -> fw_eval_track_ll, one after the other on the stream"""
-        from . import _lib
-        from .rollout import _p, _stream
-        env, venv = self.env, self.venv
-        L, st = _lib.lib(), _stream(self.dev)
-        _lib.check(L.fw_collect_act_a(_p(self._flat), _p(venv.obs), int(venv.obs.dtype == torch.float64), self.n, env.obs_dim, 6,
-                                      _p(env.obs_rms.mean), _p(env.obs_rms.var), float(env.clip_obs), float(env.epsilon), 1, 1, None,
-                                      int(getattr(venv, "global_env_offset", 0)), None, _p(self._act_raw), _p(self._act_env),
-                                      int(self._act_env.dtype == torch.float64), _p(self._logp), None,
-                                      None, None, None, None, None, 0, 0.0, 0.0, 0.0, None, None, st))
-        venv.step_tensor(self._act_env)
-        self._track_step()
-
-    def _fused3_step(self) -> None:
-        """a vec-step of the three-action policy: fw_collect_act_hl (commander and controller, policy nets only, deterministic, frozen
-        statistics, nothing of the previous step to finalise) -> fw_step -> fw_eval_track_hl, one after the other on the stream"""
-        env, venv = self.env, self.venv
-        a = K.FwCollectHlArgs()
-        a.params, a.nets, a.deterministic = self._flat.data_ptr(), 1, 1
-        a.obs_mean, a.obs_var = env.obs_rms.mean.data_ptr(), env.obs_rms.var.data_ptr()
-        a.clip_obs, a.eps_obs = float(env.clip_obs), float(env.epsilon)
-        a.act_raw, a.logp = self._act_raw.data_ptr(), self._logp.data_ptr()
-        venv.collect_act_hl(a)
-        venv.step_low()
-        self._track_hl_step()
+    fused = property(lambda self: self.step.kind != "torch")
+    books = property(lambda self: self._books.__get__(self), doc="the bookkeeping of a vec-step, as a callable")
 
     def _track_hl_step(self) -> None:
         """the high-level command task's bookkeeping of a vec-step, command sums included: one fw_eval_track_hl launch"""
-        from . import _lib
-        from .rollout import _p, _stream
         venv, fi = self.venv, self.fin_info
         _lib.check(_lib.lib().fw_eval_track_hl(
             _p(venv.rewards), int(venv.rewards.dtype == torch.float64), _p(venv.terminated), _p(venv.truncated),
@@ -595,121 +502,42 @@ class ReplayedEvaluation:
             _p(venv.obs), _p(venv.terminal_obs), _p(venv.command), int(venv.obs.dtype == torch.float64), int(venv.obs.shape[1]),
             self.hl[0], self.hl[1], _p(self.tg), _p(self.counts), _p(self.cur_rew), _p(self.cur_len), _p(self.step_ctr),
             _p(self.cur_track), _p(self.prev_cmd), _p(self.fin_rew), _p(self.fin_len), _p(self.fin_step),
-            _p(fi) if fi is not None else None, _p(self.fin_track), self.n, self.E, _stream(self.dev)))
+            _p(fi), _p(self.fin_track), self.n, self.E, _stream(self.dev)))
 
     def _track_step(self) -> None:
         """the low-level task's bookkeeping of a vec-step, tracking sums included: one fw_eval_track_ll launch"""
-        from . import _lib
-        from .rollout import _p, _stream
         venv, fi = self.venv, self.fin_info
         _lib.check(_lib.lib().fw_eval_track_ll(
             _p(venv.rewards), int(venv.rewards.dtype == torch.float64), _p(venv.terminated), _p(venv.truncated),
             _p(venv.info) if fi is not None else None, int(venv.info.shape[1]) if fi is not None else 0,
             _p(venv.obs), _p(venv.terminal_obs), int(venv.obs.dtype == torch.float64), int(venv.obs.shape[1]),
             _p(self.tg), _p(self.counts), _p(self.cur_rew), _p(self.cur_len), _p(self.step_ctr), _p(self.cur_track),
-            _p(self.fin_rew), _p(self.fin_len), _p(self.fin_step), _p(fi) if fi is not None else None, _p(self.fin_track),
+            _p(self.fin_rew), _p(self.fin_len), _p(self.fin_step), _p(fi), _p(self.fin_track),
             self.n, self.E, _stream(self.dev)))
 
     def _track_wp_step(self) -> None:
         """the bookkeeping of a vec-step with the path sums: one fw_eval_track_wp launch (path_figures=True)"""
-        from . import _lib
-        from .rollout import _p, _stream
         venv, fi, lay = self.venv, self.fin_info, self.path_layout
         _lib.check(_lib.lib().fw_eval_track_wp(
             _p(venv.rewards), int(venv.rewards.dtype == torch.float64), _p(venv.terminated), _p(venv.truncated),
             _p(venv.info) if fi is not None else None, int(venv.info.shape[1]) if fi is not None else 0,
             _p(venv.obs), _p(venv.terminal_obs), int(venv.obs.dtype == torch.float64), int(venv.obs.shape[1]), lay.att_dim, lay.act_dim,
             _p(self.tg), _p(self.counts), _p(self.cur_rew), _p(self.cur_len), _p(self.step_ctr), _p(self.cur_path), _p(self.carry),
-            _p(self.fin_rew), _p(self.fin_len), _p(self.fin_step), _p(fi) if fi is not None else None, _p(self.fin_path),
+            _p(self.fin_rew), _p(self.fin_len), _p(self.fin_step), _p(fi), _p(self.fin_path),
             self.n, self.E, _stream(self.dev)))
 
-    def _collect_prepare(self) -> None:
-        """fw_collect_step's workspace, initialised once (in front of the first launch, outside any capture)"""
-        from . import _lib
-        from .rollout import _stream
-        if not self._ws_ready:
-            venv = self.venv
-            _lib.check(_lib.lib().fw_collect_workspace_init(venv._h, self._ws.data_ptr(), self._ws.numel() * 8, _stream(self.dev)), venv._h)
-            self._ws_ready = True
+    def _track_plain_step(self) -> None:
+        """the bookkeeping of a vec-step behind fw_collect_step: one fw_eval_track launch"""
+        venv, fi = self.venv, self.fin_info
+        _lib.check(_lib.lib().fw_eval_track(
+            _p(venv.rewards), int(venv.rewards.dtype == torch.float64), _p(venv.terminated), _p(venv.truncated),
+            _p(venv.info) if fi is not None else None, int(venv.info.shape[1]) if fi is not None else 0,
+            _p(self.tg), _p(self.counts), _p(self.cur_rew), _p(self.cur_len), _p(self.step_ctr), _p(self.fin_rew), _p(self.fin_len),
+            _p(self.fin_step), _p(fi), self.n, self.E, _stream(self.dev)))
 
-    def _fused_step(self) -> None:
-        from . import _lib
-        from .rollout import _stream
-        if self.fused6:
-            self._fused6_step()
-            return
-        if self.fused3:
-            self._fused3_step()
-            return
-        self._collect_step()
-        if self.path_layout is not None:
-            self._track_wp_step()
-            return
-        # ... and the episode bookkeeping of the step in one more (fw_eval_track)
-        venv, L, st = self.venv, _lib.lib(), _stream(self.dev)
-        fi = self.fin_info
-        _lib.check(L.fw_eval_track(venv.rewards.data_ptr(), int(venv.rewards.dtype == torch.float64), venv.terminated.data_ptr(),
-                                   venv.truncated.data_ptr(), venv.info.data_ptr() if fi is not None else None,
-                                   int(venv.info.shape[1]) if fi is not None else 0, self.tg.data_ptr(), self.counts.data_ptr(),
-                                   self.cur_rew.data_ptr(), self.cur_len.data_ptr(), self.step_ctr.data_ptr(), self.fin_rew.data_ptr(),
-                                   self.fin_len.data_ptr(), self.fin_step.data_ptr(), fi.data_ptr() if fi is not None else None,
-                                   self.n, self.E, st))
-
-    def _collect_step(self) -> None:
-        """act + env step of the four-action policy as ONE fw_collect_step launch (deterministic, statistics frozen)"""
-        import ctypes as C
-        from . import _lib
-        from .rollout import _stream
-        env, venv = self.env, self.venv
-        L, st = _lib.lib(), _stream(self.dev)
-        self._collect_prepare()
-        a = K.FwCollectArgs()
-        a.params = self._flat.data_ptr()
-        a.obs_mean, a.obs_var, a.obs_count = env.obs_rms.mean.data_ptr(), env.obs_rms.var.data_ptr(), env.obs_rms.count.data_ptr()
-        a.returns = env.returns.data_ptr()
-        a.ret_mean, a.ret_var, a.ret_count = env.ret_rms.mean.data_ptr(), env.ret_rms.var.data_ptr(), env.ret_rms.count.data_ptr()
-        a.rng = self._rng.data_ptr()
-        a.act_raw, a.logp, a.value = self._act_raw.data_ptr(), self._logp.data_ptr(), self._val.data_ptr()
-        a.act_env = self._act_env.data_ptr()
-        a.obs, a.reward = venv.obs.data_ptr(), venv.rewards.data_ptr()
-        a.terminated, a.truncated = venv.terminated.data_ptr(), venv.truncated.data_ptr()
-        a.terminal_obs, a.info_i32 = venv.terminal_obs.data_ptr(), venv.info.data_ptr()
-        a.workspace, a.workspace_bytes = self._ws.data_ptr(), self._ws.numel() * 8
-        a.gamma = float(env.gamma)
-        a.clip_obs, a.eps_obs, a.clip_reward, a.eps_reward = float(env.clip_obs), float(env.epsilon), float(env.clip_reward), float(env.epsilon)
-        a.update_obs, a.update_ret, a.norm_reward, a.deterministic = 0, 0, 0, 1
-        _lib.check(L.fw_collect_step(venv._h, C.byref(a), st), venv._h)
-
-    def _fused_check(self) -> None:
-        """fw_collect_step's status word: a wait inside one of the launches ran out -> the evaluation is void ("returns or raises")"""
-        import ctypes as C
-        from . import _lib
-        from .rollout import _stream
-        if not self.fused or self.fused6 or self.fused3 or not self._ws_ready:      # (the six- and three-action paths have no fw_collect_step and no status word)
-            return
-        stw = C.c_uint32(0)
-        _lib.check(_lib.lib().fw_collect_status(self.venv._h, self._ws.data_ptr(), self._ws.numel() * 8, C.byref(stw), _stream(self.dev)), self.venv._h)
-        if stw.value:
-            raise RuntimeError(f"fw_collect_step: status word {stw.value} during the evaluation; its figures are void")
-
-    def _body(self):
-        venv, ar, tg, E, counts = self.venv, self.ar, self.tg, self.E, self.counts
-        if self.fused:
-            self._fused_step()
-            return
-        else:
-            actions, _, _ = self.policy(self.obs, deterministic=True, generator=None, **policy_inputs(self.policy, self.env))
-            o, _, dones, _, _ = self.env.step(clip_actions(actions, venv).to(venv.torch_dtype))
-            self.obs.copy_(o)
-        if self.track:
-            self._track_step()
-            return
-        if self.hl is not None:
-            self._track_hl_step()
-            return
-        if self.path_layout is not None:
-            self._track_wp_step()
-            return
+    def _track_torch(self) -> None:
+        """the bookkeeping of a vec-step behind the torch forward, in framework ops"""
+        venv, ar, tg, E, counts, dones = self.venv, self.ar, self.tg, self.E, self.counts, self.step.dones
         self.cur_rew.add_(venv.rewards.to(torch.float64))            # un-normalised reward of the wrapped env
         self.cur_len.add_(1); self.step_ctr.add_(1)
         take = dones & (counts < tg)
@@ -722,13 +550,17 @@ class ReplayedEvaluation:
         counts.add_(take.to(torch.int64))
         self.cur_rew.masked_fill_(dones, 0.0); self.cur_len.masked_fill_(dones, 0)
 
-    def _begin(self):
+    def _body(self) -> None:
+        self.step()
+        self._books(self)
+
+    def begin(self):
         """reset, two eager steps (they are evaluation steps like any other), capture: on the side stream"""
         self.side.wait_stream(torch.cuda.current_stream(self.dev))
         with torch.cuda.stream(self.side):
             if self.hl is not None:
                 self.venv.rejected.zero_()
-            self.obs = self.env.reset().clone()
+            self.obs = self.step.obs = self.env.reset().clone()      # (the torch forward's fixed input buffer)
             if self.path_layout is not None:
                 from . import flight
                 self.carry.copy_(flight.seed_carry(self.venv.obs, self.path_layout))
@@ -736,24 +568,24 @@ class ReplayedEvaluation:
                 self._body(); self.steps += 1
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph, stream=self.side):
-                for _ in range(_REPLAY_STEPS):
+                for _ in range(REPLAY_STEPS):
                     self._body()
 
     def run(self, max_vec_steps: Optional[int] = None) -> "EvalResult":
-        self._begin()
+        self.begin()
         with torch.cuda.stream(self.side):
             while True:
-                self.graph.replay(); self.steps += _REPLAY_STEPS
+                self.graph.replay(); self.steps += REPLAY_STEPS
                 if not bool((self.counts < self.tg).any().item()) or (max_vec_steps is not None and self.steps >= max_vec_steps):
                     break
         torch.cuda.current_stream(self.dev).wait_stream(self.side)
         return self.result()
 
     def launch(self, bound_vec_steps: int) -> "ReplayedEvaluation":
-        self._begin()
+        self.begin()
         with torch.cuda.stream(self.side):
-            for _ in range(-(-max(bound_vec_steps - 2, 1) // _REPLAY_STEPS)):
-                self.graph.replay(); self.steps += _REPLAY_STEPS
+            for _ in range(-(-max(bound_vec_steps - 2, 1) // REPLAY_STEPS)):
+                self.graph.replay(); self.steps += REPLAY_STEPS
             self.done_event = torch.cuda.Event()
             self.done_event.record(self.side)
         return self
@@ -766,7 +598,7 @@ class ReplayedEvaluation:
             self.done_event.synchronize()
         else:
             self.side.synchronize()
-        self._fused_check()
+        self.step.check()
         n, has_info = self.n, self.has_info
         res = EvalResult([], [])
         c_h = torch.minimum(self.counts, self.tg).cpu().numpy()
@@ -796,8 +628,7 @@ def start_evaluation(policy, env, n_eval_episodes: int = 10, callback=None, use_
                      path_figures: bool = False) -> ReplayedEvaluation:
     """Asynchronous :func:`evaluate_policy` (deterministic, device envs whose config bounds the episode length): returns a
     running :class:`ReplayedEvaluation`; ``.result()`` waits for it."""
-    n = env.num_envs
-    targets = np.array([(n_eval_episodes + i) // n for i in range(n)], dtype=np.int64)
+    targets = _targets(n_eval_episodes, env.num_envs)
     bound = int(targets.max()) * (K.max_steps(env.venv.cfg) + 2)
     return ReplayedEvaluation(policy, env, targets, callback, use_fused=use_fused, path_figures=path_figures).launch(bound)
 

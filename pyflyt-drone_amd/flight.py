@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from . import config as K
-from .vec_env import _devptr
+from ._lib import devptr as _devptr
 
 # the per-episode path sums, in the column order of fw_eval_track_wp's cur_path / fin_path
 PATH_SUMS = ("path_len", "speed_sum", "alt_sum", "alt_min", "ang_vel_sum", "act_delta_sum", "throttle_sum", "first_reach_step",
@@ -247,13 +247,12 @@ def fly(policy, env, n_steps: int, use_fused: Optional[bool] = None, graph_steps
     """Fly ``policy`` (deterministic, frozen normaliser statistics) for ``n_steps`` vec-steps on ``env``, a
     ``VecNormalizeDevice(training=False)`` around a waypoints, ObjLock, combined or direct-command waypoints env.  ``env.reset()``
     first; then per vec-step k: act -> step -> ``fw_trace_rows`` (row k of the trace).  The act and the step are the torch forward
-    followed by ``step_tensor`` (``use_fused`` None / False) or the one ``fw_collect_step`` launch of
-    ``ReplayedEvaluation._fused_step`` (``use_fused=True``, where ``_fused_applies`` holds).  With ``graph_steps > 0`` the body is
+    followed by ``step_tensor`` (``use_fused`` None / False) or the one ``fw_collect_step`` launch of ``evalstep.CollectStep``
+    (``use_fused=True``, where ``evalstep.select`` finds that it applies).  With ``graph_steps > 0`` the body is
     captured as a hipGraph of that many vec-steps and replayed (the trace row is picked on the device); the steps that do not fill a
     whole graph run eagerly after it.  ``graph_steps <= 0`` runs every step eagerly; both give the same trace bit for bit.  A policy
     with a CNN front end (``uses_image``) flies eagerly: MIOpen stays out of captures, as in ``evaluate_policy``."""
-    from .evaluate import ReplayedEvaluation
-    from .rollout import clip_actions, policy_inputs
+    from . import evalstep
     venv = _flight_env(env, "fly")
     if getattr(env, "training", True):
         raise ValueError("fly needs an evaluation normaliser (training=False): the statistics stay frozen")
@@ -262,13 +261,9 @@ def fly(policy, env, n_steps: int, use_fused: Optional[bool] = None, graph_steps
         raise ValueError(f"n_steps must be positive, got {n_steps}")
     n, dev = env.num_envs, env.device
     layout = RowLayout.of(venv.cfg)
-    fused = bool(use_fused)
-    job = None
-    if fused:
-        if not ReplayedEvaluation._fused_applies(policy, env):
-            raise ValueError("use_fused=True needs the four-action MlpPolicy, a device env on the 8-lane mapping and an evaluation "
-                             "normaliser (training=False) on the GPU")
-        job = ReplayedEvaluation(policy, env, np.ones(n, dtype=np.int64), use_fused=True)      # (its fw_collect_step launch and buffers)
+    kind = evalstep.select(policy, env, use_fused, ("collect_step",), "use_fused=True needs the four-action MlpPolicy, a device env on "
+                           "the 8-lane mapping and an evaluation normaliser (training=False) on the GPU")
+    step = evalstep.make(kind, policy, env)
     if getattr(policy, "uses_image", False):
         graph_steps = 0
     L = _lib.lib()
@@ -277,48 +272,18 @@ def fly(policy, env, n_steps: int, use_fused: Optional[bool] = None, graph_steps
     trace = torch.zeros((T, n, D + 2), dtype=torch.float64, device=dev)
     is_f64 = int(venv.obs.dtype == torch.float64)
 
-    def actions():
-        obs_n = env._process_obs(venv.obs, update=False)
-        with torch.no_grad():
-            a, _, _ = policy(obs_n, deterministic=True, **policy_inputs(policy, env))
-        return clip_actions(a, venv).to(venv.torch_dtype)
-
     def body():
-        if fused:
-            job._collect_step()
-        else:
-            venv.step_tensor(actions())
+        step()
         _lib.check(L.fw_trace_rows(_devptr(venv.obs), _devptr(venv.terminal_obs), _devptr(venv.terminated), _devptr(venv.truncated),
                                    _devptr(venv.info), int(venv.info.shape[1]), is_f64, n, D, _devptr(trace), T, _devptr(step_idx),
-                                   torch.cuda.current_stream(dev).cuda_stream))
+                                   _lib.stream(dev)))
 
-    side = torch.cuda.Stream(device=dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(side):
-        env.reset()
-        start = trace_rows(venv.obs)
-        reps = T // graph_steps if graph_steps and graph_steps > 0 else 0
-        if reps:
-            if not fused:
-                actions()                    # one forward outside the capture warms its libraries up (no env state)
-            else:
-                job._collect_prepare()       # (the workspace initialisation is no part of a step)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side):
-                for _ in range(graph_steps):
-                    body()
-            for _ in range(reps):
-                graph.replay()
-        for _ in range(T - reps * (graph_steps if reps else 0)):
-            body()
-        side.synchronize()
-        if job is not None:
-            job._fused_check()
-    torch.cuda.current_stream(dev).wait_stream(side)
-    tr = trace.cpu().numpy()
-    done = tr[:, :, D + 1] != FLAG_RUNNING
-    ended_at = np.where(done.any(axis=0), done.argmax(axis=0), -1).astype(np.int64)
-    return FlightTrace(trace=tr, start=start.cpu().numpy(), dt=1.0 / float(venv.cfg.agent_hz), ended_at=ended_at, layout=layout)
+    def finish():                            # the status word is read once the stream has drained
+        torch.cuda.current_stream(dev).synchronize()
+        step.check()
+
+    tr, start, ended_at = evalstep.replay_flight(env, trace, graph_steps, body, step.prepare, lambda: trace_rows(venv.obs), D + 1, finish)
+    return FlightTrace(trace=tr, start=start, dt=1.0 / float(venv.cfg.agent_hz), ended_at=ended_at, layout=layout)
 
 
 def path_figures(trace: FlightTrace) -> dict:

@@ -226,12 +226,10 @@ class HighLevelCmdVecEnv(FusedVecEnv):
                                    _devptr(self.low_obs), _devptr(self.command), _devptr(self.rejected), st), b._h)
         if self.controller_in_step:
             return self.step_low()
-        f64 = int(self.torch_dtype == torch.float64)
         # the controller: policy net only, deterministic, frozen statistics, nothing of a previous step to finalise
-        _lib.check(L.fw_collect_act_a(_devptr(self._flat), _devptr(self.low_obs), f64, n, LOW_OBS_DIM, LOW_ACT_DIM,
-                                      _devptr(self.low_mean), _devptr(self.low_var), self.clip_obs, self.epsilon, 1, 1, None,
-                                      int(self.global_env_offset), None, _devptr(self._act_raw), _devptr(self.low_action), f64,
-                                      _devptr(self._logp), None, None, None, None, None, None, 0, 0.0, 0.0, 0.0, None, None, st))
+        _lib.collect_act_a(self._flat, self.low_obs, n, LOW_OBS_DIM, LOW_ACT_DIM, self.low_mean, self.low_var, self.clip_obs, self.epsilon,
+                           nets=1, deterministic=1, env_offset=self.global_env_offset, act_raw=self._act_raw, act_env=self.low_action,
+                           logp=self._logp, stream=st)
         return b.step_tensor(self.low_action)
 
     # ------------------------------------------------------------------ the fused collector (rollout.PPO, fused_three_actions)
@@ -341,13 +339,12 @@ def fly(policy, env, n_steps: int, use_fused: Optional[bool] = None, graph_steps
     ``VecNormalizeDevice(training=False)`` around a :class:`HighLevelCmdVecEnv` with the 30-value observation.  ``env.reset()``
     first; then per vec-step k: act -> step -> ``fw_trace_hl`` (row k of the trace).  The act is the torch forward followed by
     ``step_tensor`` (``use_fused`` None / False) or ``fw_collect_act_hl`` followed by ``step_low`` (``use_fused=True``, the launches
-    of ``ReplayedEvaluation._fused3_step``).  With ``graph_steps > 0`` the body is captured as a hipGraph of that many vec-steps and
+    of ``evalstep.ActHlStep``).  With ``graph_steps > 0`` the body is captured as a hipGraph of that many vec-steps and
     replayed (the trace row is picked on the device); the steps that do not fill a whole graph run eagerly after it.
     ``graph_steps <= 0`` runs every step eagerly; both give the same trace bit for bit."""
-    from .evaluate import ReplayedEvaluation, _hl_bounds
-    from .rollout import clip_actions
+    from . import evalstep
     venv = getattr(env, "venv", None)
-    if venv is None or _hl_bounds(venv) is None:
+    if venv is None or not evalstep.is_highlevel(venv):
         raise ValueError("fly needs a VecNormalizeDevice around a HighLevelCmdVecEnv with the 30-value observation")
     if getattr(env, "training", True):
         raise ValueError("fly needs an evaluation normaliser (training=False): the statistics stay frozen")
@@ -355,63 +352,24 @@ def fly(policy, env, n_steps: int, use_fused: Optional[bool] = None, graph_steps
     if T <= 0:
         raise ValueError(f"n_steps must be positive, got {n_steps}")
     n, dev = env.num_envs, env.device
-    fused = bool(use_fused)
-    if fused and not ReplayedEvaluation._fused3_applies(policy, env):
-        raise ValueError("use_fused=True needs the three-action MlpPolicy and an evaluation normaliser (training=False) on the GPU")
+    kind = evalstep.select(policy, env, use_fused, ("act_hl",),
+                           "use_fused=True needs the three-action MlpPolicy and an evaluation normaliser (training=False) on the GPU")
+    step = evalstep.make(kind, policy, env)
     L = _lib.lib()
     step_idx = torch.zeros((), dtype=torch.int64, device=dev)
     trace = torch.zeros((T, n, len(HL_TRACE_COLS)), dtype=torch.float64, device=dev)
     is_f64 = int(venv.obs.dtype == torch.float64)
-    if fused:
-        from .rollout import FusedPpoUpdate
-        f = FusedPpoUpdate(policy, None, env.obs_dim)
-        f.load_params_from_torch()
-        flat = f.flat
-        act_raw = torch.zeros((n, 3), dtype=torch.float32, device=dev)
-        logp = torch.zeros(n, dtype=torch.float32, device=dev)
-
-    def actions():
-        obs_n = env._process_obs(venv.obs, update=False)
-        with torch.no_grad():
-            a, _, _ = policy(obs_n, deterministic=True)
-        return clip_actions(a, venv).to(venv.torch_dtype)
 
     def body():
-        if fused:
-            a = K.FwCollectHlArgs()
-            a.params, a.nets, a.deterministic = flat.data_ptr(), 1, 1
-            a.obs_mean, a.obs_var = env.obs_rms.mean.data_ptr(), env.obs_rms.var.data_ptr()
-            a.clip_obs, a.eps_obs = float(env.clip_obs), float(env.epsilon)
-            a.act_raw, a.logp = act_raw.data_ptr(), logp.data_ptr()
-            venv.collect_act_hl(a)
-            venv.step_low()
-        else:
-            venv.step_tensor(actions())
+        step()
         _lib.check(L.fw_trace_hl(_devptr(venv.obs), _devptr(venv.terminal_obs), _devptr(venv.terminated), _devptr(venv.truncated),
                                  _devptr(venv.command), _devptr(venv.info), int(venv.info.shape[1]), is_f64, n, _devptr(trace), T,
-                                 _devptr(step_idx), torch.cuda.current_stream(dev).cuda_stream))
+                                 _devptr(step_idx), _lib.stream(dev)))
 
-    side = torch.cuda.Stream(device=dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(side):
-        env.reset()
-        side.synchronize()                   # (get_state copies on the default stream)
+    def start_row():
+        torch.cuda.current_stream(dev).synchronize()      # (the side stream the flight runs on: get_state copies on the default stream)
         stored = torch.as_tensor(venv.get_state()[:, K.S_TASK:K.S_TASK + 3], dtype=torch.float64, device=dev)   # the FW_SL_TARGET tail
-        start = trace_rows_hl(venv.obs, stored)
-        reps = T // graph_steps if graph_steps and graph_steps > 0 else 0
-        if reps:
-            if not fused:
-                actions()                    # one forward outside the capture warms its libraries up (no env state)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side):
-                for _ in range(graph_steps):
-                    body()
-            for _ in range(reps):
-                graph.replay()
-        for _ in range(T - reps * (graph_steps if reps else 0)):
-            body()
-    torch.cuda.current_stream(dev).wait_stream(side)
-    tr = trace.cpu().numpy()
-    done = tr[:, :, len(HL_TRACE_COLS) - 1] != FLAG_RUNNING
-    ended_at = np.where(done.any(axis=0), done.argmax(axis=0), -1).astype(np.int64)
-    return HighLevelTrace(trace=tr, start=start.cpu().numpy(), dt=1.0 / float(venv.cfg.agent_hz), ended_at=ended_at)
+        return trace_rows_hl(venv.obs, stored)
+
+    tr, start, ended_at = evalstep.replay_flight(env, trace, graph_steps, body, step.prepare, start_row, len(HL_TRACE_COLS) - 1)
+    return HighLevelTrace(trace=tr, start=start, dt=1.0 / float(venv.cfg.agent_hz), ended_at=ended_at)

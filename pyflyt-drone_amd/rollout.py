@@ -34,14 +34,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+from ._lib import devptr as _p, stream as _stream
 
 
 def _rehearse_one_rank() -> bool:
@@ -1066,19 +1059,18 @@ class PPO:
         def act(t, nets, value_out, prev_t):
             """prev_t: index of the step to finalise (its rewards go to buf_rew[prev_t], the starts of the NEXT step to
             buf_start[prev_t + 1] / last_starts), or None."""
-            bo = _p(self.buf_obs[t]) if t is not None else None
-            ba = _p(self.buf_act[t]) if t is not None else None
-            bl = _p(self.buf_logp[t]) if t is not None else None
+            bo = self.buf_obs[t] if t is not None else None
+            ba = self.buf_act[t] if t is not None else None
+            bl = self.buf_logp[t] if t is not None else None
             if prev_t is None:
-                prev = (None, None, None, None, None, 0, 0.0, 0.0, 0.0, None, None)
+                prev = _lib.NOTHING_TO_FINALISE
             else:
                 nxt = self.buf_start[prev_t + 1] if prev_t + 1 < T else self.last_starts
                 prev = (_p(venv.rewards), _p(venv.terminated), _p(venv.truncated), _p(venv.terminal_obs), _p(env.ret_rms.var),
                         int(env.norm_reward), float(env.clip_reward), float(env.epsilon), float(cfg.gamma), _p(self.buf_rew[prev_t]), _p(nxt))
-            _lib.check(L.fw_collect_act_a(_p(self._fused.flat), _p(venv.obs), f64, N, D, self.act_dim, _p(env.obs_rms.mean), _p(env.obs_rms.var),
-                                          float(env.clip_obs), float(env.epsilon), nets, 0, _p(self._rng),
-                                        int(getattr(venv, "global_env_offset", 0)), bo, ba, _p(self._act_env),
-                                        int(self._act_env.dtype == torch.float64), bl, _p(value_out), *prev, st))
+            _lib.collect_act_a(self._fused.flat, venv.obs, N, D, self.act_dim, env.obs_rms.mean, env.obs_rms.var, env.clip_obs, env.epsilon,
+                               nets=nets, deterministic=0, rng=self._rng, env_offset=getattr(venv, "global_env_offset", 0), obs_copy=bo,
+                               act_raw=ba, act_env=self._act_env, logp=bl, value=value_out, prev=prev, stream=st)
 
         if self._one_launch:
             # ONE launch per vec-step (fw_collect_step): act waves, the env's step waves and the statistics fold share a grid
@@ -1139,12 +1131,11 @@ class PPO:
             self._fold_episodes()
         # V(last observation) for GAE + the finalisation of step T-1 (nothing is sampled; the normalised last observation lands
         # in last_obs for callers that look at it)
-        _lib.check(L.fw_collect_act_a(_p(self._fused.flat), _p(venv.obs), f64, N, D, self.act_dim, _p(env.obs_rms.mean), _p(env.obs_rms.var),
-                                      float(env.clip_obs), float(env.epsilon), 2, 0, _p(self._rng), int(getattr(venv, "global_env_offset", 0)),
-                                    None, None, None, 0, None, _p(self.last_values),
-                                    _p(venv.rewards), _p(venv.terminated), _p(venv.truncated), _p(venv.terminal_obs), _p(env.ret_rms.var),
-                                    int(env.norm_reward), float(env.clip_reward), float(env.epsilon), float(cfg.gamma),
-                                    _p(self.buf_rew[T - 1]), _p(self.last_starts), st))
+        _lib.collect_act_a(self._fused.flat, venv.obs, N, D, self.act_dim, env.obs_rms.mean, env.obs_rms.var, env.clip_obs, env.epsilon,
+                           nets=2, deterministic=0, rng=self._rng, env_offset=getattr(venv, "global_env_offset", 0), value=self.last_values,
+                           prev=(_p(venv.rewards), _p(venv.terminated), _p(venv.truncated), _p(venv.terminal_obs), _p(env.ret_rms.var),
+                                 int(env.norm_reward), float(env.clip_reward), float(env.epsilon), float(cfg.gamma),
+                                 _p(self.buf_rew[T - 1]), _p(self.last_starts)), stream=st)
         _lib.check(L.fw_normalize_obs(_p(venv.obs), f64, N, D, _p(env.obs_rms.mean), _p(env.obs_rms.var), _p(env.obs_rms.count), 0,
                                       float(env.clip_obs), float(env.epsilon), _p(self.last_obs), None, None, st))
 

@@ -26,11 +26,8 @@ import torch
 
 from . import _lib
 from . import config as K
+from ._lib import devptr as _devptr
 from .spaces import Box
-
-
-def _devptr(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 try:        # Stable-Baselines3 asserts isinstance(env, VecEnv): subclass the real base class when it is importable

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from pyflyt_drone_amd import _lib, evaluate, flight
+from pyflyt_drone_amd import _lib, evalstep, evaluate, flight
 from pyflyt_drone_amd import config as K
 from pyflyt_drone_amd import rollout as R
 from pyflyt_drone_amd.flight import RowLayout
@@ -311,7 +311,7 @@ def test_the_three_evaluation_paths_record_the_same_flights(lanes):
         env = _waypoints_env(tg)
         assert env.venv.lanes_per_env == lanes
         pol = _zero_policy(env.obs_dim)
-        if kw.get("use_fused") and not evaluate.ReplayedEvaluation._fused_applies(pol, env):
+        if kw.get("use_fused") and not evalstep.applies("collect_step", pol, env):
             assert lanes == 1
             with pytest.raises(ValueError, match="use_fused=True"):
                 evaluate.evaluate_policy(pol, env, n_eval_episodes=N_ENVS, path_figures=True, **kw)

@@ -280,7 +280,7 @@ def test_fused_three_action_evaluation_flies_the_episodes_of_the_torch_evaluatio
         env = _env(24, "random", identity=False)
         assert env.venv.lanes_per_env == lanes
         job = evaluate.ReplayedEvaluation(_commander(gain=(1.0, 10.0, 1.0)), env, _targets(61, 24), use_fused=fused)
-        assert job.fused == bool(fused) and job.fused3 == bool(fused) and not job.fused6
+        assert job.fused == bool(fused) and job.step.kind == ("act_hl" if fused else "torch")
         out.append(job.run(None))
         env.venv.close()
     a, b = out
@@ -385,7 +385,7 @@ def test_async_evaluation_and_eval_callback_carry_the_command_figures(tmp_path):
     env.venv.close()
     env = _env(16, "zeroed", seed=4)
     job = evaluate.start_evaluation(pol, env, n_eval_episodes=20, use_fused=True)
-    assert job.fused3
+    assert job.step.kind == "act_hl"
     r = job.result()
     env.venv.close()
     assert r.episode_lengths == sync.episode_lengths and r.episode_rewards == sync.episode_rewards

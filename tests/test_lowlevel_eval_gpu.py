@@ -113,7 +113,7 @@ def test_fused_six_action_evaluation_flies_the_episodes_of_the_torch_evaluation(
         with torch.no_grad():
             pol.action_net.weight.mul_(30.0)
         job = evaluate.ReplayedEvaluation(pol, env, _targets(61, 24), use_fused=fused)
-        assert job.fused == bool(fused) and job.fused6 == bool(fused)
+        assert job.fused == bool(fused) and job.step.kind == ("act_a" if fused else "torch")
         out.append(job.run(None))
     a, b = out
     assert len(a.episode_lengths) == 61 == len(b.episode_lengths)

@@ -32,7 +32,7 @@ def main():
     import numpy as np
     import torch
     import pyflyt_drone_amd as P
-    from pyflyt_drone_amd import _lib, evaluate, flight, config as K, rollout as R
+    from pyflyt_drone_amd import _lib, evalstep, evaluate, flight, config as K, rollout as R
     assert torch.cuda.is_available(), "bench_flight.py needs a HIP device"
     dev_name = torch.cuda.get_device_name(0)
     lines = []
@@ -59,20 +59,20 @@ def main():
         torch.manual_seed(31)
         pol = R.MlpPolicy(K.obs_dim(cfg), 4).cuda()
         targets = np.ones(n, dtype=np.int64)                # (the replays run on past the episodes: the loop body is what is timed)
-        replays = max(a.steps // evaluate._REPLAY_STEPS, 1)
+        replays = max(a.steps // evaluate.REPLAY_STEPS, 1)
         for fused in (False, True):
             for on in (False, True):
                 env = R.VecNormalizeDevice(P.FixedwingVecEnv(cfg, n, seed=3), training=False, norm_reward=False, clip_obs=10.0)
-                if fused and not evaluate.ReplayedEvaluation._fused_applies(pol, env):
+                if fused and not evalstep.applies("collect_step", pol, env):
                     env.venv.close()
                     continue
                 job = evaluate.ReplayedEvaluation(pol, env, targets, use_fused=fused, path_figures=on)
-                job._begin()
+                job.begin()
                 with torch.cuda.stream(job.side):
-                    t = timed(job.graph.replay, evaluate._REPLAY_STEPS, replays)
-                job._fused_check()
+                    t = timed(job.graph.replay, evaluate.REPLAY_STEPS, replays)
+                job.step.check()
                 emit({"leg": "eval", "body": "fw_collect_step" if fused else "torch_forward", "path_figures": on, "envs": n, "dtype": "float64",
-                      "us_per_vec_step": t["us"], "us_min": t["us_min"], "us_max": t["us_max"], "vec_steps": replays * evaluate._REPLAY_STEPS,
+                      "us_per_vec_step": t["us"], "us_min": t["us_min"], "us_max": t["us_max"], "vec_steps": replays * evaluate.REPLAY_STEPS,
                       "repeats": a.repeats, "device": dev_name})
                 env.venv.close()
         # the kernels alone, on the buffers of an env that has been stepped
@@ -98,7 +98,7 @@ def main():
                                        venv.info.data_ptr(), int(venv.info.shape[1]), 1, n, venv.obs_dim, trace.data_ptr(), T, idx.data_ptr(),
                                        torch.cuda.current_stream().cuda_stream))
 
-        for name, fn in (("fw_eval_track", track), ("fw_eval_track_wp", job._track_wp_step), ("fw_trace_rows", rows)):
+        for name, fn in (("fw_eval_track", track), ("fw_eval_track_wp", job.books), ("fw_trace_rows", rows)):
             with torch.cuda.stream(st):
                 fn()
                 torch.cuda.synchronize()

@@ -88,12 +88,12 @@ def main():
                 q.add_(0.1 * torch.randn_like(q))
             pol.action_net.bias.copy_(torch.tensor([0.0, 100.0, 15.0]))
         targets = np.ones(n, dtype=np.int64)                # (the replays run on past the episodes: the loop body is what is timed)
-        replays = max(a.steps // evaluate._REPLAY_STEPS, 1)
+        replays = max(a.steps // evaluate.REPLAY_STEPS, 1)
         for name, fused in (("replayed_torch_forward", False), ("fused_three_actions", True)):
             venv = HighLevelCmdVecEnv(n, ctl, (mean, var), seed=3)
             env = R.VecNormalizeDevice(venv, training=False, norm_reward=False, clip_obs=10.0)
             job = evaluate.ReplayedEvaluation(pol, env, targets, use_fused=fused)
-            job._begin()
+            job.begin()
             with torch.cuda.stream(job.side):
                 for _ in range(16):                         # warm-up replays
                     job.graph.replay()
@@ -104,10 +104,10 @@ def main():
                     for _ in range(replays):
                         job.graph.replay()
                     torch.cuda.synchronize()
-                    us.append((time.perf_counter() - t0) / (replays * evaluate._REPLAY_STEPS) * 1e6)
-            emit({"leg": "eval", "path": name, "fused": bool(job.fused), "fused3": bool(job.fused3), "envs": n, "dtype": "float64",
+                    us.append((time.perf_counter() - t0) / (replays * evaluate.REPLAY_STEPS) * 1e6)
+            emit({"leg": "eval", "path": name, "fused": bool(job.fused), "fused3": job.step.kind == "act_hl", "envs": n, "dtype": "float64",
                   "us_per_vec_step": round(float(np.median(us)), 2), "us_min": round(min(us), 2), "us_max": round(max(us), 2),
-                  "vec_steps": replays * evaluate._REPLAY_STEPS, "repeats": a.repeats, "rejected_actions": int(venv.rejected.item()),
+                  "vec_steps": replays * evaluate.REPLAY_STEPS, "repeats": a.repeats, "rejected_actions": int(venv.rejected.item()),
                   "device": dev_name})
             venv.close()
     if a.out:
