@@ -20,6 +20,11 @@ is one gradient step per vec-step on a batch as large as the env count (the wide
 
 ``--n_steps k`` (1 ... 16, default 1) trains on k-step returns gathered from the ring (``SACConfig.n_steps``): with so
 few gradient steps per sample each one carries reward information k steps back instead of one.
+
+``--her_goals n`` (default 0: off) relabels goals in hindsight as SB3's ``HerReplayBuffer(n_sampled_goal=n)`` with the "future"
+strategy does: a sampled transition keeps its episode's target with probability 1 / (n + 1); otherwise its target becomes the heading,
+altitude and airspeed the same episode reached at most ``--her_horizon`` - 1 steps later (1 ... 64, default 64) and its reward is
+recomputed for that target (``SACConfig.her_goals``).  Both env variants; not together with ``--n_steps`` above 1.
 """
 import argparse
 import json
@@ -50,6 +55,10 @@ def main():
                          "--num_envs 4096 --batch_size 4096 --gradient_steps 1")
     ap.add_argument("--n_steps", type=int, default=1,
                     help="n-step returns (1 ... 16): the target is r_0 + gamma r_1 + ... + gamma^k bootstrap, cut at episode ends; 1: the 1-step target")
+    ap.add_argument("--her_goals", type=int, default=0,
+                    help="hindsight goal relabelling, SB3's n_sampled_goal: a sampled row is relabelled with probability n / (n + 1); 0: off")
+    ap.add_argument("--her_horizon", type=int, default=64,
+                    help="the relabelled goal is one the episode achieved at most this many steps ahead, minus one (1 ... 64)")
     ap.add_argument("--fused_update", action=argparse.BooleanOptionalAction, default=True,
                     help="fw_sac_update (default) or the torch gradient step")
     ap.add_argument("--use_graphs", action=argparse.BooleanOptionalAction, default=True)
@@ -79,7 +88,8 @@ def main():
                                    gamma=c["gamma"], tau=c["tau"], gradient_steps=a.gradient_steps,
                                    target_update_interval=c["target_update_interval"], learning_starts=c["learning_starts"],
                                    net_arch=c["net_arch"], seed=c["seed"], use_graphs=a.use_graphs, fused_update=a.fused_update,
-                                   episode_stats=a.episode_stats, episode_fold=a.episode_fold, n_steps=a.n_steps))
+                                   episode_stats=a.episode_stats, episode_fold=a.episode_fold, n_steps=a.n_steps,
+                                   her_goals=a.her_goals, her_horizon=a.her_horizon))
     t0 = time.perf_counter()
     state = {"next_eval": a.eval_freq, "train_s": 0.0, "mark": t0}
 
@@ -108,6 +118,7 @@ def main():
 
     print(json.dumps({"config": {**{k: v for k, v in c.items()}, "batch_size": a.batch_size, "total_timesteps": a.total_timesteps, "eval_freq": a.eval_freq, **({"env": a.env} if demo else {}), "num_envs": a.num_envs, "gradient_steps": model.G,
                                  **({"n_steps": a.n_steps} if a.n_steps != 1 else {}),
+                                 **({"her_goals": a.her_goals, "her_horizon": a.her_horizon} if a.her_goals else {}),
                                  "fused_update": a.fused_update, "use_graphs": a.use_graphs}}), flush=True)
     evaluate_now(model)                      # the untrained actor: the line later evaluations are read against
     try:

@@ -983,6 +983,32 @@ int32_t fw_replay_mark_ends(uint8_t* ends, int64_t capacity, const int64_t* coun
 int32_t fw_replay_sample_nstep(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
                                float* out, int32_t* idx_out, const uint8_t* ends, int32_t obs_dim, int32_t N, int32_t n_steps, float gamma,
                                int32_t* k_out, void* hip_stream);
+/* Hindsight goal relabelling (SB3's HerReplayBuffer, "future" strategy) for the low-level task, whose goal (psi_ref, h_ref, V_ref) is
+ * obs[18:21] and whose reward is a closed function of the post-step observation and that goal.  Built for obs_dim 21 and row_floats 50
+ * (Euler attitude): anything else FW_EUNSUPPORTED. */
+typedef struct fw_her_task {      /* the low-level task's reward, the part the relabelled goal changes */
+  int32_t variant;                /* 0: fixedwing_lowlevel_env.py   1: FW_LL_VARIANT_SAC_DEMO */
+  float dome, min_speed;          /* variant 1 only: flight_dome_size, lowlevel_min_speed */
+} fw_her_task;
+int32_t fw_sizeof_her_task(void);
+/* fw_replay_sample with relabelled goals.  The start index i of batch row b is fw_replay_sample's draw (equal counters: equal idx_out).
+ * A second Philox block, counter words (b, 0, gs, gs >> 32 ^ 0x5AC0E000) under the same key, gives o[0] and o[1].  The row is relabelled
+ * iff (uint64)o[0] < (uint64)((double)relabel_prob 2^32): 0 never, 1 always.  A row that is not relabelled is the ring row, bit for bit.
+ * Candidates: row_j = (i + j N) mod capacity, j < horizon; row_j is used, and the walk stops behind it when j + 1 == horizon, or
+ * ends[row_j] != 0, or row_j lies in the newest vec-step stored -- fw_replay_sample_nstep's rule.  With k rows used, j* = umulhi(o[1], k)
+ * in [0, k - 1] (0: the goal this very transition achieved) and the achieved goal g' = (next_obs[5], next_obs[11], |next_obs[6:9]|) of
+ * row_j*, the norm in double from the fp32 values, rounded to fp32.  Output row, in fw_replay_sample's layout: obs[0:18], action,
+ * next_obs[0:18] and the last column of row_0 bit for bit; obs[18:21] = next_obs[18:21] = g'; reward = the task's reward for
+ * (next_obs[0:18] of row_0, g', done of row_0), in double, rounded once to fp32; the airspeed it reads is the achieved one as above
+ * (rounded to fp32), so with j* = 0 the tracking errors are exactly 0.  done stays what it was.  j_out (optional) [batch]: -1 where the row
+ * was not relabelled, else j*.  horizon in [1, 64] (FW_EUNSUPPORTED otherwise); relabel_prob outside [0, 1] or a variant other than
+ * 0 / 1: FW_EINVAL.  Reads counters only, no atomics; every row index is taken mod capacity. */
+int32_t fw_replay_sample_her(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
+                             float* out, int32_t* idx_out, const uint8_t* ends, int32_t obs_dim, int32_t N, int32_t horizon, float relabel_prob,
+                             const fw_her_task* task, int32_t* j_out, void* hip_stream);
+/* The same reward on caller-given goals [batch, 3]: reward_out[b] for (next_obs[0:18] of rows[b], goals[b], done of rows[b]). */
+int32_t fw_her_reward(const float* rows, int32_t row_floats, int32_t batch, int32_t obs_dim, const float* goals, const fw_her_task* task,
+                      float* reward_out, void* hip_stream);
 /* eps and eps' [2][batch][act_dim] of gradient step counters[3]: the values fw_sac_update draws inside.  A row's noise does not
  * depend on the batch size.  Any positive batch, as fw_replay_sample. */
 int32_t fw_sac_noise(uint64_t seed, const int64_t* counters, int32_t batch, int32_t act_dim, float* out, void* hip_stream);

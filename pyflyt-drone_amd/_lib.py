@@ -36,6 +36,7 @@ EXPORTS = (
     "fw_sizeof_sac_hyper", "fw_sac_param_count", "fw_sac_update_workspace_bytes", "fw_sac_act", "fw_replay_store", "fw_replay_sample",
     "fw_sac_noise", "fw_sac_update",
     "fw_replay_mark_ends", "fw_replay_sample_nstep",
+    "fw_sizeof_her_task", "fw_replay_sample_her", "fw_her_reward",
 )
 
 
@@ -222,6 +223,11 @@ def lib() -> C.CDLL:
             L.fw_replay_mark_ends.restype = i32; L.fw_replay_mark_ends.argtypes = [vp, i64, vp, vp, vp, i32, vp]
             L.fw_replay_sample_nstep.restype = i32
             L.fw_replay_sample_nstep.argtypes = [vp, i64, vp, u64, i32, i32, vp, vp, vp, i32, i32, i32, C.c_float, vp, vp]
+        if hasattr(L, "fw_replay_sample_her"):     # hindsight relabelling (an A/B library of an older commit predates the three; build() insists on them)
+            L.fw_sizeof_her_task.restype = i32; L.fw_sizeof_her_task.argtypes = []
+            L.fw_replay_sample_her.restype = i32
+            L.fw_replay_sample_her.argtypes = [vp, i64, vp, u64, i32, i32, vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp]
+            L.fw_her_reward.restype = i32; L.fw_her_reward.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
         L.fw_policy_act_a.restype = i32
         L.fw_policy_act_a.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
         L.fw_collect_act_a.restype = i32

@@ -3568,6 +3568,40 @@ int32_t fw_replay_sample_nstep(const float* ring, int64_t capacity, const int64_
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }
+int32_t fw_sizeof_her_task(void) { return (int32_t)sizeof(fw_her_task); }
+static_assert(sizeof(fw_her_task) == sizeof(HerTask), "HerTask mirrors fw_her_task");
+static bool her_task_ok(const fw_her_task* t) { return t->variant == FW_LL_VARIANT_TRACKING || t->variant == FW_LL_VARIANT_SAC_DEMO; }
+int32_t fw_replay_sample_her(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
+                             float* out, int32_t* idx_out, const uint8_t* ends, int32_t obs_dim, int32_t N, int32_t horizon, float relabel_prob,
+                             const fw_her_task* task, int32_t* j_out, void* hip_stream) {
+  if (!ring || !counters || !out || !ends || !task) { g_err = "fw_replay_sample_her: ring, counters, out, ends and task must be non-NULL"; return FW_EINVAL; }
+  if (capacity <= 0 || capacity > 0x7fffffffLL || row_floats <= 0 || batch <= 0 || obs_dim <= 0) { g_err = "fw_replay_sample_her: capacity (below 2^31), row_floats, batch and obs_dim must be positive"; return FW_EINVAL; }
+  if (N <= 0 || capacity < N || capacity % N != 0) { g_err = "fw_replay_sample_her: N must be positive and capacity a positive multiple of N"; return FW_EINVAL; }
+  if (!(relabel_prob >= 0.0f && relabel_prob <= 1.0f)) { g_err = "fw_replay_sample_her: relabel_prob must lie in [0, 1]"; return FW_EINVAL; }
+  if (!her_task_ok(task)) { g_err = "fw_replay_sample_her: task variant must be 0 (tracking) or 1 (FW_LL_VARIANT_SAC_DEMO)"; return FW_EINVAL; }
+  if (obs_dim != kHerObsDim || row_floats != kHerRowFloats) { g_err = "fw_replay_sample_her: built for the low-level task with Euler attitude, obs_dim 21 and row_floats 50"; return FW_EUNSUPPORTED; }
+  if (horizon < 1 || horizon > kSacMaxHerHorizon) { g_err = "fw_replay_sample_her: built for horizon in [1, 64]"; return FW_EUNSUPPORTED; }
+  const HerTask T{task->variant, task->dome, task->min_speed};
+  const uint64_t thresh = (uint64_t)((double)relabel_prob * 4294967296.0);
+  DeviceGuard g(device_of(ring));
+  hipLaunchKernelGGL(fw_replay_sample_her_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, ring, capacity, counters,
+                     seed, batch, out, idx_out, ends, N, horizon, thresh, T, j_out);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+int32_t fw_her_reward(const float* rows, int32_t row_floats, int32_t batch, int32_t obs_dim, const float* goals, const fw_her_task* task,
+                      float* reward_out, void* hip_stream) {
+  if (!rows || !goals || !task || !reward_out) { g_err = "fw_her_reward: every pointer must be non-NULL"; return FW_EINVAL; }
+  if (row_floats <= 0 || batch <= 0 || obs_dim <= 0) { g_err = "fw_her_reward: row_floats, batch and obs_dim must be positive"; return FW_EINVAL; }
+  if (!her_task_ok(task)) { g_err = "fw_her_reward: task variant must be 0 (tracking) or 1 (FW_LL_VARIANT_SAC_DEMO)"; return FW_EINVAL; }
+  if (obs_dim != kHerObsDim || row_floats != kHerRowFloats) { g_err = "fw_her_reward: built for the low-level task with Euler attitude, obs_dim 21 and row_floats 50"; return FW_EUNSUPPORTED; }
+  const HerTask T{task->variant, task->dome, task->min_speed};
+  DeviceGuard g(device_of(rows));
+  hipLaunchKernelGGL(fw_her_reward_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, rows, row_floats, batch, obs_dim,
+                     goals, T, reward_out);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
 int32_t fw_sac_noise(uint64_t seed, const int64_t* counters, int32_t batch, int32_t act_dim, float* out, void* hip_stream) {
   if (!counters || !out) { g_err = "fw_sac_noise: counters and out must be non-NULL"; return FW_EINVAL; }
   if (batch <= 0 || act_dim <= 0) { g_err = "fw_sac_noise: batch and act_dim must be positive"; return FW_EINVAL; }

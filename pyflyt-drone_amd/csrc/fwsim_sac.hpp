@@ -818,4 +818,102 @@ __global__ __launch_bounds__(256) void fw_replay_sample_nstep_kernel(const float
   }
 }
 
+// ---- hindsight goal relabelling from the ring ----
+// The low-level task is goal-conditioned: the episode's target (psi_ref, h_ref, V_ref) is obs[18:21], and the reward is a closed function
+// of the post-step observation and that target.  SB3's HerReplayBuffer ("future" strategy) gives some sampled transitions a goal the
+// same episode achieved at or after them and recomputes the reward.  The rows of an episode are N apart and `ends` marks where it stopped,
+// so this is the n-step walk again -- without the reward loads -- and one more row read.
+constexpr int kSacMaxHerHorizon = 64, kHerObsDim = 21, kHerRowFloats = 50;
+constexpr uint32_t kSacTagHer = 0x5AC0E000u;
+struct HerTask { int32_t variant; float dome, min_speed; };          // mirrors fw_her_task (include/fwsim.h)
+// the goal a post-step observation achieved: (psi, z, |v|), the norm in double from the fp32 components, rounded to fp32
+__device__ __forceinline__ float her_speed(const float* no) {
+  const double vx = no[6], vy = no[7], vz = no[8];
+  return (float)::sqrt(vx * vx + vy * vy + vz * vz);
+}
+// The task's reward (fwsim_lowlevel.hpp, the block behind "observation, reward, termination" of fw_step_kernel_ll) restated on a stored
+// row: `no` is next_obs[0:18], g the goal, done the row's `terminated`.  In double, rounded once.  The airspeed it reads is the achieved
+// goal's, her_speed(): a goal the transition itself achieved then has tracking errors of exactly 0.
+__device__ __forceinline__ float her_reward(const HerTask& t, const float* no, const float g[3], bool done) {
+  const double roll = no[3], pitch = no[4], psi = no[5], z = no[11], speed = (double)her_speed(no);
+  const double psi_err = ::fabs(ll_wrap_pi<double>((double)g[0] - psi)), h_err = ::fabs((double)g[1] - z), v_err = ::fabs((double)g[2] - speed);
+  double rew;
+  if (t.variant == FW_LL_VARIANT_SAC_DEMO) {
+    const double x = no[9], y = no[10], rho = ::sqrt(x * x + y * y);
+    double aa = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) aa += (double)no[12 + k] * (double)no[12 + k];
+    rew = -(1.5 * psi_err + 1.2 * h_err + 0.8 * v_err);
+    rew -= 0.3 * ::fmax(::fabs(roll) - 35.0 * kPi / 180.0, 0.0);
+    rew -= 0.3 * ::fmax(::fabs(pitch) - 20.0 * kPi / 180.0, 0.0);
+    rew -= 0.05 * ::sqrt(aa);
+    rew -= ::fmax(rho - (double)t.dome, 0.0);
+    if (speed < (double)t.min_speed) rew -= 2.0;
+  } else {
+    rew = -(psi_err + h_err + 0.5 * v_err);
+    rew += 0.1;
+    if (done) rew -= 100.0;
+  }
+  return (float)rew;
+}
+// fw_her_reward: her_reward() on caller-given goals, one thread per row (the tests hold the restatement to the env with it)
+__global__ __launch_bounds__(256) void fw_her_reward_kernel(const float* __restrict__ rows, int R, int B, int d, const float* __restrict__ goals,
+                                                            HerTask task, float* __restrict__ out) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const float* row = rows + (size_t)b * R;
+  const float g[3] = { goals[(size_t)b * 3], goals[(size_t)b * 3 + 1], goals[(size_t)b * 3 + 2] };
+  out[b] = her_reward(task, row + (R - d - 1), g, row[R - 1] != 0.0f);
+}
+// One wave per batch row, the start index drawn exactly as fw_replay_sample_kernel draws it; a second Philox block under kSacTagHer
+// decides whether the row is relabelled (o[0] against `thresh` = relabel_prob 2^32, formed on the host) and which of the k candidate
+// rows gives the goal (__umulhi(o[1], k)).  A row that is not relabelled is the 1-step gather.  Otherwise lane j < horizon looks at
+// row_j = (i + j N) mod capacity: its ends byte and whether it lies in the newest vec-step -- independent loads, one round trip whatever
+// the horizon -- and the first lane that has to stop gives k from a ballot (the compiler builtin: see the n-step section).  The goal
+// row's index follows from j* by arithmetic, so no lane read is needed.  Every lane forms the goal and the reward (uniform addresses),
+// and the copy replaces seven columns of row_0 (two goals and the reward).  d = 21 and R = 50 (the entry point insists): one column per lane.
+__global__ __launch_bounds__(256) void fw_replay_sample_her_kernel(const float* __restrict__ ring, int64_t capacity, const int64_t* __restrict__ ctr,
+                                                                   uint64_t seed, int B, float* __restrict__ batch, int32_t* __restrict__ idx_out,
+                                                                   const uint8_t* __restrict__ ends, int N, int horizon, uint64_t thresh,
+                                                                   HerTask task, int32_t* __restrict__ j_out) {
+  constexpr int R = kHerRowFloats, d = kHerObsDim, rcol = R - d - 2, nobs = rcol + 1;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (b >= B) return;
+  int64_t size = ctr[1];
+  size = size < 1 ? 1 : (size > capacity ? capacity : size);
+  const uint64_t gs = (uint64_t)ctr[3];
+  uint32_t o[4], h[4];
+  philox4x32_10((uint32_t)b, 0u, (uint32_t)gs, (uint32_t)(gs >> 32) ^ kSacTagSample, (uint32_t)seed, (uint32_t)(seed >> 32), o);
+  philox4x32_10((uint32_t)b, 0u, (uint32_t)gs, (uint32_t)(gs >> 32) ^ kSacTagHer, (uint32_t)seed, (uint32_t)(seed >> 32), h);
+  const uint32_t idx = __umulhi(o[0], (uint32_t)size);
+  const float* row0 = ring + (size_t)idx * R;
+  float v = lane < R ? row0[lane] : 0.0f;
+  int jstar = -1;
+  if ((uint64_t)h[0] < thresh) {                    // (the same in every lane of the wave)
+    int64_t cursor = ctr[0];
+    if (cursor < 0 || cursor + N > capacity) cursor = 0;
+    const uint32_t cap = (uint32_t)capacity, newest = (uint32_t)(cursor == 0 ? capacity - N : cursor - N);
+    bool stop = false;
+    if (lane < horizon) {
+      const uint32_t row = (uint32_t)(((uint64_t)idx + (uint64_t)lane * (uint32_t)N) % cap);
+      stop = lane + 1 == horizon || ends[row] != 0 || row - row % (uint32_t)N == newest;
+    }
+    const int k = __builtin_ctzll(__builtin_amdgcn_ballot_w64(stop)) + 1;          // lane horizon - 1 always stops: 1 <= k <= horizon
+    jstar = (int)__umulhi(h[1], (uint32_t)k);                                      // in [0, k - 1]
+    const uint32_t fut = (uint32_t)(((uint64_t)idx + (uint64_t)jstar * (uint32_t)N) % cap);
+    const float* fno = ring + (size_t)fut * R + nobs;
+    const float g[3] = { fno[5], fno[11], her_speed(fno) };
+    const float rew = her_reward(task, row0 + nobs, g, row0[R - 1] != 0.0f);
+    if (lane == rcol) v = rew;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)                     // obs[18:21] and next_obs[18:21]
+      if (lane == d - 3 + c || lane == nobs + d - 3 + c) v = g[c];
+  }
+  if (lane < R) batch[(size_t)b * R + lane] = v;
+  if (lane == 0) {
+    if (idx_out) idx_out[b] = (int32_t)idx;
+    if (j_out) j_out[b] = jstar;
+  }
+}
+
 }  // namespace fwsim

@@ -10,6 +10,8 @@ Everything between two env steps runs on the device (csrc/fwsim_sac.hpp, include
 * ``fw_replay_sample`` draws a batch from the ring by a counter-based generator;
 * ``fw_replay_mark_ends`` / ``fw_replay_sample_nstep``  (``SACConfig.n_steps > 1`` only) one flag byte per row for the episode ends,
                        and the same draw gathered as an n-step transition (:func:`nstep_rows_reference` restates its contract);
+* ``fw_replay_sample_her``  (``SACConfig.her_goals > 0`` only) the same draw with hindsight goals: some rows get a goal their episode
+                       achieved at or after them and the reward that goal earns (:func:`her_rows_reference` restates its contract);
 * ``fw_sac_noise``     the two noise blocks of a gradient step;
 * ``fw_sac_update``    one gradient step of SB3's ``SAC.train()`` on a flat image of all five networks and their Adam moments.
 
@@ -39,6 +41,8 @@ MAX_OBS_DIM, MAX_ACT_DIM, HIDDEN_WIDTHS, MAX_BATCH = 64, 8, (64, 256), 512
 MAX_BATCH_WIDE, WIDE_BATCH_MULTIPLE = 8192, 64                  # above MAX_BATCH: the wide form of the gradient step
 MAX_N_STEPS = 16                                                # fw_replay_sample_nstep
 END_TERMINATED, END_TRUNCATED = 1, 2                            # bits of the `ends` side ring
+MAX_HER_HORIZON, HER_OBS_DIM, HER_ROW_FLOATS = 64, 21, 50       # fw_replay_sample_her: the low-level task with Euler attitude
+HER_TAG = 0x5AC0E000                                            # the Philox tag of its second draw (kSacTagHer)
 CTR_CURSOR, CTR_SIZE, CTR_STEPS, CTR_GRAD = 0, 1, 2, 3          # the device counters (int64[4])
 
 
@@ -71,11 +75,22 @@ class SACConfig:
     stats_window_size: int = 100         #     SB3's stats_window_size: episodes in the window
     episode_fold: str = "one"            #     the fold's device form: "one", "wide" or "auto" (monitor.EpisodeMonitor)
     n_steps: int = 1                     # n-step returns from the ring (1 ... 16); 1: the 1-step target, nothing changes
+    her_goals: int = 0                   # hindsight goal relabelling, SB3's n_sampled_goal: a sampled row is relabelled with probability
+                                         # her_goals / (her_goals + 1); 0: off, nothing changes.  Not built together with n_steps > 1
+    her_horizon: int = 64                #     the relabelled goal comes from at most her_horizon - 1 steps ahead (1 ... 64)
 
     def __post_init__(self):
+        if isinstance(self.her_goals, bool) or int(self.her_goals) != self.her_goals or int(self.her_goals) < 0:
+            raise ValueError(f"her_goals must be a non-negative integer, got {self.her_goals!r}")
+        if (isinstance(self.her_horizon, bool) or int(self.her_horizon) != self.her_horizon
+                or not 1 <= int(self.her_horizon) <= MAX_HER_HORIZON):
+            raise ValueError(f"her_horizon must be an integer in [1, {MAX_HER_HORIZON}], got {self.her_horizon!r}")
+        self.her_goals, self.her_horizon = int(self.her_goals), int(self.her_horizon)
         if isinstance(self.n_steps, bool) or int(self.n_steps) != self.n_steps or not 1 <= int(self.n_steps) <= MAX_N_STEPS:
             raise ValueError(f"n_steps must be an integer in [1, {MAX_N_STEPS}], got {self.n_steps!r}")
         self.n_steps = int(self.n_steps)
+        if self.her_goals > 0 and self.n_steps > 1:
+            raise ValueError("her_goals > 0 together with n_steps > 1 is not built: the relabelled gather forms 1-step transitions only")
         if self.episode_fold not in ("one", "wide", "auto"):
             raise ValueError(f"episode_fold must be 'one', 'wide' or 'auto', got {self.episode_fold!r}")
         if int(self.stats_window_size) <= 0:
@@ -101,6 +116,11 @@ class SACConfig:
     @property
     def auto_ent(self) -> bool:
         return self.ent_coef == "auto"
+
+    @property
+    def her_relabel_prob(self) -> float:
+        """SB3's ``her_ratio``: ``1 - 1 / (n_sampled_goal + 1)``."""
+        return self.her_goals / (self.her_goals + 1.0)
 
     def resolved_gradient_steps(self, num_envs: int) -> int:
         return int(num_envs) if self.gradient_steps == -1 else int(self.gradient_steps)
@@ -175,6 +195,112 @@ def nstep_rows_reference(ring, ends, cursor, size, N, idx, n_steps, gamma, obs_d
         rows[b, R - 1] = np.float32(one - np.float32(np.float32(one - ring[row, R - 1]) * g))
         ks[b] = j + 1
     return rows, ks
+
+
+class HerTask(C.Structure):
+    """``fw_her_task``: which of the low-level task's two rewards a relabelled row earns, and the two env settings the second reads."""
+    _fields_ = [("variant", C.c_int32), ("dome", C.c_float), ("min_speed", C.c_float)]
+
+
+def her_task_of(cfg) -> HerTask:
+    """The ``fw_her_task`` of an env's ``fw_config``.  ``ValueError`` unless it is the low-level task with Euler attitude (21
+    observations, the goal in columns 18:21)."""
+    from . import config as K
+    if cfg is None or cfg.task != K.FW_TASK_LOWLEVEL or int(cfg.angle_representation) != 0 or K.obs_dim(cfg) != HER_OBS_DIM:
+        raise ValueError("hindsight relabelling (her_goals > 0) needs the low-level task (FW_TASK_LOWLEVEL) with Euler attitude: "
+                         f"{HER_OBS_DIM} observations, the goal in columns 18:21")
+    return HerTask(int(cfg.lowlevel_variant), float(cfg.flight_dome_size), float(cfg.lowlevel_min_speed))
+
+
+def her_achieved_goal(next_obs):
+    """The goal ``(psi, z, |v|)`` a post-step observation achieved, float32 ``[..., 3]``: the norm in float64 from the float32
+    components, rounded to float32."""
+    import numpy as np
+    no = np.asarray(next_obs, dtype=np.float32)
+    v = no[..., 6:9].astype(np.float64)
+    speed = np.sqrt(v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1] + v[..., 2] * v[..., 2])
+    return np.stack([no[..., 5], no[..., 11], speed.astype(np.float32)], axis=-1)
+
+
+def her_reward_reference(next_obs, goal, done, task):
+    """The low-level task's reward for (post-step observation, goal, ``terminated``) in float64, not rounded: what ``fw_her_reward`` and
+    ``fw_replay_sample_her`` round once to float32.  ``next_obs`` ``[..., >= 18]`` and ``goal`` ``[..., 3]`` float32 values.  The
+    airspeed it reads is the achieved goal's (:func:`her_achieved_goal`, rounded to float32), so a goal the observation itself achieved
+    has tracking errors of exactly 0.  Variant 0 (fixedwing_lowlevel_env.py): ``-(|wrap(psi_ref - psi)| + |h_ref - z| + 0.5 |V_ref - V|)
+    + 0.1``, and 100 less where done.  Variant 1 (the SAC script's env): ``-(1.5, 1.2, 0.8) . errors``, 0.3 per radian of roll beyond
+    35 deg and of pitch beyond 20 deg, 0.05 |next_obs[12:18]|, the distance beyond the dome, and 2 below ``min_speed``."""
+    import numpy as np
+    no = np.asarray(next_obs, dtype=np.float32).astype(np.float64)
+    g = np.asarray(goal, dtype=np.float32).astype(np.float64)
+    done = np.asarray(done) != 0
+    roll, pitch, psi, z = no[..., 3], no[..., 4], no[..., 5], no[..., 11]
+    speed = her_achieved_goal(next_obs)[..., 2].astype(np.float64)
+    psi_err = np.abs((g[..., 0] - psi + np.pi) % (2.0 * np.pi) - np.pi)
+    h_err, v_err = np.abs(g[..., 1] - z), np.abs(g[..., 2] - speed)
+    if int(task.variant) == 1:
+        rho = np.sqrt(no[..., 9] * no[..., 9] + no[..., 10] * no[..., 10])
+        aa = np.zeros_like(psi)
+        for k in range(12, 18):
+            aa = aa + no[..., k] * no[..., k]
+        rew = -(1.5 * psi_err + 1.2 * h_err + 0.8 * v_err)
+        rew = rew - 0.3 * np.maximum(np.abs(roll) - 35.0 * np.pi / 180.0, 0.0)
+        rew = rew - 0.3 * np.maximum(np.abs(pitch) - 20.0 * np.pi / 180.0, 0.0)
+        rew = rew - 0.05 * np.sqrt(aa)
+        rew = rew - np.maximum(rho - float(np.float32(task.dome)), 0.0)
+        return np.where(speed < float(np.float32(task.min_speed)), rew - 2.0, rew)
+    if int(task.variant) != 0:
+        raise ValueError("task.variant must be 0 or 1")
+    rew = -(psi_err + h_err + 0.5 * v_err) + 0.1
+    return np.where(done, rew - 100.0, rew)
+
+
+def her_rows_reference(ring, ends, cursor, size, N, idx, relabel, j_star_draw, horizon, task):
+    """``fw_replay_sample_her`` in plain numpy on CPU arrays: ``(rows [B, 50] float32, j [B] int32)`` of the start rows ``idx``.
+
+    ``ring`` ``[capacity, 50]`` float32 (21 observations, 6 actions), ``ends`` ``[capacity]`` uint8, ``cursor`` / ``size`` the first two
+    device counters, ``N`` the env count.  ``relabel`` ``[B]`` says which rows are relabelled and ``j_star_draw`` ``[B]`` is the uint32
+    word that picks the future row: the kernel takes both from its second Philox block (``o[0] < relabel_prob 2^32``, ``o[1]``; counter
+    words ``(b, 0, gs, gs >> 32 ^ HER_TAG)``).  A row that is not relabelled is the ring row and its ``j`` is -1.  Otherwise walk ``row_j =
+    (i + j N) mod capacity`` by :func:`nstep_rows_reference`'s rule with ``horizon`` in the place of ``n_steps``; with k rows used,
+    ``j* = (j_star_draw k) >> 32``, the goal ``g'`` is :func:`her_achieved_goal` of ``row_j*``'s next_obs, it replaces columns 18:21 of
+    obs and of next_obs, and the reward column is :func:`her_reward_reference` of (row_0's next_obs, ``g'``, row_0's done) rounded to
+    float32.  Everything else is row_0."""
+    import numpy as np
+    ring, ends = np.asarray(ring, dtype=np.float32), np.asarray(ends, dtype=np.uint8)
+    capacity, R = ring.shape
+    N, horizon, d = int(N), int(horizon), HER_OBS_DIM
+    if not 1 <= horizon <= MAX_HER_HORIZON:
+        raise ValueError(f"horizon must be in [1, {MAX_HER_HORIZON}]")
+    if N <= 0 or capacity % N or ends.shape != (capacity,) or R != HER_ROW_FLOATS:
+        raise ValueError(f"capacity must be a multiple of N, ends one byte per row and a row {HER_ROW_FLOATS} floats")
+    idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+    relabel, draw = np.asarray(relabel).reshape(-1) != 0, np.asarray(j_star_draw).reshape(-1)
+    if relabel.shape != idx.shape or draw.shape != idx.shape:
+        raise ValueError("relabel and j_star_draw must have one entry per row of idx")
+    if idx.size and (idx.min() < 0 or idx.max() >= max(int(size), 1)):
+        raise ValueError("idx must lie in [0, size)")
+    cursor = int(cursor)
+    if cursor < 0 or cursor + N > capacity:
+        cursor = 0
+    newest = (cursor - N + capacity) % capacity
+    rcol, nobs = R - d - 2, R - d - 1
+    rows, js = ring[idx].copy(), np.full(idx.size, -1, dtype=np.int32)
+    for b, i in enumerate(idx):
+        if not relabel[b]:
+            continue
+        k = 0
+        while True:
+            row = (int(i) + k * N) % capacity
+            k += 1
+            if k == horizon or ends[row] != 0 or row - row % N == newest:
+                break
+        j = (int(draw[b]) * k) >> 32
+        goal = her_achieved_goal(ring[(int(i) + j * N) % capacity, nobs:nobs + d])
+        rows[b, d - 3:d] = goal
+        rows[b, nobs + d - 3:nobs + d] = goal
+        rows[b, rcol] = np.float32(her_reward_reference(ring[i, nobs:nobs + d], goal, ring[i, R - 1], task))
+        js[b] = j
+    return rows, js
 
 
 # ---------------------------------------------------------------------------------------------
@@ -419,18 +545,28 @@ class FusedSacUpdate:
 class ReplayBufferDevice:
     """Flat fp32 ring ``[capacity, 2d + A + 2]`` and the device counters (cursor, rows filled, vec-steps stored, gradient steps):
     the host reads none of them on the training path.  ``n_steps > 1`` adds the episode-end side ring ``ends`` (uint8 per row:
-    ``END_TERMINATED`` | ``END_TRUNCATED``), marked in front of every store, and ``sample`` gathers n-step transitions."""
+    ``END_TERMINATED`` | ``END_TRUNCATED``), marked in front of every store, and ``sample`` gathers n-step transitions.
+    ``her_goals > 0`` (with ``her_task``, :func:`her_task_of`) owns the same side ring and ``sample`` relabels goals in hindsight."""
 
-    def __init__(self, buffer_size: int, num_envs: int, obs_dim: int, act_dim: int, device, n_steps: int = 1):
+    def __init__(self, buffer_size: int, num_envs: int, obs_dim: int, act_dim: int, device, n_steps: int = 1, her_goals: int = 0,
+                 her_horizon: int = MAX_HER_HORIZON, her_task: Optional[HerTask] = None):
         if not 1 <= int(n_steps) <= MAX_N_STEPS:
             raise ValueError(f"n_steps must be in [1, {MAX_N_STEPS}], got {n_steps}")
         self.n_steps = int(n_steps)
+        self.her_goals, self.her_horizon, self.her_task = int(her_goals), int(her_horizon), her_task
+        if self.her_goals < 0 or not 1 <= self.her_horizon <= MAX_HER_HORIZON:
+            raise ValueError(f"her_goals must be non-negative and her_horizon in [1, {MAX_HER_HORIZON}], got {her_goals} and {her_horizon}")
+        if self.her_goals > 0 and (self.n_steps > 1 or her_task is None or int(obs_dim) != HER_OBS_DIM
+                                   or row_floats(obs_dim, act_dim) != HER_ROW_FLOATS):
+            raise ValueError("her_goals > 0 needs her_task, n_steps 1 and the low-level task's rows "
+                             f"({HER_OBS_DIM} observations, {HER_ROW_FLOATS} floats)")
+        self.her_prob = self.her_goals / (self.her_goals + 1.0)
         self.num_envs, self.obs_dim, self.act_dim = int(num_envs), int(obs_dim), int(act_dim)
         self.capacity = ring_capacity(buffer_size, num_envs)
         self.row = row_floats(obs_dim, act_dim)
         self.ring = torch.zeros((self.capacity, self.row), dtype=torch.float32, device=device)
         self.counters = torch.zeros(4, dtype=torch.int64, device=device)
-        self.ends = torch.zeros(self.capacity, dtype=torch.uint8, device=device) if self.n_steps > 1 else None
+        self.ends = torch.zeros(self.capacity, dtype=torch.uint8, device=device) if self.n_steps > 1 or self.her_goals > 0 else None
 
     def store(self, obs_stage, act_f32, reward, next_obs, terminal_obs, terminated, truncated) -> None:
         if self.ends is not None:        # the rows this store is about to write: the mark reads the cursor the store advances
@@ -442,9 +578,16 @@ class ReplayBufferDevice:
                                               _stream(self.ring.device)))
 
     def sample(self, seed: int, out: torch.Tensor, idx_out: Optional[torch.Tensor] = None, gamma: Optional[float] = None,
-               k_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               k_out: Optional[torch.Tensor] = None, j_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """A batch into ``out``.  With ``n_steps > 1``: n-step transitions, which need ``gamma`` (``k_out`` [B] int32 receives the
-        rows each one spans)."""
+        rows each one spans).  With ``her_goals > 0``: 1-step transitions, relabelled with probability ``her_prob`` (``j_out`` [B] int32
+        receives -1, or how many steps ahead the goal was achieved)."""
+        if self.her_goals > 0:
+            _lib.check(_lib.lib().fw_replay_sample_her(_p(self.ring), self.capacity, _p(self.counters), int(seed) & (2**64 - 1), self.row,
+                                                       out.shape[0], _p(out), _p(idx_out), _p(self.ends), self.obs_dim, self.num_envs,
+                                                       self.her_horizon, float(self.her_prob), C.byref(self.her_task), _p(j_out),
+                                                       _stream(self.ring.device)))
+            return out
         if self.ends is not None:
             if gamma is None:
                 raise ValueError("an n-step sample needs gamma")
@@ -476,8 +619,8 @@ class ReplayBufferDevice:
         if int(sd["capacity"]) != self.capacity:
             raise ValueError(f"the checkpoint's ring has {sd['capacity']} rows, this one {self.capacity}")
         if self.ends is not None and "ring" in sd and "ends" not in sd:
-            raise ValueError("the checkpoint carries the ring's rows but not their episode ends (it was written with n_steps 1): "
-                             "n-step returns cannot be formed from them")
+            raise ValueError("the checkpoint carries the ring's rows but not their episode ends (it was written with n_steps 1 and "
+                             "without her_goals): neither n-step returns nor hindsight goals can be formed from them")
         self.counters.copy_(sd["counters"])
         if "ring" in sd:
             self.ring.copy_(sd["ring"])
@@ -526,7 +669,9 @@ class SAC:
                              f"({MAX_BATCH}, {MAX_BATCH_WIDE}]; got ({self.d}, {self.A}, {cfg.hidden}, {cfg.batch_size})")
         if cfg.buffer_size < self.N:
             raise ValueError(f"buffer_size {cfg.buffer_size} cannot hold one vec-step of {self.N} envs")
-        self.buffer = ReplayBufferDevice(cfg.buffer_size, self.N, self.d, self.A, self.device, n_steps=cfg.n_steps)
+        her_task = her_task_of(getattr(env, "cfg", None)) if cfg.her_goals > 0 else None      # (ValueError unless it is the low-level task)
+        self.buffer = ReplayBufferDevice(cfg.buffer_size, self.N, self.d, self.A, self.device, n_steps=cfg.n_steps, her_goals=cfg.her_goals,
+                                         her_horizon=cfg.her_horizon, her_task=her_task)
         self.fused = FusedSacUpdate(self._policy, self.optimizers, cfg)
         kw = dict(dtype=torch.float32, device=self.device)
         self.obs_stage, self.act_f32 = torch.zeros((self.N, self.d), **kw), torch.zeros((self.N, self.A), **kw)

@@ -1,13 +1,15 @@
 """SAC on one MI355X, one JSON line per measurement (profiles/rNN_sac_bench.jsonl):
 
   * act / store / sample microseconds at 16 and 4096 envs, and the 1-step sample against the n-step sample (n_steps 3 and 8, B 256
-    and 4096, with the ratio to the 1-step sample of the same job) and the mark + store of an n-step buffer;
+    and 4096, with the ratio to the 1-step sample of the same job) and the mark + store of an n-step buffer; the hindsight-relabelling
+    sample (her_goals 4, horizon 8 and 64) against the same 1-step sample;
   * one gradient step at (d 21, A 6, B 256) and H 256 / 64: fw_sac_update (as launched, and replayed from a captured graph), the torch
     step eager and the torch step replayed from a captured graph (capturable Adam) -- the baseline is this project's own torch path;
   * the same four at H 256 for every batch size of --batches (default 256 ... 8192: up to 512 rows the 24-launch form, above it the
     wide form), with microseconds per step and per sample;
   * end-to-end env-steps/s of sac.SAC at 16 envs with gradient_steps 1 and -1, and at 4096 envs with one 4096-row gradient step per
-    vec-step on both env variants (the large-env recipe of examples/train_lowlevel_sac.py), the tracking variant with n_steps 3 too.
+    vec-step on both env variants (the large-env recipe of examples/train_lowlevel_sac.py), the tracking variant with n_steps 3 and
+    with her_goals 4 too.
 
 Timing: device events around `iters` back-to-back calls after `warmup` calls, median of `repeats` such blocks.  --runs N repeats the
 chosen sections N times (a "run" field tells them apart): the spread between runs is the run-to-run noise of a figure.
@@ -132,6 +134,13 @@ def bench_nstep_sample(sac, n, it):
             buf.ends[::50] = 1
             t = timed_us(lambda: buf.sample(0, out, idx, gamma=0.99), *it)
             emit(what="sample", envs=n, batch=B, n_steps=k, **t, ratio_to_one_step=round(t["us"] / base["us"], 3))
+        for h in (8, 64):            # the relabelling gather: 4 of 5 rows walk up to h rows, read one more row and recompute the reward
+            buf = S.ReplayBufferDevice(one.capacity, n, one.obs_dim, one.act_dim, "cuda", her_goals=4, her_horizon=h,
+                                       her_task=S.her_task_of(sac.env.cfg))
+            buf.ring, buf.counters = one.ring, one.counters
+            buf.ends[::50] = 1
+            t = timed_us(lambda: buf.sample(0, out, idx), *it)
+            emit(what="sample", envs=n, batch=B, her_goals=4, her_horizon=h, **t, ratio_to_one_step=round(t["us"] / base["us"], 3))
     e = sac.env
     buf = S.ReplayBufferDevice(one.capacity, n, one.obs_dim, one.act_dim, "cuda", n_steps=3)
     t = timed_us(lambda: buf.store(sac.obs_stage, sac.act_f32, e.rewards, e.obs, e.terminal_obs, e.terminated, e.truncated), *it)
@@ -151,17 +160,17 @@ def bench_end_to_end(gradient_steps, fused, graphs, vec_steps):
     env.close()
 
 
-def bench_end_to_end_large(variant, envs, batch, vec_steps, n_steps=1):
+def bench_end_to_end_large(variant, envs, batch, vec_steps, n_steps=1, her_goals=0):
     """The large-env recipe: one `batch`-row gradient step per vec-step of `envs` envs, fused, one captured graph per vec-step."""
     make = P.FixedwingLowLevelDemoVecEnv if variant == "demo" else P.FixedwingLowLevelVecEnv
     env = make(num_envs=envs, seed=0)
-    sac = S.SAC(env, S.SACConfig(seed=0, batch_size=batch, gradient_steps=1, learning_starts=envs, n_steps=n_steps))
+    sac = S.SAC(env, S.SACConfig(seed=0, batch_size=batch, gradient_steps=1, learning_starts=envs, n_steps=n_steps, her_goals=her_goals))
     sac.learn(envs * 8)                      # the warm-up step, the first trained steps, the captures
     torch.cuda.synchronize()
     t0, n0 = time.perf_counter(), sac.num_timesteps
     sac.learn(envs * vec_steps)
     dt = time.perf_counter() - t0
-    emit(what="end_to_end", env=variant, envs=envs, batch=batch, n_steps=n_steps, gradient_steps=sac.G, fused_update=True, use_graphs=True, vec_steps=vec_steps,
+    emit(what="end_to_end", env=variant, envs=envs, batch=batch, n_steps=n_steps, **({"her_goals": her_goals} if her_goals else {}), gradient_steps=sac.G, fused_update=True, use_graphs=True, vec_steps=vec_steps,
          env_steps_per_s=round((sac.num_timesteps - n0) / dt, 1), us_per_vec_step=round(dt * 1e6 / vec_steps, 1))
     env.close()
 
@@ -208,6 +217,8 @@ def main():
             for variant in ("tracking", "demo"):
                 bench_end_to_end_large(variant, 4096, 4096, max(vs // 2, 20))
             bench_end_to_end_large("tracking", 4096, 4096, max(vs // 2, 20), n_steps=3)
+            if hasattr(S._lib.lib(), "fw_replay_sample_her"):      # (an A/B library of an older commit predates it)
+                bench_end_to_end_large("tracking", 4096, 4096, max(vs // 2, 20), her_goals=4)
 
 
 if __name__ == "__main__":
