@@ -401,6 +401,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
       if (FW_SH(has_noise) && FW_SH(step_ratio) <= G && !(a_flags & (FL_TERM | FL_TRUNC)))
         rng_normal2<T>(P, (uint32_t)(P.env_offset + envc), (uint32_t)a_episode, (uint32_t)(a_tick / FW_SH(ticks_per_aviary)) + (uint32_t)sub, a_z0, a_z1);
       aux_nz[2 * lane] = a_z0; aux_nz[2 * lane + 1] = a_z1;
+      FWP(const long long o_tb1 = FWP_NOW();)          // arrival at barrier 1 (the stamp behind it, o_t1, includes the wait)
       __syncthreads();                               // barrier 1 (the step wave's is in front of its sub-step loop)
       if constexpr (OBSG) {
         // ---- the scenario worker of this tile: requests of earlier launches only (the step wave writes this launch's `sreq` behind
@@ -487,12 +488,14 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
         FWP(const long long o_t5 = FWP_NOW();)
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
         // flush_obs_tile on this wave's lanes, without the rows the step wave stores itself (mode 2)
-        flush_obs_tile_rows<T>(tile, ld, obs, env0, EPW, o_n, Dobs, lane,
-                               [&](int r) { return reinterpret_cast<const int*>(obs_hand + r * kObsHandWords + 19)[1] != 2; });
+        flush_obs_tile_fixed<T, SH::obs_dim, EPW>(tile, obs, env0, o_n, lane,
+                                                  [&](int r) { return reinterpret_cast<const int*>(obs_hand + r * kObsHandWords + 19)[1]; },
+                                                  [](int mode) { return mode != 2; });
         FWP(if (D.prof && lane == 0) {               // this wave's slot: the one a worker workgroup of the two-half grid has
           long long* w = D.prof + ((size_t)(o_launch % kProfSlots) * 2 * nblk + nblk + blockIdx.x) * kProfWords;
           const long long o_t6 = FWP_NOW();
-          w[0] = o_t2 - o_t1; w[1] = o_t1 - p_t0; w[2] = o_t3 - o_t2; w[3] = o_t4 - o_t3; w[4] = o_t5 - o_t4; w[5] = o_t6 - o_t5; w[6] = o_t6 - p_t0; w[7] = p_t0; })
+          w[0] = o_t2 - o_t1; w[1] = o_t1 - p_t0; w[2] = o_t3 - o_t2; w[3] = o_t4 - o_t3; w[4] = o_t5 - o_t4; w[5] = o_t6 - o_t5; w[6] = o_t6 - p_t0; w[7] = p_t0;
+          w[8] = o_tb1 - p_t0; w[9] = o_t3 - p_t0; })   // arrival at barrier 1 and at barrier 2, from this wave's first stamp
         }
       }
       return;
@@ -652,6 +655,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
     asm("" : "+s"(k_max_steps)); asm("" : "+s"(k_auto_reset)); asm("" : "+s"(k_dome)); asm("" : "+s"(k_reach));
   }
   if constexpr (SH::kFixed) asm volatile("" : "+v"(lctr_v));       // the counter load stays in the prologue (see above)
+  FWP(const long long p_b1 = FWP_NOW(); long long p_b2 = 0;)      // arrival at barrier 1, at barrier 2 (OBSW)
   if constexpr (AUX) {                               // barrier 1: every lane of both waves, whatever its env does
     __syncthreads();
     nz0 = aux_nz[2 * lane]; nz1 = aux_nz[2 * lane + 1];
@@ -1083,7 +1087,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
       reinterpret_cast<int*>(hr + 19)[1] = resetting ? (pre ? 1 : 2) : 0;
     }
     if (sub < FW_NUM_SURFACES) hr[13 + sub] = LA.a;
-    FWP(p_r1 = FWP_NOW();)
+    FWP(p_r1 = p_b2 = FWP_NOW();)
     __syncthreads();
     FWP(p_r1 = FWP_NOW() - p_r1;)                    // the wait at barrier 2
 #pragma unroll
@@ -1340,6 +1344,7 @@ void step_body(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict__ OCp
       const long long t3 = FWP_NOW();
       w[0] = t3 - p_t0; w[1] = p_t1 - p_t0; w[2] = p_reset; w[3] = p_avi; w[4] = p_task; w[5] = t3 - p_t2; w[6] = it | (nr << 8) | (nh << 16); w[7] = p_t0; w[8] = p_r1; w[9] = p_r2; w[10] = p_r3;
       w[11] = p_capmax | ((long long)p_ncapw << 48);
+      if (OBSW) w[11] = (p_b1 - p_t0) | ((p_b2 - p_t0) << 32);      // (no camera: the word carries the two arrivals, from this wave's first stamp, 32 bits each)
       if (HELP) { w[8] = p_nhit; w[9] = n_posted; w[7] = p_r1; w[10] = p_r2; w[11] = p_r3; }
       else if (HASOBJ) { w[8] = O.p_capm[0]; w[9] = O.p_capm[1]; w[10] = O.p_capm[2]; w[7] = O.p_capm[3];
         if (getenv_ph) { w[1] = O.p_ph[0]; w[3] = O.p_ph[1]; w[4] = O.p_ph[2]; w[5] = O.p_ph[3]; w[9] = O.p_ph[4]; w[6] = O.p_ph[5]; } }     // (the reset split is unused by these kernels)

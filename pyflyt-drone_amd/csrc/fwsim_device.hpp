@@ -1292,6 +1292,33 @@ __device__ __forceinline__ void flush_obs_tile_rows(const T* tile, int ld, T* ob
     if (keep(row)) dst[e] = tile[row * ld + col];
   }
 }
+// The same flush by ONE wave for a tile whose shape is a constant (ROWS rows of D words, ld = D + 1; fw_step_kernel_g8xo): the loop above
+// compiles to a rolled loop of two dependent LDS round trips per trip (the row's `keep` word, then the tile word).  Here every trip's
+// element index, row and column are this lane's constants, and all reads are issued unconditionally (the index is clamped into the tile,
+// so a lane past the end reads the last word and stores nothing): `word(row)` is the raw LDS word that decides about a row, `keep(word)`
+// the decision.  The raw words and the tile words all pass ONE empty asm before anything is computed from them -- the compiler otherwise
+// sinks a trip's reads into the branch of its store, or compares the first words before it issues the remaining reads, one round trip
+// behind the other -- so the wave waits once; then the stores go out: the same words from the same lanes to the same addresses, in the
+// same order.
+template <typename T, int D, int ROWS, typename W, typename K>
+__device__ __forceinline__ void flush_obs_tile_fixed(const T* tile, T* obs, int blk_env0, int n, int lane, W&& word, K&& keep) {
+  constexpr int LD = D + 1, TRIPS = (ROWS * D + kWave - 1) / kWave;
+  static_assert(TRIPS == 4, "the one asm below takes the words of four trips");
+  const int total = min(ROWS, n - blk_env0) * D;
+  T* dst = obs + (size_t)blk_env0 * D;
+  T w[TRIPS]; int k[TRIPS];
+#pragma unroll
+  for (int j = 0; j < TRIPS; ++j) {
+    const int e = min(lane + j * kWave, ROWS * D - 1), row = e / D, col = e - row * D;
+    k[j] = word(row); w[j] = tile[row * LD + col];
+  }
+  asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(k[0]), "+v"(k[1]), "+v"(k[2]), "+v"(k[3]));
+#pragma unroll
+  for (int j = 0; j < TRIPS; ++j) {
+    const int e = lane + j * kWave;
+    if (e < total && keep(k[j])) dst[e] = w[j];
+  }
+}
 template <typename T>
 __device__ __forceinline__ void flush_obs_tile(const T* tile, int ld, T* obs, int blk_env0, int rows_max, int n, int D) {
   flush_obs_tile_rows<T>(tile, ld, obs, blk_env0, rows_max, n, D, (int)threadIdx.x, [](int) { return true; });

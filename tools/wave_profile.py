@@ -53,6 +53,8 @@ print(f"  loop iterations: mean {it.mean():.2f}  slowest-wave mean {(S[:, 6] & 0
 print(f"  env resets/launch {nr.sum(axis=1).mean():.1f}  of which swapped-in shadows {nh.sum(axis=1).mean():.1f}")
 print(f"  waves with a reset: {100.0 * (nr > 0).mean():.1f}%   with an in-kernel (fallback) reset: {100.0 * ((nr - nh) > 0).mean():.1f}%")
 cap = st[:, :, 11] & ((1 << 48) - 1); ncap = st[:, :, 11] >> 48
+if OBSW:                                            # (no camera: word 11 of a step wave carries its arrivals at the two barriers, below)
+    cap = np.zeros_like(cap)
 if cap.any():
     print(f"  camera: envs capturing per wave-step {ncap.mean():.2f} of {N // nblk}; cycles in captures per wave-step: mean {cap.mean():.0f}  "
           f"slowest wave {(S[:, 11] & ((1 << 48) - 1)).mean():.0f}; waves with a capture {100.0 * (ncap > 0).mean():.1f}%")
@@ -91,6 +93,19 @@ if OBSW:
     print(f"  workgroup length (first stamp to the later end): mean {wg_len.mean():.0f}  longest of a launch {wg_len.max(axis=1).mean():.0f}")
     print(f"  the observation wave ends after the step wave in {100.0 * (end_obs > end_step).mean():.1f}% of the workgroups, by {(end_obs - end_step)[end_obs > end_step].mean() if (end_obs > end_step).any() else 0:.0f} cycles; "
           f"in the workgroup {lastname} in {100.0 * (end_obs[ar, last] > end_step[ar, last]).mean():.1f}% of the launches")
+    # Which wave gates each barrier: both waves stamp immediately in front of barrier 1 and barrier 2 (from their own first stamp: word 11
+    # of the step wave, 32 bits each; words 8 and 9 of the observation wave), so the wait is not part of either side's figure.
+    if (W[:, :, 9] > 0).any():                      # (a profile build of a commit without these stamps leaves the words zero)
+        arr_step = [st[:, :, 7] + (st[:, :, 11] & 0xFFFFFFFF), st[:, :, 7] + (st[:, :, 11] >> 32)]
+        arr_obs = [W[:, :, 7] + W[:, :, 8], W[:, :, 7] + W[:, :, 9]]
+        for b, what in ((0, "step wave's prologue against the noise draw"), (1, "step wave's sub-steps and latch against the worker and the pre-loads")):
+            d = arr_step[b] - arr_obs[b]              # > 0: the step wave arrives last
+            late = d > 0
+            dl = d[ar, last]
+            print(f"  barrier {b + 1} ({what}): the step wave arrives last in {100.0 * late.mean():.1f}% of the workgroups, by {d[late].mean() if late.any() else 0:.0f} cycles; "
+                  f"the observation wave in {100.0 * (~late).mean():.1f}%, by {(-d[~late]).mean() if (~late).any() else 0:.0f}; "
+                  f"mean arrival step {(arr_step[b] - st[:, :, 7]).mean():.0f} / obs {(arr_obs[b] - W[:, :, 7]).mean():.0f} after each wave's start; "
+                  f"workgroup {lastname}: step wave last in {100.0 * (dl > 0).mean():.1f}% of the launches, step - obs mean {dl.mean():.0f}")
     K = int(os.environ.get("PROF_LAUNCHES", 8))
     print(f"  per launch (the last {K}; the workgroup {lastname}): step wave total / wait b2 / tail | obs wave worker / wait b2 / pass / flush / total | later end - workgroup's first stamp, which wave")
     order = [(steps - k) % 256 for k in range(K - 1, -1, -1)]        # slots are launch % 256 and launches count from 1: the newest K
