@@ -25,6 +25,11 @@ few gradient steps per sample each one carries reward information k steps back i
 strategy does: a sampled transition keeps its episode's target with probability 1 / (n + 1); otherwise its target becomes the heading,
 altitude and airspeed the same episode reached at most ``--her_horizon`` - 1 steps later (1 ... 64, default 64) and its reward is
 recomputed for that target (``SACConfig.her_goals``).  Both env variants; not together with ``--n_steps`` above 1.
+
+``--prioritized`` draws every batch in proportion to the rows' priorities ``(|td| + 1e-6)^per_alpha`` (Schaul et al. 2016, the
+proportional variant; ``SACConfig.prioritized``) and weights the critic loss by ``(N P(row))^-per_beta`` over its
+maximum; ``--per_beta_steps n`` anneals that exponent from ``--per_beta`` to 1 over n gradient steps.  New rows enter with the largest
+priority seen so far.  Both env variants; not together with ``--n_steps`` above 1 or ``--her_goals``.
 """
 import argparse
 import json
@@ -59,6 +64,10 @@ def main():
                     help="hindsight goal relabelling, SB3's n_sampled_goal: a sampled row is relabelled with probability n / (n + 1); 0: off")
     ap.add_argument("--her_horizon", type=int, default=64,
                     help="the relabelled goal is one the episode achieved at most this many steps ahead, minus one (1 ... 64)")
+    ap.add_argument("--prioritized", action="store_true", help="prioritized replay (proportional): batches drawn by |TD error|, the critic loss importance-weighted")
+    ap.add_argument("--per_alpha", type=float, default=0.6, help="priority exponent in [0, 1]; 0 draws uniformly over the filled rows")
+    ap.add_argument("--per_beta", type=float, default=0.4, help="importance-weight exponent in [0, 1]")
+    ap.add_argument("--per_beta_steps", type=int, default=0, help="> 0: anneal the importance-weight exponent from --per_beta to 1 over this many gradient steps")
     ap.add_argument("--fused_update", action=argparse.BooleanOptionalAction, default=True,
                     help="fw_sac_update (default) or the torch gradient step")
     ap.add_argument("--use_graphs", action=argparse.BooleanOptionalAction, default=True)
@@ -89,7 +98,8 @@ def main():
                                    target_update_interval=c["target_update_interval"], learning_starts=c["learning_starts"],
                                    net_arch=c["net_arch"], seed=c["seed"], use_graphs=a.use_graphs, fused_update=a.fused_update,
                                    episode_stats=a.episode_stats, episode_fold=a.episode_fold, n_steps=a.n_steps,
-                                   her_goals=a.her_goals, her_horizon=a.her_horizon))
+                                   her_goals=a.her_goals, her_horizon=a.her_horizon, prioritized=a.prioritized, per_alpha=a.per_alpha,
+                                   per_beta=a.per_beta, per_beta_steps=a.per_beta_steps))
     t0 = time.perf_counter()
     state = {"next_eval": a.eval_freq, "train_s": 0.0, "mark": t0}
 
@@ -119,6 +129,7 @@ def main():
     print(json.dumps({"config": {**{k: v for k, v in c.items()}, "batch_size": a.batch_size, "total_timesteps": a.total_timesteps, "eval_freq": a.eval_freq, **({"env": a.env} if demo else {}), "num_envs": a.num_envs, "gradient_steps": model.G,
                                  **({"n_steps": a.n_steps} if a.n_steps != 1 else {}),
                                  **({"her_goals": a.her_goals, "her_horizon": a.her_horizon} if a.her_goals else {}),
+                                 **({"prioritized": True, "per_alpha": a.per_alpha, "per_beta": a.per_beta, "per_beta_steps": a.per_beta_steps} if a.prioritized else {}),
                                  "fused_update": a.fused_update, "use_graphs": a.use_graphs}}), flush=True)
     evaluate_now(model)                      # the untrained actor: the line later evaluations are read against
     try:

@@ -1022,6 +1022,54 @@ int32_t fw_sac_noise(uint64_t seed, const int64_t* counters, int32_t batch, int3
  * give the same bits.  fw_sac_update_workspace_bytes grows by the partial sums for these sizes only. */
 int32_t fw_sac_update(float* image, const float* batch_rows, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch, const fw_sac_hyper* hyper,
                       int64_t* counters, float* out, void* workspace, int64_t workspace_bytes, void* hip_stream);
+/* ---- Prioritized experience replay on the ring (csrc/fwsim_per.hpp; Schaul et al. 2016, the proportional variant) ----
+ * Caller-owned device state, all float32: prio [capacity], one leaf (|td| + eps)^alpha per ring row, 0 for a row never written;
+ * sum1 / min1 [ceil(capacity / 256)], the sum and the smallest positive entry of 256 consecutive leaves; sum2 / min2
+ * [ceil(len(sum1) / 256)], the same over sum1 / min1 (a min is +inf where nothing below it is positive); per_state [4]: [0] the
+ * running max leaf (the caller initialises it, 1.0), [1] the total, [2] the smallest positive leaf, [3] spare.  capacity above 2^22
+ * rows (more than 64 level-2 entries; beyond it an fp32 sum stops resolving one leaf): FW_EUNSUPPORTED.  NULL pointers and
+ * non-positive sizes FW_EINVAL.  Nothing allocates, synchronises or reads device state on the host: all five entry points can be
+ * captured into a graph.
+ * The order of a group of 256 entries x_0 .. x_255 (missing entries are 0), in fp32: p(4l) = x_(4l), p(4l + j) = p(4l + j - 1) +
+ * x_(4l + j) for j = 1, 2, 3 (64 chains of four); E_0 = 0, E_(l+1) = E_l + p(4l + 3) (one chain of 64).  The running sum up to and
+ * including entry 4l + j is S(4l + j) = E_l + p(4l + j), the group's sum is E_64, and the running sum in front of an entry is S of
+ * the entry before it (0 in front of entry 0).  Both the rebuild and the draw use it, so two runs give the same bits.
+ *
+ * fw_replay_per_mark_new writes per_state[0] into the N leaves of the rows the NEXT fw_replay_store will write: launch it in front of
+ * that call on the same stream.  It reads counters[0] (normalised as fw_replay_mark_ends does) and writes no counter. */
+int32_t fw_replay_per_mark_new(float* prio, int64_t capacity, const int64_t* counters, const float* per_state, int32_t N, void* hip_stream);
+/* Recomputes sum1 / min1, sum2 / min2, per_state[1] (the group sum of sum2) and per_state[2] from the leaves -- always from the leaves,
+ * never incrementally, so nothing drifts.  Two launches, no in-grid wait, no atomics. */
+int32_t fw_replay_per_rebuild(const float* prio, int64_t capacity, float* sum1, float* min1, float* sum2, float* min2, float* per_state,
+                              void* hip_stream);
+/* fw_replay_sample with a proportional draw.  Row b takes fw_replay_sample's Philox block (same counter words, same tag): u = (o[0] +
+ * 0.5) 2^-32 in double, t = (float)(u (double)per_state[1]).  Descent through sum2, the chosen group of sum1, the chosen group of
+ * prio: at each level the FIRST positive entry whose running sum S exceeds t; if rounding leaves none, the LAST positive entry of the
+ * group; t becomes t - (the running sum in front of the entry).  With sums a rebuild wrote, the chosen row has a positive leaf and lies
+ * below counters[1].  (A group with no positive entry -- sums that no rebuild followed, or an empty ring -- gives its entry 0: no index
+ * leaves the ring and nothing is read out of bounds; the result is unspecified, as fw_replay_sample's on an empty ring.)  The row is
+ * gathered as fw_replay_sample gathers it; idx_out [batch] (optional) receives it; w_out [batch] (optional) receives the importance
+ * weight (per_state[2] / prio[row])^beta, which is (n P(row))^-beta divided by its maximum over the ring, as exp(beta log x) in fp32.
+ * beta = beta_steps > 0 ? min(1, beta0 + (1 - beta0) counters[3] / beta_steps) : beta0, in fp32 on the device: the annealing lives
+ * inside a captured graph.  beta0 outside [0, 1] or beta_steps < 0: FW_EINVAL.  One wave per batch row; reads counters only. */
+int32_t fw_replay_sample_per(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
+                             float* out, int32_t* idx_out, float* w_out, const float* prio, const float* sum1, const float* sum2,
+                             const float* per_state, float beta0, int64_t beta_steps, void* hip_stream);
+/* prio[idx[b]] = (|td[b]| + eps)^alpha (exp(alpha log x) in fp32) for the batch's rows; a row that occurs more than once receives the
+ * LARGEST of its leaves, and per_state[0] becomes the max of itself and the batch's leaves.  Two launches: the touched leaves are
+ * zeroed, then an integer max on the float bits goes through the vector memory path -- the result does not depend on execution order.
+ * An idx outside [0, capacity) is skipped, and so is a td that is not finite (its leaf stays 0: the row is not drawn again).  alpha
+ * outside [0, 1] or eps not positive: FW_EINVAL.  The sums are stale behind it: follow it with fw_replay_per_rebuild. */
+int32_t fw_replay_per_update(float* prio, int64_t capacity, const int32_t* idx, const float* td, int32_t batch, float alpha, float eps,
+                             float* per_state, void* hip_stream);
+/* fw_sac_update with importance weights on the critic loss: the same launch sequence with ONE launch inserted behind the target stage
+ * (25 launches up to 512 rows, 30 in the wide form).  It writes td_out[b] = (|Q1 - y| + |Q2 - y|) / 2 (optional; recovered from the
+ * target stage's dL/dQ_i as |dL/dQ_i| batch) and scales dL/dQ_1 and dL/dQ_2 of row b by weights[b] [batch]: the critics train on
+ * mean(w (Q_i - y)^2) / 2.  The actor and entropy losses are not weighted, and out[0] stays the unweighted critic loss.  With all
+ * weights 1.0 the image holds fw_sac_update's bits.  Workspace and every other argument as fw_sac_update. */
+int32_t fw_sac_update_weighted(float* image, const float* batch_rows, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch,
+                               const fw_sac_hyper* hyper, int64_t* counters, float* out, void* workspace, int64_t workspace_bytes,
+                               const float* weights, float* td_out, void* hip_stream);
 const char* fw_last_error(fw_handle h); /* h may be NULL: last create/validate error */
 int32_t fw_destroy(fw_handle h);
 

@@ -37,6 +37,7 @@ EXPORTS = (
     "fw_sac_noise", "fw_sac_update",
     "fw_replay_mark_ends", "fw_replay_sample_nstep",
     "fw_sizeof_her_task", "fw_replay_sample_her", "fw_her_reward",
+    "fw_replay_per_mark_new", "fw_replay_per_rebuild", "fw_replay_sample_per", "fw_replay_per_update", "fw_sac_update_weighted",
 )
 
 
@@ -228,6 +229,15 @@ def lib() -> C.CDLL:
             L.fw_replay_sample_her.restype = i32
             L.fw_replay_sample_her.argtypes = [vp, i64, vp, u64, i32, i32, vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp]
             L.fw_her_reward.restype = i32; L.fw_her_reward.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp]
+        if hasattr(L, "fw_replay_sample_per"):     # prioritized replay (an A/B library of an older commit predates the five; build() insists on them)
+            f32 = C.c_float
+            L.fw_replay_per_mark_new.restype = i32; L.fw_replay_per_mark_new.argtypes = [vp, i64, vp, vp, i32, vp]
+            L.fw_replay_per_rebuild.restype = i32; L.fw_replay_per_rebuild.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp]
+            L.fw_replay_sample_per.restype = i32
+            L.fw_replay_sample_per.argtypes = [vp, i64, vp, u64, i32, i32, vp, vp, vp, vp, vp, vp, vp, f32, i64, vp]
+            L.fw_replay_per_update.restype = i32; L.fw_replay_per_update.argtypes = [vp, i64, vp, vp, i32, f32, f32, vp, vp]
+            L.fw_sac_update_weighted.restype = i32
+            L.fw_sac_update_weighted.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp]
         L.fw_policy_act_a.restype = i32
         L.fw_policy_act_a.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
         L.fw_collect_act_a.restype = i32

@@ -1639,6 +1639,8 @@ void fw_reset_kernel(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict
 #include "fwsim_probe.hpp"
 // ... and the off-policy learner of the low-level task (fw_sac_act, fw_replay_store / _sample, fw_sac_noise, fw_sac_update)
 #include "fwsim_sac.hpp"
+// ... and prioritized replay on its ring (fw_replay_per_*, fw_replay_sample_per, fw_sac_update_weighted)
+#include "fwsim_per.hpp"
 
 // ======================================================================
 // host side
@@ -3631,6 +3633,85 @@ int32_t fw_sac_update(float* image, const float* batch_rows, int32_t obs_dim, in
   S.d = obs_dim; S.A = act_dim; S.H = hidden; S.B = batch;
   std::memcpy(&S.hp, hyper, sizeof(SacHyper));
   sac_update_launch((hipStream_t)hip_stream, S);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+
+// ---- prioritized replay (csrc/fwsim_per.hpp) ----
+static int32_t per_check_capacity(const char* who, int64_t capacity) {
+  if (capacity <= 0) { g_err = std::string(who) + ": capacity must be positive"; return FW_EINVAL; }
+  if (capacity > kPerMaxCapacity) { g_err = std::string(who) + ": built for a capacity of at most 2^22 rows (64 level-2 entries), got " + std::to_string((long long)capacity); return FW_EUNSUPPORTED; }
+  return FW_OK;
+}
+int32_t fw_replay_per_mark_new(float* prio, int64_t capacity, const int64_t* counters, const float* per_state, int32_t N, void* hip_stream) {
+  if (!prio || !counters || !per_state) { g_err = "fw_replay_per_mark_new: every pointer must be non-NULL"; return FW_EINVAL; }
+  if (N <= 0 || capacity < N || capacity % N != 0) { g_err = "fw_replay_per_mark_new: N must be positive and capacity a positive multiple of N"; return FW_EINVAL; }
+  const int32_t rc = per_check_capacity("fw_replay_per_mark_new", capacity);
+  if (rc != FW_OK) return rc;
+  DeviceGuard g(device_of(prio));
+  hipLaunchKernelGGL(fw_replay_per_mark_new_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, prio, capacity, counters,
+                     per_state, N);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+int32_t fw_replay_per_rebuild(const float* prio, int64_t capacity, float* sum1, float* min1, float* sum2, float* min2, float* per_state,
+                              void* hip_stream) {
+  if (!prio || !sum1 || !min1 || !sum2 || !min2 || !per_state) { g_err = "fw_replay_per_rebuild: every pointer must be non-NULL"; return FW_EINVAL; }
+  const int32_t rc = per_check_capacity("fw_replay_per_rebuild", capacity);
+  if (rc != FW_OK) return rc;
+  DeviceGuard g(device_of(prio));
+  const int n1 = per_groups(capacity);
+  hipLaunchKernelGGL(fw_replay_per_level1_kernel, dim3((unsigned)((n1 + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, prio, (int)capacity, sum1, min1);
+  hipLaunchKernelGGL(fw_replay_per_level2_kernel, dim3(1), dim3(256), 0, (hipStream_t)hip_stream, (const float*)sum1, (const float*)min1, n1, sum2, min2,
+                     per_state);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+int32_t fw_replay_sample_per(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
+                             float* out, int32_t* idx_out, float* w_out, const float* prio, const float* sum1, const float* sum2,
+                             const float* per_state, float beta0, int64_t beta_steps, void* hip_stream) {
+  if (!ring || !counters || !out || !prio || !sum1 || !sum2 || !per_state) { g_err = "fw_replay_sample_per: ring, counters, out, prio, sum1, sum2 and per_state must be non-NULL"; return FW_EINVAL; }
+  if (row_floats <= 0 || batch <= 0) { g_err = "fw_replay_sample_per: row_floats and batch must be positive"; return FW_EINVAL; }
+  if (!(beta0 >= 0.0f && beta0 <= 1.0f) || beta_steps < 0) { g_err = "fw_replay_sample_per: beta0 must lie in [0, 1] and beta_steps must not be negative"; return FW_EINVAL; }
+  const int32_t rc = per_check_capacity("fw_replay_sample_per", capacity);
+  if (rc != FW_OK) return rc;
+  DeviceGuard g(device_of(ring));
+  hipLaunchKernelGGL(fw_replay_sample_per_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, ring, (int)capacity, counters,
+                     seed, row_floats, batch, out, idx_out, w_out, prio, sum1, sum2, per_state, beta0, beta_steps);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+int32_t fw_replay_per_update(float* prio, int64_t capacity, const int32_t* idx, const float* td, int32_t batch, float alpha, float eps,
+                             float* per_state, void* hip_stream) {
+  if (!prio || !idx || !td || !per_state) { g_err = "fw_replay_per_update: every pointer must be non-NULL"; return FW_EINVAL; }
+  if (batch <= 0) { g_err = "fw_replay_per_update: batch must be positive"; return FW_EINVAL; }
+  if (!(alpha >= 0.0f && alpha <= 1.0f) || !(eps > 0.0f) || !(eps < 1e30f)) { g_err = "fw_replay_per_update: alpha must lie in [0, 1] and eps must be positive and finite"; return FW_EINVAL; }
+  const int32_t rc = per_check_capacity("fw_replay_per_update", capacity);
+  if (rc != FW_OK) return rc;
+  DeviceGuard g(device_of(prio));
+  const dim3 grid((unsigned)((batch + 255) / 256)), block(256);
+  hipLaunchKernelGGL(fw_replay_per_clear_kernel, grid, block, 0, (hipStream_t)hip_stream, prio, (int)capacity, idx, batch);
+  hipLaunchKernelGGL(fw_replay_per_max_kernel, grid, block, 0, (hipStream_t)hip_stream, prio, (int)capacity, idx, td, batch, alpha, eps, per_state);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+int32_t fw_sac_update_weighted(float* image, const float* batch_rows, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch,
+                               const fw_sac_hyper* hyper, int64_t* counters, float* out, void* workspace, int64_t workspace_bytes,
+                               const float* weights, float* td_out, void* hip_stream) {
+  if (!image || !batch_rows || !hyper || !counters || !workspace || !weights) { g_err = "fw_sac_update_weighted: image, batch_rows, hyper, counters, workspace and weights must be non-NULL"; return FW_EINVAL; }
+  int32_t rc = sac_check_shape("fw_sac_update_weighted", obs_dim, act_dim, hidden);
+  if (rc == FW_OK) rc = sac_check_batch("fw_sac_update_weighted", batch);
+  if (rc != FW_OK) return rc;
+  if (workspace_bytes < sac_ws_floats(obs_dim, act_dim, hidden, batch) * (int64_t)sizeof(float)) { g_err = "fw_sac_update_weighted: the workspace is smaller than fw_sac_update_workspace_bytes asks for"; return FW_EINVAL; }
+  DeviceGuard g(device_of(image));
+  SacStepArgs S{};
+  S.image = image; S.batch = batch_rows; S.ws = (float*)workspace; S.ctr = counters; S.out = out;
+  S.d = obs_dim; S.A = act_dim; S.H = hidden; S.B = batch;
+  std::memcpy(&S.hp, hyper, sizeof(SacHyper));
+  float* g3 = S.ws + sac_ws(obs_dim, act_dim, hidden, batch).g3;
+  sac_update_launch((hipStream_t)hip_stream, S, [&](hipStream_t st) {
+    hipLaunchKernelGGL(fw_sac_per_weight_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, g3, batch, weights, td_out);
+  });
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }

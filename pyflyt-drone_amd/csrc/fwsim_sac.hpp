@@ -651,8 +651,10 @@ inline void sac_launch_wgrad_wide(hipStream_t st, const SacStepArgs& S, const Sa
 }
 // One gradient step.  Up to kSacMaxB rows: 24 launches.  The wide form: 29 -- each of the three batch-sum stages is a grid and a fold
 // (+3), each of the two weight-gradient launches a split grid and a fold with Adam (+2); everything else is the same launch on a
-// grid that grows with B.
-inline void sac_update_launch(hipStream_t st, const SacStepArgs& S) {
+// grid that grows with B.  `after_target(st)` runs behind the target stage, in front of the critics' backward pass: fw_sac_update passes
+// nothing, fw_sac_update_weighted (csrc/fwsim_per.hpp) its one launch on g3.
+template <typename AfterTarget>
+inline void sac_update_launch(hipStream_t st, const SacStepArgs& S, AfterTarget&& after_target) {
   const int d = S.d, A = S.A, H = S.H, B = S.B, Kc = d + A, O = 2 * A, R = 2 * d + A + 2;
   const bool wide = B > kSacMaxB;
   const SacLayout L = sac_layout(d, A, H);
@@ -719,6 +721,7 @@ inline void sac_update_launch(hipStream_t st, const SacStepArgs& S) {
   };
   critic_forward(4, bt, R, ws + W.xnext);
   stage(fw_sac_target_kernel, fw_sac_stage_wide_kernel<SAC_STAGE_TARGET>, SAC_STAGE_TARGET, B);
+  after_target(st);
   // 9-11: the critics' backward pass, then all six weight gradients with Adam in one grid
   critic_backward();
   for (int k = 0; k < 2; ++k) {
@@ -746,6 +749,7 @@ inline void sac_update_launch(hipStream_t st, const SacStepArgs& S) {
   // 23: Polyak, outputs, counters
   hipLaunchKernelGGL(fw_sac_finish_kernel, dim3((2 * nc.n + 255) / 256), dim3(256), 0, st, S);
 }
+inline void sac_update_launch(hipStream_t st, const SacStepArgs& S) { sac_update_launch(st, S, [](hipStream_t) {}); }
 
 // ---- n-step returns from the ring ----
 // Env e's consecutive steps sit exactly N rows apart, so the k-step transition that starts at row i is rows i, i + N, ... (mod capacity).

@@ -12,8 +12,15 @@ Everything between two env steps runs on the device (csrc/fwsim_sac.hpp, include
                        and the same draw gathered as an n-step transition (:func:`nstep_rows_reference` restates its contract);
 * ``fw_replay_sample_her``  (``SACConfig.her_goals > 0`` only) the same draw with hindsight goals: some rows get a goal their episode
                        achieved at or after them and the reward that goal earns (:func:`her_rows_reference` restates its contract);
+* ``fw_replay_per_mark_new`` / ``fw_replay_per_rebuild`` / ``fw_replay_sample_per`` / ``fw_replay_per_update``
+                       (``SACConfig.prioritized`` only) prioritized replay, Schaul et al. 2016, proportional variant: one priority leaf
+                       per ring row under a three-level sum structure, the proportional draw with its importance weights, and the
+                       write-back of the new priorities (:func:`per_sums_reference`, :func:`per_draw_reference` and
+                       :func:`per_update_reference` restate their contracts);
 * ``fw_sac_noise``     the two noise blocks of a gradient step;
-* ``fw_sac_update``    one gradient step of SB3's ``SAC.train()`` on a flat image of all five networks and their Adam moments.
+* ``fw_sac_update``    one gradient step of SB3's ``SAC.train()`` on a flat image of all five networks and their Adam moments;
+* ``fw_sac_update_weighted``  (``SACConfig.prioritized`` only) the same step with the importance weights on the critic loss; it
+                       reports the per-row TD errors the new priorities are made of.
 
 :func:`sac_update_torch` is the same gradient step in plain torch (CPU tensors too): the reference the kernels are tested against
 and the ``fused_update=False`` path.
@@ -44,6 +51,8 @@ END_TERMINATED, END_TRUNCATED = 1, 2                            # bits of the `e
 MAX_HER_HORIZON, HER_OBS_DIM, HER_ROW_FLOATS = 64, 21, 50       # fw_replay_sample_her: the low-level task with Euler attitude
 HER_TAG = 0x5AC0E000                                            # the Philox tag of its second draw (kSacTagHer)
 CTR_CURSOR, CTR_SIZE, CTR_STEPS, CTR_GRAD = 0, 1, 2, 3          # the device counters (int64[4])
+PER_GROUP, PER_MAX_CAPACITY = 256, 1 << 22                      # prioritized replay: entries per group of a level; rows at most
+PER_MAX, PER_TOTAL, PER_MIN = 0, 1, 2                           # per_state (float32[4]): running max leaf, total, smallest positive leaf
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -78,8 +87,23 @@ class SACConfig:
     her_goals: int = 0                   # hindsight goal relabelling, SB3's n_sampled_goal: a sampled row is relabelled with probability
                                          # her_goals / (her_goals + 1); 0: off, nothing changes.  Not built together with n_steps > 1
     her_horizon: int = 64                #     the relabelled goal comes from at most her_horizon - 1 steps ahead (1 ... 64)
+    prioritized: bool = False            # prioritized replay (Schaul et al. 2016, proportional); off: nothing changes.  Not built together
+                                         # with n_steps > 1 or her_goals > 0
+    per_alpha: float = 0.6               #     a row's priority is (|td| + per_eps)^per_alpha, in [0, 1]; 0: uniform over the filled rows
+    per_beta: float = 0.4                #     exponent of the importance weights, in [0, 1]; 0: no correction
+    per_beta_steps: int = 0              #     > 0: the exponent grows linearly from per_beta to 1 over this many gradient steps
+    per_eps: float = 1e-6
 
     def __post_init__(self):
+        self.prioritized = bool(self.prioritized)
+        if not (0.0 <= float(self.per_alpha) <= 1.0 and 0.0 <= float(self.per_beta) <= 1.0):
+            raise ValueError(f"per_alpha and per_beta must lie in [0, 1], got {self.per_alpha!r} and {self.per_beta!r}")
+        if isinstance(self.per_beta_steps, bool) or int(self.per_beta_steps) != self.per_beta_steps or int(self.per_beta_steps) < 0:
+            raise ValueError(f"per_beta_steps must be a non-negative integer, got {self.per_beta_steps!r}")
+        if not (float(self.per_eps) > 0.0 and math.isfinite(float(self.per_eps))):
+            raise ValueError(f"per_eps must be positive, got {self.per_eps!r}")
+        self.per_alpha, self.per_beta, self.per_beta_steps, self.per_eps = (float(self.per_alpha), float(self.per_beta),
+                                                                            int(self.per_beta_steps), float(self.per_eps))
         if isinstance(self.her_goals, bool) or int(self.her_goals) != self.her_goals or int(self.her_goals) < 0:
             raise ValueError(f"her_goals must be a non-negative integer, got {self.her_goals!r}")
         if (isinstance(self.her_horizon, bool) or int(self.her_horizon) != self.her_horizon
@@ -91,6 +115,8 @@ class SACConfig:
         self.n_steps = int(self.n_steps)
         if self.her_goals > 0 and self.n_steps > 1:
             raise ValueError("her_goals > 0 together with n_steps > 1 is not built: the relabelled gather forms 1-step transitions only")
+        if self.prioritized and (self.n_steps > 1 or self.her_goals > 0):
+            raise ValueError("prioritized together with n_steps > 1 or her_goals > 0 is not built: those gathers draw their own indices")
         if self.episode_fold not in ("one", "wide", "auto"):
             raise ValueError(f"episode_fold must be 'one', 'wide' or 'auto', got {self.episode_fold!r}")
         if int(self.stats_window_size) <= 0:
@@ -304,6 +330,131 @@ def her_rows_reference(ring, ends, cursor, size, N, idx, relabel, j_star_draw, h
 
 
 # ---------------------------------------------------------------------------------------------
+# prioritized replay in plain numpy (the contract of csrc/fwsim_per.hpp)
+# ---------------------------------------------------------------------------------------------
+def per_group_sums(x):
+    """THE order of a group, in float32: ``x`` ``[..., 256]`` -> ``(S, F, total)``.  Entry ``4l + j`` belongs to chain ``l``:
+    ``p(4l) = x(4l)``, ``p(4l + j) = p(4l + j - 1) + x(4l + j)``; ``E_0 = 0``, ``E_(l+1) = E_l + p(4l + 3)``.  ``S(4l + j) = E_l +
+    p(4l + j)`` is the running sum up to and including the entry, ``F`` the running sum in front of it (``S`` of the entry before,
+    0 in front of entry 0) and ``total = E_64`` the group's sum."""
+    import numpy as np
+    x = np.asarray(x, dtype=np.float32)
+    assert x.shape[-1] == PER_GROUP
+    q = x.reshape(x.shape[:-1] + (PER_GROUP // 4, 4))
+    p = np.empty_like(q)
+    p[..., 0] = q[..., 0]
+    for j in range(1, 4):
+        p[..., j] = p[..., j - 1] + q[..., j]
+    E, run = np.empty(q.shape[:-1], dtype=np.float32), np.zeros(q.shape[:-2], dtype=np.float32)
+    for l in range(PER_GROUP // 4):
+        E[..., l] = run
+        run = (run + p[..., l, 3]).astype(np.float32)
+    S = (E[..., None] + p).astype(np.float32)
+    F = np.concatenate([E[..., None], S[..., :3]], axis=-1)
+    return S.reshape(x.shape), F.reshape(x.shape), run
+
+
+def _per_groups(v, pad):
+    """``v`` [n] as groups ``[ceil(n / 256), 256]``, the missing entries ``pad``."""
+    import numpy as np
+    v = np.asarray(v, dtype=np.float32).reshape(-1)
+    n = -(-v.size // PER_GROUP)
+    out = np.full(n * PER_GROUP, pad, dtype=np.float32)
+    out[:v.size] = v
+    return out.reshape(n, PER_GROUP)
+
+
+def per_sums_reference(prio):
+    """``fw_replay_per_rebuild`` in plain numpy: ``dict(sum1, min1, sum2, min2, total, pmin)`` of the leaves ``prio`` [capacity]
+    (float32, non-negative).  A sum is :func:`per_group_sums`' total of its 256 entries (missing ones 0), a min the smallest positive
+    entry below it (+inf where there is none); ``total`` is the group sum of ``sum2`` (at most 64 entries: the capacity limit) and
+    ``pmin`` the smallest positive leaf."""
+    import numpy as np
+    prio = np.asarray(prio, dtype=np.float32).reshape(-1)
+    if not 0 < prio.size <= PER_MAX_CAPACITY:
+        raise ValueError(f"capacity must lie in [1, {PER_MAX_CAPACITY}]")
+    inf = np.float32(np.inf)
+    g0 = _per_groups(prio, 0.0)
+    sum1 = per_group_sums(g0)[2]
+    min1 = np.where(g0 > 0, g0, inf).min(axis=1)
+    sum2 = per_group_sums(_per_groups(sum1, 0.0))[2]
+    min2 = _per_groups(min1, inf).min(axis=1)
+    total = per_group_sums(_per_groups(sum2, 0.0))[2][0]
+    return dict(sum1=sum1, min1=min1, sum2=sum2, min2=min2, total=np.float32(total), pmin=np.float32(min2.min()))
+
+
+def _per_pick(values, group, t):
+    """One level of the descent for a batch: in group ``group[b]`` of ``values`` the first positive entry whose running sum exceeds
+    ``t[b]``, else the last positive entry, else entry 0 with t = 0 -> (entry index inside the group, t - front)."""
+    import numpy as np
+    x = _per_groups(values, 0.0)[group]
+    S, F, _ = per_group_sums(x)
+    pos = x > 0
+    hit = pos & (S > t[:, None])
+    k = np.where(hit.any(1), hit.argmax(1), PER_GROUP - 1 - pos[:, ::-1].argmax(1))
+    none = ~pos.any(1)
+    k = np.where(none, 0, k)
+    left = (t - F[np.arange(len(t)), k]).astype(np.float32)
+    return k.astype(np.int64), np.where(none, np.float32(0.0), left).astype(np.float32)
+
+
+def per_draw_reference(prio, sums, o0, t=None):
+    """The draw of ``fw_replay_sample_per`` in plain numpy: the row index [B] (int64) of each batch row.  ``prio`` [capacity] the
+    leaves, ``sums`` what :func:`per_sums_reference` made of them, ``o0`` [B] the first word (uint32) of each row's Philox block
+    (``fw_replay_sample``'s: counter words ``(b, 0, gs, gs >> 32 ^ 0x5AC0C000)``, key the seed).  ``u = (o0 + 0.5) 2^-32`` in float64,
+    ``t = float32(u float64(total))`` (``t`` [B] float32 overrides it: the clamp rule can then be driven directly).  Three levels --
+    ``sum2``, the chosen group of ``sum1``, the chosen group of ``prio`` -- each takes the FIRST positive entry whose running sum
+    (:func:`per_group_sums`) exceeds t, or, where rounding leaves none, the LAST positive entry, and carries ``t - front`` down."""
+    import numpy as np
+    prio = np.asarray(prio, dtype=np.float32).reshape(-1)
+    if t is None:
+        u = (np.asarray(o0).astype(np.float64) + 0.5) * 2.0 ** -32
+        t = (u * np.float64(sums["total"])).astype(np.float32)
+    t = np.asarray(t, dtype=np.float32).reshape(-1).copy()
+    k2, t = _per_pick(sums["sum2"], np.zeros(len(t), dtype=np.int64), t)
+    k1, t = _per_pick(sums["sum1"], k2, t)
+    g = k2 * PER_GROUP + k1
+    k0, t = _per_pick(prio, g, t)
+    return g * PER_GROUP + k0
+
+
+def per_beta_reference(beta0, beta_steps, grad_step):
+    """The exponent ``fw_replay_sample_per`` uses at gradient step ``grad_step`` (``counters[3]``), in float32 as the device forms it."""
+    import numpy as np
+    b0 = np.float32(beta0)
+    if int(beta_steps) <= 0:
+        return b0
+    frac = np.float32(np.float32(grad_step) / np.float32(beta_steps))
+    return np.float32(min(np.float32(1.0), np.float32(b0 + np.float32(np.float32(1.0) - b0) * frac)))
+
+
+def per_weights_reference(prio, idx, pmin, beta):
+    """The importance weights ``(p_min / p_row)^beta`` of the rows ``idx`` in float64 (the kernel: ``exp(beta log x)`` in float32).
+    With ``P(row) = p_row / total`` this is ``(n P(row))^-beta`` divided by its maximum over the ring, which the row of ``p_min`` has."""
+    import numpy as np
+    p = np.asarray(prio, dtype=np.float32)[np.asarray(idx, dtype=np.int64)].astype(np.float64)
+    return (np.float64(np.float32(pmin)) / p) ** np.float64(np.float32(beta))
+
+
+def per_update_reference(prio, idx, td, alpha, eps, pmax):
+    """``fw_replay_per_update`` in plain numpy: ``(prio', pmax')``.  The leaf of batch row b is ``(|td[b]| + eps)^alpha``, the sum in
+    float32, the power in float64 rounded to float32 (the kernel: ``exp(alpha log x)`` in float32); a row that occurs more than once
+    receives the largest of its leaves, and ``pmax'`` is the max of ``pmax`` and the batch's leaves.  An index outside the ring and a
+    td that is not finite are skipped (a skipped row that is in the batch only this way keeps a leaf of 0)."""
+    import numpy as np
+    out = np.asarray(prio, dtype=np.float32).copy()
+    idx, td = np.asarray(idx, dtype=np.int64).reshape(-1), np.asarray(td, dtype=np.float32).reshape(-1)
+    x = (np.abs(td) + np.float32(eps)).astype(np.float32)
+    with np.errstate(all="ignore"):
+        leaf = (x.astype(np.float64) ** np.float64(np.float32(alpha))).astype(np.float32)
+    inside = (idx >= 0) & (idx < out.size)
+    out[idx[inside]] = 0.0
+    ok = inside & np.isfinite(leaf) & (leaf > 0)
+    np.maximum.at(out, idx[ok], leaf[ok])
+    return out, np.float32(max([np.float32(pmax)] + list(leaf[ok])))
+
+
+# ---------------------------------------------------------------------------------------------
 # the torch modules
 # ---------------------------------------------------------------------------------------------
 def _mlp(n_in: int, hidden: int, n_out: int) -> nn.Sequential:
@@ -362,10 +513,12 @@ def make_optimizers(policy: SacPolicy, cfg: SACConfig, capturable: bool = False)
             "ent": torch.optim.Adam([policy.log_ent_coef], **kw) if cfg.auto_ent else None}
 
 
-def sac_update_torch(policy: SacPolicy, optimizers, batch, eps, eps_next, cfg: SACConfig) -> Dict[str, torch.Tensor]:
+def sac_update_torch(policy: SacPolicy, optimizers, batch, eps, eps_next, cfg: SACConfig, weights=None) -> Dict[str, torch.Tensor]:
     """One gradient step of SB3's ``SAC.train()`` in the order DESIGN.md section 4c spells out (the numbers at the right).  ``batch``: ``(s, a, r, s', done)`` or
     rows ``[B, 2d + A + 2]``; ``eps`` / ``eps_next``: N(0, 1) of shape ``[B, A]``.  Returns the five scalars ``fw_sac_update``
-    reports (tensors, no host read)."""
+    reports (tensors, no host read) and ``"td"`` [B], the rows' ``(|Q1 - y| + |Q2 - y|) / 2``.  ``weights`` [B] (prioritized replay's
+    importance weights, ``fw_sac_update_weighted``): the critics train on ``mean(w (Q_i - y)^2) / 2``; the actor and entropy losses
+    are not weighted and the critic loss reported stays the unweighted one."""
     if torch.is_tensor(batch):
         batch = split_rows(batch, policy.obs_dim, policy.act_dim)
     s, a, r, s2, done = batch
@@ -383,7 +536,9 @@ def sac_update_torch(policy: SacPolicy, optimizers, batch, eps, eps_next, cfg: S
     x = torch.cat([s, a], dim=-1)
     q1, q2 = policy.q1(x).squeeze(-1), policy.q2(x).squeeze(-1)
     critic_loss = 0.5 * (((q1 - y) ** 2).mean() + ((q2 - y) ** 2).mean())                       # 7
-    optimizers["critic"].zero_grad(set_to_none=True); critic_loss.backward(); optimizers["critic"].step()
+    trained = critic_loss if weights is None else 0.5 * ((weights * (q1 - y) ** 2).mean() + (weights * (q2 - y) ** 2).mean())
+    td = 0.5 * ((q1 - y).abs() + (q2 - y).abs()).detach()
+    optimizers["critic"].zero_grad(set_to_none=True); trained.backward(); optimizers["critic"].step()
     actor_loss = (alpha * logp - policy.q_min(s, a_pi)).mean()                                 # 8: the critics after their step
     optimizers["actor"].zero_grad(set_to_none=True); actor_loss.backward(); optimizers["actor"].step()
     optimizers["critic"].zero_grad(set_to_none=True)      # (the actor loss left gradients in the critics: they are not theirs)
@@ -394,7 +549,7 @@ def sac_update_torch(policy: SacPolicy, optimizers, batch, eps, eps_next, cfg: S
                 for p, t in zip(net.parameters(), tgt.parameters()):
                     t.mul_(1.0 - cfg.tau).add_(p, alpha=cfg.tau)
     return {"critic_loss": critic_loss.detach(), "actor_loss": actor_loss.detach(), "ent_coef_loss": ent_loss.detach(),
-            "ent_coef": alpha.detach(), "mean_logp": logp.detach().mean()}
+            "ent_coef": alpha.detach(), "mean_logp": logp.detach().mean(), "td": td}
 
 
 SCALARS = ("critic_loss", "actor_loss", "ent_coef_loss", "ent_coef", "mean_logp")
@@ -525,13 +680,23 @@ class FusedSacUpdate:
             self._ws = torch.zeros(need, dtype=torch.uint8, device=self.image.device)
         return self._ws
 
-    def run(self, rows: torch.Tensor, counters: torch.Tensor) -> None:
+    def run(self, rows: torch.Tensor, counters: torch.Tensor, weights: Optional[torch.Tensor] = None,
+            td_out: Optional[torch.Tensor] = None) -> None:
         """One gradient step on the image (the caller packs before, counts the step in ``ahead`` and unpacks when the modules are
-        wanted; nothing here reads the device)."""
+        wanted; nothing here reads the device).  With ``weights`` [B] it is ``fw_sac_update_weighted``: the critic loss is weighted
+        row by row and ``td_out`` [B] (optional) receives the rows' TD errors."""
         assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.shape[1] == row_floats(self.d, self.A)
         B = rows.shape[0]
         ws = self.workspace(B) if fits(self.d, self.A, self.H, B) else self.out          # (an unsupported shape: let the ABI say so)
         H = self.hyper()
+        if weights is not None:
+            assert weights.dtype == torch.float32 and weights.is_contiguous() and weights.numel() == B
+            assert td_out is None or (td_out.dtype == torch.float32 and td_out.is_contiguous() and td_out.numel() == B)
+            _lib.check(_lib.lib().fw_sac_update_weighted(_p(self.image), _p(rows), self.d, self.A, self.H, B, C.byref(H), _p(counters),
+                                                         _p(self.out), _p(ws), ws.numel(), _p(weights), _p(td_out), _stream(rows.device)))
+            return
+        if td_out is not None:
+            raise ValueError("td_out is written by the weighted step: pass weights (ones for an unweighted one)")
         _lib.check(_lib.lib().fw_sac_update(_p(self.image), _p(rows), self.d, self.A, self.H, B, C.byref(H), _p(counters), _p(self.out),
                                             _p(ws), ws.numel(), _stream(rows.device)))
 
@@ -546,10 +711,14 @@ class ReplayBufferDevice:
     """Flat fp32 ring ``[capacity, 2d + A + 2]`` and the device counters (cursor, rows filled, vec-steps stored, gradient steps):
     the host reads none of them on the training path.  ``n_steps > 1`` adds the episode-end side ring ``ends`` (uint8 per row:
     ``END_TERMINATED`` | ``END_TRUNCATED``), marked in front of every store, and ``sample`` gathers n-step transitions.
-    ``her_goals > 0`` (with ``her_task``, :func:`her_task_of`) owns the same side ring and ``sample`` relabels goals in hindsight."""
+    ``her_goals > 0`` (with ``her_task``, :func:`her_task_of`) owns the same side ring and ``sample`` relabels goals in hindsight.
+    ``prioritized`` owns one priority leaf per row (``prio``), the two levels of sums and mins above them and ``per_state``: a store
+    gives its rows the running max leaf and rebuilds the sums, ``sample`` draws in proportion to the leaves and reports the importance
+    weights, ``update_priorities`` writes the new leaves back and rebuilds."""
 
     def __init__(self, buffer_size: int, num_envs: int, obs_dim: int, act_dim: int, device, n_steps: int = 1, her_goals: int = 0,
-                 her_horizon: int = MAX_HER_HORIZON, her_task: Optional[HerTask] = None):
+                 her_horizon: int = MAX_HER_HORIZON, her_task: Optional[HerTask] = None, prioritized: bool = False,
+                 per_alpha: float = 0.6, per_beta: float = 0.4, per_beta_steps: int = 0, per_eps: float = 1e-6):
         if not 1 <= int(n_steps) <= MAX_N_STEPS:
             raise ValueError(f"n_steps must be in [1, {MAX_N_STEPS}], got {n_steps}")
         self.n_steps = int(n_steps)
@@ -567,21 +736,72 @@ class ReplayBufferDevice:
         self.ring = torch.zeros((self.capacity, self.row), dtype=torch.float32, device=device)
         self.counters = torch.zeros(4, dtype=torch.int64, device=device)
         self.ends = torch.zeros(self.capacity, dtype=torch.uint8, device=device) if self.n_steps > 1 or self.her_goals > 0 else None
+        self.prioritized = bool(prioritized)
+        self.per_alpha, self.per_beta, self.per_beta_steps, self.per_eps = float(per_alpha), float(per_beta), int(per_beta_steps), float(per_eps)
+        self.prio = self.sum1 = self.min1 = self.sum2 = self.min2 = self.per_state = None
+        if self.prioritized:
+            if self.n_steps > 1 or self.her_goals > 0:
+                raise ValueError("prioritized together with n_steps > 1 or her_goals > 0 is not built: those gathers draw their own indices")
+            if not (0.0 <= self.per_alpha <= 1.0 and 0.0 <= self.per_beta <= 1.0 and self.per_beta_steps >= 0 and self.per_eps > 0.0):
+                raise ValueError("per_alpha and per_beta must lie in [0, 1], per_beta_steps must not be negative and per_eps must be positive")
+            if self.capacity > PER_MAX_CAPACITY:
+                raise ValueError(f"a prioritized ring holds at most 2^22 = {PER_MAX_CAPACITY} rows (above that a float32 sum stops resolving "
+                                 f"one leaf), got {self.capacity}")
+            n1 = -(-self.capacity // PER_GROUP)
+            n2 = -(-n1 // PER_GROUP)
+            kw = dict(dtype=torch.float32, device=device)
+            self.prio = torch.zeros(self.capacity, **kw)
+            self.sum1, self.min1 = torch.zeros(n1, **kw), torch.full((n1,), math.inf, **kw)
+            self.sum2, self.min2 = torch.zeros(n2, **kw), torch.full((n2,), math.inf, **kw)
+            self.per_state = torch.tensor([1.0, 0.0, math.inf, 0.0], **kw)
+
+    def rebuild(self) -> None:
+        """Both levels of sums and mins, the total and the smallest positive leaf from the leaves (``fw_replay_per_rebuild``; for a
+        ring of CPU tensors -- checkpoints are inspected there -- :func:`per_sums_reference`)."""
+        if not self.prio.is_cuda:
+            r = per_sums_reference(self.prio.numpy())
+            for name in ("sum1", "min1", "sum2", "min2"):
+                getattr(self, name).copy_(torch.from_numpy(r[name]))
+            self.per_state[PER_TOTAL], self.per_state[PER_MIN] = float(r["total"]), float(r["pmin"])
+            return
+        _lib.check(_lib.lib().fw_replay_per_rebuild(_p(self.prio), self.capacity, _p(self.sum1), _p(self.min1), _p(self.sum2), _p(self.min2),
+                                                    _p(self.per_state), _stream(self.ring.device)))
+
+    def update_priorities(self, idx: torch.Tensor, td: torch.Tensor) -> None:
+        """The leaves of the batch's rows ``idx`` [B] int32 become ``(|td| + per_eps)^per_alpha`` (the largest one where a row was
+        drawn more than once), the running max follows, and the sums are rebuilt."""
+        assert idx.dtype == torch.int32 and td.dtype == torch.float32 and idx.is_contiguous() and td.is_contiguous() and idx.numel() == td.numel()
+        _lib.check(_lib.lib().fw_replay_per_update(_p(self.prio), self.capacity, _p(idx), _p(td), idx.numel(), self.per_alpha, self.per_eps,
+                                                   _p(self.per_state), _stream(self.ring.device)))
+        self.rebuild()
 
     def store(self, obs_stage, act_f32, reward, next_obs, terminal_obs, terminated, truncated) -> None:
         if self.ends is not None:        # the rows this store is about to write: the mark reads the cursor the store advances
             _lib.check(_lib.lib().fw_replay_mark_ends(_p(self.ends), self.capacity, _p(self.counters), _p(terminated), _p(truncated),
                                                       self.num_envs, _stream(self.ring.device)))
+        if self.prioritized:             # new rows enter with the running max leaf, so every one of them is drawn at least once soon
+            _lib.check(_lib.lib().fw_replay_per_mark_new(_p(self.prio), self.capacity, _p(self.counters), _p(self.per_state), self.num_envs,
+                                                         _stream(self.ring.device)))
         _lib.check(_lib.lib().fw_replay_store(_p(self.ring), self.capacity, _p(self.counters), _p(obs_stage), _p(act_f32), _p(reward),
                                               _p(next_obs), _p(terminal_obs), _p(terminated), _p(truncated),
                                               int(reward.dtype == torch.float64), self.num_envs, self.obs_dim, self.act_dim,
                                               _stream(self.ring.device)))
+        if self.prioritized:
+            self.rebuild()
 
     def sample(self, seed: int, out: torch.Tensor, idx_out: Optional[torch.Tensor] = None, gamma: Optional[float] = None,
-               k_out: Optional[torch.Tensor] = None, j_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               k_out: Optional[torch.Tensor] = None, j_out: Optional[torch.Tensor] = None, w_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """A batch into ``out``.  With ``n_steps > 1``: n-step transitions, which need ``gamma`` (``k_out`` [B] int32 receives the
         rows each one spans).  With ``her_goals > 0``: 1-step transitions, relabelled with probability ``her_prob`` (``j_out`` [B] int32
-        receives -1, or how many steps ahead the goal was achieved)."""
+        receives -1, or how many steps ahead the goal was achieved).  With ``prioritized``: rows drawn in proportion to their leaves
+        (``w_out`` [B] float32 receives the importance weights)."""
+        if self.prioritized:
+            _lib.check(_lib.lib().fw_replay_sample_per(_p(self.ring), self.capacity, _p(self.counters), int(seed) & (2**64 - 1), self.row,
+                                                       out.shape[0], _p(out), _p(idx_out), _p(w_out), _p(self.prio), _p(self.sum1), _p(self.sum2),
+                                                       _p(self.per_state), self.per_beta, self.per_beta_steps, _stream(self.ring.device)))
+            return out
+        if w_out is not None:
+            raise ValueError("w_out is written by a prioritized buffer's sample")
         if self.her_goals > 0:
             _lib.check(_lib.lib().fw_replay_sample_her(_p(self.ring), self.capacity, _p(self.counters), int(seed) & (2**64 - 1), self.row,
                                                        out.shape[0], _p(out), _p(idx_out), _p(self.ends), self.obs_dim, self.num_envs,
@@ -613,6 +833,8 @@ class ReplayBufferDevice:
             sd["ring"] = self.ring.cpu().clone()
             if self.ends is not None:
                 sd["ends"] = self.ends.cpu().clone()
+            if self.prioritized:
+                sd["prio"], sd["per_state"] = self.prio.cpu().clone(), self.per_state.cpu().clone()
         return sd
 
     def load_state_dict(self, sd) -> None:
@@ -631,6 +853,15 @@ class ReplayBufferDevice:
             if self.ends is not None:
                 self.ends.zero_()
             self.counters[CTR_CURSOR] = 0; self.counters[CTR_SIZE] = 0
+        if self.prioritized:             # rows that come without priorities enter as new rows do, with a leaf of 1.0; no rows: no leaves
+            if "ring" in sd and "prio" in sd:
+                self.prio.copy_(sd["prio"]); self.per_state.copy_(sd["per_state"])
+            else:
+                filled = min(max(int(sd["counters"][CTR_SIZE]), 0), self.capacity) if "ring" in sd else 0
+                self.prio.zero_()
+                self.prio[:filled] = 1.0
+                self.per_state.copy_(torch.tensor([1.0, 0.0, math.inf, 0.0]))
+            self.rebuild()
 
 
 def sac_noise(seed: int, counters: torch.Tensor, batch: int, act_dim: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -671,7 +902,8 @@ class SAC:
             raise ValueError(f"buffer_size {cfg.buffer_size} cannot hold one vec-step of {self.N} envs")
         her_task = her_task_of(getattr(env, "cfg", None)) if cfg.her_goals > 0 else None      # (ValueError unless it is the low-level task)
         self.buffer = ReplayBufferDevice(cfg.buffer_size, self.N, self.d, self.A, self.device, n_steps=cfg.n_steps, her_goals=cfg.her_goals,
-                                         her_horizon=cfg.her_horizon, her_task=her_task)
+                                         her_horizon=cfg.her_horizon, her_task=her_task, prioritized=cfg.prioritized, per_alpha=cfg.per_alpha,
+                                         per_beta=cfg.per_beta, per_beta_steps=cfg.per_beta_steps, per_eps=cfg.per_eps)
         self.fused = FusedSacUpdate(self._policy, self.optimizers, cfg)
         kw = dict(dtype=torch.float32, device=self.device)
         self.obs_stage, self.act_f32 = torch.zeros((self.N, self.d), **kw), torch.zeros((self.N, self.A), **kw)
@@ -679,6 +911,8 @@ class SAC:
         self.batch = torch.zeros((cfg.batch_size, self.buffer.row), **kw)
         self.batch_idx = torch.zeros(cfg.batch_size, dtype=torch.int32, device=self.device)
         self.noise = torch.zeros((2, cfg.batch_size, self.A), **kw)
+        self.batch_w = torch.ones(cfg.batch_size, **kw) if cfg.prioritized else None        # the batch's importance weights ...
+        self.batch_td = torch.zeros(cfg.batch_size, **kw) if cfg.prioritized else None      # ... and TD errors (prioritized only)
         self.scal = torch.zeros(5, **kw)          # the torch path's last scalars
         self.num_timesteps = 0
         self.env_offset = int(getattr(env, "global_env_offset", 0))
@@ -740,15 +974,25 @@ class SAC:
         self.buffer.store(self.obs_stage, self.act_f32, e.rewards, e.obs, e.terminal_obs, e.terminated, e.truncated)
 
     def _gradient_step_fused(self) -> None:
+        if self.cfg.prioritized:         # sample -> weighted update -> priorities -> rebuild, all stream-ordered: one graph still
+            self.buffer.sample(self.cfg.seed, self.batch, self.batch_idx, w_out=self.batch_w)
+            self.fused.run(self.batch, self.buffer.counters, weights=self.batch_w, td_out=self.batch_td)
+            self.buffer.update_priorities(self.batch_idx, self.batch_td)
+            return
         self.buffer.sample(self.cfg.seed, self.batch, self.batch_idx, gamma=self.cfg.gamma)
         self.fused.run(self.batch, self.buffer.counters)
 
     def _gradient_step_torch(self) -> None:
-        self.buffer.sample(self.cfg.seed, self.batch, self.batch_idx, gamma=self.cfg.gamma)
+        pri = self.cfg.prioritized
+        self.buffer.sample(self.cfg.seed, self.batch, self.batch_idx, gamma=self.cfg.gamma, w_out=self.batch_w)
         sac_noise(self.cfg.seed, self.buffer.counters, self.cfg.batch_size, self.A, out=self.noise)
-        s = sac_update_torch(self._policy, self.optimizers, self.batch, self.noise[0], self.noise[1], self.cfg)
+        s = sac_update_torch(self._policy, self.optimizers, self.batch, self.noise[0], self.noise[1], self.cfg,
+                             weights=self.batch_w if pri else None)
         self.scal.copy_(torch.stack([s[k].float() for k in SCALARS]))
         self.buffer.counters[CTR_GRAD] += 1
+        if pri:
+            self.batch_td.copy_(s["td"].float())
+            self.buffer.update_priorities(self.batch_idx, self.batch_td)
 
     def _vec_step_body(self, warm: bool, with_train: bool) -> None:
         self.act(ACT_WARMUP if warm else ACT_STOCHASTIC)

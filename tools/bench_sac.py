@@ -8,13 +8,16 @@
   * the same four at H 256 for every batch size of --batches (default 256 ... 8192: up to 512 rows the 24-launch form, above it the
     wide form), with microseconds per step and per sample;
   * end-to-end env-steps/s of sac.SAC at 16 envs with gradient_steps 1 and -1, and at 4096 envs with one 4096-row gradient step per
-    vec-step on both env variants (the large-env recipe of examples/train_lowlevel_sac.py), the tracking variant with n_steps 3 and
-    with her_goals 4 too.
+    vec-step on both env variants (the large-env recipe of examples/train_lowlevel_sac.py), the tracking variant with n_steps 3,
+    with her_goals 4 and with prioritized replay too;
+  * prioritized replay (`per`), on the ring of a 16-env and of a 4096-env learner: the prioritized sample against the 1-step sample
+    (B 256 and 4096), mark-new + store + rebuild against the store alone, the rebuild and the priority write-back alone, and the
+    weighted gradient step with its write-back and rebuild against the plain step (H 256, B 256 and 4096).
 
 Timing: device events around `iters` back-to-back calls after `warmup` calls, median of `repeats` such blocks.  --runs N repeats the
 chosen sections N times (a "run" field tells them apart): the spread between runs is the run-to-run noise of a figure.
 
-    python tools/bench_sac.py [--quick] [--sections pieces,update,batches,end_to_end,end_to_end_large] [--batches 256,4096] [--runs 3]
+    python tools/bench_sac.py [--quick] [--sections pieces,update,batches,end_to_end,end_to_end_large,per] [--batches 256,4096] [--runs 3]
 """
 import argparse
 import json
@@ -147,6 +150,51 @@ def bench_nstep_sample(sac, n, it):
     emit(what="mark_and_store", envs=n, n_steps=3, **t)
 
 
+def bench_per(n, it):
+    """Prioritized replay on the ring of an n-env learner (the reference's 200 000-row buffer, d 21, A 6, H 256), every figure beside
+    the plain one of the same process: sample, store, and the gradient step with everything prioritization adds around it."""
+    env = P.FixedwingLowLevelVecEnv(num_envs=n, seed=0)
+    sac = S.SAC(env, S.SACConfig(seed=0, use_graphs=False))
+    env.reset_tensor(); sac._started = True
+    for _ in range(4):
+        sac.collect_step(train=False)
+    one, e = sac.buffer, sac.env
+    per = S.ReplayBufferDevice(one.capacity, n, one.obs_dim, one.act_dim, "cuda", prioritized=True)
+    per.ring, per.counters = one.ring, one.counters
+    g = torch.Generator(device="cuda").manual_seed(3)
+    one.counters[S.CTR_SIZE] = one.capacity                      # a full ring: every group of the sum structure is in play
+    per.prio.copy_(torch.rand(per.capacity, device="cuda", generator=g) * 0.99 + 0.01)
+    per.rebuild()
+    args = (sac.obs_stage, sac.act_f32, e.rewards, e.obs, e.terminal_obs, e.terminated, e.truncated)
+    base = timed_us(lambda: one.store(*args), *it)
+    emit(what="store", envs=n, **base)
+    t = timed_us(lambda: per.store(*args), *it)
+    emit(what="mark_new_store_rebuild", envs=n, capacity=per.capacity, **t, ratio_to_store=round(t["us"] / base["us"], 3))
+    emit(what="per_rebuild", envs=n, capacity=per.capacity, **timed_us(per.rebuild, *it))
+    for B in (256, 4096):
+        out, idx, w = torch.zeros((B, one.row), device="cuda"), torch.zeros(B, dtype=torch.int32, device="cuda"), torch.zeros(B, device="cuda")
+        base = timed_us(lambda: one.sample(0, out, idx), *it)
+        emit(what="sample", envs=n, batch=B, n_steps=1, **base)
+        t = timed_us(lambda: per.sample(0, out, idx, w_out=w), *it)
+        emit(what="sample", envs=n, batch=B, prioritized=True, capacity=per.capacity, **t, ratio_to_one_step=round(t["us"] / base["us"], 3))
+        td = torch.rand(B, device="cuda", generator=g)
+        emit(what="per_update_and_rebuild", envs=n, batch=B, capacity=per.capacity, **timed_us(lambda: per.update_priorities(idx, td), *it))
+        cfg = S.SACConfig(batch_size=B, seed=1)
+        fused = S.FusedSacUpdate(sac._policy, sac.optimizers, cfg); fused.pack()
+        rows = one.sample(0, torch.zeros((B, one.row), device="cuda"))
+        rows[:, -1] = (rows[:, -1] > 0.5).float()
+        base = timed_us(lambda: fused.run(rows, one.counters), *it)
+        emit(what="gradient_step", path="fused", envs=n, batch=B, hidden=256, **base)
+
+        def weighted():
+            fused.run(rows, one.counters, weights=w, td_out=td)
+            per.update_priorities(idx, td)
+        t = timed_us(weighted, *it)
+        emit(what="gradient_step", path="fused_weighted_update_rebuild", envs=n, batch=B, hidden=256, capacity=per.capacity, **t,
+             ratio_to_plain=round(t["us"] / base["us"], 3))
+    env.close()
+
+
 def bench_end_to_end(gradient_steps, fused, graphs, vec_steps):
     env = P.FixedwingLowLevelVecEnv(num_envs=16, seed=0)
     sac = S.SAC(env, S.SACConfig(seed=0, gradient_steps=gradient_steps, fused_update=fused, use_graphs=graphs))
@@ -160,22 +208,23 @@ def bench_end_to_end(gradient_steps, fused, graphs, vec_steps):
     env.close()
 
 
-def bench_end_to_end_large(variant, envs, batch, vec_steps, n_steps=1, her_goals=0):
+def bench_end_to_end_large(variant, envs, batch, vec_steps, n_steps=1, her_goals=0, prioritized=False):
     """The large-env recipe: one `batch`-row gradient step per vec-step of `envs` envs, fused, one captured graph per vec-step."""
     make = P.FixedwingLowLevelDemoVecEnv if variant == "demo" else P.FixedwingLowLevelVecEnv
     env = make(num_envs=envs, seed=0)
-    sac = S.SAC(env, S.SACConfig(seed=0, batch_size=batch, gradient_steps=1, learning_starts=envs, n_steps=n_steps, her_goals=her_goals))
+    sac = S.SAC(env, S.SACConfig(seed=0, batch_size=batch, gradient_steps=1, learning_starts=envs, n_steps=n_steps, her_goals=her_goals,
+                                 **({"prioritized": True} if prioritized else {})))
     sac.learn(envs * 8)                      # the warm-up step, the first trained steps, the captures
     torch.cuda.synchronize()
     t0, n0 = time.perf_counter(), sac.num_timesteps
     sac.learn(envs * vec_steps)
     dt = time.perf_counter() - t0
-    emit(what="end_to_end", env=variant, envs=envs, batch=batch, n_steps=n_steps, **({"her_goals": her_goals} if her_goals else {}), gradient_steps=sac.G, fused_update=True, use_graphs=True, vec_steps=vec_steps,
+    emit(what="end_to_end", env=variant, envs=envs, batch=batch, n_steps=n_steps, **({"her_goals": her_goals} if her_goals else {}), **({"prioritized": True} if prioritized else {}), gradient_steps=sac.G, fused_update=True, use_graphs=True, vec_steps=vec_steps,
          env_steps_per_s=round((sac.num_timesteps - n0) / dt, 1), us_per_vec_step=round(dt * 1e6 / vec_steps, 1))
     env.close()
 
 
-SECTIONS = ("pieces", "update", "batches", "end_to_end", "end_to_end_large")
+SECTIONS = ("pieces", "update", "batches", "end_to_end", "end_to_end_large", "per")
 BATCHES = (256, 512, 576, 1024, 2048, 4096, 8192)
 
 
@@ -219,6 +268,11 @@ def main():
             bench_end_to_end_large("tracking", 4096, 4096, max(vs // 2, 20), n_steps=3)
             if hasattr(S._lib.lib(), "fw_replay_sample_her"):      # (an A/B library of an older commit predates it)
                 bench_end_to_end_large("tracking", 4096, 4096, max(vs // 2, 20), her_goals=4)
+            if hasattr(S._lib.lib(), "fw_replay_sample_per"):      # (likewise)
+                bench_end_to_end_large("tracking", 4096, 4096, max(vs // 2, 20), prioritized=True)
+        if "per" in sections:
+            for n in (16, 4096):
+                bench_per(n, it)
 
 
 if __name__ == "__main__":
