@@ -30,6 +30,12 @@ recomputed for that target (``SACConfig.her_goals``).  Bot
 proportional variant; ``SACConfig.prioritized``) and weights the critic loss by ``(N P(row))^-per_beta`` over its
 maximum; ``--per_beta_steps n`` anneals that exponent from ``--per_beta`` to 1 over n gradient steps.  New rows enter with the largest
 priority seen so far.  Both env variants; not together with ``--n_steps`` above 1 or ``--her_goals``.
+
+``--normalize_obs`` / ``--normalize_reward`` put SB3's ``VecNormalize`` in front of the learner as it works with an off-policy buffer
+(``SACConfig.normalize_obs`` / ``normalize_reward``): running statistics of the observations and of the
+discounted return, moved after every env step; the ring keeps raw rows, the actor and every sampled batch read normalised ones
+(clipped to ``--clip_obs`` / ``--clip_reward``, default 10).  The evaluation env is built by ``SAC.eval_env`` and reads the learner's
+own statistics.  Both env variants, together with any of the options above.
 """
 import argparse
 import json
@@ -42,7 +48,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pyflyt_drone_amd as P  # noqa: E402
-from pyflyt_drone_amd import evaluate, rollout as R, sac as S  # noqa: E402
+from pyflyt_drone_amd import evaluate, sac as S  # noqa: E402
 
 TRAIN_CONFIG = dict(total_timesteps=100_000, learning_rate=3e-4, buffer_size=200_000, batch_size=256, gamma=0.99, tau=0.02,
                     target_update_interval=1, learning_starts=100, net_arch=(256, 256), seed=0, n_eval_episodes=16, eval_freq=10_000)
@@ -68,6 +74,10 @@ def main():
     ap.add_argument("--per_alpha", type=float, default=0.6, help="priority exponent in [0, 1]; 0 draws uniformly over the filled rows")
     ap.add_argument("--per_beta", type=float, default=0.4, help="importance-weight exponent in [0, 1]")
     ap.add_argument("--per_beta_steps", type=int, default=0, help="> 0: anneal the importance-weight exponent from --per_beta to 1 over this many gradient steps")
+    ap.add_argument("--normalize_obs", action="store_true", help="running observation normalisation (VecNormalize's norm_obs) in front of actor and critics")
+    ap.add_argument("--normalize_reward", action="store_true", help="sampled rewards divided by the running std of the discounted return (VecNormalize's norm_reward)")
+    ap.add_argument("--clip_obs", type=float, default=10.0, help="a normalised observation is clipped to +-clip_obs")
+    ap.add_argument("--clip_reward", type=float, default=10.0, help="a normalised reward is clipped to +-clip_reward")
     ap.add_argument("--fused_update", action=argparse.BooleanOptionalAction, default=True,
                     help="fw_sac_update (default) or the torch gradient step")
     ap.add_argument("--use_graphs", action=argparse.BooleanOptionalAction, default=True)
@@ -91,15 +101,16 @@ def main():
     else:
         env = P.FixedwingLowLevelVecEnv(num_envs=a.num_envs, seed=c["seed"])
         eval_cfg = K.lowlevel_config(max_episode_steps=a.eval_max_steps)
-    eval_env = R.VecNormalizeDevice(P.FixedwingVecEnv(eval_cfg, 16, seed=c["seed"], global_env_offset=a.num_envs),
-                                    training=False, norm_obs=False, norm_reward=False)
     model = S.SAC(env, S.SACConfig(learning_rate=c["learning_rate"], buffer_size=c["buffer_size"], batch_size=a.batch_size,
                                    gamma=c["gamma"], tau=c["tau"], gradient_steps=a.gradient_steps,
                                    target_update_interval=c["target_update_interval"], learning_starts=c["learning_starts"],
                                    net_arch=c["net_arch"], seed=c["seed"], use_graphs=a.use_graphs, fused_update=a.fused_update,
                                    episode_stats=a.episode_stats, episode_fold=a.episode_fold, n_steps=a.n_steps,
                                    her_goals=a.her_goals, her_horizon=a.her_horizon, prioritized=a.prioritized, per_alpha=a.per_alpha,
-                                   per_beta=a.per_beta, per_beta_steps=a.per_beta_steps))
+                                   per_beta=a.per_beta, per_beta_steps=a.per_beta_steps, normalize_obs=a.normalize_obs,
+                                   normalize_reward=a.normalize_reward, clip_obs=a.clip_obs, clip_reward=a.clip_reward))
+    # (with both flags off: a pass-through wrapper; with --normalize_obs it reads the learner's own, live statistics)
+    eval_env = model.eval_env(P.FixedwingVecEnv(eval_cfg, 16, seed=c["seed"], global_env_offset=a.num_envs))
     t0 = time.perf_counter()
     state = {"next_eval": a.eval_freq, "train_s": 0.0, "mark": t0}
 
@@ -130,6 +141,8 @@ def main():
                                  **({"n_steps": a.n_steps} if a.n_steps != 1 else {}),
                                  **({"her_goals": a.her_goals, "her_horizon": a.her_horizon} if a.her_goals else {}),
                                  **({"prioritized": True, "per_alpha": a.per_alpha, "per_beta": a.per_beta, "per_beta_steps": a.per_beta_steps} if a.prioritized else {}),
+                                 **({"normalize_obs": a.normalize_obs, "normalize_reward": a.normalize_reward, "clip_obs": a.clip_obs, "clip_reward": a.clip_reward}
+                                    if a.normalize_obs or a.normalize_reward else {}),
                                  "fused_update": a.fused_update, "use_graphs": a.use_graphs}}), flush=True)
     evaluate_now(model)                      # the untrained actor: the line later evaluations are read against
     try:

@@ -1070,6 +1070,26 @@ int32_t fw_replay_per_update(float* prio, int64_t capacity, const int32_t* idx, 
 int32_t fw_sac_update_weighted(float* image, const float* batch_rows, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch,
                                const fw_sac_hyper* hyper, int64_t* counters, float* out, void* workspace, int64_t workspace_bytes,
                                const float* weights, float* td_out, void* hip_stream);
+/* ---- Running observation / reward normalisation for the off-policy learner (SB3's VecNormalize with a replay buffer) ----
+ * The ring keeps RAW rows; the statistics (fw_collect_stats writes them, behind the env step) are applied where a value is read.
+ *
+ * fw_sac_act_norm is fw_sac_act on clip((float)(((double)x - obs_mean[k]) / sqrt(obs_var[k] + (double)eps_obs)), +-clip_obs) -- the
+ * arithmetic of fw_normalize_obs(update = 0), so its actions, logp and eps are those of fw_sac_act on that call's fp32 output, bit for
+ * bit.  The observation is normalised as it is loaded in front of the forward pass (the obs_dim means and standard deviations are formed
+ * once per workgroup); obs_stage still receives the RAW fp32 observation.  Mode 2 runs no forward pass and reads no statistics
+ * (obs_mean / obs_var may be NULL there; in modes 0 and 1 a NULL one is FW_EINVAL). */
+int32_t fw_sac_act_norm(const float* image, const void* obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, int32_t act_dim, int32_t hidden,
+                        int32_t mode, uint64_t seed, int64_t env_offset, const int64_t* counters, float* act_f32, void* act_env, float* obs_stage,
+                        float* logp, float* eps, const double* obs_mean, const double* obs_var, float clip_obs, float eps_obs, void* hip_stream);
+/* One launch, in place on a gathered batch [batch, 2 obs_dim + act_dim + 2] (behind any of the four samplers; hindsight rewards and
+ * n-step sums are formed on raw values before it, so an n-step row's summed reward is scaled and clipped as one number).  With obs_mean
+ * / obs_var [obs_dim]: the columns [0, obs_dim) and [obs_dim + act_dim + 1, 2 obs_dim + act_dim + 1) become the expression above.
+ * With ret_var [1]: column obs_dim + act_dim becomes clip((float)((double)r / sqrt(ret_var[0] + (double)eps_reward)), +-clip_reward).
+ * The action and done columns are not written.  obs_mean == NULL leaves the observations alone, ret_var == NULL the reward; both NULL,
+ * or obs_mean without obs_var: FW_EINVAL.  Any positive batch; obs_dim <= 64 and act_dim <= 8 (FW_EUNSUPPORTED otherwise).  Every
+ * element is written by one thread from its own old value: no atomics, no in-grid wait. */
+int32_t fw_replay_normalize(float* batch_rows, int32_t batch, int32_t obs_dim, int32_t act_dim, const double* obs_mean, const double* obs_var,
+                            float clip_obs, float eps_obs, const double* ret_var, float clip_reward, float eps_reward, void* hip_stream);
 const char* fw_last_error(fw_handle h); /* h may be NULL: last create/validate error */
 int32_t fw_destroy(fw_handle h);
 

@@ -38,6 +38,7 @@ EXPORTS = (
     "fw_replay_mark_ends", "fw_replay_sample_nstep",
     "fw_sizeof_her_task", "fw_replay_sample_her", "fw_her_reward",
     "fw_replay_per_mark_new", "fw_replay_per_rebuild", "fw_replay_sample_per", "fw_replay_per_update", "fw_sac_update_weighted",
+    "fw_sac_act_norm", "fw_replay_normalize",
 )
 
 
@@ -238,6 +239,12 @@ def lib() -> C.CDLL:
             L.fw_replay_per_update.restype = i32; L.fw_replay_per_update.argtypes = [vp, i64, vp, vp, i32, f32, f32, vp, vp]
             L.fw_sac_update_weighted.restype = i32
             L.fw_sac_update_weighted.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp, vp, vp]
+        if hasattr(L, "fw_replay_normalize"):      # running normalisation for SAC (an A/B library of an older commit predates the pair; build() insists on it)
+            f32 = C.c_float
+            L.fw_sac_act_norm.restype = i32
+            L.fw_sac_act_norm.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp]
+            L.fw_replay_normalize.restype = i32
+            L.fw_replay_normalize.argtypes = [vp, i32, i32, i32, vp, vp, f32, f32, vp, f32, f32, vp]
         L.fw_policy_act_a.restype = i32
         L.fw_policy_act_a.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
         L.fw_collect_act_a.restype = i32

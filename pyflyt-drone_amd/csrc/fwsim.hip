@@ -3524,6 +3524,43 @@ int32_t fw_sac_act(const float* image, const void* obs, int32_t obs_is_f64, int3
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }
+int32_t fw_sac_act_norm(const float* image, const void* obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, int32_t act_dim, int32_t hidden,
+                        int32_t mode, uint64_t seed, int64_t env_offset, const int64_t* counters, float* act_f32, void* act_env, float* obs_stage,
+                        float* logp, float* eps, const double* obs_mean, const double* obs_var, float clip_obs, float eps_obs, void* hip_stream) {
+  if (!image || !obs || !counters || !act_f32 || !act_env || !obs_stage) { g_err = "fw_sac_act_norm: image, obs, counters, act_f32, act_env and obs_stage must be non-NULL"; return FW_EINVAL; }
+  if (N <= 0 || mode < 0 || mode > 2 || env_offset < 0) { g_err = "fw_sac_act_norm: N must be positive, mode 0, 1 or 2 and env_offset non-negative"; return FW_EINVAL; }
+  if (mode != 2 && (!obs_mean || !obs_var)) { g_err = "fw_sac_act_norm: modes 0 and 1 need obs_mean and obs_var"; return FW_EINVAL; }
+  if (mode != 2 && !(clip_obs > 0.0f && eps_obs >= 0.0f)) { g_err = "fw_sac_act_norm: clip_obs must be positive and eps_obs non-negative"; return FW_EINVAL; }
+  const int32_t rc = sac_check_shape("fw_sac_act_norm", obs_dim, act_dim, hidden);
+  if (rc != FW_OK) return rc;
+  DeviceGuard g(device_of(image));
+  SacActNormArgs a{{image, obs, N, obs_dim, act_dim, mode, seed, env_offset, counters, act_f32, act_env, obs_stage, logp, eps},
+                   obs_mean, obs_var, clip_obs, eps_obs};
+  const dim3 grid((unsigned)((N + 15) / 16)), block(256);
+  with_real(obs_is_f64 != 0, [&](auto t) {
+    using T = decltype(t);
+    if (hidden == 64) hipLaunchKernelGGL((fw_sac_act_kernel<T, 64, true>), grid, block, 0, (hipStream_t)hip_stream, a);
+    else hipLaunchKernelGGL((fw_sac_act_kernel<T, 256, true>), grid, block, 0, (hipStream_t)hip_stream, a);
+  });
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
+int32_t fw_replay_normalize(float* batch_rows, int32_t batch, int32_t obs_dim, int32_t act_dim, const double* obs_mean, const double* obs_var,
+                            float clip_obs, float eps_obs, const double* ret_var, float clip_reward, float eps_reward, void* hip_stream) {
+  if (!batch_rows || (!obs_mean && !ret_var) || (!obs_mean != !obs_var)) {
+    g_err = "fw_replay_normalize: batch_rows must be non-NULL, obs_mean and obs_var come together, and one of obs_mean and ret_var must be given"; return FW_EINVAL;
+  }
+  if (batch <= 0 || obs_dim <= 0 || act_dim <= 0) { g_err = "fw_replay_normalize: batch, obs_dim and act_dim must be positive"; return FW_EINVAL; }
+  if ((obs_mean && !(clip_obs > 0.0f && eps_obs >= 0.0f)) || (ret_var && !(clip_reward > 0.0f && eps_reward >= 0.0f))) {
+    g_err = "fw_replay_normalize: a clip must be positive and an epsilon non-negative"; return FW_EINVAL;
+  }
+  if (obs_dim > kSacMaxD || act_dim > kSacMaxA) { g_err = "fw_replay_normalize: built for obs_dim <= 64 and act_dim <= 8"; return FW_EUNSUPPORTED; }
+  DeviceGuard g(device_of(batch_rows));
+  SacBatchNormArgs n{batch_rows, batch, obs_dim, act_dim, obs_mean, obs_var, ret_var, clip_obs, eps_obs, clip_reward, eps_reward};
+  hipLaunchKernelGGL(fw_replay_normalize_kernel, dim3((unsigned)(((int64_t)batch + kSacNormRows - 1) / kSacNormRows)), dim3(256), 0, (hipStream_t)hip_stream, n);
+  HIP_TRY((fw_env*)nullptr, hipGetLastError());
+  return FW_OK;
+}
 int32_t fw_replay_store(float* ring, int64_t capacity, int64_t* counters, const float* obs_stage, const float* act_f32, const void* reward,
                         const void* next_obs, const void* terminal_obs, const uint8_t* terminated, const uint8_t* truncated, int32_t env_is_f64,
                         int32_t N, int32_t obs_dim, int32_t act_dim, void* hip_stream) {

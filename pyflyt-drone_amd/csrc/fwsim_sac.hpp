@@ -30,6 +30,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "fwsim_device.hpp"
 #include "fwsim_ppo.hpp"
 
@@ -165,20 +167,46 @@ struct SacActArgs {
   uint64_t seed; int64_t env_offset; const int64_t* ctr;
   float* act_f32; void* act_env; float* obs_stage; float* logp; float* eps;
 };
-template <typename T, int H>
-__global__ __launch_bounds__(256) void fw_sac_act_kernel(SacActArgs a) {
+// fw_sac_act_norm's argument block: fw_sac_act's and VecNormalize's statistics.  The observation enters the forward pass as
+//   clip((float)(((double)x - mean[k]) / sqrt(var[k] + (double)eps)), +-clip)   -- fw_obs_normalize_kernel's arithmetic, bit for bit --
+// while obs_stage keeps the raw fp32 value, because the ring stores raw rows
+struct SacActNormArgs : SacActArgs { const double *obs_mean, *obs_var; float clip_obs, eps_obs; };
+// NORM = false is fw_sac_act, NORM = true fw_sac_act_norm: every addition sits under `if constexpr (NORM)`, so the first instantiation's
+// statements and argument block are the ones the kernel had before it gained the parameter.
+template <typename T, int H, bool NORM = false>
+__global__ __launch_bounds__(256) void fw_sac_act_kernel(std::conditional_t<NORM, SacActNormArgs, SacActArgs> a) {
   constexpr int LDX = 65, LDH = H + 1, LDO = 17;
   __shared__ float X[16 * LDX], H1[16 * LDH], H2[16 * LDH], O[16 * LDO];
   const int t = threadIdx.x, r0 = blockIdx.x * 16, d = a.d, A = a.A;
   const T* obs = (const T*)a.obs;
-  for (int idx = t; idx < 16 * 64; idx += 256) {
-    const int row = idx >> 6, k = idx & 63;
-    float x = 0.f;
-    if (r0 + row < a.N && k < d) {
-      x = (float)obs[(size_t)(r0 + row) * d + k];
-      a.obs_stage[(size_t)(r0 + row) * d + k] = x;
+  if constexpr (NORM) {
+    // the d <= 64 means and standard deviations once per workgroup: no square root per element (the division stays per element)
+    __shared__ double cmean[kSacMaxD], cstd[kSacMaxD];
+    const bool fwd = a.mode != 2;                  // warm-up runs no forward pass: X is not read and no statistics are needed
+    if (fwd) {
+      if (t < d) { cmean[t] = a.obs_mean[t]; cstd[t] = sqrt(a.obs_var[t] + (double)a.eps_obs); }
+      __syncthreads();
     }
-    X[row * LDX + k] = x;
+    for (int idx = t; idx < 16 * 64; idx += 256) {
+      const int row = idx >> 6, k = idx & 63;
+      float x = 0.f;
+      if (r0 + row < a.N && k < d) {
+        const T raw = obs[(size_t)(r0 + row) * d + k];
+        a.obs_stage[(size_t)(r0 + row) * d + k] = (float)raw;
+        if (fwd) x = fminf(fmaxf((float)(((double)raw - cmean[k]) / cstd[k]), -a.clip_obs), a.clip_obs);
+      }
+      X[row * LDX + k] = x;
+    }
+  } else {
+    for (int idx = t; idx < 16 * 64; idx += 256) {
+      const int row = idx >> 6, k = idx & 63;
+      float x = 0.f;
+      if (r0 + row < a.N && k < d) {
+        x = (float)obs[(size_t)(r0 + row) * d + k];
+        a.obs_stage[(size_t)(r0 + row) * d + k] = x;
+      }
+      X[row * LDX + k] = x;
+    }
   }
   if (a.mode != 2) {
     const SacNet n = sac_net(d, H, 2 * A);
@@ -917,6 +945,42 @@ __global__ __launch_bounds__(256) void fw_replay_sample_her_kernel(const float* 
   if (lane == 0) {
     if (idx_out) idx_out[b] = (int32_t)idx;
     if (j_out) j_out[b] = jstar;
+  }
+}
+
+// ---- fw_replay_normalize: VecNormalize's statistics applied to a gathered batch, in place (SB3's ReplayBuffer._normalize_obs /
+// _normalize_reward: the ring keeps raw rows, a batch is normalised with the statistics of the moment it is sampled) ----
+// One launch behind whichever sampler gathered the batch.  A workgroup takes 64 rows, a wave 16 of them, a lane the columns lane,
+// lane + 64, ... of the 2 d (+ 1) columns that change: both observation blocks by fw_obs_normalize_kernel's arithmetic (double, one
+// division per element; the d means and standard deviations are formed once per workgroup) and the reward column as
+// clip((float)((double)r / sqrt(ret_var + eps)), +-clip).  The action and done columns are never written, every element is written by
+// the one lane that read it, and nothing waits on another workgroup.
+struct SacBatchNormArgs {
+  float* batch; int32_t B, d, A;
+  const double *mean, *var, *ret_var;              // mean / var NULL: the observations stay; ret_var NULL: the reward stays
+  float clip_obs, eps_obs, clip_rew, eps_rew;
+};
+constexpr int kSacNormRows = 64;
+__global__ __launch_bounds__(256) void fw_replay_normalize_kernel(SacBatchNormArgs n) {
+  __shared__ double cmean[kSacMaxD], cstd[kSacMaxD], rstd;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, d = n.d, A = n.A;
+  if (n.mean && t < d) { cmean[t] = n.mean[t]; cstd[t] = sqrt(n.var[t] + (double)n.eps_obs); }
+  if (n.ret_var && t == 64) rstd = sqrt(n.ret_var[0] + (double)n.eps_rew);
+  __syncthreads();
+  const int R = 2 * d + A + 2, nobs = n.mean ? 2 * d : 0, W = nobs + (n.ret_var ? 1 : 0);
+  const long long first = (long long)blockIdx.x * kSacNormRows + w * (kSacNormRows / 4);
+  for (int i = 0; i < kSacNormRows / 4; ++i) {
+    const long long b = first + i;
+    if (b >= n.B) break;
+    float* row = n.batch + (size_t)b * R;
+    for (int j = lane; j < W; j += 64) {
+      if (j < nobs) {
+        const int k = j < d ? j : j - d, c = j < d ? j : j + A + 1;          // obs column k, or next_obs column k behind action and reward
+        row[c] = fminf(fmaxf((float)(((double)row[c] - cmean[k]) / cstd[k]), -n.clip_obs), n.clip_obs);
+      } else {
+        row[d + A] = fminf(fmaxf((float)((double)row[d + A] / rstd), -n.clip_rew), n.clip_rew);
+      }
+    }
   }
 }
 

@@ -17,6 +17,11 @@ Everything between two env steps runs on the device (csrc/fwsim_sac.hpp, include
                        per ring row under a three-level sum structure, the proportional draw with its importance weights, and the
                        write-back of the new priorities (:func:`per_sums_reference`, :func:`per_draw_reference` and
                        :func:`per_update_reference` restate their contracts);
+* ``fw_sac_act_norm`` / ``fw_replay_normalize`` / ``fw_collect_stats``  (``SACConfig.normalize_obs`` / ``normalize_reward`` only) SB3's
+                       ``VecNormalize`` with an off-policy buffer: the ring keeps raw rows, the actor reads observations normalised as
+                       they are loaded, a sampled batch is normalised in place with the statistics of that moment, and one statistics
+                       launch behind every env step moves them (:func:`normalize_rows_reference` and :func:`stats_step_reference`
+                       restate their contracts);
 * ``fw_sac_noise``     the two noise blocks of a gradient step;
 * ``fw_sac_update``    one gradient step of SB3's ``SAC.train()`` on a flat image of all five networks and their Adam moments;
 * ``fw_sac_update_weighted``  (``SACConfig.prioritized`` only) the same step with the importance weights on the critic loss; it
@@ -93,8 +98,21 @@ class SACConfig:
     per_beta: float = 0.4                #     exponent of the importance weights, in [0, 1]; 0: no correction
     per_beta_steps: int = 0              #     > 0: the exponent grows linearly from per_beta to 1 over this many gradient steps
     per_eps: float = 1e-6
+    normalize_obs: bool = False          # SB3's VecNormalize(norm_obs) in front of an off-policy learner: running statistics of the env's
+                                         # observations; the ring keeps raw rows, the actor and every sampled batch read normalised ones.
+                                         # Off (both flags): nothing changes
+    normalize_reward: bool = False       #     VecNormalize(norm_reward): a sampled reward is divided by the std of the discounted return
+    clip_obs: float = 10.0               #     a normalised observation is clipped to +-clip_obs ...
+    clip_reward: float = 10.0            #     ... and a normalised reward to +-clip_reward
+    norm_epsilon: float = 1e-8           #     added to a variance under the square root
 
     def __post_init__(self):
+        self.normalize_obs, self.normalize_reward = bool(self.normalize_obs), bool(self.normalize_reward)
+        for name in ("clip_obs", "clip_reward", "norm_epsilon"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(float(v)) and float(v) > 0.0):
+                raise ValueError(f"{name} must be a positive finite number, got {v!r}")
+            setattr(self, name, float(v))
         self.prioritized = bool(self.prioritized)
         if not (0.0 <= float(self.per_alpha) <= 1.0 and 0.0 <= float(self.per_beta) <= 1.0):
             raise ValueError(f"per_alpha and per_beta must lie in [0, 1], got {self.per_alpha!r} and {self.per_beta!r}")
@@ -147,6 +165,10 @@ class SACConfig:
     def her_relabel_prob(self) -> float:
         """SB3's ``her_ratio``: ``1 - 1 / (n_sampled_goal + 1)``."""
         return self.her_goals / (self.her_goals + 1.0)
+
+    @property
+    def normalizes(self) -> bool:
+        return self.normalize_obs or self.normalize_reward
 
     def resolved_gradient_steps(self, num_envs: int) -> int:
         return int(num_envs) if self.gradient_steps == -1 else int(self.gradient_steps)
@@ -452,6 +474,77 @@ def per_update_reference(prio, idx, td, alpha, eps, pmax):
     ok = inside & np.isfinite(leaf) & (leaf > 0)
     np.maximum.at(out, idx[ok], leaf[ok])
     return out, np.float32(max([np.float32(pmax)] + list(leaf[ok])))
+
+
+# ---------------------------------------------------------------------------------------------
+# running normalisation in plain torch (the contracts of fw_sac_act_norm's load, fw_replay_normalize and fw_collect_stats)
+# ---------------------------------------------------------------------------------------------
+def _eps64(eps: float) -> float:
+    """An epsilon as the entry points receive it: a C float, widened to double on the device."""
+    return float(torch.tensor(float(eps), dtype=torch.float32).double())
+
+
+def normalize_obs_reference(obs, mean, var, clip: float = 10.0, eps: float = 1e-8):
+    """``clip((float32)((x - mean) / sqrt(var + eps)), +-clip)`` with the arithmetic in float64 and one division per element: what
+    ``fw_normalize_obs(update=0)``, ``fw_sac_act_norm``'s load and ``fw_replay_normalize`` compute.  CPU tensors too."""
+    mean, var = torch.as_tensor(mean, dtype=torch.float64), torch.as_tensor(var, dtype=torch.float64)
+    z = (obs.to(torch.float64) - mean.to(obs.device)) / torch.sqrt(var.to(obs.device) + _eps64(eps))
+    return z.to(torch.float32).clamp_(-float(clip), float(clip))
+
+
+def normalize_rows_reference(rows, obs_dim: int, act_dim: int, obs_mean=None, obs_var=None, clip_obs: float = 10.0, eps_obs: float = 1e-8,
+                             ret_var=None, clip_reward: float = 10.0, eps_reward: float = 1e-8):
+    """``fw_replay_normalize`` in plain torch (CPU tensors too): a copy of ``rows`` ``[B, 2d + A + 2]`` float32 with both observation
+    blocks replaced by :func:`normalize_obs_reference` (``obs_mean`` / ``obs_var`` ``[d]`` float64; ``None``: left alone) and the reward
+    column by ``clip((float32)(r / sqrt(ret_var + eps_reward)), +-clip_reward)`` in float64 (``ret_var`` a float64 scalar; ``None``:
+    left alone).  The action and done columns are the input's."""
+    d, A = int(obs_dim), int(act_dim)
+    if rows.dim() != 2 or rows.shape[1] != row_floats(d, A) or rows.dtype != torch.float32:
+        raise ValueError(f"rows must be float32 [B, {row_floats(d, A)}]")
+    if obs_mean is None and ret_var is None:
+        raise ValueError("one of obs_mean and ret_var must be given")
+    if (obs_mean is None) != (obs_var is None):
+        raise ValueError("obs_mean and obs_var come together")
+    out = rows.clone()
+    if obs_mean is not None:
+        for lo in (0, d + A + 1):
+            out[:, lo:lo + d] = normalize_obs_reference(rows[:, lo:lo + d], obs_mean, obs_var, clip_obs, eps_obs)
+    if ret_var is not None:
+        rv = torch.as_tensor(ret_var, dtype=torch.float64).reshape(()).to(rows.device)
+        r = rows[:, d + A].to(torch.float64) / torch.sqrt(rv + _eps64(eps_reward))
+        out[:, d + A] = r.to(torch.float32).clamp_(-float(clip_reward), float(clip_reward))
+    return out
+
+
+def running_moments_reference(mean, var, count, x):
+    """One update of SB3's ``RunningMeanStd`` in float64, as ``fw_collect_stats`` merges a batch: ``(mean', var', count')`` from the
+    column sums and sums of squares of ``x`` ``[n, ...]`` -- batch mean ``s / n``, population variance ``max(s2 / n - bm^2, 0)``, then
+    the merge of Chan et al.  Nothing is written in place."""
+    mean, var = torch.as_tensor(mean, dtype=torch.float64), torch.as_tensor(var, dtype=torch.float64)
+    cnt = torch.as_tensor(count, dtype=torch.float64).reshape(-1)[0]
+    x = x.to(torch.float64).reshape(x.shape[0], -1)
+    n = float(x.shape[0])
+    bm = x.sum(0) / n
+    bv = ((x * x).sum(0) / n - bm * bm).clamp_min(0.0)
+    bm, bv = bm.reshape(mean.shape), bv.reshape(var.shape)
+    delta, tot = bm - mean, cnt + n
+    m2 = var * cnt + bv * n + delta * delta * cnt * n / tot
+    return mean + delta * n / tot, m2 / tot, tot.reshape(1)
+
+
+def stats_step_reference(obs_stats, ret_stats, returns, obs, reward, ended, gamma: float, update_obs: bool = True, update_ret: bool = True):
+    """What the statistics launch behind an env step does (``VecNormalize.step_wait``'s bookkeeping), in plain torch on any device:
+    ``(obs_stats', ret_stats', returns')``, each ``*_stats`` a ``(mean, var, count)`` triple.  The new observations ``obs`` ``[N, d]``
+    (the reset rows of the envs that ended, never a terminal observation) go into ``obs_stats``; ``returns gamma + reward`` goes into
+    ``ret_stats``; then ``returns`` is zeroed where ``ended``."""
+    returns = torch.as_tensor(returns, dtype=torch.float64).clone()
+    if update_obs:
+        obs_stats = running_moments_reference(*obs_stats, obs)
+    if update_ret:
+        returns = returns * float(gamma) + reward.to(torch.float64)
+        ret_stats = running_moments_reference(*ret_stats, returns)
+    returns = torch.where(ended.bool(), torch.zeros_like(returns), returns)
+    return tuple(obs_stats), tuple(ret_stats), returns
 
 
 # ---------------------------------------------------------------------------------------------
@@ -881,7 +974,13 @@ ACT_STOCHASTIC, ACT_DETERMINISTIC, ACT_WARMUP = 0, 1, 2
 class SAC:
     """SAC on a bare device env (``FixedwingLowLevelVecEnv``; the reference uses no normaliser).  A vec-step is act -> ``env.step_tensor``
     -> store -> G x (sample -> update); with ``use_graphs`` and the fused update it is one captured graph, with a second one for the
-    warm-up steps (with the torch update the graph ends behind the store and the gradient steps run eagerly)."""
+    warm-up steps (with the torch update the graph ends behind the store and the gradient steps run eagerly).
+
+    ``SACConfig.normalize_obs`` / ``normalize_reward``: SB3's ``VecNormalize`` with an off-policy buffer.  ``normalizer`` (a
+    :class:`~.rollout.VecNormalizeDevice` over the train env, used as the holder of the statistics only: the learner never steps through
+    it) owns ``obs_rms``, ``ret_rms`` and ``returns``; a vec-step becomes act (normalising on load) -> step -> [episode fold] -> stats ->
+    store (raw rows) -> G x (sample -> normalise -> update [-> priorities]).  :meth:`eval_env` wraps an evaluation env around the same
+    statistics tensors."""
 
     def __init__(self, env, cfg: SACConfig = SACConfig(), policy: Optional[SacPolicy] = None):
         self.env, self.cfg = env, cfg
@@ -927,6 +1026,17 @@ class SAC:
             if missing:
                 raise ValueError("SACConfig.episode_stats reads the env's output buffers after every step: the env has no " + ", ".join(missing))
             self.episode_monitor = EpisodeMonitor(self.N, int(cfg.stats_window_size), self.device, cfg.episode_fold)
+        # SACConfig.normalize_obs / normalize_reward: the running statistics, moved once per vec-step behind the env step
+        self.normalizer = None
+        if cfg.normalizes:
+            from .rollout import VecNormalizeDevice
+            missing = [k for k in ("obs", "rewards", "terminated", "truncated") if not hasattr(env, k)]
+            if missing:
+                raise ValueError("SACConfig.normalize_obs / normalize_reward read the env's output buffers after every step: the env has no "
+                                 + ", ".join(missing))
+            self.normalizer = VecNormalizeDevice(env, training=True, norm_obs=cfg.normalize_obs, norm_reward=cfg.normalize_reward,
+                                                 clip_obs=cfg.clip_obs, clip_reward=cfg.clip_reward, gamma=cfg.gamma, epsilon=cfg.norm_epsilon,
+                                                 use_fused_kernel=True)
 
     @property
     def rollout_stats(self) -> Dict[str, float]:
@@ -955,6 +1065,10 @@ class SAC:
         if not self._started:
             self.env.reset_tensor()
             self._started = True
+            if self.normalizer is not None:        # VecNormalize.reset(): the returns start at 0, the reset observations enter obs_rms once
+                self.normalizer.returns.zero_()
+                if self.cfg.normalize_obs:
+                    self._update_statistics(update_ret=False)
 
     def _image_for_act(self) -> torch.Tensor:
         if not self.fused.current():
@@ -963,6 +1077,14 @@ class SAC:
 
     def act(self, mode: int = ACT_STOCHASTIC, logp: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None) -> torch.Tensor:
         env = self.env
+        if self.cfg.normalize_obs:       # the same launch with the observation normalised on load; obs_stage stays raw
+            rms = self.normalizer.obs_rms
+            _lib.check(_lib.lib().fw_sac_act_norm(_p(self._image_for_act()), _p(env.obs), int(env.torch_dtype == torch.float64), self.N, self.d,
+                                                  self.A, self.cfg.hidden, int(mode), int(self.cfg.seed) & (2**64 - 1), self.env_offset,
+                                                  _p(self.buffer.counters), _p(self.act_f32), _p(self.act_env), _p(self.obs_stage), _p(logp),
+                                                  _p(eps), _p(rms.mean), _p(rms.var), self.cfg.clip_obs, self.cfg.norm_epsilon,
+                                                  _stream(self.device)))
+            return self.act_env
         _lib.check(_lib.lib().fw_sac_act(_p(self._image_for_act()), _p(env.obs), int(env.torch_dtype == torch.float64), self.N, self.d,
                                          self.A, self.cfg.hidden, int(mode), int(self.cfg.seed) & (2**64 - 1), self.env_offset,
                                          _p(self.buffer.counters), _p(self.act_f32), _p(self.act_env), _p(self.obs_stage), _p(logp), _p(eps),
@@ -973,18 +1095,46 @@ class SAC:
         e = self.env
         self.buffer.store(self.obs_stage, self.act_f32, e.rewards, e.obs, e.terminal_obs, e.terminated, e.truncated)
 
+    def _update_statistics(self, update_ret: Optional[bool] = None) -> None:
+        """``fw_collect_stats`` on the env's output buffers: the new observations into ``obs_rms`` (``normalize_obs``), ``returns gamma +
+        reward`` into ``ret_rms`` (``normalize_reward``; ``update_ret=False``: the reset's call), ``returns = 0`` where an episode ended.
+        It writes what the act and normalise launches read, on the same stream and never in the same launch."""
+        e, nz, cfg = self.env, self.normalizer, self.cfg
+        f64 = int(e.torch_dtype == torch.float64)
+        upd_ret = cfg.normalize_reward if update_ret is None else bool(update_ret)
+        _lib.check(_lib.lib().fw_collect_stats(_p(e.obs), f64, self.N, self.d, _p(nz.obs_rms.mean), _p(nz.obs_rms.var), _p(nz.obs_rms.count),
+                                               int(cfg.normalize_obs), _p(e.rewards), int(e.rewards.dtype == torch.float64), _p(e.terminated),
+                                               _p(e.truncated), _p(nz.returns), _p(nz.ret_rms.mean), _p(nz.ret_rms.var), _p(nz.ret_rms.count),
+                                               int(upd_ret), float(cfg.gamma), None, _p(nz._ws_stats), None, None, _stream(self.device)))
+
+    def normalize_batch(self, rows: torch.Tensor) -> torch.Tensor:
+        """``fw_replay_normalize`` in place on gathered rows, with the statistics as they are now (nothing with both flags off)."""
+        nz, cfg = self.normalizer, self.cfg
+        if nz is None:
+            return rows
+        assert rows.dtype == torch.float32 and rows.is_contiguous() and rows.shape[1] == self.buffer.row
+        _lib.check(_lib.lib().fw_replay_normalize(_p(rows), rows.shape[0], self.d, self.A,
+                                                  _p(nz.obs_rms.mean) if cfg.normalize_obs else None,
+                                                  _p(nz.obs_rms.var) if cfg.normalize_obs else None, cfg.clip_obs, cfg.norm_epsilon,
+                                                  _p(nz.ret_rms.var) if cfg.normalize_reward else None, cfg.clip_reward, cfg.norm_epsilon,
+                                                  _stream(self.device)))
+        return rows
+
     def _gradient_step_fused(self) -> None:
         if self.cfg.prioritized:         # sample -> weighted update -> priorities -> rebuild, all stream-ordered: one graph still
             self.buffer.sample(self.cfg.seed, self.batch, self.batch_idx, w_out=self.batch_w)
+            self.normalize_batch(self.batch)
             self.fused.run(self.batch, self.buffer.counters, weights=self.batch_w, td_out=self.batch_td)
             self.buffer.update_priorities(self.batch_idx, self.batch_td)
             return
         self.buffer.sample(self.cfg.seed, self.batch, self.batch_idx, gamma=self.cfg.gamma)
+        self.normalize_batch(self.batch)     # (behind the gather: hindsight rewards and n-step sums are formed on raw values)
         self.fused.run(self.batch, self.buffer.counters)
 
     def _gradient_step_torch(self) -> None:
         pri = self.cfg.prioritized
         self.buffer.sample(self.cfg.seed, self.batch, self.batch_idx, gamma=self.cfg.gamma, w_out=self.batch_w)
+        self.normalize_batch(self.batch)
         sac_noise(self.cfg.seed, self.buffer.counters, self.cfg.batch_size, self.A, out=self.noise)
         s = sac_update_torch(self._policy, self.optimizers, self.batch, self.noise[0], self.noise[1], self.cfg,
                              weights=self.batch_w if pri else None)
@@ -1000,6 +1150,8 @@ class SAC:
         if self.episode_monitor is not None:       # (same stream: the env's output buffers hold the step until the next launch)
             e = self.env
             self.episode_monitor.fold(e.rewards, e.terminated, e.truncated, getattr(e, "info", None))
+        if self.normalizer is not None:
+            self._update_statistics()
         self._store()
         if with_train:
             for _ in range(self.G):
@@ -1079,6 +1231,20 @@ class SAC:
         self.logs["env_steps_per_s"] = (self.num_timesteps - n0) / max(time.perf_counter() - t0, 1e-9)
         return self
 
+    def eval_env(self, venv):
+        """An evaluation wrapper of ``venv`` for :func:`~.evaluate.evaluate_policy` on ``self.policy``: a frozen
+        :class:`~.rollout.VecNormalizeDevice` (``training=False``, ``norm_reward=False``) whose ``obs_rms`` IS the learner's -- the same
+        tensors, so every evaluation sees the statistics as they are then.  With ``normalize_obs`` off it passes observations through."""
+        from .rollout import VecNormalizeDevice
+        cfg = self.cfg
+        ev = VecNormalizeDevice(venv, training=False, norm_obs=cfg.normalize_obs, norm_reward=False, clip_obs=cfg.clip_obs,
+                                clip_reward=cfg.clip_reward, gamma=cfg.gamma, epsilon=cfg.norm_epsilon)
+        if self.normalizer is not None:
+            if ev.obs_dim != self.d:
+                raise ValueError(f"the evaluation env has {ev.obs_dim} observations, the learner's statistics {self.d}")
+            ev.obs_rms = self.normalizer.obs_rms
+        return ev
+
     # ------------------------------------------------------------------ checkpoints
     def state_dict(self, include_buffer: bool = False):
         self.sync_policy()
@@ -1087,6 +1253,9 @@ class SAC:
               "buffer": self.buffer.state_dict(include_buffer), "num_timesteps": self.num_timesteps, "config": asdict(self.cfg)}
         if self.episode_monitor is not None:
             sd["episode_stats"] = self.episode_monitor.state_dict()
+        if self.normalizer is not None:
+            nz = self.normalizer
+            sd["normalizer"] = {"obs_rms": nz.obs_rms.state_dict(), "ret_rms": nz.ret_rms.state_dict(), "returns": nz.returns.cpu().clone()}
         return sd
 
     def load_state_dict(self, sd) -> None:
@@ -1101,3 +1270,7 @@ class SAC:
         self.fused._sig = None
         if self.episode_monitor is not None and sd.get("episode_stats") is not None:
             self.episode_monitor.load_state_dict(sd["episode_stats"])
+        if self.normalizer is not None and sd.get("normalizer") is not None:       # in place: the captured graphs hold these addresses
+            nz, st = self.normalizer, sd["normalizer"]                              # (a checkpoint without them: the statistics stay)
+            nz.obs_rms.load_state_dict(st["obs_rms"]); nz.ret_rms.load_state_dict(st["ret_rms"])
+            nz.returns.copy_(st["returns"])

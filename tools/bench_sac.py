@@ -12,12 +12,15 @@
     with her_goals 4 and with prioritized replay too;
   * prioritized replay (`per`), on the ring of a 16-env and of a 4096-env learner: the prioritized sample against the 1-step sample
     (B 256 and 4096), mark-new + store + rebuild against the store alone, the rebuild and the priority write-back alone, and the
-    weighted gradient step with its write-back and rebuild against the plain step (H 256, B 256 and 4096).
+    weighted gradient step with its write-back and rebuild against the plain step (H 256, B 256 and 4096);
+  * running normalisation (`norm`): fw_sac_act_norm against fw_sac_act at 16 and 4096 envs (same process, same observations, the
+    statistics a few vec-steps made), fw_replay_normalize at B 256 and 4096 with the statistics launch beside it, and the 4096-env
+    vec-step with its 4096-row gradient step with both flags on against both flags off.
 
 Timing: device events around `iters` back-to-back calls after `warmup` calls, median of `repeats` such blocks.  --runs N repeats the
 chosen sections N times (a "run" field tells them apart): the spread between runs is the run-to-run noise of a figure.
 
-    python tools/bench_sac.py [--quick] [--sections pieces,update,batches,end_to_end,end_to_end_large,per] [--batches 256,4096] [--runs 3]
+    python tools/bench_sac.py [--quick] [--sections pieces,update,batches,end_to_end,end_to_end_large,per,norm] [--batches 256,4096] [--runs 3]
 """
 import argparse
 import json
@@ -195,6 +198,27 @@ def bench_per(n, it):
     env.close()
 
 
+def bench_norm(n, it):
+    """Running normalisation on an n-env learner (d 21, A 6, H 256): the normalising act against the plain act on the same
+    observations, the statistics launch, and the in-place normalisation of a gathered batch."""
+    env = P.FixedwingLowLevelVecEnv(num_envs=n, seed=0)
+    sac = S.SAC(env, S.SACConfig(seed=0, use_graphs=False, normalize_obs=True, normalize_reward=True))
+    for _ in range(4):
+        sac.collect_step(train=False)
+    plain = S.SAC(env, S.SACConfig(seed=0, use_graphs=False))            # the same env buffers, the plain act launch
+    plain._started = True
+    base = timed_us(lambda: plain.act(S.ACT_STOCHASTIC), *it)
+    emit(what="act", envs=n, hidden=256, **base)
+    t = timed_us(lambda: sac.act(S.ACT_STOCHASTIC), *it)
+    emit(what="act_norm", envs=n, hidden=256, **t, ratio_to_act=round(t["us"] / base["us"], 3))
+    emit(what="collect_stats", envs=n, **timed_us(sac._update_statistics, *it))
+    for B in (256, 4096):
+        rows = sac.buffer.sample(0, torch.zeros((B, sac.buffer.row), device="cuda"))
+        emit(what="sample", envs=n, batch=B, n_steps=1, **timed_us(lambda: sac.buffer.sample(0, rows), *it))
+        emit(what="replay_normalize", envs=n, batch=B, **timed_us(lambda: sac.normalize_batch(rows), *it))
+    env.close()
+
+
 def bench_end_to_end(gradient_steps, fused, graphs, vec_steps):
     env = P.FixedwingLowLevelVecEnv(num_envs=16, seed=0)
     sac = S.SAC(env, S.SACConfig(seed=0, gradient_steps=gradient_steps, fused_update=fused, use_graphs=graphs))
@@ -208,23 +232,24 @@ def bench_end_to_end(gradient_steps, fused, graphs, vec_steps):
     env.close()
 
 
-def bench_end_to_end_large(variant, envs, batch, vec_steps, n_steps=1, her_goals=0, prioritized=False):
+def bench_end_to_end_large(variant, envs, batch, vec_steps, n_steps=1, her_goals=0, prioritized=False, normalize=False):
     """The large-env recipe: one `batch`-row gradient step per vec-step of `envs` envs, fused, one captured graph per vec-step."""
     make = P.FixedwingLowLevelDemoVecEnv if variant == "demo" else P.FixedwingLowLevelVecEnv
     env = make(num_envs=envs, seed=0)
     sac = S.SAC(env, S.SACConfig(seed=0, batch_size=batch, gradient_steps=1, learning_starts=envs, n_steps=n_steps, her_goals=her_goals,
-                                 **({"prioritized": True} if prioritized else {})))
+                                 **({"prioritized": True} if prioritized else {}),
+                                 **({"normalize_obs": True, "normalize_reward": True} if normalize else {})))
     sac.learn(envs * 8)                      # the warm-up step, the first trained steps, the captures
     torch.cuda.synchronize()
     t0, n0 = time.perf_counter(), sac.num_timesteps
     sac.learn(envs * vec_steps)
     dt = time.perf_counter() - t0
-    emit(what="end_to_end", env=variant, envs=envs, batch=batch, n_steps=n_steps, **({"her_goals": her_goals} if her_goals else {}), **({"prioritized": True} if prioritized else {}), gradient_steps=sac.G, fused_update=True, use_graphs=True, vec_steps=vec_steps,
+    emit(what="end_to_end", env=variant, envs=envs, batch=batch, n_steps=n_steps, **({"her_goals": her_goals} if her_goals else {}), **({"prioritized": True} if prioritized else {}), **({"normalize": True} if normalize else {}), gradient_steps=sac.G, fused_update=True, use_graphs=True, vec_steps=vec_steps,
          env_steps_per_s=round((sac.num_timesteps - n0) / dt, 1), us_per_vec_step=round(dt * 1e6 / vec_steps, 1))
     env.close()
 
 
-SECTIONS = ("pieces", "update", "batches", "end_to_end", "end_to_end_large", "per")
+SECTIONS = ("pieces", "update", "batches", "end_to_end", "end_to_end_large", "per", "norm")
 BATCHES = (256, 512, 576, 1024, 2048, 4096, 8192)
 
 
@@ -273,6 +298,12 @@ def main():
         if "per" in sections:
             for n in (16, 4096):
                 bench_per(n, it)
+        if "norm" in sections:
+            if hasattr(S._lib.lib(), "fw_replay_normalize"):       # (an A/B library of an older commit predates it: the plain vec-step alone)
+                for n in (16, 4096):
+                    bench_norm(n, it)
+                bench_end_to_end_large("tracking", 4096, 4096, max(vs // 2, 20), normalize=True)
+            bench_end_to_end_large("tracking", 4096, 4096, max(vs // 2, 20))
 
 
 if __name__ == "__main__":
