@@ -1639,7 +1639,7 @@ void fw_reset_kernel(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict
 #include "fwsim_probe.hpp"
 // ... and the off-policy learner of the low-level task (fw_sac_act, fw_replay_store / _sample, fw_sac_noise, fw_sac_update)
 #include "fwsim_sac.hpp"
-// ... and prioritized replay on its ring (fw_replay_per_*, fw_replay_sample_per, fw_sac_update_weighted)
+// ... and its replay ring (fwsim_replay.hpp) with prioritized replay on it (fw_replay_per_*, fw_replay_sample_per, fw_sac_update_weighted)
 #include "fwsim_per.hpp"
 
 // ======================================================================
@@ -3481,69 +3481,83 @@ int32_t fw_destroy(fw_handle h) {
   return FW_OK;
 }
 
-// ---- soft actor-critic (csrc/fwsim_sac.hpp) ----
+// ---- soft actor-critic (csrc/fwsim_sac.hpp) and its replay ring (csrc/fwsim_replay.hpp) ----
+#define FW_TRY(expr) do { const int32_t rc_ = (expr); if (rc_ != FW_OK) return rc_; } while (0)
+static int32_t sac_fail(int32_t rc, const char* who, const std::string& what) { g_err = std::string(who) + ": " + what; return rc; }
+static int32_t sac_launched() { HIP_TRY((fw_env*)nullptr, hipGetLastError()); return FW_OK; }          // the end of every entry point here
 static int32_t sac_check_shape(const char* who, int32_t d, int32_t A, int32_t H) {
-  if (d <= 0 || A <= 0 || H <= 0) { g_err = std::string(who) + ": obs_dim, act_dim and hidden must be positive"; return FW_EINVAL; }
-  if (!sac_shape_ok(d, A, H)) {
-    g_err = std::string(who) + ": built for obs_dim <= 64, act_dim <= 8 and hidden 64 or 256, got (" + std::to_string(d) + ", " + std::to_string(A) + ", " + std::to_string(H) + ")";
-    return FW_EUNSUPPORTED;
-  }
+  if (d <= 0 || A <= 0 || H <= 0) return sac_fail(FW_EINVAL, who, "obs_dim, act_dim and hidden must be positive");
+  if (!sac_shape_ok(d, A, H))
+    return sac_fail(FW_EUNSUPPORTED, who, "built for obs_dim <= 64, act_dim <= 8 and hidden 64 or 256, got (" + std::to_string(d) + ", " + std::to_string(A) + ", " + std::to_string(H) + ")");
   return FW_OK;
 }
 static int32_t sac_check_batch(const char* who, int32_t B) {
-  if (B <= 0) { g_err = std::string(who) + ": the batch size must be positive"; return FW_EINVAL; }
-  if (!sac_batch_ok(B)) { g_err = std::string(who) + ": built for batch sizes that are multiples of 16 in [16, 512] or multiples of 64 in (512, 8192], got " + std::to_string(B); return FW_EUNSUPPORTED; }
+  if (B <= 0) return sac_fail(FW_EINVAL, who, "the batch size must be positive");
+  if (!sac_batch_ok(B)) return sac_fail(FW_EUNSUPPORTED, who, "built for batch sizes that are multiples of 16 in [16, 512] or multiples of 64 in (512, 8192], got " + std::to_string(B));
+  return FW_OK;
+}
+static int32_t replay_check_ring(const char* who, int64_t capacity, int32_t row_floats, int32_t batch) {          // the ring as a sampler sees it
+  const bool ok = capacity > 0 && capacity <= 0x7fffffffLL && row_floats > 0 && batch > 0;
+  return ok ? FW_OK : sac_fail(FW_EINVAL, who, "capacity (below 2^31), row_floats and batch must be positive");
+}
+static int32_t replay_check_envs(const char* who, int64_t capacity, int32_t N) {          // the ring as whole vec-steps of N envs
+  return N > 0 && capacity >= N && capacity % N == 0 ? FW_OK : sac_fail(FW_EINVAL, who, "N must be positive and capacity a positive multiple of N");
+}
+static_assert(sizeof(fw_her_task) == sizeof(HerTask), "HerTask mirrors fw_her_task");
+static int32_t her_check(const char* who, const fw_her_task* task, int32_t obs_dim, int32_t row_floats) {
+  if (task->variant != FW_LL_VARIANT_TRACKING && task->variant != FW_LL_VARIANT_SAC_DEMO) return sac_fail(FW_EINVAL, who, "task variant must be 0 (tracking) or 1 (FW_LL_VARIANT_SAC_DEMO)");
+  if (obs_dim != kHerObsDim || row_floats != kHerRowFloats) return sac_fail(FW_EUNSUPPORTED, who, "built for the low-level task with Euler attitude, obs_dim 21 and row_floats 50");
+  return FW_OK;
+}
+static int32_t sac_act_check(const char* who, bool pointers, int32_t N, int32_t mode, int64_t env_offset) {
+  if (!pointers) return sac_fail(FW_EINVAL, who, "image, obs, counters, act_f32, act_env and obs_stage must be non-NULL");
+  if (N <= 0 || mode < 0 || mode > 2 || env_offset < 0) return sac_fail(FW_EINVAL, who, "N must be positive, mode 0, 1 or 2 and env_offset non-negative");
   return FW_OK;
 }
 static int64_t sac_ws_floats(int32_t d, int32_t A, int32_t H, int32_t B) { return (int64_t)sac_ws_wide(d, A, H, B).total; }
+// what fw_sac_update and fw_sac_update_weighted check behind their pointers, then the argument block both launch with
+static int32_t sac_step_args(const char* who, float* image, const float* batch_rows, int32_t d, int32_t A, int32_t H, int32_t B, const fw_sac_hyper* hyper,
+                             int64_t* counters, float* out, void* workspace, int64_t workspace_bytes, SacStepArgs* S) {
+  FW_TRY(sac_check_shape(who, d, A, H));
+  FW_TRY(sac_check_batch(who, B));
+  if (workspace_bytes < sac_ws_floats(d, A, H, B) * (int64_t)sizeof(float)) return sac_fail(FW_EINVAL, who, "the workspace is smaller than fw_sac_update_workspace_bytes asks for");
+  static_assert(sizeof(fw_sac_hyper) == sizeof(SacHyper), "fw_sac_hyper and SacHyper must agree");
+  *S = SacStepArgs{image, batch_rows, (float*)workspace, counters, out, d, A, H, B, {}};
+  std::memcpy(&S->hp, hyper, sizeof(SacHyper));
+  return FW_OK;
+}
 int32_t fw_sizeof_sac_hyper(void) { return (int32_t)sizeof(fw_sac_hyper); }
 int32_t fw_sac_param_count(int32_t obs_dim, int32_t act_dim, int32_t hidden) {
-  const int32_t rc = sac_check_shape("fw_sac_param_count", obs_dim, act_dim, hidden);
-  return rc != FW_OK ? rc : sac_layout(obs_dim, act_dim, hidden).total;
+  FW_TRY(sac_check_shape("fw_sac_param_count", obs_dim, act_dim, hidden));
+  return sac_layout(obs_dim, act_dim, hidden).total;
 }
 int64_t fw_sac_update_workspace_bytes(int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch) {
-  int32_t rc = sac_check_shape("fw_sac_update_workspace_bytes", obs_dim, act_dim, hidden);
-  if (rc == FW_OK) rc = sac_check_batch("fw_sac_update_workspace_bytes", batch);
-  return rc != FW_OK ? rc : sac_ws_floats(obs_dim, act_dim, hidden, batch) * (int64_t)sizeof(float);
+  FW_TRY(sac_check_shape("fw_sac_update_workspace_bytes", obs_dim, act_dim, hidden));
+  FW_TRY(sac_check_batch("fw_sac_update_workspace_bytes", batch));
+  return sac_ws_floats(obs_dim, act_dim, hidden, batch) * (int64_t)sizeof(float);
 }
 int32_t fw_sac_act(const float* image, const void* obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t mode,
                    uint64_t seed, int64_t env_offset, const int64_t* counters, float* act_f32, void* act_env, float* obs_stage, float* logp,
                    float* eps, void* hip_stream) {
-  if (!image || !obs || !counters || !act_f32 || !act_env || !obs_stage) { g_err = "fw_sac_act: image, obs, counters, act_f32, act_env and obs_stage must be non-NULL"; return FW_EINVAL; }
-  if (N <= 0 || mode < 0 || mode > 2 || env_offset < 0) { g_err = "fw_sac_act: N must be positive, mode 0, 1 or 2 and env_offset non-negative"; return FW_EINVAL; }
-  const int32_t rc = sac_check_shape("fw_sac_act", obs_dim, act_dim, hidden);
-  if (rc != FW_OK) return rc;
+  FW_TRY(sac_act_check("fw_sac_act", image && obs && counters && act_f32 && act_env && obs_stage, N, mode, env_offset));
+  FW_TRY(sac_check_shape("fw_sac_act", obs_dim, act_dim, hidden));
   DeviceGuard g(device_of(image));
-  SacActArgs a{image, obs, N, obs_dim, act_dim, mode, seed, env_offset, counters, act_f32, act_env, obs_stage, logp, eps};
-  const dim3 grid((unsigned)((N + 15) / 16)), block(256);
-  with_real(obs_is_f64 != 0, [&](auto t) {
-    using T = decltype(t);
-    if (hidden == 64) hipLaunchKernelGGL((fw_sac_act_kernel<T, 64>), grid, block, 0, (hipStream_t)hip_stream, a);
-    else hipLaunchKernelGGL((fw_sac_act_kernel<T, 256>), grid, block, 0, (hipStream_t)hip_stream, a);
-  });
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  const SacActArgs a{image, obs, N, obs_dim, act_dim, mode, seed, env_offset, counters, act_f32, act_env, obs_stage, logp, eps};
+  with_real(obs_is_f64 != 0, [&](auto t) { sac_act_launch<decltype(t), false>((hipStream_t)hip_stream, a, hidden); });
+  return sac_launched();
 }
 int32_t fw_sac_act_norm(const float* image, const void* obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, int32_t act_dim, int32_t hidden,
                         int32_t mode, uint64_t seed, int64_t env_offset, const int64_t* counters, float* act_f32, void* act_env, float* obs_stage,
                         float* logp, float* eps, const double* obs_mean, const double* obs_var, float clip_obs, float eps_obs, void* hip_stream) {
-  if (!image || !obs || !counters || !act_f32 || !act_env || !obs_stage) { g_err = "fw_sac_act_norm: image, obs, counters, act_f32, act_env and obs_stage must be non-NULL"; return FW_EINVAL; }
-  if (N <= 0 || mode < 0 || mode > 2 || env_offset < 0) { g_err = "fw_sac_act_norm: N must be positive, mode 0, 1 or 2 and env_offset non-negative"; return FW_EINVAL; }
+  FW_TRY(sac_act_check("fw_sac_act_norm", image && obs && counters && act_f32 && act_env && obs_stage, N, mode, env_offset));
   if (mode != 2 && (!obs_mean || !obs_var)) { g_err = "fw_sac_act_norm: modes 0 and 1 need obs_mean and obs_var"; return FW_EINVAL; }
   if (mode != 2 && !(clip_obs > 0.0f && eps_obs >= 0.0f)) { g_err = "fw_sac_act_norm: clip_obs must be positive and eps_obs non-negative"; return FW_EINVAL; }
-  const int32_t rc = sac_check_shape("fw_sac_act_norm", obs_dim, act_dim, hidden);
-  if (rc != FW_OK) return rc;
+  FW_TRY(sac_check_shape("fw_sac_act_norm", obs_dim, act_dim, hidden));
   DeviceGuard g(device_of(image));
-  SacActNormArgs a{{image, obs, N, obs_dim, act_dim, mode, seed, env_offset, counters, act_f32, act_env, obs_stage, logp, eps},
-                   obs_mean, obs_var, clip_obs, eps_obs};
-  const dim3 grid((unsigned)((N + 15) / 16)), block(256);
-  with_real(obs_is_f64 != 0, [&](auto t) {
-    using T = decltype(t);
-    if (hidden == 64) hipLaunchKernelGGL((fw_sac_act_kernel<T, 64, true>), grid, block, 0, (hipStream_t)hip_stream, a);
-    else hipLaunchKernelGGL((fw_sac_act_kernel<T, 256, true>), grid, block, 0, (hipStream_t)hip_stream, a);
-  });
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  const SacActNormArgs a{{image, obs, N, obs_dim, act_dim, mode, seed, env_offset, counters, act_f32, act_env, obs_stage, logp, eps},
+                         obs_mean, obs_var, clip_obs, eps_obs};
+  with_real(obs_is_f64 != 0, [&](auto t) { sac_act_launch<decltype(t), true>((hipStream_t)hip_stream, a, hidden); });
+  return sac_launched();
 }
 int32_t fw_replay_normalize(float* batch_rows, int32_t batch, int32_t obs_dim, int32_t act_dim, const double* obs_mean, const double* obs_var,
                             float clip_obs, float eps_obs, const double* ret_var, float clip_reward, float eps_reward, void* hip_stream) {
@@ -3558,8 +3572,7 @@ int32_t fw_replay_normalize(float* batch_rows, int32_t batch, int32_t obs_dim, i
   DeviceGuard g(device_of(batch_rows));
   SacBatchNormArgs n{batch_rows, batch, obs_dim, act_dim, obs_mean, obs_var, ret_var, clip_obs, eps_obs, clip_reward, eps_reward};
   hipLaunchKernelGGL(fw_replay_normalize_kernel, dim3((unsigned)(((int64_t)batch + kSacNormRows - 1) / kSacNormRows)), dim3(256), 0, (hipStream_t)hip_stream, n);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return sac_launched();
 }
 int32_t fw_replay_store(float* ring, int64_t capacity, int64_t* counters, const float* obs_stage, const float* act_f32, const void* reward,
                         const void* next_obs, const void* terminal_obs, const uint8_t* terminated, const uint8_t* truncated, int32_t env_is_f64,
@@ -3575,76 +3588,66 @@ int32_t fw_replay_store(float* ring, int64_t capacity, int64_t* counters, const 
     hipLaunchKernelGGL((fw_replay_store_kernel<T>), dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, s);
   });
   hipLaunchKernelGGL(fw_replay_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, counters, capacity, N);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return sac_launched();
 }
 int32_t fw_replay_sample(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
                          float* out, int32_t* idx_out, void* hip_stream) {
   if (!ring || !counters || !out) { g_err = "fw_replay_sample: ring, counters and out must be non-NULL"; return FW_EINVAL; }
-  if (capacity <= 0 || capacity > 0x7fffffffLL || row_floats <= 0 || batch <= 0) { g_err = "fw_replay_sample: capacity (below 2^31), row_floats and batch must be positive"; return FW_EINVAL; }
+  FW_TRY(replay_check_ring("fw_replay_sample", capacity, row_floats, batch));
   DeviceGuard g(device_of(ring));
   hipLaunchKernelGGL(fw_replay_sample_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, ring, capacity, counters, seed,
                      row_floats, batch, out, idx_out);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return sac_launched();
 }
 int32_t fw_replay_mark_ends(uint8_t* ends, int64_t capacity, const int64_t* counters, const uint8_t* terminated, const uint8_t* truncated, int32_t N,
                             void* hip_stream) {
   if (!ends || !counters || !terminated || !truncated) { g_err = "fw_replay_mark_ends: every pointer must be non-NULL"; return FW_EINVAL; }
-  if (N <= 0 || capacity < N || capacity % N != 0) { g_err = "fw_replay_mark_ends: N must be positive and capacity a positive multiple of N"; return FW_EINVAL; }
+  FW_TRY(replay_check_envs("fw_replay_mark_ends", capacity, N));
   DeviceGuard g(device_of(ends));
   hipLaunchKernelGGL(fw_replay_mark_ends_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, ends, capacity, counters,
                      terminated, truncated, N);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return sac_launched();
 }
 int32_t fw_replay_sample_nstep(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
                                float* out, int32_t* idx_out, const uint8_t* ends, int32_t obs_dim, int32_t N, int32_t n_steps, float gamma,
                                int32_t* k_out, void* hip_stream) {
   if (!ring || !counters || !out || !ends) { g_err = "fw_replay_sample_nstep: ring, counters, out and ends must be non-NULL"; return FW_EINVAL; }
-  if (capacity <= 0 || capacity > 0x7fffffffLL || row_floats <= 0 || batch <= 0) { g_err = "fw_replay_sample_nstep: capacity (below 2^31), row_floats and batch must be positive"; return FW_EINVAL; }
-  if (N <= 0 || capacity < N || capacity % N != 0) { g_err = "fw_replay_sample_nstep: N must be positive and capacity a positive multiple of N"; return FW_EINVAL; }
+  FW_TRY(replay_check_ring("fw_replay_sample_nstep", capacity, row_floats, batch));
+  FW_TRY(replay_check_envs("fw_replay_sample_nstep", capacity, N));
   if (obs_dim <= 0 || row_floats < 2 * obs_dim + 3) { g_err = "fw_replay_sample_nstep: row_floats must be 2 obs_dim + act_dim + 2 with positive obs_dim and act_dim"; return FW_EINVAL; }
   if (n_steps < 1 || n_steps > kSacMaxNStep) { g_err = "fw_replay_sample_nstep: built for n_steps in [1, 16]"; return FW_EUNSUPPORTED; }
   DeviceGuard g(device_of(ring));
   hipLaunchKernelGGL(fw_replay_sample_nstep_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, ring, capacity, counters,
                      seed, row_floats, batch, out, idx_out, ends, obs_dim, N, n_steps, gamma, k_out);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return sac_launched();
 }
 int32_t fw_sizeof_her_task(void) { return (int32_t)sizeof(fw_her_task); }
-static_assert(sizeof(fw_her_task) == sizeof(HerTask), "HerTask mirrors fw_her_task");
-static bool her_task_ok(const fw_her_task* t) { return t->variant == FW_LL_VARIANT_TRACKING || t->variant == FW_LL_VARIANT_SAC_DEMO; }
 int32_t fw_replay_sample_her(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
                              float* out, int32_t* idx_out, const uint8_t* ends, int32_t obs_dim, int32_t N, int32_t horizon, float relabel_prob,
                              const fw_her_task* task, int32_t* j_out, void* hip_stream) {
   if (!ring || !counters || !out || !ends || !task) { g_err = "fw_replay_sample_her: ring, counters, out, ends and task must be non-NULL"; return FW_EINVAL; }
   if (capacity <= 0 || capacity > 0x7fffffffLL || row_floats <= 0 || batch <= 0 || obs_dim <= 0) { g_err = "fw_replay_sample_her: capacity (below 2^31), row_floats, batch and obs_dim must be positive"; return FW_EINVAL; }
-  if (N <= 0 || capacity < N || capacity % N != 0) { g_err = "fw_replay_sample_her: N must be positive and capacity a positive multiple of N"; return FW_EINVAL; }
+  FW_TRY(replay_check_envs("fw_replay_sample_her", capacity, N));
   if (!(relabel_prob >= 0.0f && relabel_prob <= 1.0f)) { g_err = "fw_replay_sample_her: relabel_prob must lie in [0, 1]"; return FW_EINVAL; }
-  if (!her_task_ok(task)) { g_err = "fw_replay_sample_her: task variant must be 0 (tracking) or 1 (FW_LL_VARIANT_SAC_DEMO)"; return FW_EINVAL; }
-  if (obs_dim != kHerObsDim || row_floats != kHerRowFloats) { g_err = "fw_replay_sample_her: built for the low-level task with Euler attitude, obs_dim 21 and row_floats 50"; return FW_EUNSUPPORTED; }
+  FW_TRY(her_check("fw_replay_sample_her", task, obs_dim, row_floats));
   if (horizon < 1 || horizon > kSacMaxHerHorizon) { g_err = "fw_replay_sample_her: built for horizon in [1, 64]"; return FW_EUNSUPPORTED; }
   const HerTask T{task->variant, task->dome, task->min_speed};
   const uint64_t thresh = (uint64_t)((double)relabel_prob * 4294967296.0);
   DeviceGuard g(device_of(ring));
   hipLaunchKernelGGL(fw_replay_sample_her_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, ring, capacity, counters,
                      seed, batch, out, idx_out, ends, N, horizon, thresh, T, j_out);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return sac_launched();
 }
 int32_t fw_her_reward(const float* rows, int32_t row_floats, int32_t batch, int32_t obs_dim, const float* goals, const fw_her_task* task,
                       float* reward_out, void* hip_stream) {
   if (!rows || !goals || !task || !reward_out) { g_err = "fw_her_reward: every pointer must be non-NULL"; return FW_EINVAL; }
   if (row_floats <= 0 || batch <= 0 || obs_dim <= 0) { g_err = "fw_her_reward: row_floats, batch and obs_dim must be positive"; return FW_EINVAL; }
-  if (!her_task_ok(task)) { g_err = "fw_her_reward: task variant must be 0 (tracking) or 1 (FW_LL_VARIANT_SAC_DEMO)"; return FW_EINVAL; }
-  if (obs_dim != kHerObsDim || row_floats != kHerRowFloats) { g_err = "fw_her_reward: built for the low-level task with Euler attitude, obs_dim 21 and row_floats 50"; return FW_EUNSUPPORTED; }
+  FW_TRY(her_check("fw_her_reward", task, obs_dim, row_floats));
   const HerTask T{task->variant, task->dome, task->min_speed};
   DeviceGuard g(device_of(rows));
   hipLaunchKernelGGL(fw_her_reward_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, rows, row_floats, batch, obs_dim,
                      goals, T, reward_out);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return sac_launched();
 }
 int32_t fw_sac_noise(uint64_t seed, const int64_t* counters, int32_t batch, int32_t act_dim, float* out, void* hip_stream) {
   if (!counters || !out) { g_err = "fw_sac_noise: counters and out must be non-NULL"; return FW_EINVAL; }
@@ -3653,56 +3656,43 @@ int32_t fw_sac_noise(uint64_t seed, const int64_t* counters, int32_t batch, int3
   DeviceGuard g(device_of(out));
   hipLaunchKernelGGL(fw_sac_noise_kernel, dim3((unsigned)((2 * batch * ((act_dim + 3) / 4) + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, seed,
                      counters, batch, act_dim, out);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return sac_launched();
 }
 int32_t fw_sac_update(float* image, const float* batch_rows, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch, const fw_sac_hyper* hyper,
                       int64_t* counters, float* out, void* workspace, int64_t workspace_bytes, void* hip_stream) {
   if (!image || !batch_rows || !hyper || !counters || !workspace) { g_err = "fw_sac_update: image, batch_rows, hyper, counters and workspace must be non-NULL"; return FW_EINVAL; }
-  int32_t rc = sac_check_shape("fw_sac_update", obs_dim, act_dim, hidden);
-  if (rc == FW_OK) rc = sac_check_batch("fw_sac_update", batch);
-  if (rc != FW_OK) return rc;
-  if (workspace_bytes < sac_ws_floats(obs_dim, act_dim, hidden, batch) * (int64_t)sizeof(float)) { g_err = "fw_sac_update: the workspace is smaller than fw_sac_update_workspace_bytes asks for"; return FW_EINVAL; }
-  static_assert(sizeof(fw_sac_hyper) == sizeof(SacHyper), "fw_sac_hyper and SacHyper must agree");
+  SacStepArgs S;
+  FW_TRY(sac_step_args("fw_sac_update", image, batch_rows, obs_dim, act_dim, hidden, batch, hyper, counters, out, workspace, workspace_bytes, &S));
   DeviceGuard g(device_of(image));
-  SacStepArgs S{};
-  S.image = image; S.batch = batch_rows; S.ws = (float*)workspace; S.ctr = counters; S.out = out;
-  S.d = obs_dim; S.A = act_dim; S.H = hidden; S.B = batch;
-  std::memcpy(&S.hp, hyper, sizeof(SacHyper));
   sac_update_launch((hipStream_t)hip_stream, S);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return sac_launched();
 }
 
 // ---- prioritized replay (csrc/fwsim_per.hpp) ----
 static int32_t per_check_capacity(const char* who, int64_t capacity) {
-  if (capacity <= 0) { g_err = std::string(who) + ": capacity must be positive"; return FW_EINVAL; }
-  if (capacity > kPerMaxCapacity) { g_err = std::string(who) + ": built for a capacity of at most 2^22 rows (64 level-2 entries), got " + std::to_string((long long)capacity); return FW_EUNSUPPORTED; }
+  if (capacity <= 0) return sac_fail(FW_EINVAL, who, "capacity must be positive");
+  if (capacity > kPerMaxCapacity) return sac_fail(FW_EUNSUPPORTED, who, "built for a capacity of at most 2^22 rows (64 level-2 entries), got " + std::to_string((long long)capacity));
   return FW_OK;
 }
 int32_t fw_replay_per_mark_new(float* prio, int64_t capacity, const int64_t* counters, const float* per_state, int32_t N, void* hip_stream) {
   if (!prio || !counters || !per_state) { g_err = "fw_replay_per_mark_new: every pointer must be non-NULL"; return FW_EINVAL; }
-  if (N <= 0 || capacity < N || capacity % N != 0) { g_err = "fw_replay_per_mark_new: N must be positive and capacity a positive multiple of N"; return FW_EINVAL; }
-  const int32_t rc = per_check_capacity("fw_replay_per_mark_new", capacity);
-  if (rc != FW_OK) return rc;
+  FW_TRY(replay_check_envs("fw_replay_per_mark_new", capacity, N));
+  FW_TRY(per_check_capacity("fw_replay_per_mark_new", capacity));
   DeviceGuard g(device_of(prio));
   hipLaunchKernelGGL(fw_replay_per_mark_new_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)hip_stream, prio, capacity, counters,
                      per_state, N);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return sac_launched();
 }
 int32_t fw_replay_per_rebuild(const float* prio, int64_t capacity, float* sum1, float* min1, float* sum2, float* min2, float* per_state,
                               void* hip_stream) {
   if (!prio || !sum1 || !min1 || !sum2 || !min2 || !per_state) { g_err = "fw_replay_per_rebuild: every pointer must be non-NULL"; return FW_EINVAL; }
-  const int32_t rc = per_check_capacity("fw_replay_per_rebuild", capacity);
-  if (rc != FW_OK) return rc;
+  FW_TRY(per_check_capacity("fw_replay_per_rebuild", capacity));
   DeviceGuard g(device_of(prio));
   const int n1 = per_groups(capacity);
   hipLaunchKernelGGL(fw_replay_per_level1_kernel, dim3((unsigned)((n1 + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, prio, (int)capacity, sum1, min1);
   hipLaunchKernelGGL(fw_replay_per_level2_kernel, dim3(1), dim3(256), 0, (hipStream_t)hip_stream, (const float*)sum1, (const float*)min1, n1, sum2, min2,
                      per_state);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return sac_launched();
 }
 int32_t fw_replay_sample_per(const float* ring, int64_t capacity, const int64_t* counters, uint64_t seed, int32_t row_floats, int32_t batch,
                              float* out, int32_t* idx_out, float* w_out, const float* prio, const float* sum1, const float* sum2,
@@ -3710,47 +3700,36 @@ int32_t fw_replay_sample_per(const float* ring, int64_t capacity, const int64_t*
   if (!ring || !counters || !out || !prio || !sum1 || !sum2 || !per_state) { g_err = "fw_replay_sample_per: ring, counters, out, prio, sum1, sum2 and per_state must be non-NULL"; return FW_EINVAL; }
   if (row_floats <= 0 || batch <= 0) { g_err = "fw_replay_sample_per: row_floats and batch must be positive"; return FW_EINVAL; }
   if (!(beta0 >= 0.0f && beta0 <= 1.0f) || beta_steps < 0) { g_err = "fw_replay_sample_per: beta0 must lie in [0, 1] and beta_steps must not be negative"; return FW_EINVAL; }
-  const int32_t rc = per_check_capacity("fw_replay_sample_per", capacity);
-  if (rc != FW_OK) return rc;
+  FW_TRY(per_check_capacity("fw_replay_sample_per", capacity));
   DeviceGuard g(device_of(ring));
   hipLaunchKernelGGL(fw_replay_sample_per_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, (hipStream_t)hip_stream, ring, (int)capacity, counters,
                      seed, row_floats, batch, out, idx_out, w_out, prio, sum1, sum2, per_state, beta0, beta_steps);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return sac_launched();
 }
 int32_t fw_replay_per_update(float* prio, int64_t capacity, const int32_t* idx, const float* td, int32_t batch, float alpha, float eps,
                              float* per_state, void* hip_stream) {
   if (!prio || !idx || !td || !per_state) { g_err = "fw_replay_per_update: every pointer must be non-NULL"; return FW_EINVAL; }
   if (batch <= 0) { g_err = "fw_replay_per_update: batch must be positive"; return FW_EINVAL; }
   if (!(alpha >= 0.0f && alpha <= 1.0f) || !(eps > 0.0f) || !(eps < 1e30f)) { g_err = "fw_replay_per_update: alpha must lie in [0, 1] and eps must be positive and finite"; return FW_EINVAL; }
-  const int32_t rc = per_check_capacity("fw_replay_per_update", capacity);
-  if (rc != FW_OK) return rc;
+  FW_TRY(per_check_capacity("fw_replay_per_update", capacity));
   DeviceGuard g(device_of(prio));
   const dim3 grid((unsigned)((batch + 255) / 256)), block(256);
   hipLaunchKernelGGL(fw_replay_per_clear_kernel, grid, block, 0, (hipStream_t)hip_stream, prio, (int)capacity, idx, batch);
   hipLaunchKernelGGL(fw_replay_per_max_kernel, grid, block, 0, (hipStream_t)hip_stream, prio, (int)capacity, idx, td, batch, alpha, eps, per_state);
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return sac_launched();
 }
 int32_t fw_sac_update_weighted(float* image, const float* batch_rows, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch,
                                const fw_sac_hyper* hyper, int64_t* counters, float* out, void* workspace, int64_t workspace_bytes,
                                const float* weights, float* td_out, void* hip_stream) {
   if (!image || !batch_rows || !hyper || !counters || !workspace || !weights) { g_err = "fw_sac_update_weighted: image, batch_rows, hyper, counters, workspace and weights must be non-NULL"; return FW_EINVAL; }
-  int32_t rc = sac_check_shape("fw_sac_update_weighted", obs_dim, act_dim, hidden);
-  if (rc == FW_OK) rc = sac_check_batch("fw_sac_update_weighted", batch);
-  if (rc != FW_OK) return rc;
-  if (workspace_bytes < sac_ws_floats(obs_dim, act_dim, hidden, batch) * (int64_t)sizeof(float)) { g_err = "fw_sac_update_weighted: the workspace is smaller than fw_sac_update_workspace_bytes asks for"; return FW_EINVAL; }
+  SacStepArgs S;
+  FW_TRY(sac_step_args("fw_sac_update_weighted", image, batch_rows, obs_dim, act_dim, hidden, batch, hyper, counters, out, workspace, workspace_bytes, &S));
   DeviceGuard g(device_of(image));
-  SacStepArgs S{};
-  S.image = image; S.batch = batch_rows; S.ws = (float*)workspace; S.ctr = counters; S.out = out;
-  S.d = obs_dim; S.A = act_dim; S.H = hidden; S.B = batch;
-  std::memcpy(&S.hp, hyper, sizeof(SacHyper));
   float* g3 = S.ws + sac_ws(obs_dim, act_dim, hidden, batch).g3;
   sac_update_launch((hipStream_t)hip_stream, S, [&](hipStream_t st) {
     hipLaunchKernelGGL(fw_sac_per_weight_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, g3, batch, weights, td_out);
   });
-  HIP_TRY((fw_env*)nullptr, hipGetLastError());
-  return FW_OK;
+  return sac_launched();
 }
 
 #ifdef FW_PROFILE

@@ -15,12 +15,9 @@
 // 4l + j is E_l for j = 0 and E_l + p_(j-1) otherwise -- the running sum of the entry before it, so the sequence never decreases.
 // The rebuild and the draw share this code: the sums are recomputed from the leaves every time, never adjusted, and two runs give the
 // same bits.  No atomics but the integer max of fw_replay_per_update, no in-grid wait.
-// (Lane reads and ballots are the compiler builtins, as in the n-step gather of fwsim_sac.hpp.)
+// (Lane reads and ballots are the compiler builtins: see csrc/fwsim_replay.hpp.)
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "fwsim_sac.hpp"
+#include "fwsim_replay.hpp"
 
 namespace fwsim {
 
@@ -102,8 +99,7 @@ __global__ __launch_bounds__(256) void fw_replay_per_mark_new_kernel(float* __re
                                                                      const float* __restrict__ per_state, int32_t N) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
-  int64_t cursor = ctr[0];
-  if (cursor < 0 || cursor + N > capacity) cursor = 0;
+  const int64_t cursor = replay_cursor(ctr, capacity, N);
   prio[cursor + i] = per_state[PER_S_MAX];
 }
 
@@ -138,8 +134,8 @@ __device__ __forceinline__ int per_pick(const float* __restrict__ base, int n, i
   t = t - per_lane_read(sel_front, L);
   return 4 * L + j;
 }
-// One wave per batch row, fw_replay_sample_kernel's Philox block; u = (o[0] + 0.5) 2^-32 in double, t = (float)(u total), three levels
-// of per_pick, then fw_replay_sample_kernel's gather.  w = (p_min / p_row)^beta as exp(beta log x) in fp32.
+// One wave per batch row, the word every sampler draws from (replay_draw_word: o0); u = (o0 + 0.5) 2^-32 in double, t = (float)(u total),
+// three levels of per_pick, then the uniform sampler's row copy.  w = (p_min / p_row)^beta as exp(beta log x) in fp32.
 __global__ __launch_bounds__(256) void fw_replay_sample_per_kernel(const float* __restrict__ ring, int capacity, const int64_t* __restrict__ ctr,
                                                                    uint64_t seed, int R, int B, float* __restrict__ batch, int32_t* __restrict__ idx_out,
                                                                    float* __restrict__ w_out, const float* __restrict__ prio,
@@ -147,11 +143,9 @@ __global__ __launch_bounds__(256) void fw_replay_sample_per_kernel(const float* 
                                                                    const float* __restrict__ per_state, float beta0, int64_t beta_steps) {
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (b >= B) return;
-  const uint64_t gs = (uint64_t)ctr[3];
-  uint32_t o[4];
-  philox4x32_10((uint32_t)b, 0u, (uint32_t)gs, (uint32_t)(gs >> 32) ^ kSacTagSample, (uint32_t)seed, (uint32_t)(seed >> 32), o);
+  const uint32_t o0 = replay_draw_word(b, (uint64_t)ctr[3], seed);
   const int n1 = (capacity + kPerGroup - 1) / kPerGroup, n2 = (n1 + kPerGroup - 1) / kPerGroup;
-  const double u = ((double)o[0] + 0.5) * (1.0 / 4294967296.0);
+  const double u = ((double)o0 + 0.5) * (1.0 / 4294967296.0);
   float t = (float)(u * (double)per_state[PER_S_TOTAL]);
   const int k2 = per_pick(sum2, n2, lane, t);                                   // k2 < n2
   const int left1 = n1 - k2 * kPerGroup;
@@ -159,7 +153,7 @@ __global__ __launch_bounds__(256) void fw_replay_sample_per_kernel(const float* 
   const int left0 = capacity - g * kPerGroup;
   uint32_t idx = (uint32_t)(g * kPerGroup + per_pick(prio + (size_t)g * kPerGroup, left0 < kPerGroup ? left0 : kPerGroup, lane, t));
   if (idx >= (uint32_t)capacity) idx = 0u;                                       // (cannot happen: every pick stays inside its group)
-  for (int c = lane; c < R; c += 64) batch[(size_t)b * R + c] = ring[(size_t)idx * R + c];
+  replay_copy_row(batch, b, ring, idx, R, lane);
   if (lane == 0) {
     if (idx_out) idx_out[b] = (int32_t)idx;
     if (w_out) {

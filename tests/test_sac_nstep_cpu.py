@@ -136,3 +136,27 @@ def test_checkpoint_rules():
     assert torch.equal(three.ends, torch.arange(24, dtype=torch.uint8) % 4)          # (the refused load changed nothing)
     one.load_state_dict(sd)
     assert torch.equal(one.ring, three.ring) and one.ends is None
+
+
+# (i, limit, cursor, rows whose ends byte is set) -> k on a 24-row ring of 4 envs (vec-step t is rows 4 t .. 4 t + 3), worked out by hand
+WALKS = [
+    (1, 3, 20, (), 3),           # stops at the limit: rows 1, 5, 9; no end, and the newest vec-step (rows 16 .. 19) is further on
+    (2, 5, 20, (6,), 2),         # stops at an ends byte: rows 2, 6
+    (9, 5, 20, (), 3),           # stops at the newest vec-step: rows 9, 13, 17, and 17 lies in rows 16 .. 19
+    (19, 5, 8, (), 4),           # wraps past the end of the ring: rows 19, 23, 3, 7, and 7 lies in the newest vec-step, rows 4 .. 7
+    (14, 5, 0, (), 3),           # cursor == 0: the newest vec-step is the ring's last one, rows 20 .. 23; rows 14, 18, 22
+]
+
+
+@pytest.mark.parametrize("i,limit,cursor,marked,k", WALKS)
+def test_the_walk_by_hand(i, limit, cursor, marked, k):
+    cap, n = 24, 4
+    ends = np.zeros(cap, dtype=np.uint8)
+    ends[list(marked)] = S.END_TRUNCATED
+    assert S._walk(i, limit, ends, n, cap, (cursor - n) % cap) == k
+    rng = np.random.default_rng(i)
+    ring = rng.standard_normal((cap, S.row_floats(D, A))).astype(np.float32)
+    assert S.nstep_rows_reference(ring, ends, cursor, cap, n, [i], limit, GAMMA, D)[1].tolist() == [k]
+    her_ring = rng.standard_normal((cap, S.HER_ROW_FLOATS)).astype(np.float32)
+    js = S.her_rows_reference(her_ring, ends, cursor, cap, n, [i], [1], [2 ** 32 - 1], limit, S.HerTask(0, 100.0, 5.0))[1]
+    assert js.tolist() == [k - 1]
