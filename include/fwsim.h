@@ -1090,6 +1090,41 @@ int32_t fw_sac_act_norm(const float* image, const void* obs, int32_t obs_is_f64,
  * element is written by one thread from its own old value: no atomics, no in-grid wait. */
 int32_t fw_replay_normalize(float* batch_rows, int32_t batch, int32_t obs_dim, int32_t act_dim, const double* obs_mean, const double* obs_var,
                             float clip_obs, float eps_obs, const double* ret_var, float clip_reward, float eps_reward, void* hip_stream);
+/* ---- TD3 for the low-level task (csrc/fwsim_td3.hpp; SB3 `TD3("MlpPolicy")`, one gradient step of `TD3.train()`) ----
+ * ReLU MLPs in fp32: the actor obs_dim -> hidden -> hidden -> act_dim (tanh on its output), two critics (obs_dim + act_dim) -> hidden ->
+ * hidden -> 1, and a target of each of the three.  Built for obs_dim <= 64, act_dim <= 8, hidden 64 or 256 and batches that are multiples
+ * of 16 in [16, 512]: anything else FW_EUNSUPPORTED; NULL pointers and non-positive sizes FW_EINVAL.  No handle, caller-owned device
+ * buffers, stream-ordered, nothing allocates, synchronises or reads device state on the host: both entry points can be captured into a
+ * graph.  The replay ring, its counters, its rows and every sampler are the ones above.
+ *
+ * Flat image (floats, fw_td3_param_count of them), W[in][out] = torch Linear.weight^T, one network as in the SAC image:
+ *   actor | q1 | q2 | actor target | q1 target | q2 target | exp_avg[T] | exp_avg_sq[T] | tail[4]
+ *   T = actor + 2 critics (the moments cover the trained range actor | q1 | q2);  tail[0] = gradient steps taken, tail[1] = actor steps
+ *   taken (int32): the critics' Adam bias correction counts the first, the actor's the second. */
+typedef struct fw_td3_hyper {
+  float lr, gamma, tau, beta1, beta2, eps;
+  float policy_noise, noise_clip;             /* target policy smoothing: clamp(policy_noise eps, +-noise_clip) */
+  uint64_t seed;                              /* of the smoothing noise (fw_sac_noise's first block) */
+} fw_td3_hyper;
+int32_t fw_sizeof_td3_hyper(void);
+int32_t fw_td3_param_count(int32_t obs_dim, int32_t act_dim, int32_t hidden);
+int64_t fw_td3_update_workspace_bytes(int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch);
+/* fw_sac_act's launch for the deterministic actor, with its modes: 0 exploring, clamp(tanh(mean) + sigma eps, -1, 1) with eps keyed as
+ * fw_sac_act keys it (seed, env_offset + row, counters[2]); 1 deterministic, tanh(mean); 2 uniform in [-1, 1) without a forward.  Writes
+ * act_f32, act_env (the env's dtype), obs_stage (the fp32 copy of obs) and, where non-NULL, eps [N, act_dim] (the draw, also in mode 1;
+ * zeros in mode 2).  sigma must be non-negative. */
+int32_t fw_td3_act(const float* image, const void* obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t mode,
+                   uint64_t seed, int64_t env_offset, const int64_t* counters, float* act_f32, void* act_env, float* obs_stage, float sigma,
+                   float* eps, void* hip_stream);
+/* One gradient step on the image from batch_rows [batch, 2 obs_dim + act_dim + 2]: a fixed launch sequence over the SAC product kernel.
+ * The critics train on mse(Q1, y) + mse(Q2, y), y = r + (1 - last) gamma min(Q1t, Q2t)(s', a'), a' = clamp(tanh(actor_target(s')) +
+ * clamp(policy_noise eps, +-noise_clip), -1, 1), eps = fw_sac_noise's first block at counters[3].  with_actor != 0 (the caller passes it on
+ * every policy_delay-th step) adds the actor's step on -mean Q1(s, tanh(actor(s))) with the stepped critics and the Polyak step of all
+ * three targets: 28 launches.  with_actor == 0: 13 launches; the actor, its moments, all three targets and tail[1] are not written.
+ * out (optional) [2]: critic loss, actor loss (written with the actor part only).  Increments tail[0] and counters[3].  Every sum over
+ * the batch runs in a fixed order: two runs give the same bits. */
+int32_t fw_td3_update(float* image, const float* batch_rows, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch, const fw_td3_hyper* hyper,
+                      int32_t with_actor, int64_t* counters, float* out, void* workspace, int64_t workspace_bytes, void* hip_stream);
 const char* fw_last_error(fw_handle h); /* h may be NULL: last create/validate error */
 int32_t fw_destroy(fw_handle h);
 

@@ -39,6 +39,7 @@ EXPORTS = (
     "fw_sizeof_her_task", "fw_replay_sample_her", "fw_her_reward",
     "fw_replay_per_mark_new", "fw_replay_per_rebuild", "fw_replay_sample_per", "fw_replay_per_update", "fw_sac_update_weighted",
     "fw_sac_act_norm", "fw_replay_normalize",
+    "fw_sizeof_td3_hyper", "fw_td3_param_count", "fw_td3_update_workspace_bytes", "fw_td3_act", "fw_td3_update",
 )
 
 
@@ -245,6 +246,14 @@ def lib() -> C.CDLL:
             L.fw_sac_act_norm.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp]
             L.fw_replay_normalize.restype = i32
             L.fw_replay_normalize.argtypes = [vp, i32, i32, i32, vp, vp, f32, f32, vp, f32, f32, vp]
+        if hasattr(L, "fw_td3_update"):            # TD3 (an A/B library of an older commit predates the five; build() insists on them)
+            f32 = C.c_float
+            L.fw_sizeof_td3_hyper.restype = i32; L.fw_sizeof_td3_hyper.argtypes = []
+            L.fw_td3_param_count.restype = i32; L.fw_td3_param_count.argtypes = [i32, i32, i32]
+            L.fw_td3_update_workspace_bytes.restype = i64; L.fw_td3_update_workspace_bytes.argtypes = [i32, i32, i32, i32]
+            L.fw_td3_act.restype = i32
+            L.fw_td3_act.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, u64, i64, vp, vp, vp, vp, f32, vp, vp]
+            L.fw_td3_update.restype = i32; L.fw_td3_update.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i64, vp]
         L.fw_policy_act_a.restype = i32
         L.fw_policy_act_a.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp, vp]
         L.fw_collect_act_a.restype = i32

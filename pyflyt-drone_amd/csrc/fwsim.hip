@@ -1641,6 +1641,8 @@ void fw_reset_kernel(const Params<T>* __restrict__ Pp, const ObjC<T>* __restrict
 #include "fwsim_sac.hpp"
 // ... and its replay ring (fwsim_replay.hpp) with prioritized replay on it (fw_replay_per_*, fw_replay_sample_per, fw_sac_update_weighted)
 #include "fwsim_per.hpp"
+// ... and TD3 on the same ring and the same product kernel (fw_td3_act, fw_td3_update)
+#include "fwsim_td3.hpp"
 
 // ======================================================================
 // host side
@@ -3665,6 +3667,49 @@ int32_t fw_sac_update(float* image, const float* batch_rows, int32_t obs_dim, in
   FW_TRY(sac_step_args("fw_sac_update", image, batch_rows, obs_dim, act_dim, hidden, batch, hyper, counters, out, workspace, workspace_bytes, &S));
   DeviceGuard g(device_of(image));
   sac_update_launch((hipStream_t)hip_stream, S);
+  return sac_launched();
+}
+
+// ---- TD3 (csrc/fwsim_td3.hpp) ----
+static int32_t td3_check_batch(const char* who, int32_t B) {
+  if (B <= 0) return sac_fail(FW_EINVAL, who, "the batch size must be positive");
+  if (!td3_batch_ok(B)) return sac_fail(FW_EUNSUPPORTED, who, "built for batch sizes that are multiples of 16 in [16, 512], got " + std::to_string(B));
+  return FW_OK;
+}
+int32_t fw_sizeof_td3_hyper(void) { return (int32_t)sizeof(fw_td3_hyper); }
+int32_t fw_td3_param_count(int32_t obs_dim, int32_t act_dim, int32_t hidden) {
+  FW_TRY(sac_check_shape("fw_td3_param_count", obs_dim, act_dim, hidden));
+  return td3_layout(obs_dim, act_dim, hidden).total;
+}
+int64_t fw_td3_update_workspace_bytes(int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch) {
+  FW_TRY(sac_check_shape("fw_td3_update_workspace_bytes", obs_dim, act_dim, hidden));
+  FW_TRY(td3_check_batch("fw_td3_update_workspace_bytes", batch));
+  return (int64_t)td3_ws(obs_dim, act_dim, hidden, batch).total * (int64_t)sizeof(float);
+}
+int32_t fw_td3_act(const float* image, const void* obs, int32_t obs_is_f64, int32_t N, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t mode,
+                   uint64_t seed, int64_t env_offset, const int64_t* counters, float* act_f32, void* act_env, float* obs_stage, float sigma,
+                   float* eps, void* hip_stream) {
+  FW_TRY(sac_act_check("fw_td3_act", image && obs && counters && act_f32 && act_env && obs_stage, N, mode, env_offset));
+  if (!(sigma >= 0.0f)) return sac_fail(FW_EINVAL, "fw_td3_act", "sigma must be non-negative");
+  FW_TRY(sac_check_shape("fw_td3_act", obs_dim, act_dim, hidden));
+  DeviceGuard g(device_of(image));
+  const Td3ActArgs a{image, obs, N, obs_dim, act_dim, mode, seed, env_offset, counters, act_f32, act_env, obs_stage, eps, sigma};
+  with_real(obs_is_f64 != 0, [&](auto t) { td3_act_launch<decltype(t)>((hipStream_t)hip_stream, a, hidden); });
+  return sac_launched();
+}
+int32_t fw_td3_update(float* image, const float* batch_rows, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t batch, const fw_td3_hyper* hyper,
+                      int32_t with_actor, int64_t* counters, float* out, void* workspace, int64_t workspace_bytes, void* hip_stream) {
+  const char* who = "fw_td3_update";
+  if (!image || !batch_rows || !hyper || !counters || !workspace) return sac_fail(FW_EINVAL, who, "image, batch_rows, hyper, counters and workspace must be non-NULL");
+  FW_TRY(sac_check_shape(who, obs_dim, act_dim, hidden));
+  FW_TRY(td3_check_batch(who, batch));
+  if (workspace_bytes < (int64_t)td3_ws(obs_dim, act_dim, hidden, batch).total * (int64_t)sizeof(float))
+    return sac_fail(FW_EINVAL, who, "the workspace is smaller than fw_td3_update_workspace_bytes asks for");
+  static_assert(sizeof(fw_td3_hyper) == sizeof(Td3Hyper), "fw_td3_hyper and Td3Hyper must agree");
+  Td3StepArgs S{image, batch_rows, (float*)workspace, counters, out, obs_dim, act_dim, hidden, batch, with_actor != 0, {}};
+  std::memcpy(&S.hp, hyper, sizeof(Td3Hyper));
+  DeviceGuard g(device_of(image));
+  td3_update_launch((hipStream_t)hip_stream, S);
   return sac_launched();
 }
 
