@@ -48,6 +48,8 @@ def main():
                          "(large env counts), or chosen by the env count")
     ap.add_argument("--diagnostics", action="store_true",
                     help="SB3's train/* figures (approx_kl, clip_fraction, explained_variance, ...) in every printed update line")
+    ap.add_argument("--target_kl", type=float, default=None,
+                    help="SB3's target_kl: end an update at the first minibatch whose approx_kl is above 1.5 x this (default: off)")
     a = ap.parse_args()
     cfg = TRAIN_CFG
     num_envs = a.num_envs if a.num_envs is not None else cfg["num_envs"]
@@ -62,7 +64,7 @@ def main():
     env = R.VecNormalizeDevice(venv, norm_obs=True, norm_reward=True, clip_obs=10.0, gamma=cfg["gamma"])
     eval_env = R.VecNormalizeDevice(make(16, cfg["seed"] + 1000), training=False, norm_reward=False, clip_obs=10.0, gamma=cfg["gamma"])
     n_steps = a.n_steps if a.n_steps is not None else R.n_steps_for(cfg["num_envs"] * cfg["n_steps"], num_envs)
-    model = R.PPO(env, R.PPOConfig(diagnostics=a.diagnostics, episode_stats=a.episode_stats, episode_fold=a.episode_fold, n_steps=n_steps, batch_size=cfg["batch_size"], n_epochs=cfg["n_epochs"], learning_rate=cfg["learning_rate"],
+    model = R.PPO(env, R.PPOConfig(diagnostics=a.diagnostics, target_kl=a.target_kl, episode_stats=a.episode_stats, episode_fold=a.episode_fold, n_steps=n_steps, batch_size=cfg["batch_size"], n_epochs=cfg["n_epochs"], learning_rate=cfg["learning_rate"],
                                    gamma=cfg["gamma"], gae_lambda=cfg["gae_lambda"], clip_range=cfg["clip_range"], ent_coef=cfg["ent_coef"],
                                    vf_coef=cfg["vf_coef"], max_grad_norm=cfg["max_grad_norm"], seed=cfg["seed"],
                                    fused_three_actions=a.fused_learner))
@@ -74,6 +76,9 @@ def main():
     class Progress:
         t0, last = time.perf_counter(), 0
         def on_rollout_end(self, ppo):
+            msg = ppo.early_stop_message()     # (--target_kl; learn() calls this hook right after train(): the update that just ended)
+            if msg:
+                print(msg, flush=True)
             if ppo.num_timesteps - self.last >= 5 * per_update:
                 dt = time.perf_counter() - self.t0
                 print(json.dumps({"timesteps": ppo.num_timesteps, "fps": round(ppo.num_timesteps / dt), **{k: round(v, 5) for k, v in ppo.logs.items()}, **{k: round(v, 6) for k, v in ppo.diagnostics.items()}, **{k: round(v, 5) for k, v in ppo.rollout_stats.items()},

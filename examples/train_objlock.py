@@ -45,6 +45,8 @@ def main():
                          "(large env counts), or chosen by the env count")
     ap.add_argument("--diagnostics", action="store_true",
                     help="SB3's train/* figures (approx_kl, clip_fraction, explained_variance, ...) in every printed update line")
+    ap.add_argument("--target_kl", type=float, default=None,
+                    help="SB3's target_kl: end an update at the first minibatch whose approx_kl is above 1.5 x this (default: off)")
     a = ap.parse_args()
     cfg = TRAIN_CONFIG
     model_dir, log_dir = os.path.join(a.out, "models"), os.path.join(a.out, "logs")
@@ -60,7 +62,7 @@ def main():
     if vecnorm:
         checkpoint.load_vecnormalize(vecnorm, env, training=True, norm_reward=True)
     n_steps = R.n_steps_for(cfg["samples_per_update"], a.num_envs, world)      # holds the samples per update: n_steps ~ 1 / (envs x world)
-    model = R.PPO(env, R.PPOConfig(diagnostics=a.diagnostics, episode_stats=a.episode_stats, episode_fold=a.episode_fold, n_steps=n_steps, batch_size=cfg["batch_size"], n_epochs=cfg["n_epochs"], learning_rate=cfg["learning_rate"],
+    model = R.PPO(env, R.PPOConfig(diagnostics=a.diagnostics, target_kl=a.target_kl, episode_stats=a.episode_stats, episode_fold=a.episode_fold, n_steps=n_steps, batch_size=cfg["batch_size"], n_epochs=cfg["n_epochs"], learning_rate=cfg["learning_rate"],
                                    gamma=cfg["gamma"], gae_lambda=cfg["gae_lambda"], clip_range=cfg["clip_range"], ent_coef=cfg["ent_coef"],
                                    vf_coef=cfg["vf_coef"], max_grad_norm=cfg["max_grad_norm"], seed=cfg["seed"]))
     if a.pretrained_model:
@@ -72,6 +74,9 @@ def main():
     class Progress:
         t0, last = time.perf_counter(), 0
         def on_rollout_end(self, ppo):
+            msg = ppo.early_stop_message()     # (--target_kl; learn() calls this hook right after train(): the update that just ended)
+            if msg:
+                print(msg, flush=True)
             if ppo.num_timesteps - self.last >= 20 * n_steps * a.num_envs * world:
                 dt = time.perf_counter() - self.t0
                 print(json.dumps({"timesteps": ppo.num_timesteps, "fps": round(ppo.num_timesteps / dt), **{k: round(v, 5) for k, v in ppo.logs.items()}, **{k: round(v, 6) for k, v in ppo.diagnostics.items()}, **{k: round(v, 5) for k, v in ppo.rollout_stats.items()},

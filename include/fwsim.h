@@ -671,6 +671,30 @@ int32_t fw_ppo_update_diag(float* params, float* mom_m, float* mom_v, const floa
                            float* loss_acc, void* workspace, int64_t workspace_bytes, void* hip_stream,
                            float* diag, int64_t diag_floats);
 
+/* The learner with SB3's `target_kl` EARLY STOPPING: the arguments of fw_ppo_update_diag, then the limit and where the number of
+ * optimiser steps taken goes.  SB3's PPO.train() looks at approx_kl = mean((ratio - 1) - log ratio) of every minibatch after its
+ * losses are computed and before its optimiser step, and ends the update at the first one above 1.5 * target_kl.  Here the decision is
+ * taken inside the launch: every policy workgroup's KL sum rides on the gradient-norm exchange (one tagged word per workgroup, in the
+ * per-call zeroed region of the workspace; no further wait round), every workgroup of both networks adds the words in part order,
+ * scales by 1 / batch_size and compares in float32 with kl_stop = (float)(1.5 * (double)target_kl) -- the same bits, so the same
+ * verdict, everywhere.  With the stop at minibatch m (0-based):
+ *   params, mom_m, mom_v   the plain call's over minibatches 0 .. m - 1 (m Adam steps from hyper->step0), bit for bit; m = 0: untouched;
+ *   loss_acc               += the plain call's sums over minibatches 0 .. m: the stopping minibatch's losses count (SB3 books them);
+ *   *minibatches_stepped   m.  Without a stop: n_minibatches, and everything as the plain call leaves it.
+ *   diag                   may be NULL here (then nothing is written; diag_floats is ignored).  Otherwise as fw_ppo_update_diag for
+ *                          minibatches 0 .. m; the rows of later minibatches stay as the caller zeroed them.
+ * minibatches_stepped is a DEVICE pointer to one int32, written once by the workgroup that writes the closing verdict; it is valid
+ * after fw_ppo_update_status reported 0, like everything else: a non-zero status leaves all outputs undefined, as above.
+ * target_kl <= 0 or not finite, a NULL minibatches_stepped, an act_dim other than 3, 4, 6: FW_EINVAL, nothing runs.  The workspace is
+ * that of the width's own size function; the status word, the closing verdict and the FWSIM_PPO_* / FWSIM_SPIN_LOG2 switches are
+ * those of the plain entry points, which themselves take and refuse exactly what they did. */
+int32_t fw_ppo_update_kl(float* params, float* mom_m, float* mom_v, const float* obs, const float* act,
+                         const float* old_logp, const float* adv, const float* ret, const int32_t* perm,
+                         int32_t n_minibatches, int32_t batch_size, int32_t obs_dim, int32_t act_dim, const fw_ppo_hyper* hyper,
+                         float* loss_acc, void* workspace, int64_t workspace_bytes, void* hip_stream,
+                         float* diag /* may be NULL */, int64_t diag_floats, float target_kl,
+                         int32_t* minibatches_stepped /* device, one int32 */);
+
 /* Rollout collection between two env steps (SB3 OnPolicyAlgorithm.collect_rollouts + VecNormalize reward path,
  * train/train_Fixedwing_Waypoints_v3.py:260,293-310), for the same MlpPolicy / flat parameter image as fw_ppo_update.
  * fw_policy_act: obs[N,obs_dim] (normalised, float32) -> for `nets` bit 0 (policy): act_raw[N,4] = mean + sigma * z

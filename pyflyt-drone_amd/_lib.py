@@ -27,7 +27,7 @@ EXPORTS = (
     "fw_policy_act_a", "fw_collect_act_a",
     "fw_ppo_param_count_a3", "fw_ppo_moment_count_a3", "fw_ppo_moment_map_a3", "fw_ppo_update_workspace_bytes_a3", "fw_ppo_update_a3",
     "fw_collect_act_hl", "fw_sizeof_collect_hl_args", "fw_eval_track_hl", "fw_trace_hl",
-    "fw_ppo_diag_floats", "fw_ppo_update_diag",
+    "fw_ppo_diag_floats", "fw_ppo_update_diag", "fw_ppo_update_kl",
     "fw_episode_state_bytes", "fw_episode_fold",
     "fw_episode_fold_span", "fw_episode_fold_workspace_bytes", "fw_episode_fold_wide",
     "fw_trace_rows", "fw_eval_track_wp",
@@ -200,6 +200,10 @@ def lib() -> C.CDLL:
         L.fw_ppo_diag_floats.restype = i64; L.fw_ppo_diag_floats.argtypes = [i32]
         L.fw_ppo_update_diag.restype = i32
         L.fw_ppo_update_diag.argtypes = [vp] * 9 + [i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, i64]
+        if hasattr(L, "fw_ppo_update_kl"):     # target_kl early stopping (an A/B library of an older commit predates it; build() insists on it)
+            # fw_ppo_update_diag's list (diag may be None), then target_kl and the device int32 the stepped count goes to
+            L.fw_ppo_update_kl.restype = i32
+            L.fw_ppo_update_kl.argtypes = [vp] * 9 + [i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, i64, C.c_float, vp]
         L.fw_collect_act_hl.restype = i32; L.fw_collect_act_hl.argtypes = [vp, vp, vp]
         L.fw_sizeof_collect_hl_args.restype = i32; L.fw_sizeof_collect_hl_args.argtypes = []
         if hasattr(L, "fw_step_hl"):           # (an A/B library of an older commit predates the pair; build() insists on it)

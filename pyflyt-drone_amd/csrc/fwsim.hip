@@ -2300,17 +2300,22 @@ int set_state_T(fw_env* h, const double* in) {
 
 namespace {
 // The learner's kernels: one lookup per family, used by the launch and by the LDS opt-in in front of it.
-// (diag: the diagnostics form of the same row -- fw_ppo_update_diag; the plain entry points never ask for it)
-const void* ppo_update_kernel(int act_dim, int ch /*samples per pass*/, int ns /*blocks per network of the reduce-scatter form, 0: all-to-all*/, bool diag = false) {
-  struct Row { int ch, ns; const void* a4; const void* a6; const void* a3; const void* d4; const void* d6; const void* d3; };
+// (form 1: the diagnostics form of the same row -- fw_ppo_update_diag; form 2: the KL-stop form -- fw_ppo_update_kl; the plain entry
+// points never ask for either)
+enum { PPO_FORM_PLAIN = 0, PPO_FORM_DIAG = 1, PPO_FORM_KL = 2 };
+const void* ppo_update_kernel(int act_dim, int ch /*samples per pass*/, int ns /*blocks per network of the reduce-scatter form, 0: all-to-all*/, int form = PPO_FORM_PLAIN) {
+  struct Row { int ch, ns; const void* a4; const void* a6; const void* a3; const void* d4; const void* d6; const void* d3; const void* k4; const void* k6; const void* k3; };
 #define FW_PPO_ROW(CH, NS) {CH, NS, kfn(fw_ppo_update_kernel<CH, NS>), kfn(fw_ppo_update_kernel_a6<CH, NS>), kfn(fw_ppo_update_kernel_a3<CH, NS>), \
-                            kfn(fw_ppo_update_diag_kernel<CH, NS, 4>), kfn(fw_ppo_update_diag_kernel<CH, NS, 6>), kfn(fw_ppo_update_diag_kernel<CH, NS, 3>)}
+                            kfn(fw_ppo_update_diag_kernel<CH, NS, 4>), kfn(fw_ppo_update_diag_kernel<CH, NS, 6>), kfn(fw_ppo_update_diag_kernel<CH, NS, 3>), \
+                            kfn(fw_ppo_update_kl_kernel<CH, NS, 4>), kfn(fw_ppo_update_kl_kernel<CH, NS, 6>), kfn(fw_ppo_update_kl_kernel<CH, NS, 3>)}
   static const Row rows[] = {
     FW_PPO_ROW(64, 8), FW_PPO_ROW(64, 4), FW_PPO_ROW(64, 0), FW_PPO_ROW(32, 8), FW_PPO_ROW(32, 4), FW_PPO_ROW(32, 0),
     FW_PPO_ROW(16, 8), FW_PPO_ROW(16, 4), FW_PPO_ROW(16, 0),
   };
 #undef FW_PPO_ROW
-  for (const Row& r : rows) if (r.ch == ch && r.ns == ns) return diag ? (act_dim == 6 ? r.d6 : act_dim == 3 ? r.d3 : r.d4) : (act_dim == 6 ? r.a6 : act_dim == 3 ? r.a3 : r.a4);
+  for (const Row& r : rows) if (r.ch == ch && r.ns == ns)
+    return form == PPO_FORM_KL ? (act_dim == 6 ? r.k6 : act_dim == 3 ? r.k3 : r.k4)
+         : form == PPO_FORM_DIAG ? (act_dim == 6 ? r.d6 : act_dim == 3 ? r.d3 : r.d4) : (act_dim == 6 ? r.a6 : act_dim == 3 ? r.a3 : r.a4);
   return nullptr;
 }
 // the pre-pass that packs the rows, and the entry point that sizes the workspace (for the message), by action width
@@ -2972,6 +2977,8 @@ static long long spin_budget(long long dflt) {
 // gradient hand-off buffer | the packed rows of every minibatch, in walking order (fw_ppo_pack_kernel)
 // (the words first -- everything that is polled -- and the data a whole 64 KB behind them: the blocks that wait spin on these lines with
 // loads past their L1, and whatever part of the L2 serves the words should not also serve the first partial's tiles)
+// (the KL-stop form's words, kPpoWordKl .., are part of kPpoWords -- zeroed per call with the rest -- and of this fixed region: the
+// workspace-size functions cover them without growing)
 static constexpr size_t kPpoWsXch = 65536;
 static_assert(kPpoWords * sizeof(unsigned long long) <= kPpoWsXch, "exchange words");
 static constexpr size_t kPpoWsGx = sizeof(float) * (4 * kPMaxSplit * (size_t)kPGxSlots);      // [parity][net][part]: gradient partial + weight share
@@ -2998,7 +3005,8 @@ int64_t fw_ppo_update_workspace_bytes_a3(int32_t n_minibatches, int32_t batch_si
 static int32_t ppo_update(float* params, float* mom_m, float* mom_v, const float* obs, const float* act, const float* old_logp,
                           const float* adv, const float* ret, const int32_t* perm, int32_t n_minibatches, int32_t batch_size,
                           int32_t obs_dim, int32_t act_dim, const fw_ppo_hyper* hyper, float* loss_acc, void* workspace, int64_t workspace_bytes,
-                          void* hip_stream, const char* who, float* diag = nullptr /* fw_ppo_update_diag: the diagnostics buffer, checked by the caller */) {
+                          void* hip_stream, const char* who, float* diag = nullptr /* fw_ppo_update_diag: the diagnostics buffer, checked by the caller */,
+                          const PpoKlArgs* kl = nullptr /* fw_ppo_update_kl: the limit and the count's place (its diag may be null), checked by the caller */) {
   static_assert(sizeof(fw_ppo_hyper) == sizeof(PpoHyper), "fw_ppo_hyper layout");
   const std::string w = who;
   if (!params || !mom_m || !mom_v || !obs || !act || !old_logp || !adv || !ret || !perm || !hyper || n_minibatches <= 0) {
@@ -3012,7 +3020,7 @@ static int32_t ppo_update(float* params, float* mom_m, float* mom_v, const float
     g_err = w + ": workspace smaller than " + width->ws_fn;
     return FW_EINVAL;
   }
-  const size_t lds = ppo_lds_bytes(obs_dim, act_dim);
+  const size_t lds = ppo_lds_bytes(obs_dim, act_dim, kl != nullptr);
   if (lds > 160 * 1024) { g_err = w + ": networks do not fit the 160 KB of LDS"; return FW_EINVAL; }
   hipStream_t st = (hipStream_t)hip_stream;
   const int dev = device_of(params);
@@ -3052,12 +3060,14 @@ static int32_t ppo_update(float* params, float* mom_m, float* mom_v, const float
   }
   const int ns = cut.nsplit >= 4 && rs_env ? cut.nsplit : 0;      // the kernel's NS: 0 = all-to-all swap of whole partials
   const dim3 grid(16 * cut.nsplit);                 // (every 8th block works -- see the kernel)
-  const void* fn = ppo_update_kernel(act_dim, cut.ch, ns, diag != nullptr);
+  const void* fn = ppo_update_kernel(act_dim, cut.ch, ns, kl ? PPO_FORM_KL : diag ? PPO_FORM_DIAG : PPO_FORM_PLAIN);
   if (!fn) { g_err = w + ": no kernel is built for " + std::to_string(cut.ch) + " samples per pass x " + std::to_string(ns) + " blocks per network"; return FW_EINVAL; }
   if (int rc = ensure_dynamic_lds(nullptr, dev, fn, lds)) return rc;
   void* args_plain[] = { &A };
   void* args_diag[] = { &A, &diag };                // (the diagnostics kernels take the buffer as a second parameter)
-  (void)hipLaunchKernel(fn, grid, dim3(kPThreads), diag ? args_diag : args_plain, lds, st);
+  PpoKlArgs K = kl ? *kl : PpoKlArgs{nullptr, nullptr, 0.f};
+  void* args_kl[] = { &A, &K };                     // (the KL-stop kernels: the buffer, the count's place and the limit as one struct)
+  (void)hipLaunchKernel(fn, grid, dim3(kPThreads), kl ? args_kl : diag ? args_diag : args_plain, lds, st);
   HIP_TRY((fw_env*)nullptr, hipGetLastError());
   return FW_OK;
 }
@@ -3100,6 +3110,23 @@ int32_t fw_ppo_update_diag(float* params, float* mom_m, float* mom_v, const floa
   }
   return ppo_update(params, mom_m, mom_v, obs, act, old_logp, adv, ret, perm, n_minibatches, batch_size, obs_dim, act_dim, hyper, loss_acc,
                     workspace, workspace_bytes, hip_stream, "fw_ppo_update_diag", diag);
+}
+
+// the KL-stop form: the same call on the KL-stop instantiation of the same kernel row
+int32_t fw_ppo_update_kl(float* params, float* mom_m, float* mom_v, const float* obs, const float* act, const float* old_logp,
+                         const float* adv, const float* ret, const int32_t* perm, int32_t n_minibatches, int32_t batch_size,
+                         int32_t obs_dim, int32_t act_dim, const fw_ppo_hyper* hyper, float* loss_acc, void* workspace, int64_t workspace_bytes,
+                         void* hip_stream, float* diag, int64_t diag_floats, float target_kl, int32_t* minibatches_stepped) {
+  if (act_dim != 3 && act_dim != 4 && act_dim != 6) { g_err = "fw_ppo_update_kl: act_dim must be 3, 4 or 6 (got " + std::to_string(act_dim) + ")"; return FW_EINVAL; }
+  if (!(target_kl > 0.f) || !std::isfinite(target_kl)) { g_err = "fw_ppo_update_kl: target_kl must be positive and finite"; return FW_EINVAL; }
+  if (!minibatches_stepped) { g_err = "fw_ppo_update_kl: minibatches_stepped is NULL"; return FW_EINVAL; }
+  if (n_minibatches <= 0) { g_err = "fw_ppo_update_kl: n_minibatches must be positive"; return FW_EINVAL; }
+  if (diag && diag_floats < (int64_t)ppo_diag_floats(n_minibatches)) {
+    g_err = "fw_ppo_update_kl: diag smaller than fw_ppo_diag_floats(n_minibatches)"; return FW_EINVAL;
+  }
+  const PpoKlArgs K{diag, minibatches_stepped, (float)(1.5 * (double)target_kl)};      // SB3: approx_kl > 1.5 * target_kl
+  return ppo_update(params, mom_m, mom_v, obs, act, old_logp, adv, ret, perm, n_minibatches, batch_size, obs_dim, act_dim, hyper, loss_acc,
+                    workspace, workspace_bytes, hip_stream, "fw_ppo_update_kl", nullptr, &K);
 }
 
 int32_t fw_ppo_update_status(const void* workspace, int64_t workspace_bytes, uint32_t* status_out, uint32_t* paths_out, void* hip_stream) {

@@ -44,6 +44,7 @@ constexpr int kPLdx = 65;          // row stride of the gathered observations in
                                    // address of the X-sided products is base + immediate.  (Round 3 had Dp + 1: with a run-time stride hipcc
                                    // emitted one address add, one scalar reload and one LDS wait PER MFMA of dW1 -- 5.3 k cycles for 32 MFMAs.)
 constexpr int kPThreads = 256;
+constexpr int kPKlLds = 4 + kPMaxSplit + 8;       // floats of LDS the KL-stop form adds (ppo_net_body: klw)
 
 __host__ __device__ inline int ppo_net_params(int Dp, int KO) { return Dp * kPH + kPH + kPH * kPH + kPH + kPH * KO + KO; }
 __host__ __device__ inline int ppo_total_params(int Dp) { return ppo_net_params(Dp, 4) + ppo_net_params(Dp, 1) + 4; }
@@ -434,8 +435,10 @@ constexpr int kPpoWordDone = kPpoWordLoss + 2 * kPMaxSplit;      // how many blo
 constexpr int kPpoWordArrive = kPpoWordDone + 1;     // how many blocks got through their last minibatch with every wait answered
 constexpr int kPpoWordVerdict = kPpoWordArrive + 1;  // written once, by the last arriver: 1 = every block writes its results back, 2 = nobody does
 constexpr int kPpoWordFlags2 = 13 * kPMaxSplit;      // flags of the weight all-gather [parity][net][part] (reduce-scatter form)
-constexpr int kPpoWords = kPpoWordFlags2 + 4 * kPMaxSplit;
-static_assert(kPpoWordIds + 2 * kPMaxSplit <= kPpoWordPaths && kPpoWordVerdict < kPpoWordFlags2, "exchange-word layout");
+constexpr int kPpoWordKl = kPpoWordFlags2 + 4 * kPMaxSplit;      // (KL-stop form) the policy blocks' KL sums of a minibatch [parity][part]: (minibatch + 1) << 32 | float bits
+constexpr int kPpoWords = kPpoWordKl + 2 * kPMaxSplit;
+static_assert(kPpoWordIds + 2 * kPMaxSplit <= kPpoWordPaths && kPpoWordVerdict < kPpoWordFlags2 && kPpoWordFlags2 + 4 * kPMaxSplit <= kPpoWordKl &&
+              kPpoWordKl + 2 * kPMaxSplit <= kPpoWords, "exchange-word layout");
 enum { PPO_ST_IDS = 1, PPO_ST_SWAP = 2, PPO_ST_NORM = 4, PPO_ST_COMMIT = 8 };
 
 // (Measured, round 5: an `s_sleep 1` between two looks -- to take pressure off the lines sixteen blocks spin on -- costs 0.1-0.2 us per
@@ -461,6 +464,23 @@ __host__ __device__ inline size_t ppo_diag_row(int mb, int net, int part, int wa
   return (size_t)mb * kPDiagMb + (size_t)(((net * kPMaxSplit + part) * 4 + wave) * kPDiagRow);
 }
 __host__ __device__ inline long long ppo_diag_floats(int n_mb) { return (long long)n_mb * kPDiagMb; }
+
+// (KL-stop form, see ppo_net_body) a policy block's KL sum of the minibatch: its four waves' sums (klw[0 .. 3]) in wave order
+__device__ __forceinline__ float ppo_kl_fold(const float* klw) { return ((klw[0] + klw[1]) + klw[2]) + klw[3]; }
+// ... and the collection of the nsplit words of a minibatch by the threads behind the norm's collectors -- one word each, into klw[4 ..]
+// in part order; a policy block (own_part >= 0) takes its own from LDS.  The bounded wait of the norm exchange, under its status bit.
+template <bool RS>
+__device__ __forceinline__ void ppo_kl_collect(const PpoArgs& A, int mb, int nsplit, int own_part, float* klw, float* red) {
+  unsigned long long* const klwords = A.xch + kPpoWordKl + (mb & 1) * kPMaxSplit;
+  const int kq = (int)threadIdx.x - (RS ? 2 * kPMaxSplit : 1);
+  if (kq >= 0 && kq < nsplit) {
+    unsigned long long w = 0ull;
+    if (kq == own_part) w = (unsigned long long)__float_as_uint(ppo_kl_fold(klw));
+    else if (!ppo_wait(A, [&]() { return ppo_word_load(klwords + kq, false); }, [&](unsigned long long x) { return (unsigned)(x >> 32) == (unsigned)(mb + 1); },
+                       (unsigned long long)PPO_ST_NORM, w)) red[7] = 1.f;     // a policy block is gone
+    klw[4 + kq] = __uint_as_float((unsigned)w);
+  }
+}
 
 // CH = samples per pass through the network (64: 2 x 2 tiles of 32 x 32 per product; 32 / 16: 2 / 1 x 4 tiles of 16 x 16, see ppo_mfma16_rows);
 // part / nsplit: this block's place among the blocks of its network (chunk c of a minibatch is run by block c % nsplit).
@@ -521,8 +541,23 @@ template <int N> __device__ __forceinline__ float ppo_tree_sum(const float (&v)[
 // row of `diag` (layout: include/fwsim.h, ppo_diag_row) -- the values are in registers in the head phase anyway, the wave sum runs on the
 // vector ALU and the row is one plain 16-byte store of lane 0: no barrier, no LDS, no exchange word, no wait.  Nothing of it feeds
 // back: what reaches params / mom_m / mom_v / loss_acc is the arithmetic of the plain form, bit for bit.
-template <int NET, int CH, int NS, int NA, bool DIAG = false>
-__device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const int part, const int nsplit, float* diag = nullptr) {
+// KL: the KL-stop form (fw_ppo_update_kl; always with DIAG, whose sums it needs -- `diag` itself may be null there, the rows are then not
+// written).  SB3's `target_kl`: the update ends at the first minibatch whose approx_kl = mean((ratio - 1) - log ratio) is above `kl_stop`, after
+// its losses are booked and before its optimiser step.  Every policy block folds its four waves' KL sums in wave order and publishes
+// the result as one tagged word (xch + kPpoWordKl, [parity][part]) in front of its norm word; every block of BOTH networks collects the
+// nsplit words in the round of the norm exchange -- the same bounded wait, under PPO_ST_NORM, by threads that would otherwise idle
+// behind the norm's -- adds them in part order, scales by 1 / B and compares: the same words in the same order, so the same verdict
+// everywhere.  Above the limit nobody clips, steps or gathers weights for this minibatch: all blocks leave the loop at the same
+// minibatch and go to the closing verdict as blocks that got through.  The word's parity is safe for the norm words' reason: a block
+// writes minibatch mb + 2's word only after the round of mb + 1, which every block enters after it has read mb's words.
+// What differs in the results: `*stepped` (the Adam steps taken, written by the block that writes the verdict), and loss_acc, which
+// includes the stopping minibatch -- its entropy term keeps the plain form's convention (the log_std behind the last computed
+// minibatch's step, times the minibatches computed), so the three sums are those of a plain call over the computed minibatches.
+// The words are always stored at device scope: their readers are all the blocks of the call, not only those an XCD check covers.
+template <int NET, int CH, int NS, int NA, bool DIAG = false, bool KL = false>
+__device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const int part, const int nsplit, float* diag = nullptr,
+                                             const float kl_stop = 0.f, int32_t* stepped = nullptr) {
+  static_assert(!KL || DIAG, "the KL-stop form is built on the diagnostics sums");
   static_assert(NA == 3 || NA == 4 || NA == 6, "action width");
   static_assert(NS == 0 || NS == 4 || NS == 8, "blocks per network in the reduce-scatter form");
   constexpr bool RS = NS != 0;
@@ -569,6 +604,10 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
                                                   // [0, 4) dbo, [4, 8) dlog_std of components 0-3, [8, 10) dbo, [12, 14) dlog_std of 4-5)
   float* sink = p; p += kPThreads;                // one word per thread: where the Adam of a W1 tile "updates" the rows the network does not have
   float* red8 = p; p += 2 * kPMaxSplit;           // (RS) the blocks' shares of the squared gradient norm, [net][part]
+  // (KL; carved in every form, used and sized -- ppo_lds_bytes -- in that one only) [0, 4) the waves' KL sums, [4, 4 + kPMaxSplit) the policy
+  // blocks' sums in part order, [12, 12 + NA) log_std behind the step not taken (the entropy term of loss_acc)
+  [[maybe_unused]] float* const klw = p;
+  [[maybe_unused]] int n_stepped = n_mb;          // (KL) Adam steps taken: the index of the stopping minibatch, or all of them
 
   // flat offsets of this net
   const int nP0 = ppo_net_params(Dp, NA);
@@ -1108,9 +1147,13 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
     if constexpr (DIAG) {
       // this wave's row of the minibatch: [loss sum / B, KL sum / B, clipped count / B, entropy loss (first wave of the policy's part 0)]
       const float s0 = ppo_wave_sum(dg_a), s1 = NET == 0 ? ppo_wave_sum(dg_kl) : 0.f, s2 = NET == 0 ? ppo_wave_sum(dg_cf) : 0.f;
-      if (lane == 0)
+      bool wr = lane == 0;
+      if constexpr (KL) wr = wr && diag != nullptr;
+      if (wr)
         *reinterpret_cast<float4*>(diag + ppo_diag_row(mb, NET, part, wave)) =
             make_float4(s0 * invB, s1 * invB, s2 * invB, NET == 0 && part == 0 && wave == 0 ? dg_ent : 0.f);
+      // (KL: the wave's sum, for the block's fold behind the next barrier; the previous minibatch's readers are several barriers back)
+      if constexpr (KL && NET == 0) { if (lane == 0) klw[wave] = s1; }
     }
     // ---- finish the per-thread gradients: the four row-block partials of the biases; dWo over the quad's sample quarters;
     // dbo / dlog_std component hq over all samples ----
@@ -1398,6 +1441,12 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
 #ifdef FW_PPO_PROF
     const long long pfx = PPO_T(); pf_norm += pfx - pfb;
 #endif
+    // (KL) the KL words of this minibatch: published by thread 0 of every policy block in front of its norm word; collected, once
+    // the block's norm word is out, ahead of the barrier the norm exchange ends with (ppo_kl_collect)
+    if constexpr (KL && NET == 0) {
+      if (t == 0) ppo_word_store(A.xch + kPpoWordKl + (mb & 1) * kPMaxSplit + part,
+                                 ((unsigned long long)(unsigned)(mb + 1) << 32) | (unsigned long long)__float_as_uint(ppo_kl_fold(klw)), false);
+    }
     if constexpr (RS) {
       // all 2 NS shares, summed in word order ([net][part]) by everybody: lane i of the first wave fetches word i
       unsigned long long* words = A.xch + (mb & 1) * 2 * kPMaxSplit;
@@ -1409,6 +1458,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
                                  (unsigned long long)PPO_ST_NORM, w)) red[7] = 1.f;     // a block is gone
         red8[t] = __uint_as_float((unsigned)w);
       }
+      if constexpr (KL) ppo_kl_collect<RS>(A, mb, nsplit, NET == 0 ? part : -1, klw, red);
       __syncthreads();
       if (red[7] != 0.f) { dead = true; break; }
       float tot = red8[0];
@@ -1427,6 +1477,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
                       (unsigned long long)PPO_ST_NORM, w)) red[7] = 1.f;     // the other network's block is gone
         red[4] = __uint_as_float((unsigned)w);
       }
+      if constexpr (KL) ppo_kl_collect<RS>(A, mb, nsplit, NET == 0 ? part : -1, klw, red);
       __syncthreads();
       if (red[7] != 0.f) { dead = true; break; }
       ss_other = red[4];
@@ -1440,6 +1491,21 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
     // ---- Adam on the elements each lane holds (moments: registers, see above) ----
     bc1 *= H.beta1; bc2 *= H.beta2;
     const float c1 = H.lr / (1.0f - bc1), sc2 = 1.0f / sqrtf(1.0f - bc2);      // step size, 1 / sqrt(bias correction 2)
+    if constexpr (KL) {
+      float kl = klw[4];
+      for (int q = 1; q < nsplit; ++q) kl += klw[4 + q];
+      if (kl * invB > kl_stop) {                  // (block-uniform, and the same bits in every block of the call)
+        // no clipping, no Adam, no all-gather: this minibatch's losses are booked, its step is not taken.  Only log_std's step is
+        // worked out -- the arithmetic of the per-thread Adam below, on copies -- for the entropy term of loss_acc (see above).
+        if (NET == 0 && t < NA) {
+          const float gg = my_gls * clipc;
+          const float mn = H.beta1 * smm[NQ - 1] + (1.0f - H.beta1) * gg, vn = H.beta2 * svv[NQ - 1] + (1.0f - H.beta2) * gg * gg;
+          klw[12 + t] = log_std[t] - c1 * mn * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(vn) * sc2 + H.eps);
+        }
+        n_stepped = mb;
+        break;
+      }
+    }
     auto adam_tile = [&](const f32x16& g, float4 (&m4)[4], float4 (&v4)[4], auto&& lds_of /* v -> weight in LDS (rows the network does not have: the lane's sink word) */) {
       // the 16 weights are read in one batch, updated in registers and written in one batch (element by element the compiler
       // keeps each read behind the previous write: 32 exposed LDS round trips per minibatch, ~3 k cycles)
@@ -1654,6 +1720,7 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
       const unsigned long long before = __hip_atomic_fetch_add(A.xch + kPpoWordArrive, 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
       if (before == (unsigned long long)(total - 1)) {
         commit = __hip_atomic_load(A.xch + kPpoWordStatus, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0ull;
+        if constexpr (KL) { if (commit) *stepped = n_stepped; }       // (every block that got through holds the same count)
         __hip_atomic_store(A.xch + kPpoWordVerdict, commit ? 1ull : 2ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
       } else {
         unsigned long long w = 0ull;
@@ -1707,8 +1774,14 @@ __device__ __forceinline__ void ppo_net_body(const PpoArgs& A, float* lds, const
     }
     if (NET == 0 && part == 0) {
       float ent = 0.f;
-      for (int k = 0; k < NA; ++k) ent += 1.4189385332046727f + log_std[k];
-      atomicAdd(&A.loss_acc[2], -ent * (float)n_mb);                  // entropy loss at the final log_std (it is state-independent)
+      if constexpr (KL) {                         // (the stopping minibatch counts: its loss was computed)
+        const bool stopped = n_stepped < n_mb;
+        for (int k = 0; k < NA; ++k) ent += 1.4189385332046727f + (stopped ? klw[12 + k] : log_std[k]);
+        atomicAdd(&A.loss_acc[2], -ent * (float)(stopped ? n_stepped + 1 : n_mb));
+      } else {
+        for (int k = 0; k < NA; ++k) ent += 1.4189385332046727f + log_std[k];
+        atomicAdd(&A.loss_acc[2], -ent * (float)n_mb);                // entropy loss at the final log_std (it is state-independent)
+      }
     }
 #ifdef FW_PPO_PROF
     float* pr = A.loss_acc + 3 + NET * 4;
@@ -1766,6 +1839,18 @@ __global__ __launch_bounds__(kPThreads) void fw_ppo_update_diag_kernel(PpoArgs A
   if ((i & 1) == 0) ppo_net_body<0, CH, NS, NA, true>(A, lds, part, nsplit, diag); else ppo_net_body<1, CH, NS, NA, true>(A, lds, part, nsplit, diag);
 }
 
+// the KL-stop form, every action width: the diagnostics kernel's grid and arguments (diag may be null), plus the limit and the count
+struct PpoKlArgs { float* diag; int32_t* stepped; float kl_stop; };
+template <int CH, int NS, int NA>
+__global__ __launch_bounds__(kPThreads) void fw_ppo_update_kl_kernel(PpoArgs A, PpoKlArgs K) {
+  extern __shared__ __align__(16) float lds[];
+  if (blockIdx.x & 7) return;
+  const int i = (int)blockIdx.x >> 3;
+  const int part = i >> 1, nsplit = NS ? NS : (int)gridDim.x >> 4;
+  if ((i & 1) == 0) ppo_net_body<0, CH, NS, NA, true, true>(A, lds, part, nsplit, K.diag, K.kl_stop, K.stepped);
+  else ppo_net_body<1, CH, NS, NA, true, true>(A, lds, part, nsplit, K.diag, K.kl_stop, K.stepped);
+}
+
 // How a minibatch of B samples is cut: samples per pass (64, 32 or 16) and blocks per network.  The path is sequential, so the
 // smaller the share of a block the better -- down to 16 samples (one 16 x 16 row tile per wave) and up to eight blocks: from four
 // on they reduce-scatter, so the exchange volume per block does not grow with their number.  `max_blocks` = 4: the cuts of round 4
@@ -1782,11 +1867,11 @@ inline PpoSplit ppo_split(int B, int max_blocks = kPMaxSplit) {
   return best;
 }
 
-inline size_t ppo_lds_bytes(int D, int NA = 4) {
+inline size_t ppo_lds_bytes(int D, int NA = 4, bool kl = false) {
   (void)D;                                          // (sized for the larger of the two forms: W1 as 64 rows of 65)
   const int ldx = kPLdx, SA = NA == 6 ? 8 : 4;
   size_t f = (size_t)(kPH * kPLdh + kPH + kPH * kPLdh + kPH + kPH * NA + NA) + (NA == 3 ? 5 : NA) + (size_t)kPChunk * ldx + 64 + 2 * (size_t)kPChunk * kPLdh +
-             (2 * (size_t)SA + 4) * kPChunk + 8 * kPH + 8 + 4 * (NA == 6 ? 16 : 8) + kPThreads + 2 * kPMaxSplit;
+             (2 * (size_t)SA + 4) * kPChunk + 8 * kPH + 8 + 4 * (NA == 6 ? 16 : 8) + kPThreads + 2 * kPMaxSplit + (kl ? kPKlLds : 0);
   return f * sizeof(float);
 }
 

@@ -574,10 +574,26 @@ class PPOConfig:
                                            #        workgroup per span of envs, three launches: large env counts), "auto" (by monitor.WIDE_FROM_ENVS)
     dist_update: str = "replicated"        # multi-process job: "replicated" = all-gather the rollout shards, every rank runs the same
                                            # minibatch sequence (no per-minibatch collective); "allreduce" = local minibatches + gradient all-reduce
+    target_kl: Optional[float] = None      # SB3's target_kl: end the update at the first minibatch whose approx_kl is above 1.5 * target_kl, after
+                                           # its losses are booked and before its optimiser step; the fused learner decides inside the launch
+                                           # (fw_ppo_update_kl), the torch path reads the KL per minibatch (no captured update graph); None: off,
+                                           # nothing changes.  Not built for dist_update="allreduce" (the ranks see different minibatches)
 
     def __post_init__(self):
         if self.episode_fold not in ("one", "wide", "auto"):
             raise ValueError(f"episode_fold must be 'one', 'wide' or 'auto', got {self.episode_fold!r}")
+        if self.target_kl is not None:
+            t = self.target_kl
+            if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)) or not math.isfinite(t) or not t > 0:
+                raise ValueError(f"target_kl must be None or a positive, finite number, got {t!r}")
+            if self.dist_update == "allreduce":
+                raise ValueError("target_kl with dist_update='allreduce' is not built: the ranks walk different minibatches there, and "
+                                 "agreeing on one verdict per minibatch is a collective the update does not have")
+
+    @property
+    def kl_stop(self) -> Optional[float]:
+        """The limit approx_kl is compared with, as both learners compare it: float32(1.5 * target_kl); None when the option is off."""
+        return None if self.target_kl is None else float(np.float32(1.5 * float(self.target_kl)))
 
 
 class _PpoHyper(C.Structure):
@@ -664,6 +680,9 @@ class FusedPpoUpdate:
         self._param_sig = None             # param_signature() when `flat` was last loaded from / stored to the module
         self._diag = None                  # PPOConfig.diagnostics: the caller-owned buffer of fw_ppo_update_diag (grown here, zeroed per call)
         self.diag_series = None            # ... and the last successful call's per-minibatch figures (float64 [n_mb] each)
+        self._stepped = None               # PPOConfig.target_kl: the device int32 fw_ppo_update_kl leaves the number of Adam steps in
+        self.last_stepped = self.last_computed = 0     # the last successful call: Adam steps taken, minibatches whose loss was computed
+        self.stop_kl = None                # ... and the approx_kl that ended it (None: it ran to its end)
 
     def _workspace(self, n_mb: int, batch_size: int) -> torch.Tensor:
         # exchange words + gradient hand-off buffer + the packed rows of every minibatch (a parallel pre-pass of the call writes them)
@@ -798,13 +817,24 @@ class FusedPpoUpdate:
         assert perm_i32.dtype == torch.int32 and perm_i32.numel() == n_mb * cfg.batch_size
         ws = self._workspace(n_mb, cfg.batch_size)
         diag = bool(getattr(cfg, "diagnostics", False))
-        self.diag_series = None
-        if diag:
+        target_kl = getattr(cfg, "target_kl", None)
+        self.diag_series = self.stop_kl = None
+        if diag or target_kl is not None:
             # the diagnostics instantiation of the same kernel row: one float4 per wave and minibatch into a buffer of ours
             nd = int(_lib.lib().fw_ppo_diag_floats(n_mb))
             if self._diag is None or self._diag.numel() < nd:
                 self._diag = torch.empty(nd, dtype=torch.float32, device=self.flat.device)
             self._diag.zero_()             # (rows of parts the cut does not use stay zero: the sums below take every row)
+        if target_kl is not None:
+            # the KL-stop instantiation of the same kernel row: the verdict is taken inside the launch, the count of Adam steps comes
+            # back in a word of ours (the diagnostics buffer always goes along: the stopping minibatch's row names the KL that ended it)
+            if self._stepped is None:
+                self._stepped = torch.zeros(1, dtype=torch.int32, device=self.flat.device)
+            rc = _lib.lib().fw_ppo_update_kl(_p(self.flat), _p(self.mom_m), _p(self.mom_v), _p(obs), _p(act), _p(old_logp), _p(adv),
+                                             _p(ret), _p(perm_i32), n_mb, cfg.batch_size, self.D, self.A, C.byref(H), _p(self.loss),
+                                             _p(ws), ws.numel(), _stream(obs.device), _p(self._diag), self._diag.numel(),
+                                             float(target_kl), _p(self._stepped))
+        elif diag:
             rc = _lib.lib().fw_ppo_update_diag(_p(self.flat), _p(self.mom_m), _p(self.mom_v), _p(obs), _p(act), _p(old_logp), _p(adv),
                                                _p(ret), _p(perm_i32), n_mb, cfg.batch_size, self.D, self.A, C.byref(H), _p(self.loss),
                                                _p(ws), ws.numel(), _stream(obs.device), _p(self._diag), self._diag.numel())
@@ -825,10 +855,17 @@ class FusedPpoUpdate:
             # module and the optimiser, which only commit() writes, still hold the state of before the call)
             raise RuntimeError(f"fw_ppo_update gave up inside the launch (status {st.value}: {', '.join(names)} wait ran out); "
                                "the policy and optimiser were left as they were before the call")
-        self._pending_step = step0 + n_mb      # commit() moves the result into the module / optimiser
+        # (target_kl: the count is valid behind a zero status only)
+        stepped = n_mb if target_kl is None else int(self._stepped.item())
+        computed = min(stepped + 1, n_mb)      # the stopping minibatch's losses were computed and count (SB3 books them)
+        self.last_stepped, self.last_computed = stepped, computed
+        self._pending_step = step0 + stepped   # commit() moves the result into the module / optimiser
         if diag:                               # the one device-to-host copy of the diagnostics, behind the status check
-            self.diag_series = fused_diag_series(self._diag[:nd].cpu().numpy(), n_mb)
-        return (self.loss[:3] / n_mb).tolist()
+            self.diag_series = fused_diag_series(self._diag[:computed * (nd // n_mb)].cpu().numpy(), computed)
+        if stepped < n_mb:
+            row = nd // n_mb
+            self.stop_kl = float(fused_diag_series(self._diag[stepped * row:(stepped + 1) * row].cpu().numpy(), 1)["approx_kl"][0])
+        return (self.loss[:3] / computed).tolist()
 
     def commit(self) -> None:
         """Second half of an update: the new parameters and moments go from the flat images to the module / optimiser.  Kept apart
@@ -866,6 +903,8 @@ class PPO:
         # CNN front end: data-parallel minibatches + ONE flattened gradient all-reduce each (the images of a rollout are ~30x
         # the flat observations: gathering every rank's rollout on every rank is the wrong trade there)
         self._replicated = td is not None and cfg.dist_update == "replicated" and not self._img
+        if cfg.target_kl is not None and td is not None and not self._replicated:
+            raise ValueError("target_kl on the gradient all-reduce path of a multi-process job is not built")
         self._fused_collect_ok = (bool(cfg.fused_collect) and FusedPpoUpdate.fits(self.policy, env.obs_dim, self.device, FusedPpoUpdate.act_dims(cfg))
                                   and getattr(env, "use_fused", False) and env.norm_obs and hasattr(env.venv, "step_tensor")
                                   and hasattr(env.venv, "terminal_obs") and hasattr(env.venv, "torch_dtype")
@@ -940,6 +979,7 @@ class PPO:
         self.diagnostics: Dict[str, float] = {}
         self.diagnostic_series: Dict[str, np.ndarray] = {}
         self._n_updates = 0                # SB3's _n_updates: epochs trained so far
+        self.stop_kl = self._stop_kl = None   # PPOConfig.target_kl: the approx_kl that ended the last update early (None: it ran to its end)
         # PPOConfig.episode_stats: the device-side episode monitor, folded once per vec-step by every collector
         self.episode_monitor = None
         self._stats = {}                   # PPO.rollout_stats of the last rollout, once read
@@ -1339,7 +1379,10 @@ class PPO:
         self.num_timesteps += steps
 
     # ---- SB3 PPO.train ------------------------------------------------------------------------
-    def _minibatch_step(self, obs, act, old_logp, adv, ret, idx, g_mean, g_std, params):
+    def _minibatch_step(self, obs, act, old_logp, adv, ret, idx, g_mean, g_std, params, kl_stop=None) -> bool:
+        """One minibatch of SB3's ``PPO.train()``.  ``kl_stop`` (PPOConfig.target_kl; never inside a captured graph): SB3's order -- the
+        losses and the KL are booked, then approx_kl is read on the host (the one sync per minibatch SB3 has too) and, above the limit,
+        the step is not taken: returns False."""
         cfg = self.cfg
         kw = {"img": self.buf_img.reshape((-1,) + tuple(self.buf_img.shape[2:]))[idx]} if self._img else {}
         a = adv[idx]
@@ -1351,18 +1394,31 @@ class PPO:
         value_loss = torch.nn.functional.mse_loss(ret[idx], values)
         entropy_loss = -entropy.mean()
         loss = policy_loss + cfg.ent_coef * entropy_loss + cfg.vf_coef * value_loss
+        if kl_stop is not None:
+            self._book_minibatch(policy_loss, value_loss, entropy_loss, ratio, logp, old_logp[idx])
+            with torch.no_grad():
+                approx_kl = float(((ratio - 1) - (logp - old_logp[idx])).mean())      # float32 on the device, compared as float32
+            if approx_kl > kl_stop:
+                self._stop_kl = approx_kl
+                return False
         self.optimizer.zero_grad(set_to_none=False)
         loss.backward()
         if not self._replicated:
             allreduce_grads_(params)           # "allreduce" mode only: a replicated update needs no collective here
         torch.nn.utils.clip_grad_norm_(params, cfg.max_grad_norm)
         self.optimizer.step()
+        if kl_stop is None:
+            self._book_minibatch(policy_loss, value_loss, entropy_loss, ratio, logp, old_logp[idx])
+        return True
+
+    def _book_minibatch(self, policy_loss, value_loss, entropy_loss, ratio, logp, old_logp) -> None:
+        cfg = self.cfg
         self._loss_acc += torch.stack([policy_loss.detach(), value_loss.detach(), entropy_loss.detach()])
         if cfg.diagnostics:
             # SB3's per-minibatch figures into row `_diag_i` of a persistent buffer, the counter on the device: no host sync, and the
             # captured update graph books each replay into the next row (columns: DIAG_SERIES)
             with torch.no_grad():
-                log_ratio = logp - old_logp[idx]
+                log_ratio = logp - old_logp
                 row = torch.stack([((ratio - 1) - log_ratio).mean(), (torch.abs(ratio - 1) > cfg.clip_range).float().mean(),
                                    policy_loss.detach(), value_loss.detach(), entropy_loss.detach()])
                 self._diag_buf.index_copy_(0, self._diag_i, row.unsqueeze(0))
@@ -1495,20 +1551,26 @@ class PPO:
                 self._flat_current = False     # the flat image holds a result that was not committed
                 self._fused.synced = False
                 self._diag_clear()             # (never the figures of an earlier update next to a failed one)
+                self.stop_kl = None
+                for k in ("minibatches_stepped", "epochs_run", "kl_stopped"):
+                    self.logs.pop(k, None)
                 raise err
             self._fused.commit()
             self._g_update = None              # the torch-path graph (if any) holds stale Adam state
             self._flat_current = True          # store_to_torch left flat == the module parameters
             self.logs = {"policy_loss": la[0], "value_loss": la[1], "entropy_loss": la[2],
                          "adv_mean": float(g_mean), "adv_std": float(g_std)}
-            self._n_updates += cfg.n_epochs    # (counted with the flag off too: SB3's figure is the epochs trained, not the epochs watched)
+            # (counted with the diagnostics flag off too: SB3's figure is the epochs trained, not the epochs watched)
+            self._n_updates += self._book_kl_stop(self._fused.last_stepped, nb, B // bs, self._fused.stop_kl)
             if cfg.diagnostics:
                 self._diag_finish(self._fused.diag_series, adv, ret)
             return
         self._flat_current = False             # the torch path below moves the module parameters
         if self._fused is not None:
             self._fused.synced = False
-        use_graph = self._graphs and B % bs == 0
+        # target_kl: the verdict is a host read per minibatch (as in SB3), which a captured graph cannot hold -- the steps run eagerly
+        kl_stop = cfg.kl_stop
+        use_graph = self._graphs and B % bs == 0 and kl_stop is None
         if cfg.diagnostics:
             self._diag_begin(cfg.n_epochs * ((B + bs - 1) // bs))
         if self._g_update is not None and self._g_update_diag != bool(cfg.diagnostics):
@@ -1545,22 +1607,44 @@ class PPO:
                 self._diag_buf.zero_(); self._diag_i.zero_()
         if use_graph:
             self._adv_s.copy_(adv); self._ret_s.copy_(ret); self._gm.copy_(g_mean); self._gs.copy_(g_std)
+        stepped, self._stop_kl = 0, None
         for _ in range(cfg.n_epochs):
             perm = torch.randperm(B, device=self.device, generator=self.perm_gen)
+            if self._stop_kl is not None:
+                continue                       # (stopped: the permutations of the epochs not run are still drawn, as the fused path draws
+                                               # all of them up front -- the generator ends every update in the same state on both paths)
             for s in range(0, B, bs):
                 if use_graph:
                     self._idx.copy_(perm[s:s + bs])
                     self._g_update.replay()
-                else:
-                    self._minibatch_step(obs, act, old_logp, adv, ret, perm[s:s + bs], g_mean, g_std, params)
+                elif not self._minibatch_step(obs, act, old_logp, adv, ret, perm[s:s + bs], g_mean, g_std, params, kl_stop):
+                    nb += 1                    # (its losses were booked)
+                    break
                 nb += 1
-        la = (self._loss_acc / nb).tolist()                      # the only host sync of the update
+                stepped += 1
+        la = (self._loss_acc / nb).tolist()                      # the only host sync of the update (target_kl: one more per minibatch)
         self.logs = {"policy_loss": la[0], "value_loss": la[1], "entropy_loss": la[2],
                      "adv_mean": float(g_mean), "adv_std": float(g_std)}
-        self._n_updates += cfg.n_epochs
+        self._n_updates += self._book_kl_stop(stepped, cfg.n_epochs * ((B + bs - 1) // bs), (B + bs - 1) // bs, self._stop_kl)
         if cfg.diagnostics:
             rows = self._diag_buf[:nb].to(torch.float64).cpu().numpy()
             self._diag_finish({k: rows[:, i].copy() for i, k in enumerate(DIAG_SERIES)}, adv, ret)
+
+    def _book_kl_stop(self, stepped: int, n_mb: int, mb_per_epoch: int, stop_kl) -> int:
+        """The epochs this update started (SB3 counts the one it stopped in).  With PPOConfig.target_kl set, ``logs`` gains
+        ``minibatches_stepped`` (optimiser steps taken), ``epochs_run`` and ``kl_stopped``; ``stop_kl`` holds the KL that ended
+        the update (None: it ran to its end)."""
+        epochs = self.cfg.n_epochs if stepped >= n_mb else stepped // mb_per_epoch + 1
+        self.stop_kl = stop_kl if stepped < n_mb else None
+        if self.cfg.target_kl is not None:
+            self.logs.update(minibatches_stepped=int(stepped), epochs_run=int(epochs), kl_stopped=bool(stepped < n_mb))
+        return epochs
+
+    def early_stop_message(self) -> Optional[str]:
+        """SB3's line for an update that ``target_kl`` ended early (its epoch index is 0-based), or None."""
+        if not self.logs.get("kl_stopped"):
+            return None
+        return f"Early stopping at step {self.logs['epochs_run'] - 1} due to reaching max kl: {self.stop_kl:.2f}"
 
     # does self._fused.flat hold the current policy parameters?  Clearing it also tells the fused update that its images (parameters
     # AND Adam moments) may be behind the module / optimiser: it then reloads them at its next call instead of reusing them

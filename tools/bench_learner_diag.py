@@ -3,6 +3,9 @@
   diag     device time per minibatch of fw_ppo_update_diag against the plain entry point of the width (fw_ppo_update_a / _a3) from the
            SAME library, at the three reference shapes (obs 28 / batch 128 / 4 actions, 21 / 64 / 6, 30 / 256 / 3): the two arms
            alternate in one process, --reps regions each (one region = one launch of --n_mb minibatches, timed with events), medians
+  kl       device time per minibatch of fw_ppo_update_kl (PPOConfig.target_kl) with a limit that never triggers -- without its
+           diagnostics buffer and with it, as the learner calls it -- against the plain and the diagnostics form from the same
+           library, same shapes: four arms alternating in one process, medians
   parent   the plain entry points of this build against the parent commit's library (--parent_lib, or FWSIM_LIB), same shapes, arms
            alternating in one process; a second copy of the parent's library is a third arm, so the A/A spread of the parent against
            itself comes from the same call
@@ -11,6 +14,7 @@
            runs it), and a closing line with the medians
 
     python tools/bench_learner_diag.py --what diag --out profiles/r13_learner_diag_bench.jsonl
+    python tools/bench_learner_diag.py --what kl --out profiles/r33_ppo_target_kl.jsonl
     python tools/bench_learner_diag.py --what parent --parent_lib /path/to/parent/libfwsim_hip.so --out profiles/r13_learner_diag_bench.jsonl
     python tools/bench_learner_diag.py --what e2e --out profiles/r13_learner_diag_bench.jsonl
 """
@@ -46,7 +50,8 @@ def load(path):
                             ("fw_ppo_update_a3", i32, [vp] * 9 + [i32, i32, i32, vp, vp, vp, i64, vp]),
                             ("fw_ppo_update_status", i32, [vp, i64, vp, vp, vp]),
                             ("fw_ppo_diag_floats", i64, [i32]),
-                            ("fw_ppo_update_diag", i32, [vp] * 9 + [i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, i64])):
+                            ("fw_ppo_update_diag", i32, [vp] * 9 + [i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, i64]),
+                            ("fw_ppo_update_kl", i32, [vp] * 9 + [i32, i32, i32, i32, vp, vp, vp, i64, vp, vp, i64, C.c_float, vp])):
         if hasattr(L, name):
             getattr(L, name).restype, getattr(L, name).argtypes = res, args
     L.fw_last_error.restype = C.c_char_p; L.fw_last_error.argtypes = [vp]
@@ -75,18 +80,25 @@ class Problem:
         self.diag = None
 
     def region(self, L, diag):
-        """One timed launch; returns (us per minibatch, parameter image after it)."""
+        """One timed launch; returns (us per minibatch, parameter image after it).  diag: False (plain), True (fw_ppo_update_diag),
+        "kl" (fw_ppo_update_kl with a limit no KL reaches, its diagnostics buffer left out), "kl_diag" (the same with the buffer passed:
+        what FusedPpoUpdate.run does under PPOConfig.target_kl)."""
         torch = self.torch
         p = lambda t: C.c_void_p(t.data_ptr())
         flat, m, v = self.flat0.clone(), torch.zeros(self.ns, device="cuda"), torch.zeros(self.ns, device="cuda")
         head = [p(x) for x in (flat, m, v, self.obs, self.act, self.lp, self.adv, self.ret, self.perm)]
         tail = [C.byref(self.H), p(self.loss), p(self.ws), self.ws.numel(), None]
-        if diag and self.diag is None:
+        if diag in (True, "kl_diag") and self.diag is None:
             self.diag = torch.zeros(int(L.fw_ppo_diag_floats(self.n_mb)), device="cuda")
+        stepped = torch.zeros(1, dtype=torch.int32, device="cuda")
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
         e0.record()
-        if diag:
+        if diag == "kl":
+            rc = L.fw_ppo_update_kl(*head, self.n_mb, self.B, self.D, self.A, *tail, None, 0, 1e30, p(stepped))
+        elif diag == "kl_diag":
+            rc = L.fw_ppo_update_kl(*head, self.n_mb, self.B, self.D, self.A, *tail, p(self.diag), self.diag.numel(), 1e30, p(stepped))
+        elif diag:
             rc = L.fw_ppo_update_diag(*head, self.n_mb, self.B, self.D, self.A, *tail, p(self.diag), self.diag.numel())
         elif self.A == 3:
             rc = L.fw_ppo_update_a3(*head, self.n_mb, self.B, self.D, *tail)
@@ -99,6 +111,8 @@ class Problem:
         L.fw_ppo_update_status(p(self.ws), self.ws.numel(), C.byref(st), None, None)
         if st.value:
             raise RuntimeError(f"status word {st.value}")
+        if diag in ("kl", "kl_diag") and int(stepped.item()) != self.n_mb:
+            raise RuntimeError(f"the limit triggered: {int(stepped.item())} of {self.n_mb} minibatches stepped")
         return e0.elapsed_time(e1) * 1e3 / self.n_mb, flat
 
 
@@ -118,7 +132,7 @@ def alternate(prob, arms, reps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--what", choices=("diag", "parent", "e2e"), default="diag")
+    ap.add_argument("--what", choices=("diag", "kl", "parent", "e2e"), default="diag")
     ap.add_argument("--n_mb", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--parent_lib", type=str, default=os.environ.get("FWSIM_LIB"))
@@ -167,6 +181,19 @@ def main():
                              "diag_over_plain": round(med["diag"] / med["plain"], 4),
                              "plain_all_us": [round(x, 3) for x in times["plain"]], "diag_all_us": [round(x, 3) for x in times["diag"]],
                              "same_parameters": bool(torch.equal(images["plain"], images["diag"])), "device": dev})
+        elif a.what == "kl":
+            for D, B, A in SHAPES:
+                prob = Problem(this, D, B, A, a.n_mb)
+                med, times, images = alternate(prob, [("plain", this, False), ("diag", this, True), ("kl", this, "kl"), ("kl_diag", this, "kl_diag")], a.reps)
+                rows.append({"what": "kl", "obs_dim": D, "batch": B, "act_dim": A, "n_mb": a.n_mb, "regions": a.reps,
+                             "plain_us_per_minibatch": round(med["plain"], 3), "diag_us_per_minibatch": round(med["diag"], 3),
+                             "kl_us_per_minibatch": round(med["kl"], 3), "kl_over_plain": round(med["kl"] / med["plain"], 4),
+                             "kl_with_diag_buffer_us_per_minibatch": round(med["kl_diag"], 3),      # (what the learner runs)
+                             "kl_with_diag_buffer_over_plain": round(med["kl_diag"] / med["plain"], 4),
+                             "kl_with_diag_buffer_over_diag": round(med["kl_diag"] / med["diag"], 4),
+                             "all_us": {k: [round(x, 3) for x in v] for k, v in times.items()},
+                             "same_parameters": bool(torch.equal(images["plain"], images["kl"]) and torch.equal(images["diag"], images["kl"]) and torch.equal(images["kl_diag"], images["kl"])),
+                             "device": dev})
         else:
             if not a.parent_lib:
                 raise SystemExit("--parent_lib (or FWSIM_LIB): the parent commit's libfwsim_hip.so")
